@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- agent-steps/s of the batched MapfEnv.step() hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4|c5|c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4|c5|c2] [--full] [--dump-outputs DIR]
+
+A plain run sets up, pre-rolls and warms up, times exactly K steps in one block and prints the line.  --full adds what
+the headline does not need: the median of five K-step blocks (--repeats), value_cold, parity, the side legs, baseline_configs
+and cpu_baseline below (the --no-* options leave single ones out).  --dump-outputs DIR writes what the last timed step computed
+(its recorded trajectory and the accumulators) as DIR/<name>.npy: see dump_outputs().
 
 N > 1 without a launcher: this process starts N children itself (one rank per GPU, RCCL), before it touches
 any GPU; under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` it is one of the ranks.
@@ -24,8 +29,9 @@ its outputs (next cells, reward, done, collision, prob) to HBM.  K steps = K lau
 HIP stream between barrier + synchronize on both sides; `value` = all ranks' agent-steps / max-over-ranks wall
 time of that region.  Rank 0 prints ONE JSON line.  Keys beyond the contract:
   value / ms_per_step   MEDIAN over --repeats timed blocks of exactly K steps each (every block bracketed by barrier +
-                synchronize on both sides, max over ranks); `repeats` lists every block.  `value_cold` = the first 25
-                launches after >= 1 s of idle device, timed the same way before any warm-up (clocks not yet ramped)
+                synchronize on both sides, max over ranks; one block in a plain run, five with --full); `repeats` lists every
+                block.  `value_cold` (--full) = the first 25 launches after >= 1 s of idle device, timed the same way before
+                any warm-up (clocks not yet ramped)
   roofline      dominant kernel (the fused rollout; `kernel` = what the library reports it dispatched): algorithmic
                 bytes / HIP-event time per launch; `traffic` = HBM bytes per launch from the committed PMC passes
                 (profiles/traffic.json: per-step + fixed part), `traffic_frac` = that / the same time / peak;
@@ -55,6 +61,7 @@ time of that region.  Rank 0 prints ONE JSON line.  Keys beyond the contract:
                 `all_cores` = N = usable host cores independent processes of the C port and of the Python port (summed rates:
                 the whole-host figure; measured before this process touches the GPU)
   parity        bit-exact check of the first steps of this very run against the C oracle
+From single_step_launches on, every key above is --full only.
 """
 import argparse
 import json
@@ -666,6 +673,44 @@ def transitions_rate(n_agents, n_queries, reps=10, blocks=3, compact=False, seed
                          "bytes_per_branch": 2 * A + 18, "traffic": None}}
 
 
+def sample_ids(n_envs, n_max, salt):
+    """All local env ids when there are at most n_max, else a fixed seeded sample of n_max of them, sorted."""
+    if n_envs <= n_max:
+        return np.arange(n_envs)
+    return np.sort(np.random.RandomState([SEED, salt]).choice(n_envs, n_max, replace=False))
+
+
+def dump_outputs(dirname, rec, acc, env_id_offset, trajectory_budget=48 << 20):
+    """--dump-outputs: what the headline path handed its caller in the last timed step, one DIR/<name>.npy per array.
+    The recorded trajectory of that launch (local [T, n, A], reward / prob [T, n], done / collision [T, n]) for a fixed seeded
+    sample of at most 1024 envs that fits `trajectory_budget` bytes, and the accumulators (returns, episodes, collisions) for
+    up to 262144 envs; *_env_ids hold the global ids of the sampled envs.  Integers are written as float32 (u16, u8) or
+    float64 (u32), the float64 outputs as they are: at most ~56 MB in all."""
+    import torch
+    T, E, A = rec['local'].shape
+    n = max(1, min(1024, trajectory_budget // (T * (4 * A + 24))))
+    ids = sample_ids(E, n, 1)
+    acc_ids = sample_ids(E, 262144, 2)
+    dev = rec['local'].device
+
+    def pick(t, signed, axis, which):
+        idx = torch.from_numpy(which).to(dev)
+        return t.view(signed).index_select(axis, idx).cpu().numpy()
+
+    out = {'local': pick(rec['local'], torch.int16, 1, ids).view(np.uint16).astype(np.float32),
+           'reward': pick(rec['reward'], torch.float64, 1, ids), 'prob': pick(rec['prob'], torch.float64, 1, ids),
+           'done': pick(rec['done'], torch.uint8, 1, ids).astype(np.float32),
+           'collision': pick(rec['collision'], torch.uint8, 1, ids).astype(np.float32),
+           'trajectory_env_ids': (env_id_offset + ids).astype(np.float64),
+           'returns': pick(acc['returns'], torch.float64, 0, acc_ids),
+           'episodes': pick(acc['episodes'], torch.int32, 0, acc_ids).view(np.uint32).astype(np.float64),
+           'collisions': pick(acc['collisions'], torch.int32, 0, acc_ids).view(np.uint32).astype(np.float64),
+           'accumulator_env_ids': (env_id_offset + acc_ids).astype(np.float64)}
+    os.makedirs(dirname, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(dirname, name + '.npy'), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -696,7 +741,13 @@ def main():
     ap.add_argument('--force-dist', action='store_true',
                     help='initialise torch.distributed and run the collective legs (MAX all-reduce, gather of the returns) even '
                          'with --gpus 1: with --dist-backend nccl this is RCCL at world size 1 -- what a one-GPU box can verify')
-    ap.add_argument('--repeats', type=int, default=5, help='timed blocks of --steps steps each; value = their median')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='timed blocks of --steps steps each; value = their median (default 1, with --full 5)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline does not need: value_cold, parity, the side legs, '
+                         'baseline_configs, cpu_baseline (the --no-* options leave single ones out)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0's envs)")
     ap.add_argument('--rank-timeout', type=float, default=900.0,
                     help='self-launched ranks (--gpus N without a launcher) are all terminated after this many seconds')
     ap.add_argument('--cpu-worker', nargs=4, metavar=('KIND', 'CONFIG', 'SECONDS', 'INDEX'), default=None, help=argparse.SUPPRESS)
@@ -707,9 +758,10 @@ def main():
         return
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         spawn_ranks(args.gpus, args.rank_timeout)
+    repeats = args.repeats if args.repeats is not None else (5 if args.full else 1)
     # the whole-host CPU figure runs FIRST: its workers are child programs, which a process may only start before it touches the GPU
     all_cores = None
-    if args.gpus == 1 and not args.force_dist and not args.no_cpu_baseline and int(os.environ.get('WORLD_SIZE', '1')) == 1:
+    if args.full and args.gpus == 1 and not args.force_dist and not args.no_cpu_baseline and int(os.environ.get('WORLD_SIZE', '1')) == 1:
         all_cores = cpu_all_cores(args.config)
 
     # stdout carries ONE JSON line: whatever libraries print while they initialise (gloo's rank banner, ...) goes to stderr
@@ -773,7 +825,7 @@ def main():
 
     # ---- parity: first steps of this run vs the C oracle, every env of this rank
     parity = None
-    if rank == 0:
+    if rank == 0 and args.full:
         sys.path.insert(0, os.path.join(ROOT, 'oracle'))
         import c_oracle
         import mapf_oracle as mo
@@ -838,12 +890,14 @@ def main():
             wall = float(tmax.item())
         return wall, gpu_ms
 
-    def timed(enqueue, n_warm, n_timed, repeats, cold=0):
+    def timed(enqueue, n_warm, n_timed, repeats, cold=0, restart=None):
         """`repeats` timed blocks of exactly n_timed enqueues each (see block()); returns (list of (wall s, gpu ms), the
         cold block or None).  cold > 0: before anything else the device idles for a second and the first `cold`
         enqueues are timed as a block of their own -- what a caller sees who does not keep the device busy.  Then the
         same launches run untimed for --preroll-ms (after an idle period the device needs ~25 ms of work to reach the
-        clocks it sustains, profiles/r02_launch_series.txt), then the n_warm warm-up steps, then the blocks."""
+        clocks it sustains, profiles/r02_launch_series.txt), then the n_warm warm-up steps, then the blocks.
+        restart: called after the pre-roll, whose launch count depends on the clock; the warm-up then starts again from
+        enqueue(0), so that what the blocks compute is the same from run to run."""
         cold_block = None
         k = 0
         if cold:
@@ -857,6 +911,9 @@ def main():
                 enqueue(k)
                 k += 1
             env.sync()
+        if restart is not None:
+            restart()
+            k = 0
         for _ in range(n_warm):
             enqueue(k)
             k += 1
@@ -892,10 +949,21 @@ def main():
     def enqueue_rollout(k):
         nat.check(env._lib.mapf_rollout(env._h, ctypes.byref(ios[k % n_slots])))
 
+    def restart_rollout():
+        env.sync()
+        env.reset()
+        env.set_state(None, t=0)
+        for v in acc.values():
+            v.view(torch.uint8).zero_()
+        torch.cuda.synchronize()
+        env.sync()
+
     env.reset()
-    n_cold = 25
-    ro_blocks, ro_cold = timed(enqueue_rollout, W, K, args.repeats, cold=n_cold)
+    n_cold = 25 if args.full else 0
+    ro_blocks, ro_cold = timed(enqueue_rollout, W, K, repeats, cold=n_cold, restart=restart_rollout)
     wall, gpu_ms = median_block(ro_blocks)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, rec, acc, offset)
     rollout_kernel = env.last_kernel('rollout')
     agent_steps = float(K) * T * total_envs * A
     value = agent_steps / wall
@@ -916,15 +984,16 @@ def main():
     # ---- the BASELINE configurations that are defined over several GPUs, sharded over THIS run's ranks (multi-rank runs:
     # what a driver scaling run must report for configs[3] / configs[4]; the headline above stays configs[2] per GPU)
     baseline_legs = None
-    if dist is not None and not args.no_baseline_configs and args.config == 'c3':
+    if args.full and dist is not None and not args.no_baseline_configs and args.config == 'c3':
         baseline_legs = {}
         for leg_name, key in (('c4', 'configs[3]'), ('c5', 'configs[4]')):
             baseline_legs[key] = baseline_config_leg(leg_name, rank, world, dist, coll_dev, local_rank, T=T,
                                                      n_launch=args.baseline_config_steps)
 
     # ---- second leg: env-steps as single-step mapf_step launches (one kernel launch per env-step)
+    side_legs = args.full and not args.no_side_legs
     single = None
-    if not args.no_side_legs:
+    if side_legs:
         # recorded once, replayed: 256 mapf_step nodes; the step writes its cells once (the next observation is the
         # handle's state view) and every other output to HBM
         n_nodes = min(256, ring)                                     # (a replay boundary costs ~5 us: hipGraphLaunch + the advance node)
@@ -936,7 +1005,7 @@ def main():
             call()
         graph = env.graph_end()
         K1 = 8                                                       # replays per timed block = 2048 env-steps
-        g_blocks, _ = timed(lambda k: graph.launch(1), 4, K1, min(args.repeats, 3))
+        g_blocks, _ = timed(lambda k: graph.launch(1), 4, K1, min(repeats, 3))
         wall1, gpu_ms1 = median_block(g_blocks)
         step_kernel = env.last_kernel('step')
         n_steps1 = K1 * n_nodes
@@ -978,7 +1047,6 @@ def main():
                        "preroll_ms": args.preroll_ms,
                        "parallelism": "env-sharded x%d" % world},
             "value_hip_events": float(T) * total_envs * A / (ro_launch_ms * 1e-3),
-            "value_cold": (float(n_cold) * T * total_envs * A / ro_cold[0]) if ro_cold else None,
             "repeats": {"n": len(ro_blocks), "steps_per_block": K, "value_of": "median block",
                         "values": [agent_steps / b[0] for b in ro_blocks],
                         "ms_per_step": [b[0] * 1e3 / K for b in ro_blocks]},
@@ -993,8 +1061,10 @@ def main():
                          "note": "achieved = algorithmic bytes (5 + 18/A per agent-step, SURVEY.md 8(d)) per launch / HIP-event "
                                  "time per launch; traffic = PMC-measured HBM bytes per launch (the fused kernel keeps state "
                                  "in registers, so it moves fewer bytes than the per-step contract credits)"},
-            "parity": parity,
         }
+        if args.full:
+            line["value_cold"] = float(n_cold) * T * total_envs * A / ro_cold[0]
+            line["parity"] = parity
         if args.share_device and world > 1:
             # every rank ran on cuda:0: a plumbing rehearsal of the N > 1 path, NOT a multi-GPU measurement -- the counters
             # under profiles/ describe one process alone on the device and do not apply
@@ -1012,21 +1082,21 @@ def main():
                     leg["roofline"]["traffic"] = None
         if single is not None:
             line["single_step_launches"] = single
-        if world == 1 and not args.no_side_legs and not args.no_scalar_env:
+        if world == 1 and side_legs and not args.no_scalar_env:
             line["scalar_env"] = scalar_env_rate()
-        if world == 1 and not args.no_side_legs and not args.no_per_gpu_shapes and args.config == 'c3' and args.envs is None:
+        if world == 1 and side_legs and not args.no_per_gpu_shapes and args.config == 'c3' and args.envs is None:
             # what each GPU runs of the two BASELINE configurations that are sharded over eight
             line["per_gpu_shapes"] = {"c4_share": per_gpu_shape_rate('c4', CONFIGS['c4']['envs'] // 8),
                                       "c5_share": per_gpu_shape_rate('c5', CONFIGS['c5']['envs'] // 8)}
-        if world == 1 and not args.no_side_legs and not args.no_policy_rollout and not args.policy_actions and args.envs is None and args.kernel == 'auto':
+        if world == 1 and side_legs and not args.no_policy_rollout and not args.policy_actions and args.envs is None and args.kernel == 'auto':
             # the same batch with the policy ON the device: mapf_rollout(actions = NULL), trajectory recorded
             line["policy_rollout"] = per_gpu_shape_rate(args.config, E, T=T, n_launch=20, blocks=5, policy=True)
             line["policy_rollout"]["vs_streamed_hip_events"] = line["policy_rollout"]["value"] / line["value_hip_events"]
-        if world == 1 and not args.no_side_legs and not args.no_transitions and args.envs is None and args.config == 'c3':
+        if world == 1 and side_legs and not args.no_transitions and args.envs is None and args.config == 'c3':
             # env.P[s][a]: every branch of random queries, compacted rows; a write-bound kernel by contract
             line["transitions"] = {"a8_q20000": transitions_rate(8, 20000, compact=True), "a4_q2000000": transitions_rate(4, 2000000, compact=True),
                                    "a8_q20000_reserved_rows": transitions_rate(8, 20000, compact=False)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg)
             if all_cores is not None:
                 line["cpu_baseline"]["all_cores"] = all_cores

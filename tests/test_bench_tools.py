@@ -41,6 +41,38 @@ def test_csrc_hash_is_stable_and_counter_profiles_are_keyed_by_it(monkeypatch):
     assert bench.measured_traffic(t['kernel'], t['n_envs'], t['n_agents'], 256) > 0
 
 
+def test_dumped_outputs_are_a_fixed_exact_sample_within_budget(tmp_path):
+    """bench.py --dump-outputs: the last step's recorded trajectory (sampled envs) and accumulators as float32 / float64 .npy
+    files, value for value, the same sample every time, and no more than 64 MB at the largest bench shape (32 agents)."""
+    import numpy as np
+    import torch
+    T, E, A, offset = 256, 16384, 32, 4096
+    g = torch.Generator().manual_seed(0)
+    rec = {'local': torch.randint(-2 ** 15, 2 ** 15, (T, E, A), dtype=torch.int16, generator=g).view(torch.uint16),
+           'reward': torch.randn(T, E, dtype=torch.float64, generator=g), 'prob': torch.rand(T, E, dtype=torch.float64, generator=g),
+           'done': torch.randint(0, 2, (T, E), dtype=torch.uint8, generator=g),
+           'collision': torch.randint(0, 2, (T, E), dtype=torch.uint8, generator=g)}
+    acc = {'returns': torch.randn(E, dtype=torch.float64, generator=g),
+           'episodes': torch.randint(0, 2 ** 31 - 1, (E,), dtype=torch.int32, generator=g).view(torch.uint32),
+           'collisions': torch.randint(0, 9, (E,), dtype=torch.int32, generator=g).view(torch.uint32)}
+    bench.dump_outputs(str(tmp_path / 'a'), rec, acc, offset)
+    bench.dump_outputs(str(tmp_path / 'b'), rec, acc, offset)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == sorted(os.listdir(tmp_path / 'b')) and len(names) == 10
+    out = {n[:-4]: np.load(tmp_path / 'a' / n) for n in names}
+    assert all(np.array_equal(v, np.load(tmp_path / 'b' / (k + '.npy'))) for k, v in out.items())
+    assert all(v.dtype in (np.float32, np.float64) for v in out.values())
+    assert sum(os.path.getsize(tmp_path / 'a' / n) for n in names) <= 64 << 20
+    ids = out['trajectory_env_ids'].astype(np.int64) - offset
+    assert 0 < len(ids) < E and np.all(np.diff(ids) > 0)
+    assert np.array_equal(out['local'], rec['local'].view(torch.int16).numpy().view(np.uint16)[:, ids].astype(np.float32))
+    for key in ('reward', 'prob', 'done', 'collision'):
+        assert np.array_equal(out[key], rec[key].numpy()[:, ids]), key
+    assert np.array_equal(out['accumulator_env_ids'], offset + np.arange(E, dtype=np.float64))
+    assert np.array_equal(out['returns'], acc['returns'].numpy())
+    assert np.array_equal(out['episodes'], acc['episodes'].view(torch.int32).numpy().view(np.uint32).astype(np.float64))
+
+
 def test_valu_share_is_priced_by_kind_and_never_exceeds_one(tmp_path, monkeypatch):
     dv = _load_tool('derive_valu')
     cost = dv.issue_costs_ns()

@@ -61,7 +61,7 @@ def test_bench_with_the_rccl_legs_forced_on_at_one_gpu():
     """`bench.py --gpus 1 --dist-backend nccl --force-dist`: the bench's own init_process_group('nccl', device_id=...),
     barrier, MAX all-reduce of the block times and the gather of the returns, end to end, one JSON line."""
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--dist-backend', 'nccl', '--force-dist',
-           '--steps', '2', '--warmup', '1', '--repeats', '1', '--preroll-ms', '10', '--no-side-legs', '--no-cpu-baseline',
+           '--steps', '2', '--warmup', '1', '--repeats', '1', '--preroll-ms', '10', '--full', '--no-side-legs', '--no-cpu-baseline',
            '--envs', '4096', '--baseline-config-steps', '2']
     proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=420, env=_clean_env())
     assert proc.returncode == 0, proc.stderr.decode('utf-8', 'replace')[-3000:]
@@ -84,7 +84,7 @@ def test_three_rank_rehearsal_shards_the_baseline_configs_in_blocks():
     (weak scaling) and the baseline_configs leg, whose populations do not divide by three: shards of 88064 / 87040 / 87040 and
     44032 / 44032 / 43008 envs (whole 1024-env blocks), the packed kernels on every rank, padded gathers of all returns."""
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '3', '--dist-backend', 'gloo', '--share-device',
-           '--steps', '2', '--warmup', '1', '--repeats', '1', '--preroll-ms', '10', '--no-side-legs', '--no-cpu-baseline',
+           '--steps', '2', '--warmup', '1', '--repeats', '1', '--preroll-ms', '10', '--full', '--no-side-legs', '--no-cpu-baseline',
            '--envs', '4096', '--baseline-config-steps', '2', '--rank-timeout', '380']
     proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=420, env=_clean_env())
     assert proc.returncode == 0, proc.stderr.decode('utf-8', 'replace')[-3000:]

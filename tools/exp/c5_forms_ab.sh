@@ -13,7 +13,7 @@ for i in $(seq $N); do
     for form in "${forms[@]}"; do
       echo -n "[$form] [$cfgflags] "
       setting=$form; [ "$form" = default ] && setting=MAPF_TUNE=
-      env $setting python3 bench.py $cfgflags --steps 10 --warmup 3 --repeats 3 --no-side-legs --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.1f G  frac %.4f  %s' % (d['value']/1e9, d['roofline']['frac'], d['roofline']['kernel'][:105]))"
+      env $setting python3 bench.py --full $cfgflags --steps 10 --warmup 3 --repeats 3 --no-side-legs --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.1f G  frac %.4f  %s' % (d['value']/1e9, d['roofline']['frac'], d['roofline']['kernel'][:105]))"
     done
   done
 done

@@ -8,7 +8,7 @@ if [ -f $PWD/gym-mapf_amd/gym_mapf_amd/lib/variants/libmapf_hip_stamps.so ]; the
 fi
 : > $out/r02_configs.txt
 for spec in "c3" "c4" "c4 --envs 32768" "c5" "c5 --envs 16384" "c2"; do
-  python bench.py --config $spec --steps 20 --warmup 5 --no-cpu-baseline --no-scalar-env 2>/dev/null | python3 -c "
+  python bench.py --full --config $spec --steps 20 --warmup 5 --no-cpu-baseline --no-scalar-env 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; s=d['single_step_launches']
 print('bench.py --config $spec: %s envs/GPU x %d agents | fused rollout %.1f G agent-steps/s, roofline %.3f of 8 TB/s, %s | single-step launches %.1f G (%.3f) | parity %s' % (d['config']['envs_per_gpu'], d['config']['n_agents'], d['value']/1e9, r['frac'], r['kernel'], s['value']/1e9, s['roofline']['frac'], d['parity']['bit_exact']))" >> $out/r02_configs.txt

@@ -14,5 +14,5 @@ if [ -f $V ]; then
   MAPF_HIP_LIB=$V python3 tools/stamp_profile.py 65536 c3 > $O/${tag}_stamps_c3.txt 2>&1
   MAPF_HIP_LIB=$V python3 tools/stamp_profile.py 32768 c4 > $O/${tag}_stamps_c4s.txt 2>&1
 fi
-python3 bench.py --steps 20 --warmup 5 > $O/${tag}_bench.json 2> $O/${tag}_bench.err; echo "bench rc=$?"
-python3 bench.py --gpus 2 --dist-backend gloo --share-device --steps 3 --warmup 1 --repeats 1 --no-side-legs --no-cpu-baseline --baseline-config-steps 3 > $O/${tag}_reh2.json 2> $O/${tag}_reh2.err; echo "reh rc=$?"
+python3 bench.py --full --steps 20 --warmup 5 > $O/${tag}_bench.json 2> $O/${tag}_bench.err; echo "bench rc=$?"
+python3 bench.py --full --gpus 2 --dist-backend gloo --share-device --steps 3 --warmup 1 --repeats 1 --no-side-legs --no-cpu-baseline --baseline-config-steps 3 > $O/${tag}_reh2.json 2> $O/${tag}_reh2.err; echo "reh rc=$?"

@@ -29,7 +29,7 @@ for cfg in $configs; do
     c5)  flags="--config c5"; E=131072; A=32 ;;
     *) echo "unknown config $cfg"; exit 1 ;;
   esac
-  BENCH="python3 bench.py --steps 20 --warmup 5 --repeats 2 --no-cpu-baseline --no-scalar-env --no-per-gpu-shapes --no-policy-rollout --no-transitions $flags"
+  BENCH="python3 bench.py --full --steps 20 --warmup 5 --repeats 2 --no-cpu-baseline --no-scalar-env --no-per-gpu-shapes --no-policy-rollout --no-transitions $flags"
   pre="$out/${tag}_${cfg}"
 
   # 1. the command under the profiler: per-kernel durations
@@ -86,11 +86,11 @@ for cfg in $configs; do
     c5s) flags="--config c5 --envs 16384" ;;
     c5)  flags="--config c5" ;;
   esac
-  python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-scalar-env $flags > "$out/${tag}_${cfg}_bench.json"
+  python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-scalar-env $flags > "$out/${tag}_${cfg}_bench.json"
   if [ "$cfg" = c3 ]; then
     python3 tools/exp/launch_series.py 300 > "$out/${tag}_launch_series.txt" 2>&1
-    python3 bench.py --steps 20 --warmup 5 > "$out/${tag}_bench_steps20_warmup5.json"
-    python3 bench.py > "$out/${tag}_bench_default.json"
+    python3 bench.py --full --steps 20 --warmup 5 > "$out/${tag}_bench_steps20_warmup5.json"
+    python3 bench.py --full > "$out/${tag}_bench_default.json"
     cat "$out/${tag}_bench_default.json"
   fi
 done
