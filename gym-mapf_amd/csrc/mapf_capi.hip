@@ -108,6 +108,8 @@ struct mapf_handle_s {
     mapf::SlipRow *slip = nullptr;
     std::vector<uint16_t> nbr;        // host copy of the neighbour table (policy tables are derived from it)
     uint2 *policy_cells = nullptr;    // greedy policy table (mapf_set_policy); null = random policy stream
+    // table policy (mapf_set_policy_table): device copies of the action bytes and of the agents' row indices; table.table null = off
+    mapf::TablePolicy table{};
     uint16_t *state = nullptr, *start = nullptr, *goal = nullptr;
     // host-pointer mode staging
     DeviceBuf s_actions, s_uniforms, s_local, s_reward, s_prob, s_done, s_coll, s_term, s_mask, s_ret, s_epi, s_ncoll;
@@ -301,6 +303,8 @@ void destroy_impl(mapf_handle_t h) {
     if (h->mv8) (void)hipFree(h->mv8);
     if (h->mv4) (void)hipFree(h->mv4);
     if (h->policy_cells) (void)hipFree(h->policy_cells);
+    if (h->table.table) (void)hipFree(const_cast<uint8_t *>(h->table.table));
+    if (h->table.rows) (void)hipFree(const_cast<uint16_t *>(h->table.rows));
     if (h->slip) (void)hipFree(h->slip);
     if (h->state) (void)hipFree(h->state);
     if (h->start) (void)hipFree(h->start);
@@ -752,6 +756,8 @@ int mapf_rollout(mapf_handle_t h, const mapf_rollout_io *io) {
     a.t = h->capturing ? h->cap_steps : h->t;
     a.t_dev = h->capturing ? h->t_dev : nullptr;
     a.policy_cells = h->policy_cells;
+    // (the table policy travels beside the argument block: its kernels are instances of their own)
+    const mapf::TablePolicy *table = (h->table.table && !io->actions) ? &h->table : nullptr;
     a.start_broadcast = h->start_broadcast; a.goal_broadcast = h->goal_broadcast;
     a.auto_reset = io->step_flags & MAPF_STEP_AUTO_RESET;
     a.accumulate = io->accumulate != 0;
@@ -766,7 +772,7 @@ int mapf_rollout(mapf_handle_t h, const mapf_rollout_io *io) {
         a.out_collisions = io->out_collisions; a.rec_local = io->rec_local; a.rec_reward = io->rec_reward;
         a.rec_done = io->rec_done; a.rec_collision = io->rec_collision; a.rec_prob = io->rec_prob;
         if (int rc = complete_recording(h, a, TE, TEA)) return rc;
-        HIP_TRY(h->lane_group_rollout ? mapf::launch_rollout_lg(int(h->A), a, h->tune, h->stream) : mapf::launch_rollout(int(h->A), a, h->stream));
+        HIP_TRY(h->lane_group_rollout ? mapf::launch_rollout_lg(int(h->A), a, h->tune, h->stream, table) : mapf::launch_rollout(int(h->A), a, h->stream, table));
         if (h->last_rollout_kernel != g_noted_kernel) h->last_rollout_kernel = g_noted_kernel;
         if (h->capturing) h->cap_steps += io->n_steps; else h->t += io->n_steps;
         if (io->n_steps) (h->capturing ? h->cap_may_be_terminal : h->may_be_terminal) = a.auto_reset ? h->start_terminal_any : true;
@@ -795,7 +801,7 @@ int mapf_rollout(mapf_handle_t h, const mapf_rollout_io *io) {
     if (int rc = stage_out(h, h->s_done, io->rec_done, TE, &a.rec_done, "rec_done")) return rc;
     if (int rc = stage_out(h, h->s_coll, io->rec_collision, TE, &a.rec_collision, "rec_collision")) return rc;
     if (int rc = complete_recording(h, a, TE, TEA)) return rc;
-    HIP_TRY(h->lane_group_rollout ? mapf::launch_rollout_lg(int(h->A), a, h->tune, h->stream) : mapf::launch_rollout(int(h->A), a, h->stream));
+    HIP_TRY(h->lane_group_rollout ? mapf::launch_rollout_lg(int(h->A), a, h->tune, h->stream, table) : mapf::launch_rollout(int(h->A), a, h->stream, table));
     if (h->last_rollout_kernel != g_noted_kernel) h->last_rollout_kernel = g_noted_kernel;
     h->t += io->n_steps;
     if (io->n_steps) h->may_be_terminal = a.auto_reset ? h->start_terminal_any : true;
@@ -811,12 +817,65 @@ int mapf_rollout(mapf_handle_t h, const mapf_rollout_io *io) {
     return MAPF_OK;
 }
 
+namespace {
+void drop_policy_table(mapf_handle_t h) {
+    if (h->table.table) (void)hipFree(const_cast<uint8_t *>(h->table.table));
+    if (h->table.rows) (void)hipFree(const_cast<uint16_t *>(h->table.rows));
+    h->table = mapf::TablePolicy{};
+}
+}  // namespace
+
+int mapf_set_policy_table(mapf_handle_t h, const uint8_t *table, uint32_t n_rows, const uint16_t *row_index, uint32_t flags) {
+    if (!h) return fail(MAPF_EINVAL, "set_policy_table: null handle");
+    if (!table) return fail(MAPF_EINVAL, "set_policy_table: table is null");
+    if (!row_index) return fail(MAPF_EINVAL, "set_policy_table: row_index is null");
+    if (n_rows == 0 || n_rows > 65536u) return fail(MAPF_EINVAL, "set_policy_table: n_rows must be 1..65536");
+    if (flags & ~MAPF_POLICY_ROWS_BROADCAST) return fail(MAPF_EINVAL, "set_policy_table: unknown bits in flags");
+    if (int rc = check_handle(h)) return rc;
+    if (int rc = check_not_recording(h, "mapf_set_policy")) return rc;
+    if (!h->graphs.empty()) return fail(MAPF_EINVAL, "set_policy: recorded graphs hold the current policy table (destroy them first)");
+    const uint64_t bytes = uint64_t(n_rows) * h->V;
+    if (bytes > 0x7FFFFFFFull) return fail(MAPF_EINVAL, "set_policy_table: table (n_rows * V bytes) exceeds 2 GiB");
+    // the kernels index the move table with these bytes unclamped: every one is checked here
+    for (uint64_t i = 0; i < bytes; ++i)
+        if (table[i] > 4u)
+            return fail(MAPF_EINVAL, "set_policy_table: table[" + std::to_string(i) + "] = " + std::to_string(unsigned(table[i])) + " is not an action (0..4)");
+    const bool broadcast = (flags & MAPF_POLICY_ROWS_BROADCAST) != 0u;
+    const uint64_t n_index = broadcast ? uint64_t(h->A) : uint64_t(h->E) * h->A;
+    for (uint64_t i = 0; i < n_index; ++i)
+        if (row_index[i] >= n_rows)
+            return fail(MAPF_EINVAL, "set_policy_table: row_index[" + std::to_string(i) + "] = " + std::to_string(unsigned(row_index[i])) + " is not below n_rows");
+    HIP_TRY(hipStreamSynchronize(h->stream));   // no launch may still be reading the old copies
+    drop_policy_table(h);
+    if (h->policy_cells) { (void)hipFree(h->policy_cells); h->policy_cells = nullptr; }   // (one policy at a time)
+    // the table's allocation is padded to whole 16-byte words (the LDS form stages it sixteen bytes at a time); the row indices
+    // by one agent row (the packed kernels load an agent pair's two indices as one word)
+    const size_t padded = (size_t(bytes) + 15u) & ~size_t(15), row_bytes = (size_t(n_index) + 16u) * sizeof(uint16_t);
+    uint8_t *d_table = nullptr;
+    uint16_t *d_rows = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_table), padded));
+    if (hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_rows), row_bytes)) { (void)hipFree(d_table); return hip_fail(e, "hipMalloc"); }
+    hipError_t e = hipMemset(d_table, 0, padded);
+    if (e == hipSuccess) e = hipMemset(d_rows, 0, row_bytes);
+    if (e == hipSuccess) e = hipMemcpy(d_table, table, size_t(bytes), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_rows, row_index, size_t(n_index) * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d_table); (void)hipFree(d_rows); return hip_fail(e, "set_policy_table: copying the table"); }
+    h->table.table = d_table;
+    h->table.rows = d_rows;
+    h->table.table_bytes = uint32_t(bytes);
+    h->table.rows_broadcast = broadcast ? 1u : 0u;
+    return MAPF_OK;
+}
+
 int mapf_set_policy(mapf_handle_t h, int policy, const uint32_t *cell_rc) {
     if (int rc = check_handle(h)) return rc;
     if (int rc = check_not_recording(h, "mapf_set_policy")) return rc;
     if (!h->graphs.empty()) return fail(MAPF_EINVAL, "set_policy: recorded graphs hold the current policy table (destroy them first)");
+    if (policy == MAPF_POLICY_TABLE) return fail(MAPF_EINVAL, "set_policy: MAPF_POLICY_TABLE is set through mapf_set_policy_table (it takes the table and the row indices)");
     if (policy != MAPF_POLICY_RANDOM && policy != MAPF_POLICY_GREEDY) return fail(MAPF_EINVAL, "set_policy: unknown policy");
+    if (policy == MAPF_POLICY_GREEDY && !cell_rc) return fail(MAPF_EINVAL, "set_policy: the greedy policy needs cell_rc");
     HIP_TRY(hipStreamSynchronize(h->stream));   // no launch may still be reading the old table
+    drop_policy_table(h);                       // either policy leaves table mode
     if (policy == MAPF_POLICY_RANDOM) {
         if (h->policy_cells) { (void)hipFree(h->policy_cells); h->policy_cells = nullptr; }
         return MAPF_OK;

@@ -17,9 +17,9 @@ hipError_t launch_step(int n_agents, const StepArgs &args, hipStream_t stream) {
     MAPF_ROUTE(launch_step, n_agents, args, stream)
 }
 
-hipError_t launch_rollout(int n_agents, const RolloutArgs &args, hipStream_t stream) {
+hipError_t launch_rollout(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table) {
     if (n_agents < 1) return hipErrorInvalidValue;
-    MAPF_ROUTE(launch_rollout, n_agents, args, stream)
+    MAPF_ROUTE(launch_rollout, n_agents, args, stream, table)
 }
 
 }  // namespace mapf

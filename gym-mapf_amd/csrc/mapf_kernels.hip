@@ -71,9 +71,10 @@ __global__ void __launch_bounds__(256) step_kernel(const StepArgs p) {
     signal_step_done(p.done_flag, p.done_seq);
 }
 
-template <int A>
-__global__ void __launch_bounds__(256) rollout_kernel(const RolloutArgs p) {
-    __shared__ SlipRow slip[8];
+// (one body for the kernels below: TABLE -- the table policy, MAPF_POLICY_TABLE -- is a compile-time property of an instance of
+// its own, so the instances of the other policies are what they were without it)
+template <int A, bool TABLE>
+__device__ __forceinline__ void rollout_body(const RolloutArgs &p, const TablePolicy &tp, SlipRow *slip) {
     stage_slip_table(p.slip, slip);
     const uint64_t e = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (e >= p.n_envs) return;
@@ -86,6 +87,12 @@ __global__ void __launch_bounds__(256) rollout_kernel(const RolloutArgs p) {
     uint32_t episodes = (p.accumulate && p.out_episodes) ? p.out_episodes[e] : 0u;
     uint32_t collisions = (p.accumulate && p.out_collisions) ? p.out_collisions[e] : 0u;
     const uint64_t env_id = p.env_id_offset + e, t0 = first_step_index(p);
+    uint32_t row_base[A];
+    if constexpr (TABLE) {
+        load_cells<A>(tp.rows, e, tp.rows_broadcast != 0u, row_base);
+#pragma unroll
+        for (int i = 0; i < A; ++i) row_base[i] *= p.c.n_cells;
+    }
 
     for (uint32_t s = 0; s < p.n_steps; ++s) {
         const uint64_t t = t0 + s;
@@ -95,6 +102,9 @@ __global__ void __launch_bounds__(256) rollout_kernel(const RolloutArgs p) {
             const Row<uint8_t, A> ar = load_row<uint8_t, A>(p.actions, row);
 #pragma unroll
             for (int i = 0; i < A; ++i) act[i] = ar.v[i];
+        } else if constexpr (TABLE) {   // agent i follows its row of the caller's table: one byte per (row, cell)
+#pragma unroll
+            for (int i = 0; i < A; ++i) act[i] = tp.table[row_base[i] + cur[i]];
         } else if (p.policy_cells) {
 #pragma unroll
             for (int i = 0; i < A; ++i) act[i] = greedy_action(p.policy_cells, p.c.n_cells, cur[i], p.policy_cells[goal[i]].x);
@@ -135,6 +145,18 @@ __global__ void __launch_bounds__(256) rollout_kernel(const RolloutArgs p) {
     if (p.out_collisions) p.out_collisions[e] = collisions;
 }
 
+template <int A>
+__global__ void __launch_bounds__(256) rollout_kernel(const RolloutArgs p) {
+    __shared__ SlipRow slip[8];
+    rollout_body<A, false>(p, TablePolicy{}, slip);
+}
+
+template <int A>
+__global__ void __launch_bounds__(256) rollout_kernel_table(const RolloutArgs p, const TablePolicy tp) {
+    __shared__ SlipRow slip[8];
+    rollout_body<A, true>(p, tp, slip);
+}
+
 // ------------------------------------------------------------------- launchers
 static inline unsigned pick_block(uint64_t n) { return n <= (1u << 18) ? 64u : 256u; }
 static inline unsigned grid_for(uint64_t n, unsigned block) { return unsigned((n + block - 1) / block); }
@@ -170,21 +192,24 @@ hipError_t MAPF_G(launch_step_g)(int n_agents, const StepArgs &args, hipStream_t
 // Only the spill-free specialisations exist in the shipped objects (kTpeRolloutMaxAgents; inside a template the
 // discarded branch is not instantiated): the larger ones are built by `make tpe16` for tools/exp/tpe_spill_repro.sh only.
 template <int N>
-static hipError_t launch_tpe_rollout(const RolloutArgs &args, unsigned grid, unsigned block, hipStream_t stream) {
+static hipError_t launch_tpe_rollout(const RolloutArgs &args, unsigned grid, unsigned block, hipStream_t stream, const TablePolicy *table) {
     if constexpr (N <= kTpeRolloutMaxAgents) {
-        hipLaunchKernelGGL((rollout_kernel<N>), dim3(grid), dim3(block), 0, stream, args);
+        if (table) hipLaunchKernelGGL((rollout_kernel_table<N>), dim3(grid), dim3(block), 0, stream, args, *table);
+        else hipLaunchKernelGGL((rollout_kernel<N>), dim3(grid), dim3(block), 0, stream, args);
         return hipGetLastError();
     } else {
         return hipErrorInvalidValue;
     }
 }
 
-hipError_t MAPF_G(launch_rollout_g)(int n_agents, const RolloutArgs &args, hipStream_t stream) {
+hipError_t MAPF_G(launch_rollout_g)(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table) {
     if (args.n_envs == 0) return hipSuccess;
+    if (table && args.actions) table = nullptr;                  // (streamed actions take precedence, as over the other policies)
     const unsigned block = pick_block(args.n_envs), grid = grid_for(args.n_envs, block);
-    note_kernel("rollout_kernel<A=%d> block=%u (thread per env)", n_agents, block);
+    if (table) note_kernel("rollout_kernel_table<A=%d,TABLE> block=%u (thread per env, table policy: action bytes gathered from global memory)", n_agents, block);
+    else note_kernel("rollout_kernel<A=%d> block=%u (thread per env)", n_agents, block);
     switch (n_agents) {
-#define X(N) case N: return launch_tpe_rollout<N>(args, grid, block, stream);
+#define X(N) case N: return launch_tpe_rollout<N>(args, grid, block, stream, table);
         MAPF_FOR_EACH_A(X)
 #undef X
         default: return hipErrorInvalidValue;

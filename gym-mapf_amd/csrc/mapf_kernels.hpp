@@ -147,6 +147,16 @@ struct RolloutArgs {
     bool mv_delta8;                // every candidate cell of the move table lies within +-127 ids of its own cell (mapf_create looks)
 };
 
+// Table policy (include/mapf_hip.h MAPF_POLICY_TABLE): the device copies mapf_set_policy_table made.  Handed to the
+// table instances of the rollout kernels as an argument of their own -- RolloutArgs, and with it every kernel that exists
+// without the table policy, stays as it is.
+struct TablePolicy {
+    const uint8_t *table;          // [n_rows * V] action bytes 0..4 (the allocation is padded to a multiple of 16 bytes)
+    const uint16_t *rows;          // [E*A] or [A]: the row an agent follows
+    uint32_t table_bytes;          // n_rows * V (< 2^31)
+    uint32_t rows_broadcast;       // rows is [A]
+};
+
 // Every launcher names the kernel instance (and block size) that took the launch; the C ABI keeps the name of a
 // handle's last step / rollout launch (mapf_last_kernel) so a benchmark labels its numbers with what actually ran.
 void note_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
@@ -187,7 +197,9 @@ uint64_t transitions_scan_blocks(uint64_t n_queries);
 hipError_t launch_transition_rewards(const TransitionsArgs &args, const uint16_t *next, hipStream_t stream);
 
 hipError_t launch_step(int n_agents, const StepArgs &args, hipStream_t stream);
-hipError_t launch_rollout(int n_agents, const RolloutArgs &args, hipStream_t stream);
+// (table: the table policy of an actions == null launch, or null -- a launcher whose family has no table instance for the
+// launch's shape returns hipErrorInvalidValue: a missing kernel is an error, never another policy)
+hipError_t launch_rollout(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table = nullptr);
 hipError_t launch_reset(int n_agents, uint16_t *state, const uint16_t *start, bool start_broadcast,
                         const uint8_t *mask, uint64_t n_envs, hipStream_t stream);
 hipError_t launch_fill_actions(int n_agents, uint8_t *actions, const EnvConsts &c, uint64_t env_id_offset,
@@ -227,6 +239,8 @@ struct RolloutTuning {
     int step_delta = 1;              // step_delta: the single step's LDS table of 4-byte delta rows -- 0 never, 1 where the 16-byte rows
                                      //   do not fit and the batch gives every CU a block (default), 2 whenever it fits (tests, experiments)
     bool scen_table = true;          // scen_table=0: never build the scenario table (StepArgs::scen) -- tests compare both forms
+    int policy_table_lds = -1;       // policy_table_lds=0|1: the packed rollout under the table policy gathers its action bytes from global
+                                     //   memory / from a copy staged into LDS behind the table image whenever that fits (default: by shape)
 };
 RolloutTuning default_rollout_tuning(int device, std::string *err);   // (reads MAPF_TUNE: mapf_lg_rollout.hip)
 // ... its arithmetic: the defaults of a device with n_cu compute units, overridden by `text` ("key=value,...", may be null)
@@ -234,9 +248,9 @@ RolloutTuning rollout_tuning_for(int n_cu, const char *text, std::string *err);
 hipError_t launch_step_lg(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream);
 // packed layout of the single step (mapf_lq_step.hip): true when it took the launch (*err = its status)
 bool try_launch_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err);
-hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream);
+hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table = nullptr);
 // packed layout of the fused rollout (2 or 4 agents per lane, mapf_lq_rollout.hip): true when it took the launch (*err = its status)
-bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err);
+bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy *table = nullptr);
 // What try_launch_rollout_lq decides before it launches -- pure arithmetic over the launch's shape (args.c.n_cells, n_envs, n_steps,
 // c.top_tie, actions / mv4 / mv_delta8 present or not), the tuning and the device's CU count, so it can be swept without a
 // device (mapf_debug_rollout_plan, tests/test_cabi_and_host.py): false = no packed form applies.
@@ -249,20 +263,25 @@ struct LqPlan {
     size_t lds_total = 0;            // ... with them: the dynamic LDS segment of the launch, <= 160 KB
 };
 bool plan_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, int n_cu, LqPlan *plan);
+// ... under the table policy (args.actions == null): the packed table instances exist for two and four agents per lane over full
+// 16-byte rows and for the 32-agent bitmap form over delta rows, in blocks of at most 512 threads; *table_lds = the action bytes are
+// staged into LDS behind the image (and the bitmaps) at byte *table_at, plan->lds_total then includes them.  false = lane-group kernel.
+bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, int n_cu, size_t table_bytes, LqPlan *plan,
+                           bool *table_lds, uint32_t *table_at);
 int lg_group_size(int n_agents);
 
 // per-group entry points: group g holds the kernels specialised for A in 4g+1 .. 4g+4
 hipError_t launch_step_g0(int n_agents, const StepArgs &args, hipStream_t stream);
-hipError_t launch_rollout_g0(int n_agents, const RolloutArgs &args, hipStream_t stream);
+hipError_t launch_rollout_g0(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table);
 
 hipError_t launch_step_g1(int n_agents, const StepArgs &args, hipStream_t stream);
-hipError_t launch_rollout_g1(int n_agents, const RolloutArgs &args, hipStream_t stream);
+hipError_t launch_rollout_g1(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table);
 
 hipError_t launch_step_g2(int n_agents, const StepArgs &args, hipStream_t stream);
-hipError_t launch_rollout_g2(int n_agents, const RolloutArgs &args, hipStream_t stream);
+hipError_t launch_rollout_g2(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table);
 
 hipError_t launch_step_g3(int n_agents, const StepArgs &args, hipStream_t stream);
-hipError_t launch_rollout_g3(int n_agents, const RolloutArgs &args, hipStream_t stream);
+hipError_t launch_rollout_g3(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table);
 
 
 

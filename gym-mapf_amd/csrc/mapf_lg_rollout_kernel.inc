@@ -1,0 +1,224 @@
+// The body of the lane-group rollout kernels of mapf_lg_rollout.hip, which includes this file twice:
+//   MAPF_ROLLOUT_TABLE_KERNEL 0 -- lg_rollout_kernel: streamed actions, the policy stream, the greedy policy;
+//   MAPF_ROLLOUT_TABLE_KERNEL 1 -- lg_rollout_kernel_table: the table policy (MAPF_POLICY_TABLE): agent i of env e on cell c takes
+//     tp.table[tp.rows[e * A + i] * V + c], gathered from global memory; the row bases wait in two registers per lane as the
+//     greedy policy's goal coordinates do.
+// Textual inclusion, not a shared function template: the first kernel's token stream is what it was before the table policy
+// existed, so its instances compile to the same code.
+#if MAPF_ROLLOUT_TABLE_KERNEL
+template <int L, bool FULL, bool MV_LDS, bool RECORD, bool DENSE, bool TABLE = true>
+__global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel_table(const RolloutArgs p, const uint32_t n_agents, const TablePolicy tp) {
+    constexpr bool STREAM = false;   // (a table instance runs the launches without streamed actions)
+#else
+template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM, bool DENSE>
+__global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(const RolloutArgs p, const uint32_t n_agents) {
+#endif
+    __shared__ SlipRow slip[8];
+    __shared__ OutcomeRow outcome[16];
+    extern __shared__ __attribute__((aligned(16))) MoveEntry lds_mv[];
+    bool live_rt;
+    LaneCtx<L> x = lane_ctx<L>(n_agents, p.n_envs, live_rt);
+    const bool live = DENSE || live_rt;
+    if (DENSE) { x.v0 = true; x.v1 = true; }
+    const uint32_t e = x.e;
+    const bool leader = live && x.g == 0u;
+    const bool tail = live && x.g == uint32_t(L - 1);   // holds the step's probability product
+
+    uint32_t cur0, cur1, goal0, goal1, start0 = 0u, start1 = 0u;
+    load_pair<uint16_t>(p.state, e, n_agents, x.g, x.v0, x.v1, cur0, cur1);
+    load_pair<uint16_t>(p.goal, p.goal_broadcast ? 0 : e, n_agents, x.g, x.v0, x.v1, goal0, goal1);
+    if (p.auto_reset) load_pair<uint16_t>(p.start, p.start_broadcast ? 0 : e, n_agents, x.g, x.v0, x.v1, start0, start1);
+    if (MV_LDS) {   // batches of four independent loads per thread, then the four LDS writes (not load-wait-write)
+        const uint32_t n_words = p.c.n_cells * kMvCols;
+        for (uint32_t w0 = threadIdx.x; w0 < n_words; w0 += 4u * blockDim.x) {
+            MoveEntry part[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; ++k) {
+                const uint32_t w = w0 + k * blockDim.x;
+                part[k] = p.mv[w < n_words ? w : n_words - 1u];
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; ++k) {
+                const uint32_t w = w0 + k * blockDim.x;
+                if (w < n_words) lds_mv[w] = part[k];
+            }
+        }
+    }
+    stage_outcome_table(p.c, outcome);
+    stage_slip_table(p.slip, slip);   // ends with __syncthreads()
+    const MoveEntry *mv = MV_LDS ? lds_mv : p.mv;
+
+    // is_terminal is carried from step to step instead of re-deriving it from the cells every step
+    uint32_t terminal = lg_is_terminal<L, FULL>(x, n_agents, cur0, cur1, goal0, goal1) ? 1u : 0u;   // an integer: no wave-mask phi
+    const uint32_t start_terminal = (p.auto_reset && lg_is_terminal<L, FULL>(x, n_agents, start0, start1, goal0, goal1)) ? 1u : 0u;
+
+    // per-env totals and the scalar trajectory arrays: their addresses are parked in VGPRs so that seven base
+    // pointers do not occupy SGPRs across the step loop (it already keeps ~100 scalars live).  They stay typed as
+    // GLOBAL pointers: a generic pointer would turn the stores into flat_store, which also counts on lgkmcnt and
+    // would chain every LDS wait of the loop to the stores' completion.
+    using gf64 = __attribute__((address_space(1))) double *;
+    using gu32 = __attribute__((address_space(1))) uint32_t *;
+    using gu8 = __attribute__((address_space(1))) uint8_t *;
+    using gu16 = __attribute__((address_space(1))) uint16_t *;
+    gf64 ret_p = (gf64)(p.out_returns ? at(p.out_returns, e) : nullptr);
+    gu32 epi_p = (gu32)(p.out_episodes ? at(p.out_episodes, e) : nullptr);
+    gu32 col_p = (gu32)(p.out_collisions ? at(p.out_collisions, e) : nullptr);
+    gu8 done_base = (gu8)(RECORD ? p.rec_done : nullptr), coll_base = (gu8)(RECORD ? p.rec_collision : nullptr);
+    gf64 reward_base = (gf64)(RECORD ? p.rec_reward : nullptr), prob_base = (gf64)(RECORD ? p.rec_prob : nullptr);
+    asm volatile("" : "+v"(ret_p), "+v"(epi_p), "+v"(col_p), "+v"(done_base), "+v"(coll_base), "+v"(reward_base),
+                 "+v"(prob_base));
+    double ret = (p.accumulate && ret_p && leader) ? *ret_p : 0.0;
+    uint32_t episodes = (p.accumulate && epi_p && leader) ? *epi_p : 0u;
+    uint32_t collisions = (p.accumulate && col_p && leader) ? *col_p : 0u;
+    const uint64_t env_id = p.env_id_offset + e;
+    const uint32_t n_envs = uint32_t(p.n_envs);
+
+#ifdef MAPF_STAMPS
+    StampCtx st{};
+    { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); st.last = _t; }
+#endif
+    // Software pipeline of the loop's memory operations.  The compiler waits for the prefetched action word with
+    // vmcnt(0), i.e. for EVERYTHING outstanding, so each iteration is ordered: (1) use the word loaded one
+    // iteration ago, (2) only then issue the next load and the PREVIOUS step's trajectory stores, (3) compute.
+    // Whatever the wait at (1) sees was issued a whole transition earlier and has long completed.
+    uint32_t raw = 0u;
+    if (STREAM && p.n_steps > 0) raw = load_actions_raw<FULL>(p.actions, e, n_agents, x.g, x.v0, x.v1);
+    // consume the first word here, so that the wait at the loop head is the back edge's counted one
+    if (DENSE) asm volatile("" : "+v"(raw));
+    Words4 rng{0u, 0u, 0u, 0u}, pol{0u, 0u, 0u, 0u};   // the slip / policy words of the current four-step block
+    // step s-1's results, stored during step s (DENSE: the very first store writes zeros into step 0's row, which
+    // step 1 then overwrites with the real values)
+    uint32_t d_next0 = 0u, d_next1 = 0u, d_flags = 0u;
+    double d_reward = 0.0, d_prob = 0.0;
+    // Addresses advance by one step's worth of elements per iteration (wave-uniform strides added to per-lane
+    // pointers) -- no per-step row * width multiplications.
+    const uint64_t step_rows = n_envs, step_cells = uint64_t(n_envs) * n_agents;
+    const bool odd = (x.g & 1u) != 0u;
+    const uint32_t flag_shift = (x.g & 1u) * 8u;
+    const uint32_t lane_cell = e * n_agents + 2u * x.g;
+    gf64 reward_lane = reward_base + e, prob_lane = prob_base + e;      // the delayed step's row
+    gu8 done_lane = done_base + e, coll_lane = coll_base + e;
+    gu16 rec_lane = (gu16)(RECORD ? p.rec_local : nullptr) + lane_cell;
+    const bool wide_is_prob = x.g == uint32_t(L - 1);   // the probability product ends in the group's last lane
+    if (DENSE && L > 1) {   // last lane writes prob, the others reward; even lanes write done, odd lanes collision
+        reward_lane = wide_is_prob ? prob_lane : reward_lane;
+        done_lane = odd ? coll_lane : done_lane;
+    }
+    asm volatile("" : "+v"(reward_lane), "+v"(prob_lane), "+v"(done_lane), "+v"(coll_lane), "+v"(rec_lane));
+
+    auto store_record = [&]() __attribute__((always_inline)) {
+        const uint32_t cells = d_next0 | (d_next1 << 16);
+        if (DENSE) {
+            *(gu32)rec_lane = cells;
+            *reward_lane = (L > 1 && wide_is_prob) ? d_prob : d_reward;
+            *done_lane = uint8_t(L > 1 ? d_flags >> flag_shift : d_flags);   // flag_shift: 8 in odd lanes
+            if (L == 1) {
+                *prob_lane = d_prob;
+                *coll_lane = uint8_t(d_flags >> 8);
+            }
+        } else {
+            if (FULL || (n_agents & 1u) == 0u) {
+                if (x.v0) *(gu32)rec_lane = cells;
+            } else {
+                if (x.v0) rec_lane[0] = uint16_t(d_next0);
+                if (x.v1) rec_lane[1] = uint16_t(d_next1);
+            }
+            if (tail) *prob_lane = d_prob;
+            if (leader) {
+                *reward_lane = d_reward;
+                *done_lane = uint8_t(d_flags & 1u);
+                *coll_lane = uint8_t(d_flags >> 8);
+            }
+        }
+    };
+    auto advance_record = [&]() __attribute__((always_inline)) {
+        rec_lane += step_cells;
+        reward_lane += step_rows;
+        done_lane += step_rows;
+        if (!(DENSE && L > 1)) { prob_lane += step_rows; coll_lane += step_rows; }
+    };
+    const uint8_t *act_lane = STREAM ? p.actions + lane_cell : nullptr;   // the row being prefetched
+
+    uint32_t goal_rc0 = 0u, goal_rc1 = 0u;   // greedy policy: my agents' goal coordinates
+    if (!STREAM && p.policy_cells) { goal_rc0 = p.policy_cells[goal0].x; goal_rc1 = p.policy_cells[goal1].x; }
+
+#if MAPF_ROLLOUT_TABLE_KERNEL
+    uint32_t row_base0, row_base1;   // table policy: my agents' rows (ghost slots: row 0, whose bytes are never used)
+    load_pair<uint16_t>(tp.rows, tp.rows_broadcast ? 0 : e, n_agents, x.g, x.v0, x.v1, row_base0, row_base1);
+    row_base0 *= p.c.n_cells;
+    row_base1 *= p.c.n_cells;
+#endif
+
+    const uint64_t t_first = first_step_index(p);
+    for (uint32_t s = 0; s < p.n_steps; ++s) {
+        const uint64_t t = t_first + s;
+        uint32_t act0, act1;
+        if (STREAM) {
+            act0 = raw & 0xFFu; act1 = (raw >> 8) & 0xFFu;   // only the low half-word of `raw` is defined
+            asm volatile("" : "+v"(act0), "+v"(act1));       // (1) pins the wait for `raw` here, ahead of (2)
+            if (DENSE) {                                     // clamped, not guarded: the last step re-reads its own row
+                act_lane += (s + 1u < p.n_steps) ? step_cells : 0u;
+                raw = *reinterpret_cast<const uint16_t *>(act_lane);
+            } else if (s + 1 < p.n_steps) {
+                act_lane += step_cells;
+                raw = load_actions_raw<FULL>(act_lane, 0u, 0u, 0u, x.v0, x.v1);
+            }
+        }
+#if MAPF_ROLLOUT_TABLE_KERNEL
+        else if constexpr (TABLE) {   // table policy: the byte of (my row, my cell) -- ghost slots read byte 0 of row 0
+            act0 = tp.table[row_base0 + cur0];
+            act1 = tp.table[row_base1 + cur1];
+        }
+#endif
+        else if (p.policy_cells) {   // greedy policy (ghost slots read cell 0: their actions are never used)
+            act0 = greedy_action(p.policy_cells, p.c.n_cells, cur0, goal_rc0);
+            act1 = greedy_action(p.policy_cells, p.c.n_cells, cur1, goal_rc1);
+        } else {   // policy stream: one Philox call covers agents 4q..4q+3 for the four steps of a block; this lane's
+            // agents are bytes 2(g&1), 2(g&1)+1 of the step's word
+            if ((t & 3u) == 0u || s == 0u) pol = policy_words(p.c, env_id, t >> 2, x.g >> 1);
+            const uint32_t mine = step_word(pol, t) >> (16u * (x.g & 1u));
+            act0 = policy_action_rt(mine, 0u);
+            act1 = policy_action_rt(mine, 1u);
+        }
+        if (RECORD && (DENSE || s > 0)) {                    // (2) the previous step's outputs
+            store_record();
+            if (!DENSE || s > 0) advance_record();
+        }
+        uint32_t next0, next1;
+        EnvOut o;
+        STAMP(0);   // loop top: action fetch / policy / delayed stores
+        // my pair's words of a four-step block (one slip-stream call per lane, traded with the neighbour lane): refresh when
+        // t is a multiple of 4 (and at the first step)
+        if (p.c.need_rng && ((t & 3u) == 0u || s == 0u)) rng = pair_block_words<(L > 1)>(p.c, env_id, t, x.g);
+        lg_transition<L, FULL, false, true, MV_LDS, true>(p.c, mv, slip, outcome, x, n_agents, cur0, cur1, goal0, goal1, act0, act1, 0.0, 0.0,
+                                            env_id, t, step_word(rng, t), terminal != 0u, next0, next1, o STAMP_ARG);
+        STAMP(6);   // reward / selects
+        ret = __dadd_rn(ret, o.reward);
+        episodes += o.status & 0xFFu;
+        collisions += (o.status >> 8) & 0xFFu;
+        if (RECORD) {
+            d_next0 = next0; d_next1 = next1; d_reward = o.reward; d_prob = o.prob;
+            d_flags = o.status;                            // byte 0 done, byte 1 collision
+        }
+        const bool back = p.auto_reset && (o.status & 0xFFu) != 0u;   // MapfEnv.reset(): start cells, no reseed
+        cur0 = back ? start0 : next0;
+        cur1 = back ? start1 : next1;
+        terminal = back ? start_terminal : (o.status >> 16);
+        STAMP(7);   // reset handling
+    }
+    if (RECORD && p.n_steps > 0) store_record();             // flush the last step's outputs
+#ifdef MAPF_STAMPS
+    if (live && x.lane == 0u && epi_p) {   // diagnostic build: segment sums replace the episode counts
+        for (int k = 0; k < 8; ++k) epi_p[k] = uint32_t(st.seg[k]);
+        return;
+    }
+#endif
+    if (!live) return;
+    store_cells<FULL>(p.state, e, n_agents, x.g, x.v0, x.v1, cur0, cur1);
+    if (leader) {
+        if (ret_p) *ret_p = ret;
+        if (epi_p) *epi_p = episodes;
+        if (col_p) *col_p = collisions;
+    }
+}
+

@@ -1,0 +1,84 @@
+"""Host helpers that build per-agent lookup-table policies for ``VecMapfEnv.set_policy('table', ...)``.
+
+A table policy is what the reference's planning workflow ends with: every agent (or small group) is solved on its own
+local view (``utils.get_local_view``) and the single-agent policies are joined.  A single-agent policy of a local view
+is a function ``cell -> action``, i.e. one row of ``V`` bytes; the fused rollout follows ``table[rows[e, i], cell]``
+for agent ``i`` of env ``e`` (include/mapf_hip.h, MAPF_POLICY_TABLE).  Nothing here needs a GPU.
+"""
+import numpy as np
+
+from gym_mapf_amd.envs import ACTIONS
+
+_STAY = ACTIONS.index('STAY')
+_MOVES = tuple(ACTIONS.index(name) for name in ('UP', 'RIGHT', 'DOWN', 'LEFT'))   # the tie-break order
+
+
+def _distances(nbr, goal):
+    """Breadth-first distance of every cell to ``goal`` over the noise-free moves (-1: the goal cannot be reached)."""
+    V = nbr.shape[0]
+    dist = np.full(V, -1, dtype=np.int64)
+    dist[goal] = 0
+    frontier = np.asarray([goal], dtype=np.int64)
+    moves = nbr[:, list(_MOVES)].astype(np.int64)
+    d = 0
+    # moves are symmetric on a grid (a -> b by UP means b -> a by DOWN), so the cells that reach the frontier in one
+    # move are the frontier's own neighbours
+    while frontier.size:
+        d += 1
+        nxt = np.unique(moves[frontier].ravel())
+        nxt = nxt[dist[nxt] < 0]
+        dist[nxt] = d
+        frontier = nxt
+    return dist
+
+
+def shortest_path_table(grid, goal_cells):
+    """``(table uint8 [R, V], row_of_goal dict)`` for the DISTINCT cells of ``goal_cells`` (local ids, any shape), rows
+    in ascending order of the goal id.  ``table[row_of_goal[g], c]`` is the first action in ACTIONS order (UP, RIGHT,
+    DOWN, LEFT) whose noise-free target is one step closer to ``g`` by breadth-first distance over
+    ``grid.tables()``'s neighbour table; STAY on the goal itself and on cells that cannot reach it."""
+    _, _, nbr = grid.tables()
+    V = nbr.shape[0]
+    goals = np.unique(np.asarray(goal_cells, dtype=np.int64).ravel())
+    if goals.size == 0 or goals.min() < 0 or goals.max() >= V:
+        raise ValueError('goal_cells must be local ids 0..%d' % (V - 1))
+    table = np.full((goals.size, V), _STAY, dtype=np.uint8)
+    for r, goal in enumerate(goals):
+        dist = _distances(nbr, int(goal))
+        undecided = dist > 0
+        for a in _MOVES:
+            target = dist[nbr[:, a].astype(np.int64)]
+            take = undecided & (target >= 0) & (target == dist - 1)
+            table[r, take] = a
+            undecided &= ~take
+    return table, {int(g): r for r, g in enumerate(goals)}
+
+
+def shortest_path_policy(env):
+    """``(table, rows)`` for ``env.set_policy('table', table=table, rows=rows)``: every agent of a ``VecMapfEnv`` follows
+    the shortest path to its own goal, ignoring the others.  ``rows`` is [A] when the env's goals are shared by all
+    envs, else [E, A]."""
+    table, row_of = shortest_path_table(env.grid, env.goal_local)
+    lookup = np.zeros(table.shape[1], dtype=np.uint16)
+    for goal, r in row_of.items():
+        lookup[goal] = r
+    rows = lookup[np.asarray(env.goal_local, dtype=np.int64)]
+    if env._goal_bcast:
+        rows = rows.reshape(-1)
+    return table, np.ascontiguousarray(rows, dtype=np.uint16)
+
+
+def row_from_policy(local_env, policy):
+    """The table row uint8 [V] of a reference-style ``policy(s) -> a`` of a ONE-agent ``MapfEnv`` (for instance a
+    ``get_local_view(env, [i])`` the caller planned on): ``row[c] = policy(c)`` -- with one agent the state integer is
+    the cell's local id and the action integer the action code."""
+    if local_env.n_agents != 1:
+        raise ValueError('row_from_policy needs a one-agent env (a single-agent local view), got %d agents' % local_env.n_agents)
+    V = len(local_env.valid_locations)
+    row = np.empty(V, dtype=np.uint8)
+    for c in range(V):
+        a = int(policy(c))
+        if not 0 <= a < len(ACTIONS):
+            raise ValueError('policy(%d) = %d is not an action code 0..%d' % (c, a, len(ACTIONS) - 1))
+        row[c] = a
+    return row

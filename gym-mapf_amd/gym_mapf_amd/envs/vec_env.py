@@ -129,6 +129,7 @@ class VecMapfEnv:
         handle = ctypes.c_void_p()
         nat.check(self._lib.mapf_create(ctypes.byref(desc), ctypes.byref(handle)))
         self._h = handle
+        self.policy = 'random'         # on-device policy of rollout(actions=None): see set_policy
         self._rollout_io = None        # rollout(out=...): the argument block of the last such call, with the arrays it points into
 
     # ------------------------------------------------------------------ construction
@@ -449,20 +450,55 @@ class VecMapfEnv:
                                                      int(t0), int(n_steps)))
         return out
 
-    def set_policy(self, policy='random'):
-        """On-device policy of ``rollout(actions=None)``: ``'random'`` (default; the uniform-random action stream)
-        or ``'greedy'`` -- every agent takes the first action in ACTIONS order whose intended target is closest
-        (Manhattan distance) to its goal, i.e. the first unblocked move one step closer, else STAY.  The reference
-        has no policy; this stands in for the caller-side ``a = policy(s)`` of the loop around ``step``."""
+    def set_policy(self, policy='random', table=None, rows=None):
+        """On-device policy of ``rollout(actions=None)``: ``'random'`` (default; the uniform-random action stream),
+        ``'greedy'`` -- every agent takes the first action in ACTIONS order whose intended target is closest
+        (Manhattan distance) to its goal, i.e. the first unblocked move one step closer, else STAY -- or ``'table'``:
+        the caller's plan.  ``table`` array-like uint8 [R, V] of action codes 0..4 (``table[r, cell]`` = what an agent
+        that follows row ``r`` does on ``cell``), ``rows`` [E, A] or [A] = the row every agent follows; both HOST arrays
+        (numpy or CPU torch) in either handle mode, copied.  ``envs/policies.py`` builds such tables (shortest paths,
+        or the row of a single-agent policy planned on a ``get_local_view``).  The reference has no policy; this
+        stands in for the caller-side ``a = policy(s)`` of the loop around ``step`` (mapf_env.py:237-266)."""
+        if policy != 'table' and (table is not None or rows is not None):
+            raise ValueError("table= and rows= belong to policy='table'")
         if policy == 'random':
             nat.check(self._lib.mapf_set_policy(self._h, nat.MAPF_POLICY_RANDOM, None))
         elif policy == 'greedy':
             valid, _, _ = self.grid.tables()
             rc = np.ascontiguousarray([r | (c << 16) for r, c in valid], dtype=np.uint32)
             nat.check(self._lib.mapf_set_policy(self._h, nat.MAPF_POLICY_GREEDY, rc.ctypes.data))
+        elif policy == 'table':
+            if table is None or rows is None:
+                raise ValueError("policy='table' needs table= [R, V] and rows= [E, A] or [A]")
+            V = len(self.grid.tables()[0])
+            table, rows = self._host_ints(table, 'table'), self._host_ints(rows, 'rows')
+            if table.ndim != 2 or table.shape[1] != V or not 1 <= table.shape[0] <= 65536:
+                raise ValueError('table must be [R, V] with V = %d free cells and 1 <= R <= 65536, got %r' % (V, tuple(table.shape)))
+            if tuple(rows.shape) not in ((self.n_envs, self.n_agents), (self.n_agents,)):
+                raise ValueError('rows must be [E, A] = %r or [A], got %r' % ((self.n_envs, self.n_agents), tuple(rows.shape)))
+            if table.size and (table.min() < 0 or table.max() > 4):
+                raise ValueError('table holds action codes 0..4 (STAY, UP, RIGHT, DOWN, LEFT), found %d' % (table.max() if table.max() > 4 else table.min()))
+            if rows.min() < 0 or rows.max() >= table.shape[0]:
+                raise ValueError('rows must name table rows 0..%d, found %d' % (table.shape[0] - 1, rows.max() if rows.max() >= table.shape[0] else rows.min()))
+            table8, rows16 = np.ascontiguousarray(table, dtype=np.uint8), np.ascontiguousarray(rows, dtype=np.uint16)
+            nat.check(self._lib.mapf_set_policy_table(self._h, table8.ctypes.data, table8.shape[0], rows16.ctypes.data,
+                                                      nat.MAPF_POLICY_ROWS_BROADCAST if rows16.ndim == 1 else 0))
         else:
-            raise ValueError("policy must be 'random' or 'greedy'")
+            raise ValueError("policy must be 'random', 'greedy' or 'table'")
+        self._rollout_io = None            # (a cached argument block must not outlive a policy change)
         self.policy = policy
+
+    @staticmethod
+    def _host_ints(a, name):
+        """A host integer array from numpy / CPU torch / nested lists (the table policy's arguments are host data in both modes)."""
+        if hasattr(a, 'is_cuda'):
+            if a.is_cuda:
+                raise ValueError('%s must be a host array (numpy or CPU torch): it is copied by the library' % name)
+            a = a.numpy()
+        a = np.asarray(a)
+        if a.dtype.kind not in 'iu':
+            raise ValueError('%s must be an integer array, got %s' % (name, a.dtype))
+        return a.astype(np.int64, copy=False) if a.dtype.kind == 'i' else a
 
     def query_terminal(self, out=None):
         """``MapfEnv.is_terminal`` of every env's current state: uint8 [E]."""

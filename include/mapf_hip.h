@@ -110,6 +110,8 @@ typedef struct mapf_desc {
  *   step_big=0|1|2       the single step's resident grid with the move table in LDS: never / by batch (default) / whenever it fits
  *   step_delta=0|1|2     ... with 4-byte delta rows (64x64 maps): never / from one full residency on (default) / whenever it fits
  *   step_block=64|128|256|512   block size of the plain packed single step
+ *   policy_table_lds=0|1 the packed rollout under MAPF_POLICY_TABLE: action bytes gathered from global memory / from a copy of the
+ *                        policy table staged into LDS behind the table image whenever one block's segment fits (default: by shape)
  */
 
 /* Replaces MapfEnv.__init__'s state setup; state = start cells, step index t = 0. */
@@ -188,6 +190,31 @@ int mapf_fill_random_actions(mapf_handle_t h, uint8_t *actions, uint64_t t0, uin
 #define MAPF_POLICY_RANDOM 0
 #define MAPF_POLICY_GREEDY 1
 int mapf_set_policy(mapf_handle_t h, int policy, const uint32_t *cell_rc);
+
+/*
+ * MAPF_POLICY_TABLE: a per-agent lookup-table policy followed INSIDE the fused rollout -- the caller's plan.  It stands
+ * in for the caller-side `a = policy(s)` of the loop around MapfEnv.step (reference mapf_env.py:237-266) when the
+ * joint policy is a join of single-agent policies, which is what the reference's planning workflow produces: each
+ * agent is solved on its own local view (gym_mapf/envs/utils.py:get_local_view) and a single-agent policy of a local
+ * view is a function cell -> action, i.e. one row of V bytes.
+ *   table u8[n_rows * V]: table[r * V + cell] is the action (0..4, the action codes above) of an agent that follows
+ *     row r and stands on `cell`.  1 <= n_rows <= 65536.
+ *   row_index u16[E * A] (u16[A] with MAPF_POLICY_ROWS_BROADCAST): the row agent i of local env e follows.
+ * Both are HOST pointers in every handle mode and are copied (as cell_rc above).  In mapf_rollout calls with
+ * actions == NULL agent i of env e on cell c then takes table[row_index[e * A + i] * V + c]; slip, collisions, reward,
+ * termination, auto-reset and the slip stream's counters are exactly those of a mapf_step with that action, the policy
+ * stream is not drawn (as under MAPF_POLICY_GREEDY), an env that is terminal on entry is a no-op.  Everything is
+ * validated on the host before any device work (MAPF_EINVAL: null handle / table / row_index, n_rows out of range, a
+ * table byte > 4, a row index >= n_rows, unknown flag bits); refused while recording and while recorded graphs live.
+ * mapf_set_policy(h, MAPF_POLICY_RANDOM | MAPF_POLICY_GREEDY, ...) leaves table mode and frees the copies.
+ * mapf_last_kernel(h, MAPF_KERNEL_ROLLOUT) of a table launch says TABLE where a streamed one says STREAM.
+ * Out of scope: a policy argument for the single mapf_step, the multi-map / union-map wrappers and the scalar MapfEnv
+ * of the Python package, tables over joint states of agent groups, anything that COMPUTES a policy on the device.
+ */
+#define MAPF_POLICY_TABLE 2
+#define MAPF_POLICY_ROWS_BROADCAST 0x1u      /* row_index is [A], shared by all envs */
+int mapf_set_policy_table(mapf_handle_t h, const uint8_t *table, uint32_t n_rows,
+                          const uint16_t *row_index, uint32_t flags);
 
 /*
  * MapfEnv.P[s][a] (mapf_env.py:448-478 _get_transitions): for each of n_queries (state, joint action) pairs,
