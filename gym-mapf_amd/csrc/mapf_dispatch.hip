@@ -1,7 +1,18 @@
-// Routes a launch to the translation unit that holds the kernels specialised for its agent count.
+// Routes a launch to the translation unit that holds the kernels specialised for its shape: the thread-per-env family by agent
+// count, the packed rollout by its plan (mapf_plan.hpp).  Holds no kernel itself.
 #include "mapf_kernels.hpp"
+#include "mapf_plan.hpp"
+
+#include <cstdlib>
 
 namespace mapf {
+
+// The tuning of a handle: the device's CU count and the MAPF_TUNE override, both asked ONCE, at mapf_create.
+RolloutTuning default_rollout_tuning(int device, std::string *err) {
+    int n_cu = 256;
+    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu <= 0) n_cu = 256;
+    return rollout_tuning_for(n_cu, getenv("MAPF_TUNE"), err);
+}
 
 #define MAPF_ROUTE(fn, A, ...)                          \
     switch (((A) - 1) / 4) {                            \
@@ -20,6 +31,28 @@ hipError_t launch_step(int n_agents, const StepArgs &args, hipStream_t stream) {
 hipError_t launch_rollout(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table) {
     if (n_agents < 1) return hipErrorInvalidValue;
     MAPF_ROUTE(launch_rollout, n_agents, args, stream, table)
+}
+
+// true when a packed layout took the launch (*err = its status); false = not applicable, use the lane-group kernel
+bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy *table) {
+    LqPlan plan;
+    bool table_lds = false;
+    uint32_t table_at = 0u;
+    if (table && args.actions) table = nullptr;
+    if (table ? !plan_rollout_lq_table(n_agents, args, tune, table->table_bytes, &plan, &table_lds, &table_at)
+              : !plan_rollout_lq(n_agents, args, tune, &plan)) return false;
+    const bool record = args.rec_local != nullptr;
+    const int K = plan.K;
+    if (record && !(args.rec_reward && args.rec_prob && args.rec_done && args.rec_collision)) {
+        *err = hipErrorInvalidValue;
+        return true;
+    }
+#define LQ_ARGS plan.Q, plan.form, args, uint32_t(n_agents), plan.block, plan.lds_bytes, stream, table, table_lds, table_at
+    if (K == 8) *err = record ? launch_rollout_lq_k8_r1(LQ_ARGS) : launch_rollout_lq_k8_r0(LQ_ARGS);
+    else if (K == 4) *err = record ? launch_rollout_lq_k4_r1(LQ_ARGS) : launch_rollout_lq_k4_r0(LQ_ARGS);
+    else *err = record ? launch_rollout_lq_k2_r1(LQ_ARGS) : launch_rollout_lq_k2_r0(LQ_ARGS);
+#undef LQ_ARGS
+    return true;
 }
 
 }  // namespace mapf

@@ -1,4 +1,6 @@
-// Argument blocks and launcher prototypes shared by mapf_kernels.hip and mapf_capi.hip.
+// Argument blocks and launcher prototypes shared by the kernel files, the router (mapf_dispatch.hip) and the C ABI
+// (mapf_capi.hip).  The tables these blocks point to are built on the host by mapf_tables.hip; which packed form a launch
+// takes is planned by mapf_plan.hip (mapf_plan.hpp) over the LDS layout of mapf_layout.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -88,7 +90,7 @@ struct OutcomeRow {
 static_assert(sizeof(OutcomeRow) == 16, "read as one 16-byte LDS word");
 // The 1 KB table image every step / rollout kernel keeps in LDS: the eight slip rows, then the sixteen outcome rows.  The
 // handle's device copy (StepArgs::slip, RolloutArgs::slip) holds exactly this image -- the outcome rows built on the host
-// with the same float64 additions (build_outcome_rows in mapf_capi.hip) -- so a wave can stage it with one 16-byte load
+// with the same float64 additions (build_outcome_rows in mapf_tables.hip) -- so a wave can stage it with one 16-byte load
 // and one 16-byte LDS write per lane.
 struct TableImage {
     SlipRow slip[8];
@@ -222,6 +224,7 @@ constexpr int kTpeRolloutMaxAgents = MAPF_TPE_ROLLOUT_MAX;   // ... their rollou
 // Layout choices of the kernels, fixed per handle at mapf_create (the MAPF_TUNE override -- "key=value,..." -- is read
 // there, so a process can hold handles with different settings: the tests do).  The key of each field is named beside it.
 struct RolloutTuning {
+    int n_cu = 256;                  // compute units of the handle's device (asked once, at mapf_create; 256 when the query fails)
     bool quad_lanes = true;          // quad_lanes=0 forces the pair layout
     uint64_t quad_min_lanes = 0;     // four agents per lane need at least this many lanes (quad_min_lanes; default: one
                                      // wave on every SIMD of the device); below that two agents per lane
@@ -242,49 +245,32 @@ struct RolloutTuning {
     int policy_table_lds = -1;       // policy_table_lds=0|1: the packed rollout under the table policy gathers its action bytes from global
                                      //   memory / from a copy staged into LDS behind the table image whenever that fits (default: by shape)
 };
-RolloutTuning default_rollout_tuning(int device, std::string *err);   // (reads MAPF_TUNE: mapf_lg_rollout.hip)
-// ... its arithmetic: the defaults of a device with n_cu compute units, overridden by `text` ("key=value,...", may be null)
-RolloutTuning rollout_tuning_for(int n_cu, const char *text, std::string *err);
+RolloutTuning default_rollout_tuning(int device, std::string *err);   // (asks the device, reads MAPF_TUNE: mapf_dispatch.hip)
 hipError_t launch_step_lg(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream);
 // packed layout of the single step (mapf_lq_step.hip): true when it took the launch (*err = its status)
 bool try_launch_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err);
 hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table = nullptr);
-// packed layout of the fused rollout (2 or 4 agents per lane, mapf_lq_rollout.hip): true when it took the launch (*err = its status)
+// packed layout of the fused rollout (2, 4 or 8 agents per lane): plans the launch (mapf_plan.hpp) and routes it to the object that
+// holds its instance (mapf_dispatch.hip); true when it took the launch (*err = its status)
 bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy *table = nullptr);
-// What try_launch_rollout_lq decides before it launches -- pure arithmetic over the launch's shape (args.c.n_cells, n_envs, n_steps,
-// c.top_tie, actions / mv4 / mv_delta8 present or not), the tuning and the device's CU count, so it can be swept without a
-// device (mapf_debug_rollout_plan, tests/test_cabi_and_host.py): false = no packed form applies.
-struct LqPlan {
-    int K = 0, Q = 0;                // agents per lane, lanes per env
-    int form = 0;                    // 0 full 16-byte rows, 1 8-byte rows, 2 / 3 bitmaps behind four / five 8-byte columns, 4 bitmaps behind
-                                     // full rows, 5 bitmaps behind 4-byte delta rows
-    unsigned block = 0;              // threads per block
-    size_t lds_bytes = 0;            // the kernel's LDS image without the bitmaps (what the launcher is handed)
-    size_t lds_total = 0;            // ... with them: the dynamic LDS segment of the launch, <= 160 KB
-};
-bool plan_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, int n_cu, LqPlan *plan);
-// ... under the table policy (args.actions == null): the packed table instances exist for two and four agents per lane over full
-// 16-byte rows and for the 32-agent bitmap form over delta rows, in blocks of at most 512 threads; *table_lds = the action bytes are
-// staged into LDS behind the image (and the bitmaps) at byte *table_at, plan->lds_total then includes them.  false = lane-group kernel.
-bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, int n_cu, size_t table_bytes, LqPlan *plan,
-                           bool *table_lds, uint32_t *table_at);
+// ... the launchers of those objects: mapf_lq_rollout.hip compiled once per (agents per lane, recording) pair; form, block, lds_bytes,
+// table_lds, table_at: the plan's answers
+#define MAPF_LQ_LAUNCHER(name)                                                                                                          \
+    hipError_t name(int Q, int form, const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream, \
+                    const TablePolicy *table, bool table_lds, uint32_t table_at);
+MAPF_LQ_LAUNCHER(launch_rollout_lq_k8_r1) MAPF_LQ_LAUNCHER(launch_rollout_lq_k8_r0) MAPF_LQ_LAUNCHER(launch_rollout_lq_k4_r1)
+MAPF_LQ_LAUNCHER(launch_rollout_lq_k4_r0) MAPF_LQ_LAUNCHER(launch_rollout_lq_k2_r1) MAPF_LQ_LAUNCHER(launch_rollout_lq_k2_r0)
+#undef MAPF_LQ_LAUNCHER
 int lg_group_size(int n_agents);
 
 // per-group entry points: group g holds the kernels specialised for A in 4g+1 .. 4g+4
 hipError_t launch_step_g0(int n_agents, const StepArgs &args, hipStream_t stream);
 hipError_t launch_rollout_g0(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table);
-
 hipError_t launch_step_g1(int n_agents, const StepArgs &args, hipStream_t stream);
 hipError_t launch_rollout_g1(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table);
-
 hipError_t launch_step_g2(int n_agents, const StepArgs &args, hipStream_t stream);
 hipError_t launch_rollout_g2(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table);
-
 hipError_t launch_step_g3(int n_agents, const StepArgs &args, hipStream_t stream);
 hipError_t launch_rollout_g3(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table);
-
-
-
-
 
 }  // namespace mapf

@@ -1,8 +1,6 @@
 // Lane-group family: fused T-step rollout kernel and its launcher (device code: mapf_lg.hpp).
 #include "mapf_lg.hpp"
-
-#include <cstdlib>
-#include <string>
+#include "mapf_layout.hpp"
 
 namespace mapf {
 
@@ -47,62 +45,7 @@ __device__ __forceinline__ uint32_t load_actions_raw(const uint8_t *base, uint32
 #include "mapf_lg_rollout_kernel.inc"
 #undef MAPF_ROLLOUT_TABLE_KERNEL
 
-// LDS budget for the move table: the CU has 160 KiB; keep room for the slip rows and the outcome table
-static constexpr size_t kLdsBytes = 160 * 1024, kLdsReserve = 1024;
-static_assert(sizeof(SlipRow) * 8 + sizeof(OutcomeRow) * 16 <= kLdsReserve, "static LDS of the rollout kernel");
-
-// Defaults of the layout choices: a move table is staged into LDS while two blocks per CU still fit (a table that
-// allows only one block per CU starves the SIMDs of waves); four agents per lane need one wave on every SIMD.
-// ONE override: the environment variable MAPF_TUNE, "key=value,key=value,...", read here -- at handle creation, so a process
-// can hold handles with different settings (the tests and the A/B tools do).  Keys (include/mapf_hip.h documents them):
-//   quad_lanes, k, quad_min_lanes, oct_min_lanes, mv_lds_max_bytes, scen_table, bitmap_pairs, bitmap_block, bitmap_staycol,
-//   bitmap_delta, step_big, step_block, step_delta, policy_table_lds.
-// An unknown key or a malformed item is an error (*err names it): a typo must not silently measure the default.
-RolloutTuning default_rollout_tuning(int device, std::string *err) {
-    int n_cu = 256;
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) n_cu = 256;
-    return rollout_tuning_for(n_cu, getenv("MAPF_TUNE"), err);
-}
-
-RolloutTuning rollout_tuning_for(int n_cu, const char *text, std::string *err) {
-    RolloutTuning t;
-    // measured on 8 agents x 32768 envs (one wave per SIMD with four agents per lane, two with two): 517 G vs 467 G
-    // agent-steps/s -- fewer, fatter waves win as long as no SIMD stays empty
-    t.quad_min_lanes = uint64_t(n_cu) * 4u * 64u;        // CUs x SIMDs x lanes
-    t.oct_min_lanes = uint64_t(n_cu) * 4u * 64u * 2u;    // (eight agents per lane: see try_launch_rollout_lq)
-    t.mv_lds_max_bytes = (kLdsBytes - kLdsReserve) / 2;
-    if (!text) return t;
-    std::string items(text);
-    size_t pos = 0;
-    while (pos <= items.size()) {
-        size_t end = items.find(',', pos);
-        if (end == std::string::npos) end = items.size();
-        const std::string item = items.substr(pos, end - pos);
-        pos = end + 1;
-        if (item.empty()) continue;
-        const size_t eq = item.find('=');
-        char *rest = nullptr;
-        const std::string key = item.substr(0, eq), val = eq == std::string::npos ? "" : item.substr(eq + 1);
-        const unsigned long long v = val.empty() ? 0 : strtoull(val.c_str(), &rest, 10);
-        if (eq == std::string::npos || val.empty() || (rest && *rest)) { if (err) *err = "MAPF_TUNE: malformed item '" + item + "' (want key=integer)"; return t; }
-        if (key == "quad_lanes") t.quad_lanes = v != 0;
-        else if (key == "k") t.force_k = int(v);
-        else if (key == "quad_min_lanes") t.quad_min_lanes = v;
-        else if (key == "oct_min_lanes") t.oct_min_lanes = v;
-        else if (key == "mv_lds_max_bytes") t.mv_lds_max_bytes = size_t(v);
-        else if (key == "scen_table") t.scen_table = v != 0;
-        else if (key == "bitmap_pairs") t.bitmap_pairs = v != 0;
-        else if (key == "bitmap_block") t.bitmap_block = unsigned(v);
-        else if (key == "bitmap_staycol") t.bitmap_stay_column = v != 0;
-        else if (key == "bitmap_delta") t.bitmap_delta_rows = v != 0;
-        else if (key == "step_big") t.step_big = int(v);
-        else if (key == "step_block") t.step_block = unsigned(v);
-        else if (key == "step_delta") t.step_delta = int(v);
-        else if (key == "policy_table_lds") t.policy_table_lds = v != 0 ? 1 : 0;
-        else { if (err) *err = "MAPF_TUNE: unknown key '" + key + "'"; return t; }
-    }
-    return t;
-}
+// (LDS budget for the move table -- kLdsBytes, kLdsReserve: mapf_layout.hpp)
 
 // the table instances: the same two geometries as launch_rollout_lg_impl below
 template <int L, bool FULL, bool RECORD>

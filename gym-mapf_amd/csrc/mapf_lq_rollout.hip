@@ -44,26 +44,17 @@
 // beyond the LDS budget, single steps) stays with mapf_lg_rollout.hip; launch_rollout_lg() picks.  Same stream,
 // same arithmetic, same outputs: the parity tests run all layouts against the oracle.
 #include "mapf_lq.hpp"
+#include "mapf_layout.hpp"
 
-#include <algorithm>
-#include <atomic>
-#include <cstdlib>
 #include <type_traits>
 
 namespace mapf {
 
 namespace {
 
-constexpr size_t kLdsBytes = 160 * 1024, kLdsReserve = 1024;
-static_assert(sizeof(SlipRow) * 8 + sizeof(OutcomeRow) * 16 <= kLdsReserve, "static LDS of the rollout kernel");
-
 // RECORD: all five trajectory arrays are written every step; STREAM: actions come from memory, else from the
 // in-kernel policy.  Memory pipeline and store scheme as lg_rollout_kernel<DENSE>.
-constexpr uint32_t kSlipAt = 0, kOutcomeAt = sizeof(SlipRow) * 8, kMoveAt = kLdsReserve, kMoveCols = 6;
-constexpr uint32_t kCompactCols = 5, kCompactEntry = 8;   // COMPACT: cells + code only, no sixth column
-constexpr uint32_t kBitmapCols = 4;                       // COMPACT + BITMAP == 1: no STAY column either
-constexpr uint32_t kDeltaEntry = 4;                       // COMPACT + BITMAP == 3: 4-byte delta rows, six columns (kDeltaCols, mapf_kernels.hpp: STAY twice, as the full table)
-static_assert(kOutcomeAt + sizeof(OutcomeRow) * 16 <= kMoveAt, "LDS image: slip rows, outcome rows, then the move table");
+// (the LDS image -- kSlipAt, kOutcomeAt, kMoveAt, the column counts and entry sizes of each table form: mapf_layout.hpp)
 // The LDS copy of a table row carries its slip row's byte offset PLUS kRowBias, so that sample_slot_packed's probability
 // address -- that operand minus 8 per threshold not passed -- is never negative and packs into an unsigned field (the
 // systolic probability chain below files four of them per word); the immediates of the LDS reads absorb the bias.
@@ -85,7 +76,7 @@ static_assert(offsetof(SlipRow, thr) % 8 == 0 && kZeroFactor < 128u, "a zero fac
 // in the fourth byte -- so that SIX columns (STAY twice: an action byte is extracted and clamped by one v_min_u32, and no STAY
 // row is made up) take half the room of the five 8-byte ones: 128 bitmaps fit behind them on the 64x64 maps.
 // (the four-column form with the in-kernel policy holds its actions across the table reads -- the made-up STAY row asks for
-// them -- and does not fit the 128 registers of a 1024-thread block: launched with 512 threads, see try_launch_rollout_lq)
+// them -- and does not fit the 128 registers of a 1024-thread block: launched with 512 threads, see plan_rollout_lq)
 #define MAPF_ROLLOUT_TABLE_KERNEL 0
 #include "mapf_lq_rollout_kernel.inc"
 #undef MAPF_ROLLOUT_TABLE_KERNEL
@@ -94,9 +85,6 @@ static_assert(offsetof(SlipRow, thr) % 8 == 0 && kZeroFactor < 128u, "a zero fac
 #undef MAPF_ROLLOUT_TABLE_KERNEL
 
 #undef env_id
-
-// bytes of one env's occupancy bitmap (BITMAP instances)
-static size_t bitmap_stride(uint32_t n_cells) { return (size_t((n_cells + 31u) / 32u) * 4u + 15u) & ~size_t(15); }   // one bit per cell
 
 template <int Q, int K, bool RECORD, bool STREAM, bool COMPACT = false, int BITMAP = 0>
 hipError_t launch_impl(const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream) {
@@ -109,7 +97,7 @@ hipError_t launch_impl(const RolloutArgs &args, uint32_t A, unsigned block, size
     if (BITMAP) lds_bytes += size_t(block / unsigned(Q)) * bitmap_stride(args.c.n_cells);
     if (lds_bytes > 32 * 1024) {
         // (this kernel has no static LDS object: its dynamic segment may be the CU's whole 160 KB -- the limit every form's
-        // "does it fit" test in try_launch_rollout_lq compares against)
+        // "does it fit" test in plan_rollout_lq compares against)
         if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(kLdsBytes))) return e;
     }
     const unsigned grid = unsigned(args.n_envs / (block / unsigned(Q)));
@@ -159,7 +147,7 @@ hipError_t launch_impl_table(const RolloutArgs &args, uint32_t A, unsigned block
 }  // namespace
 
 // This file is compiled once per (agents per lane, recording) pair -- -DMAPF_LQ_K=8|4|2 -DMAPF_LQ_RECORD=1|0 -- so that
-// its kernel instances build in parallel; each object exports one launcher, the K=4 / RECORD=1 object also the router.
+// its kernel instances build in parallel; each object exports one launcher (prototypes: mapf_kernels.hpp; the router: mapf_dispatch.hip).
 #if !defined(MAPF_LQ_K) || !defined(MAPF_LQ_RECORD)
 #error "compile with -DMAPF_LQ_K=8|4|2 -DMAPF_LQ_RECORD=1|0"
 #endif
@@ -249,199 +237,6 @@ hipError_t MAPF_LQ_NAME(MAPF_LQ_K, MAPF_LQ_RECORD)(int Q, int form, const Rollou
 #undef X
         default: return hipErrorInvalidValue;
     }
-}
-#endif
-
-#if MAPF_LQ_K == 4 && MAPF_LQ_RECORD == 1
-hipError_t launch_rollout_lq_k8_r1(int Q, int form, const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream,
-                                   const TablePolicy *table, bool table_lds, uint32_t table_at);
-hipError_t launch_rollout_lq_k8_r0(int Q, int form, const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream,
-                                   const TablePolicy *table, bool table_lds, uint32_t table_at);
-hipError_t launch_rollout_lq_k4_r0(int Q, int form, const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream,
-                                   const TablePolicy *table, bool table_lds, uint32_t table_at);
-hipError_t launch_rollout_lq_k2_r1(int Q, int form, const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream,
-                                   const TablePolicy *table, bool table_lds, uint32_t table_at);
-hipError_t launch_rollout_lq_k2_r0(int Q, int form, const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream,
-                                   const TablePolicy *table, bool table_lds, uint32_t table_at);
-
-// does the K-agents-per-lane form apply to this launch?  (full groups, power-of-two group size, full blocks)
-static bool layout_fits(int n_agents, int K, const RolloutArgs &args, size_t lds_bytes, unsigned *block_out, int *q_out) {
-    if (n_agents < K || n_agents % K != 0) return false;
-    const int Q = n_agents / K;
-    if (Q > 16 || (Q & (Q - 1)) != 0 || (K == 2 && Q < 2) || (K == 8 && Q > 4)) return false;
-    const size_t copies = kLdsBytes / lds_bytes;   // blocks per CU by LDS
-    unsigned block = copies >= 4 ? 256u : 512u;
-    // a small batch is spread over the CUs in smaller blocks (down to one wave): every block stages its own table copy,
-    // which is cheap next to a rollout's steps, and an idle CU is not
-    const uint64_t lanes = args.n_envs * uint64_t(Q);
-    while (block > 64u && lanes < 256u * uint64_t(block)) block /= 2u;
-    const uint64_t per_block = block / unsigned(Q);
-    if (args.n_envs % per_block != 0 || lanes < 64 * 16) return false;
-    *block_out = block;
-    *q_out = Q;
-    return true;
-}
-
-// the dispatch decision (see LqPlan): which packed form, block size and LDS image a launch of this shape takes
-bool plan_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, const int n_cu, LqPlan *plan) {
-    // top_tie: a three-entry list whose last cumulative sum rounds below 1.0 needs a third compare per agent (hi = 65535);
-    // the packed sampling does two, so such a table (none arises from fail_prob / 2 splits) stays with the lane-group kernel
-    if (!tune.quad_lanes || args.c.top_tie || args.n_steps > 65535u) return false;   // (per-launch counts are 16-bit)
-    unsigned block = 0;
-    int Q = 0, K = 0;
-    bool compact = false, bitmap = false, stay_column = false, full_rows_bitmap = false, delta_rows = false;
-    size_t lds_bytes = kMoveAt + size_t(args.c.n_cells) * kMoveCols * sizeof(MoveEntry);   // the kernel's whole LDS image
-    if (lds_bytes <= tune.mv_lds_max_bytes && lds_bytes <= kLdsBytes - kLdsReserve) {
-        // Four agents per lane halve the waves: that form needs tune.quad_min_lanes lanes (default: enough to put one
-        // wave on every SIMD); below that the two-agents-per-lane form of the same kernel runs.
-        // Eight agents per lane halve them again (at 8 agents nothing crosses lanes any more): worth it from two waves
-        // per SIMD of THAT form on, i.e. 131072 envs at 8 agents.
-        // 32 agents: four per lane with the occupancy bitmaps behind the full table (O(A) collision tests, see below) wherever that
-        // form applies -- 496 agent pairs per env are most of either all-pairs form's step
-        if (tune.bitmap_pairs && n_agents == 32 && (tune.force_k == 0 || tune.force_k == 4) && layout_fits(n_agents, 4, args, lds_bytes, &block, &Q) &&
-            lds_bytes + (block / 8u) * bitmap_stride(args.c.n_cells) <= kLdsBytes &&
-            (tune.force_k == 4 || args.n_envs * uint64_t(Q) >= tune.quad_min_lanes)) {
-            K = 4;
-            bitmap = true;
-            full_rows_bitmap = true;
-        } else
-        if ((tune.force_k == 0 || tune.force_k == 8) && layout_fits(n_agents, 8, args, lds_bytes, &block, &Q) &&
-            (tune.force_k == 8 || args.n_envs * uint64_t(Q) >= tune.oct_min_lanes) && block <= 512u) K = 8;
-        else if (tune.force_k != 2 && tune.force_k != 8 && layout_fits(n_agents, 4, args, lds_bytes, &block, &Q) &&
-                 (tune.force_k == 4 || args.n_envs * uint64_t(Q) >= tune.quad_min_lanes)) K = 4;
-        else if (tune.force_k != 4 && tune.force_k != 8 && layout_fits(n_agents, 2, args, lds_bytes, &block, &Q)) K = 2;
-        else return false;
-    } else {
-        // the full table is too large: 8-byte rows, one block per CU (512 threads = two waves per SIMD; 1024 when the
-        // batch gives every CU a block of that size), four agents per lane, group sizes 4 / 8 / 16 only
-        lds_bytes = kMoveAt + size_t(args.c.n_cells) * kCompactCols * kCompactEntry;
-        if (tune.mv_lds_max_bytes == 0 || lds_bytes > kLdsBytes - kLdsReserve) return false;
-        const size_t bitmap_lds = kMoveAt + size_t(args.c.n_cells) * kBitmapCols * kCompactEntry;   // (no STAY column in that form)
-        // 32 agents: four per lane, collisions through per-env occupancy bitmaps behind the table (one bit per cell) -- O(A)
-        // instead of 496 pair tests per env.  64 envs per 512-thread block; 128 per 1024-thread block (four waves per SIMD)
-        // once the batch gives every CU a block of that size and 128 bitmaps fit (C5's share of one GPU: 481 G against 377 G
-        // for the all-pairs form; C5 whole: profiles/r04_c5_one_bit_bitmap_ab.txt).  MAPF_TUNE k=8 / bitmap_pairs=0 keep the
-        // all-pairs forms reachable (eight agents per lane, Q = 4, one 512-thread block per CU; four per lane below).
-        const size_t per_env = bitmap_stride(args.c.n_cells);
-        unsigned bitmap_block = 512u;
-        if (tune.bitmap_block == 1024u || (tune.bitmap_block == 0u && args.n_envs * 8u >= uint64_t(n_cu) * 1024u)) bitmap_block = 1024u;
-        if (bitmap_block == 1024u && (args.n_envs % (1024u / 8u) != 0 || bitmap_lds + (1024u / 8u) * per_env > kLdsBytes)) bitmap_block = 512u;
-        if (args.actions == nullptr) bitmap_block = 512u;           // (in-kernel policy behind 8-byte rows: that instance is built for 512 threads)
-        // ... behind 4-byte delta rows where the map's ids allow them (six columns in 79 KB on the 64x64 maps: 128 bitmaps fit, no
-        // STAY row to make up, one-instruction action clamp)
-        const size_t delta_lds = kMoveAt + delta_table_words(args.c.n_cells) * kDeltaEntry;   // (the host-built image, zero-padded to 16 bytes)
-        unsigned delta_block = (tune.bitmap_block == 1024u || (tune.bitmap_block == 0u && args.n_envs * 8u >= uint64_t(n_cu) * 1024u)) ? 1024u : 512u;
-        if (delta_block == 1024u && (args.n_envs % (1024u / 8u) != 0 || delta_lds + (1024u / 8u) * per_env > kLdsBytes)) delta_block = 512u;
-        if (tune.bitmap_pairs && tune.bitmap_delta_rows && args.mv_delta8 && args.mv4 && n_agents == 32 && tune.force_k != 8 && tune.force_k != 2 &&
-            layout_fits(n_agents, 4, args, delta_lds, &block, &Q) && args.n_envs % (delta_block / 8u) == 0 &&
-            delta_lds + (delta_block / 8u) * per_env <= kLdsBytes) {
-            block = delta_block;
-            K = 4;
-            bitmap = true;
-            delta_rows = true;
-            lds_bytes = delta_lds;
-        } else
-        if (tune.bitmap_pairs && n_agents == 32 && tune.force_k != 8 && tune.force_k != 2 && layout_fits(n_agents, 4, args, bitmap_lds, &block, &Q) &&
-            args.n_envs % (bitmap_block / 8u) == 0 && bitmap_lds + (bitmap_block / 8u) * per_env <= kLdsBytes) {
-            block = bitmap_block;
-            K = 4;
-            bitmap = true;
-            // where the five-column table (STAY included: four selects per agent-step less) still leaves room for the block's
-            // bitmaps -- 64 of them on the 64x64 maps, not 128 -- it is the one staged (C5's share: profiles/r04_c5_stay_column_ab.txt)
-            stay_column = tune.bitmap_stay_column && lds_bytes + (bitmap_block / 8u) * per_env <= kLdsBytes;
-            if (!stay_column) lds_bytes = bitmap_lds;
-        } else if ((tune.force_k == 0 || tune.force_k == 8) && n_agents == 32 && layout_fits(n_agents, 8, args, lds_bytes, &block, &Q) &&
-                   args.n_envs % (512u / 4u) == 0 && (tune.force_k == 8 || args.n_envs * 4u >= tune.oct_min_lanes)) {
-            block = 512u;
-            K = 8;
-        } else {
-            if (tune.force_k == 8 || !layout_fits(n_agents, 4, args, lds_bytes, &block, &Q) || Q < 4) return false;
-            block = 512u;
-            if (args.n_envs % (1024u / unsigned(Q)) == 0 && args.n_envs * uint64_t(Q) >= uint64_t(n_cu) * 1024u) block = 1024u;
-            if (args.n_envs % (block / unsigned(Q)) != 0) return false;
-            K = 4;
-        }
-        compact = true;
-    }
-    plan->K = K;
-    plan->Q = Q;
-    plan->form = delta_rows ? 5 : (full_rows_bitmap ? 4 : (bitmap ? (stay_column ? 3 : 2) : (compact ? 1 : 0)));
-    plan->block = block;
-    plan->lds_bytes = lds_bytes;
-    plan->lds_total = lds_bytes + (bitmap ? size_t(block / unsigned(Q)) * bitmap_stride(args.c.n_cells) : 0u);   // (as launch_impl adds them)
-    return true;
-}
-
-// ... under the table policy.  Which of the two table forms: the LDS copy whenever image + bitmaps + policy table fit the CU's LDS
-// at the residency the launch would have without it (blocks per CU: what the image alone allows, but no more than the grid
-// gives every CU); MAPF_TUNE policy_table_lds=0 never, =1 whenever one block's segment fits.  DESIGN.md has the measurements.
-bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutTuning &tune_in, const int n_cu, const size_t table_bytes, LqPlan *plan,
-                           bool *table_lds, uint32_t *table_at) {
-    RolloutTuning tune = tune_in;
-    *table_lds = false;
-    *table_at = 0u;
-    if (args.actions != nullptr || tune.force_k == 8) return false;
-    if (!plan_rollout_lq(n_agents, args, tune, n_cu, plan)) return false;
-    if (plan->K == 8) {                                         // (no table instance with eight agents per lane: four)
-        tune.force_k = 4;
-        if (!plan_rollout_lq(n_agents, args, tune, n_cu, plan)) return false;
-    }
-    if (plan->form != 0 && plan->form != 5) return false;
-    if (plan->K == 4 ? (plan->form == 5 ? plan->Q != 8 : plan->Q > 8) : (plan->K != 2 || plan->Q < 2)) return false;
-    if (plan->block > 512u) {                                   // the table instances are built for 512 threads (delta rows: 64 bitmaps)
-        plan->block = 512u;
-        if (args.n_envs % (512u / unsigned(plan->Q)) != 0) return false;
-        plan->lds_total = plan->lds_bytes + (plan->form == 5 ? size_t(512u / unsigned(plan->Q)) * bitmap_stride(args.c.n_cells) : 0u);
-    }
-    const size_t at16 = (plan->lds_total + 15u) & ~size_t(15), with_table = at16 + ((table_bytes + 15u) & ~size_t(15));
-    const uint64_t grid = args.n_envs / (plan->block / unsigned(plan->Q));
-    uint64_t resident = std::min<uint64_t>(std::min<uint64_t>(kLdsBytes / plan->lds_total, 2048u / plan->block), (grid + uint64_t(n_cu) - 1u) / uint64_t(n_cu));
-    if (resident < 1u) resident = 1u;
-    const bool lds = tune.policy_table_lds == 0 ? false : (tune.policy_table_lds == 1 ? with_table <= kLdsBytes : with_table * resident <= kLdsBytes);
-    if (lds) {
-        *table_lds = true;
-        *table_at = uint32_t(at16);
-        plan->lds_total = with_table;
-    }
-    return true;
-}
-
-// the device's CU count, asked once per device
-static int device_cu_count() {
-    static std::atomic<int> cached[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    int n = cached[dev].load(std::memory_order_relaxed);
-    if (n == 0) {
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cached[dev].store(n, std::memory_order_relaxed);
-    }
-    return n;
-}
-
-// true when a packed layout took the launch (*err = its status); false = not applicable, use the lane-group kernel
-bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy *table) {
-    LqPlan plan;
-    bool table_lds = false;
-    uint32_t table_at = 0u;
-    if (table && args.actions) table = nullptr;
-    if (table ? !plan_rollout_lq_table(n_agents, args, tune, device_cu_count(), table->table_bytes, &plan, &table_lds, &table_at)
-              : !plan_rollout_lq(n_agents, args, tune, device_cu_count(), &plan)) return false;
-    const bool record = args.rec_local != nullptr;
-    const uint32_t A = uint32_t(n_agents);
-    const int K = plan.K, Q = plan.Q, form = plan.form;
-    const unsigned block = plan.block;
-    const size_t lds_bytes = plan.lds_bytes;
-    if (record && !(args.rec_reward && args.rec_prob && args.rec_done && args.rec_collision)) {
-        *err = hipErrorInvalidValue;
-        return true;
-    }
-#define LQ_ARGS Q, form, args, A, block, lds_bytes, stream, table, table_lds, table_at
-    if (K == 8) *err = record ? launch_rollout_lq_k8_r1(LQ_ARGS) : launch_rollout_lq_k8_r0(LQ_ARGS);
-    else if (K == 4) *err = record ? launch_rollout_lq_k4_r1(LQ_ARGS) : launch_rollout_lq_k4_r0(LQ_ARGS);
-    else *err = record ? launch_rollout_lq_k2_r1(LQ_ARGS) : launch_rollout_lq_k2_r0(LQ_ARGS);
-#undef LQ_ARGS
-    return true;
 }
 #endif
 

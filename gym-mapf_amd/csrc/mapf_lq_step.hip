@@ -10,6 +10,8 @@
 // r03_kernel_end_costs.txt (round 3) and r04_step_stamps_65536.txt, r04_step_table_forms.txt, r04_single_step_scaling.txt
 // (round 4: one Philox call per lane, scalar t_dev load, no block barrier, 8-byte table rows) -- DESIGN.md 4.2.
 #include "mapf_lq.hpp"
+#include "mapf_layout.hpp"
+#include "mapf_plan.hpp"
 
 #include <type_traits>
 
@@ -87,10 +89,7 @@ constexpr uint32_t kStepSlipAt = offsetof(TableImage, slip), kStepOutcomeAt = of
 //     1024-thread blocks (two per CU) stages the whole move table into LDS once and walks the batch in chunks of 1024
 //     lanes: the table rows become ds_read_b128 (a quarter of the cost), and the argument block, the LDS image and the
 //     barrier are paid once per block instead of once per chunk.
-#ifndef MAPF_BIG_COLS
-#define MAPF_BIG_COLS 6
-#endif
-constexpr uint32_t kStepMoveAt = 1024, kBigCols = MAPF_BIG_COLS;
+// (kStepMoveAt, kBigCols -- where the BIG form's table starts, its six columns per cell: mapf_layout.hpp)
 // offset of the StepArgs block in the kernel's argument segment: five pointers and four 32-bit scalars precede it
 // (compared with the .args metadata of every compiled instance by tests/test_cabi_and_host.py: a wrong value fails the CPU suite)
 constexpr uint32_t kStepArgsOffset = 5 * 8 + 4 * 4;
@@ -516,180 +515,50 @@ __global__ void __launch_bounds__(BIG ? 1024 : 512) lq_step_kernel(uint16_t *con
 
 }  // namespace
 
+// One instance of the step kernel, launched as the plan says: the forms differ in their template arguments, the dynamic LDS
+// segment and the last argument (the plain step's grid, the resident forms' chunk count) only.
+template <int Q, int K, int BIG>
+static hipError_t launch_step_instance(const StepPlan &plan, const StepArgs &args, uint32_t A, hipStream_t stream) {
+    const bool scen = args.scen != nullptr, term = !args.state_not_terminal;
+    auto kern = scen ? (term ? lq_step_kernel<Q, K, true, true, BIG> : lq_step_kernel<Q, K, true, false, BIG>)
+                     : (term ? lq_step_kernel<Q, K, false, true, BIG> : lq_step_kernel<Q, K, false, false, BIG>);
+    if (plan.lds_bytes > 32u * 1024u) {
+        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), plan.lds_limit)) return e;
+    }
+    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(plan.block), plan.lds_bytes, stream, args.state, args.actions, args.scen, args.slip, args.t_dev,
+                       A | (plan.block << 8), uint32_t(args.t), args.c.seed_lo, args.c.seed_hi, args, plan.n_chunks);
+    return hipGetLastError();
+}
+
 // true when the packed layout took the launch (*err = its status); false = not applicable, use lg_step_kernel
 bool try_launch_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err) {
 #ifndef MAPF_STEP_STAMPS   // (the diagnostic build receives its stamp buffer through `uniforms`)
     if (args.uniforms != nullptr) return false;
 #endif
-    // top_tie: a three-entry list whose last cumulative sum rounds below 1.0 needs a third compare per agent; the packed
-    // sampling does two (as in the packed rollout), so such a table stays with the lane-group kernel
-    if (!tune.quad_lanes || args.c.top_tie) return false;
-    int K = 0;
-    if (tune.force_k != 2 && n_agents % 4 == 0) K = 4;
-    else if (tune.force_k != 4 && n_agents % 2 == 0 && n_agents >= 4) K = 2;
-    else return false;
-    const int Q = n_agents / K;
-    if (Q > 16 || (Q & (Q - 1)) != 0) return false;
-    const uint64_t lanes = args.n_envs * uint64_t(Q);
-    const uint32_t A = uint32_t(n_agents);
+    StepPlan plan;
+    if (!plan_step_lq(n_agents, args, tune, &plan)) return false;
     const bool scen = args.scen != nullptr, term = !args.state_not_terminal;
-    const uint8_t *const no_scen = nullptr;
-    // The BIG form (resident grid, move table in LDS): batches several times what the device holds at once
-    // (profiles/r04_single_step_scaling.txt), a table that leaves room for two 1024-thread blocks per CU.
-    // MAPF_TUNE step_big=0 never, =2 whenever it fits.
-    const size_t big_lds = kStepMoveAt + size_t(args.c.n_cells) * kBigCols * sizeof(MoveEntry);
-    int n_cu = 256, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu = 256;
-    const uint64_t resident_lanes = uint64_t(n_cu) * 2048u;
-    const bool big_fits = K == 4 && Q <= 8 && tune.step_big != 0 && args.n_envs > 0 && args.n_envs % (1024u / unsigned(Q)) == 0 &&
-                          2u * big_lds <= 160u * 1024u;
-    const bool big = big_fits && (tune.step_big == 2 || lanes >= 4u * resident_lanes);
-    // ... with EIGHT agents per lane where the team allows it (8, 16, 32 agents): the large-batch step is bound by its vector
-    // instructions once the gathers are gone, and what a lane does once per env (lane context, flags, outcome row, stores,
-    // the hand-over of the probability product) is then paid for 64 envs per wave instead of 32
-    // (measured, 8 agents: 0.289 against 0.262 at 0.5 M envs, 0.35 / 0.41 / 0.42 at 1 / 2 / 4 M -- this form from TWICE the
-    // device's resident lanes on, the four-agents-per-lane form below from four times)
-    if (big_fits && (tune.step_big == 2 || lanes >= 2u * resident_lanes) && Q >= 2 && args.n_envs % (1024u / unsigned(Q / 2)) == 0 &&
-        tune.force_k != 4) {
-        const int Q8 = Q / 2;
-        const unsigned block = 1024u, n_chunks = unsigned(args.n_envs * uint64_t(Q8) / block), grid = n_chunks < unsigned(n_cu) ? n_chunks : unsigned(n_cu);
-        note_kernel("lq_step_kernel<Q=%d,K=8%s%s,BIG> block=1024 resident grid (packed layout: 8 agents per lane, move table in LDS%s)", Q8,
-                    scen ? ",SCEN" : "", term ? "" : ",NO_TERMINAL", scen ? ", start / goal rows from the scenario table" : "");
-#define MAPF_LQ_BIG8(QQ, SS, TT, SCEN_PTR)                                                                                          \
-        {                                                                                                                           \
-            auto kern = lq_step_kernel<QQ, 8, SS, TT, 1>;                                                                        \
-            if (big_lds > 32u * 1024u) { if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(160u * 1024u - 1024u))) { *err = e; return true; } } \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(block), big_lds, stream, args.state, args.actions, SCEN_PTR, args.slip, args.t_dev, \
-                               A | (block << 8), uint32_t(args.t), args.c.seed_lo, args.c.seed_hi, args, n_chunks);                 \
-        }
-#define MAPF_LQ_BIG8_Q(QQ)                                                                       \
-        if (Q8 == QQ) {                                                                           \
-            if (scen && term) MAPF_LQ_BIG8(QQ, true, true, args.scen)                             \
-            else if (scen) MAPF_LQ_BIG8(QQ, true, false, args.scen)                               \
-            else if (term) MAPF_LQ_BIG8(QQ, false, true, no_scen)                                 \
-            else MAPF_LQ_BIG8(QQ, false, false, no_scen)                                          \
-            *err = hipGetLastError();                                                             \
-            return true;                                                                          \
-        }
-        MAPF_LQ_BIG8_Q(1) MAPF_LQ_BIG8_Q(2) MAPF_LQ_BIG8_Q(4)
-#undef MAPF_LQ_BIG8_Q
-#undef MAPF_LQ_BIG8
-    }
-    // The delta-row forms (BIG == 2, 3): where the 16-byte rows do not fit (64x64 maps) but the 4-byte ones do, from a batch of one
-    // full residency on (65536 envs of 32 agents) -- below that the table copy per block (79 KB through the XCD's L2 for each of
-    // its 32 CUs: 1.8 us in front of the first instruction that needs a row, profiles/r05_step_stamps_c5_share.txt) costs more
-    // than the gathers it replaces: configs[4]'s share of one GPU (16384 envs) runs 4.95 us plain against 5.7-5.9 us.
-    const size_t delta_lds = kStepMoveAt + delta_table_words(args.c.n_cells) * sizeof(uint32_t);
-    if (K == 4 && Q <= 8 && args.mv4 && tune.step_delta != 0 && delta_lds <= 160u * 1024u && args.n_envs > 0 &&
-        (tune.step_delta == 2 || (!big_fits && lanes >= resident_lanes))) {
-        // 32 agents: the occupancy bitmaps of a chunk's envs behind the table -- one block per CU then, so 1024 threads as soon as
-        // every CU gets such a block (measured on configs[4]'s map, profiles/r05_step32_forms.txt: 131072 envs 15.6 us with
-        // bitmaps in 1024-thread blocks, 18.0 without, 21.5 for the plain step; at 65536 envs 512-thread blocks with bitmaps
-        // 11.7, without 10.8, plain 11.9)
-        const size_t per_env = (size_t((args.c.n_cells + 31u) / 32u) * 4u + 15u) & ~size_t(15);
-        const bool bitmaps_1024 = Q == 8 && tune.bitmap_pairs && delta_lds + (1024u / 8u) * per_env <= 160u * 1024u && args.n_envs % (1024u / 8u) == 0 &&
-                                  lanes >= uint64_t(n_cu) * 1024u;
-        unsigned block = (bitmaps_1024 || lanes >= 2u * resident_lanes) ? 1024u : 512u;
-        if (args.n_envs % (block / unsigned(Q)) != 0) block = 512u;
-        bool bitmaps = Q == 8 && tune.bitmap_pairs && delta_lds + (block / 8u) * per_env <= 160u * 1024u;
-        if (!bitmaps && Q == 8 && tune.bitmap_pairs && block == 1024u && delta_lds + (512u / 8u) * per_env <= 160u * 1024u) { block = 512u; bitmaps = true; }
-        const size_t form_lds = delta_lds + (bitmaps ? (block / 8u) * per_env : 0u);
-        if (args.n_envs % (block / unsigned(Q)) == 0) {
-            unsigned per_cu = unsigned((160u * 1024u) / form_lds);
-            if (per_cu > 2048u / block) per_cu = 2048u / block;
-            const unsigned n_chunks = unsigned(lanes / block), grid = n_chunks < per_cu * unsigned(n_cu) ? n_chunks : per_cu * unsigned(n_cu);
-            note_kernel("lq_step_kernel<Q=%d,K=%d%s%s,DELTA%s> block=%u resident grid (packed layout: 4 agents per lane, 4-byte delta rows of the move table in LDS%s%s)", Q, K,
-                        scen ? ",SCEN" : "", term ? "" : ",NO_TERMINAL", bitmaps ? ",BITMAP" : "", block, bitmaps ? ", collisions through per-env occupancy bitmaps" : "",
-                        scen ? ", start / goal rows from the scenario table" : "");
-            if (bitmaps) {   // (Q == 8)
-#define MAPF_LQ_DELTA_BITMAP(SS, TT, SCEN_PTR)                                                                                      \
-                {                                                                                                                   \
-                    auto kern = lq_step_kernel<8, 4, SS, TT, 3>;                                                                    \
-                    if (form_lds > 32u * 1024u) { if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(160u * 1024u))) { *err = e; return true; } } \
-                    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), form_lds, stream, args.state, args.actions, SCEN_PTR, args.slip, args.t_dev, \
-                                       A | (block << 8), uint32_t(args.t), args.c.seed_lo, args.c.seed_hi, args, n_chunks);         \
-                }
-                if (scen && term) MAPF_LQ_DELTA_BITMAP(true, true, args.scen)
-                else if (scen) MAPF_LQ_DELTA_BITMAP(true, false, args.scen)
-                else if (term) MAPF_LQ_DELTA_BITMAP(false, true, no_scen)
-                else MAPF_LQ_DELTA_BITMAP(false, false, no_scen)
-#undef MAPF_LQ_DELTA_BITMAP
-                *err = hipGetLastError();
-                return true;
-            }
-#define MAPF_LQ_DELTA(QQ, SS, TT, SCEN_PTR)                                                                                         \
-            {                                                                                                                       \
-                auto kern = lq_step_kernel<QQ, 4, SS, TT, 2>;                                                                       \
-                if (delta_lds > 32u * 1024u) { if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(160u * 1024u))) { *err = e; return true; } } \
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(block), delta_lds, stream, args.state, args.actions, SCEN_PTR, args.slip, args.t_dev, \
-                                   A | (block << 8), uint32_t(args.t), args.c.seed_lo, args.c.seed_hi, args, n_chunks);             \
-            }
-#define MAPF_LQ_DELTA_Q(QQ)                                                                      \
-            if (Q == QQ) {                                                                        \
-                if (scen && term) MAPF_LQ_DELTA(QQ, true, true, args.scen)                        \
-                else if (scen) MAPF_LQ_DELTA(QQ, true, false, args.scen)                          \
-                else if (term) MAPF_LQ_DELTA(QQ, false, true, no_scen)                            \
-                else MAPF_LQ_DELTA(QQ, false, false, no_scen)                                     \
-                *err = hipGetLastError();                                                         \
-                return true;                                                                      \
-            }
-            MAPF_LQ_DELTA_Q(1) MAPF_LQ_DELTA_Q(2) MAPF_LQ_DELTA_Q(4) MAPF_LQ_DELTA_Q(8)
-#undef MAPF_LQ_DELTA_Q
-#undef MAPF_LQ_DELTA
-        }
-    }
-    if (big) {
-        const unsigned block = 1024u, n_chunks = unsigned(lanes / block), grid = n_chunks < 2u * unsigned(n_cu) ? n_chunks : 2u * unsigned(n_cu);
-        note_kernel("lq_step_kernel<Q=%d,K=%d%s%s,BIG> block=1024 resident grid (packed layout: 4 agents per lane, move table in LDS%s)", Q, K,
-                    scen ? ",SCEN" : "", term ? "" : ",NO_TERMINAL", scen ? ", start / goal rows from the scenario table" : "");
-#define MAPF_LQ_BIG(QQ, SS, TT, SCEN_PTR)                                                                                           \
-        {                                                                                                                           \
-            auto kern = lq_step_kernel<QQ, 4, SS, TT, 1>;                                                                        \
-            if (big_lds > 32u * 1024u) { if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(160u * 1024u - 1024u))) { *err = e; return true; } } \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(block), big_lds, stream, args.state, args.actions, SCEN_PTR, args.slip, args.t_dev, \
-                               A | (block << 8), uint32_t(args.t), args.c.seed_lo, args.c.seed_hi, args, n_chunks);                 \
-        }
-#define MAPF_LQ_BIG_Q(QQ)                                                                        \
-        if (Q == QQ) {                                                                            \
-            if (scen && term) MAPF_LQ_BIG(QQ, true, true, args.scen)                              \
-            else if (scen) MAPF_LQ_BIG(QQ, true, false, args.scen)                                \
-            else if (term) MAPF_LQ_BIG(QQ, false, true, no_scen)                                  \
-            else MAPF_LQ_BIG(QQ, false, false, no_scen)                                           \
-            *err = hipGetLastError();                                                             \
-            return true;                                                                          \
-        }
-        MAPF_LQ_BIG_Q(1) MAPF_LQ_BIG_Q(2) MAPF_LQ_BIG_Q(4) MAPF_LQ_BIG_Q(8)
-#undef MAPF_LQ_BIG_Q
-#undef MAPF_LQ_BIG
-    }
-    unsigned block = 256u;
-    while (block > 64u && lanes < 256u * uint64_t(block)) block /= 2u;   // small batches: spread over the CUs
-    // from two 256-thread blocks per CU on, four 128-thread blocks measure 3 % faster (65536 and 131072 envs of 8 agents: 3.22
-    // against 3.33 us, 4.45 against 4.60; equal at 262144; at ONE block per CU -- 32768 envs -- 256 threads are 1 % ahead)
-    if (lanes >= 512u * 256u) block = 128u;
-    if (tune.step_block == 64u || tune.step_block == 128u || tune.step_block == 256u || tune.step_block == 512u) block = tune.step_block;
-    const uint64_t per_block = block / unsigned(Q);
-    if (args.n_envs == 0 || args.n_envs % per_block != 0) return false;
-    const unsigned grid = unsigned(args.n_envs / per_block);
-    note_kernel("lq_step_kernel<Q=%d,K=%d%s%s> block=%u (packed layout: %d agents per lane%s)", Q, K, scen ? ",SCEN" : "",
-                term ? "" : ",NO_TERMINAL", block, K, scen ? ", start / goal rows from the scenario table" : "");
-#define MAPF_LQ_LAUNCH(QQ, KK, SS, TT, SCEN_PTR)                                                                                   \
-    hipLaunchKernelGGL((lq_step_kernel<QQ, KK, SS, TT>), dim3(grid), dim3(block), 0, stream, args.state, args.actions, SCEN_PTR,       \
-                       args.slip, args.t_dev, A | (block << 8), uint32_t(args.t), args.c.seed_lo, args.c.seed_hi, args, grid)
-#define MAPF_LQ_STEP(QQ, KK)                                                                                   \
-    if (Q == QQ && K == KK) {                                                                                  \
-        if (scen && term) MAPF_LQ_LAUNCH(QQ, KK, true, true, args.scen);                                       \
-        else if (scen) MAPF_LQ_LAUNCH(QQ, KK, true, false, args.scen);                                         \
-        else if (term) MAPF_LQ_LAUNCH(QQ, KK, false, true, no_scen);                                           \
-        else MAPF_LQ_LAUNCH(QQ, KK, false, false, no_scen);                                                    \
-        *err = hipGetLastError();                                                                              \
-        return true;                                                                                           \
-    }
-    MAPF_LQ_STEP(1, 4) MAPF_LQ_STEP(2, 4) MAPF_LQ_STEP(4, 4) MAPF_LQ_STEP(8, 4) MAPF_LQ_STEP(16, 4)
-    MAPF_LQ_STEP(2, 2) MAPF_LQ_STEP(4, 2) MAPF_LQ_STEP(8, 2) MAPF_LQ_STEP(16, 2)
-#undef MAPF_LQ_STEP
-#undef MAPF_LQ_LAUNCH
-    return false;
+    const char *const scen_tag = scen ? ",SCEN" : "", *const term_tag = term ? "" : ",NO_TERMINAL",
+               *const scen_note = scen ? ", start / goal rows from the scenario table" : "";
+    const int Q = plan.Q, K = plan.K;
+    if (plan.big == 1)
+        note_kernel("lq_step_kernel<Q=%d,K=%d%s%s,BIG> block=1024 resident grid (packed layout: %d agents per lane, move table in LDS%s)", Q, K, scen_tag, term_tag, K, scen_note);
+    else if (plan.big >= 2)
+        note_kernel("lq_step_kernel<Q=%d,K=%d%s%s,DELTA%s> block=%u resident grid (packed layout: 4 agents per lane, 4-byte delta rows of the move table in LDS%s%s)", Q, K,
+                    scen_tag, term_tag, plan.big == 3 ? ",BITMAP" : "", plan.block, plan.big == 3 ? ", collisions through per-env occupancy bitmaps" : "", scen_note);
+    else
+        note_kernel("lq_step_kernel<Q=%d,K=%d%s%s> block=%u (packed layout: %d agents per lane%s)", Q, K, scen_tag, term_tag, plan.block, K, scen_note);
+    // the instances that exist, in the order plan_step_lq tries their forms
+#define X(QQ, KK, BB) if (Q == QQ && K == KK && plan.big == BB) { *err = launch_step_instance<QQ, KK, BB>(plan, args, uint32_t(n_agents), stream); return true; }
+    X(1, 8, 1) X(2, 8, 1) X(4, 8, 1)
+    X(8, 4, 3)
+    X(1, 4, 2) X(2, 4, 2) X(4, 4, 2) X(8, 4, 2)
+    X(1, 4, 1) X(2, 4, 1) X(4, 4, 1) X(8, 4, 1)
+    X(1, 4, 0) X(2, 4, 0) X(4, 4, 0) X(8, 4, 0) X(16, 4, 0)
+    X(2, 2, 0) X(4, 2, 0) X(8, 2, 0) X(16, 2, 0)
+#undef X
+    *err = hipErrorInvalidValue;   // (plan_step_lq plans no other instance)
+    return true;
 }
 
 }  // namespace mapf

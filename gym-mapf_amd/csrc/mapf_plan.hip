@@ -1,0 +1,283 @@
+// Launch planning of the packed kernels (mapf_plan.hpp): host-only integer arithmetic, no kernel and no runtime call.
+#include "mapf_plan.hpp"
+#include "mapf_layout.hpp"
+
+#include <algorithm>
+#include <cstdlib>
+#include <string>
+
+namespace mapf {
+
+// Defaults of the layout choices: a move table is staged into LDS while two blocks per CU still fit (a table that
+// allows only one block per CU starves the SIMDs of waves); four agents per lane need one wave on every SIMD.
+// ONE override: the environment variable MAPF_TUNE, "key=value,key=value,...", read by default_rollout_tuning (mapf_dispatch.hip) at handle creation, so a process
+// can hold handles with different settings (the tests and the A/B tools do).  Keys (include/mapf_hip.h documents them):
+//   quad_lanes, k, quad_min_lanes, oct_min_lanes, mv_lds_max_bytes, scen_table, bitmap_pairs, bitmap_block, bitmap_staycol,
+//   bitmap_delta, step_big, step_block, step_delta, policy_table_lds.
+// An unknown key or a malformed item is an error (*err names it): a typo must not silently measure the default.
+RolloutTuning rollout_tuning_for(int n_cu, const char *text, std::string *err) {
+    RolloutTuning t;
+    t.n_cu = n_cu;
+    // measured on 8 agents x 32768 envs (one wave per SIMD with four agents per lane, two with two): 517 G vs 467 G
+    // agent-steps/s -- fewer, fatter waves win as long as no SIMD stays empty
+    t.quad_min_lanes = uint64_t(n_cu) * 4u * 64u;        // CUs x SIMDs x lanes
+    t.oct_min_lanes = uint64_t(n_cu) * 4u * 64u * 2u;    // (eight agents per lane: see plan_rollout_lq)
+    t.mv_lds_max_bytes = (kLdsBytes - kLdsReserve) / 2;
+    if (!text) return t;
+    std::string items(text);
+    size_t pos = 0;
+    while (pos <= items.size()) {
+        size_t end = items.find(',', pos);
+        if (end == std::string::npos) end = items.size();
+        const std::string item = items.substr(pos, end - pos);
+        pos = end + 1;
+        if (item.empty()) continue;
+        const size_t eq = item.find('=');
+        char *rest = nullptr;
+        const std::string key = item.substr(0, eq), val = eq == std::string::npos ? "" : item.substr(eq + 1);
+        const unsigned long long v = val.empty() ? 0 : strtoull(val.c_str(), &rest, 10);
+        if (eq == std::string::npos || val.empty() || (rest && *rest)) { if (err) *err = "MAPF_TUNE: malformed item '" + item + "' (want key=integer)"; return t; }
+        if (key == "quad_lanes") t.quad_lanes = v != 0;
+        else if (key == "k") t.force_k = int(v);
+        else if (key == "quad_min_lanes") t.quad_min_lanes = v;
+        else if (key == "oct_min_lanes") t.oct_min_lanes = v;
+        else if (key == "mv_lds_max_bytes") t.mv_lds_max_bytes = size_t(v);
+        else if (key == "scen_table") t.scen_table = v != 0;
+        else if (key == "bitmap_pairs") t.bitmap_pairs = v != 0;
+        else if (key == "bitmap_block") t.bitmap_block = unsigned(v);
+        else if (key == "bitmap_staycol") t.bitmap_stay_column = v != 0;
+        else if (key == "bitmap_delta") t.bitmap_delta_rows = v != 0;
+        else if (key == "step_big") t.step_big = int(v);
+        else if (key == "step_block") t.step_block = unsigned(v);
+        else if (key == "step_delta") t.step_delta = int(v);
+        else if (key == "policy_table_lds") t.policy_table_lds = v != 0 ? 1 : 0;
+        else { if (err) *err = "MAPF_TUNE: unknown key '" + key + "'"; return t; }
+    }
+    return t;
+}
+
+// does the K-agents-per-lane form apply to this launch?  (full groups, power-of-two group size, full blocks)
+static bool layout_fits(int n_agents, int K, const RolloutArgs &args, size_t lds_bytes, unsigned *block_out, int *q_out) {
+    if (n_agents < K || n_agents % K != 0) return false;
+    const int Q = n_agents / K;
+    if (Q > 16 || (Q & (Q - 1)) != 0 || (K == 2 && Q < 2) || (K == 8 && Q > 4)) return false;
+    const size_t copies = kLdsBytes / lds_bytes;   // blocks per CU by LDS
+    unsigned block = copies >= 4 ? 256u : 512u;
+    // a small batch is spread over the CUs in smaller blocks (down to one wave): every block stages its own table copy,
+    // which is cheap next to a rollout's steps, and an idle CU is not
+    const uint64_t lanes = args.n_envs * uint64_t(Q);
+    while (block > 64u && lanes < 256u * uint64_t(block)) block /= 2u;
+    const uint64_t per_block = block / unsigned(Q);
+    if (args.n_envs % per_block != 0 || lanes < 64 * 16) return false;
+    *block_out = block;
+    *q_out = Q;
+    return true;
+}
+
+// the dispatch decision (see LqPlan): which packed form, block size and LDS image a launch of this shape takes
+bool plan_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, LqPlan *plan) {
+    const int n_cu = tune.n_cu;
+    // top_tie: a three-entry list whose last cumulative sum rounds below 1.0 needs a third compare per agent (hi = 65535);
+    // the packed sampling does two, so such a table (none arises from fail_prob / 2 splits) stays with the lane-group kernel
+    if (!tune.quad_lanes || args.c.top_tie || args.n_steps > 65535u) return false;   // (per-launch counts are 16-bit)
+    unsigned block = 0;
+    int Q = 0, K = 0;
+    bool compact = false, bitmap = false, stay_column = false, full_rows_bitmap = false, delta_rows = false;
+    size_t lds_bytes = kMoveAt + size_t(args.c.n_cells) * kMoveCols * sizeof(MoveEntry);   // the kernel's whole LDS image
+    if (lds_bytes <= tune.mv_lds_max_bytes && lds_bytes <= kLdsBytes - kLdsReserve) {
+        // Four agents per lane halve the waves: that form needs tune.quad_min_lanes lanes (default: enough to put one
+        // wave on every SIMD); below that the two-agents-per-lane form of the same kernel runs.
+        // Eight agents per lane halve them again (at 8 agents nothing crosses lanes any more): worth it from two waves
+        // per SIMD of THAT form on, i.e. 131072 envs at 8 agents.
+        // 32 agents: four per lane with the occupancy bitmaps behind the full table (O(A) collision tests, see below) wherever that
+        // form applies -- 496 agent pairs per env are most of either all-pairs form's step
+        if (tune.bitmap_pairs && n_agents == 32 && (tune.force_k == 0 || tune.force_k == 4) && layout_fits(n_agents, 4, args, lds_bytes, &block, &Q) &&
+            lds_bytes + (block / 8u) * bitmap_stride(args.c.n_cells) <= kLdsBytes &&
+            (tune.force_k == 4 || args.n_envs * uint64_t(Q) >= tune.quad_min_lanes)) {
+            K = 4;
+            bitmap = true;
+            full_rows_bitmap = true;
+        } else
+        if ((tune.force_k == 0 || tune.force_k == 8) && layout_fits(n_agents, 8, args, lds_bytes, &block, &Q) &&
+            (tune.force_k == 8 || args.n_envs * uint64_t(Q) >= tune.oct_min_lanes) && block <= 512u) K = 8;
+        else if (tune.force_k != 2 && tune.force_k != 8 && layout_fits(n_agents, 4, args, lds_bytes, &block, &Q) &&
+                 (tune.force_k == 4 || args.n_envs * uint64_t(Q) >= tune.quad_min_lanes)) K = 4;
+        else if (tune.force_k != 4 && tune.force_k != 8 && layout_fits(n_agents, 2, args, lds_bytes, &block, &Q)) K = 2;
+        else return false;
+    } else {
+        // the full table is too large: 8-byte rows, one block per CU (512 threads = two waves per SIMD; 1024 when the
+        // batch gives every CU a block of that size), four agents per lane, group sizes 4 / 8 / 16 only
+        lds_bytes = kMoveAt + size_t(args.c.n_cells) * kCompactCols * kCompactEntry;
+        if (tune.mv_lds_max_bytes == 0 || lds_bytes > kLdsBytes - kLdsReserve) return false;
+        const size_t bitmap_lds = kMoveAt + size_t(args.c.n_cells) * kBitmapCols * kCompactEntry;   // (no STAY column in that form)
+        // 32 agents: four per lane, collisions through per-env occupancy bitmaps behind the table (one bit per cell) -- O(A)
+        // instead of 496 pair tests per env.  64 envs per 512-thread block; 128 per 1024-thread block (four waves per SIMD)
+        // once the batch gives every CU a block of that size and 128 bitmaps fit (C5's share of one GPU: 481 G against 377 G
+        // for the all-pairs form; C5 whole: profiles/r04_c5_one_bit_bitmap_ab.txt).  MAPF_TUNE k=8 / bitmap_pairs=0 keep the
+        // all-pairs forms reachable (eight agents per lane, Q = 4, one 512-thread block per CU; four per lane below).
+        const size_t per_env = bitmap_stride(args.c.n_cells);
+        unsigned bitmap_block = 512u;
+        if (tune.bitmap_block == 1024u || (tune.bitmap_block == 0u && args.n_envs * 8u >= uint64_t(n_cu) * 1024u)) bitmap_block = 1024u;
+        if (bitmap_block == 1024u && (args.n_envs % (1024u / 8u) != 0 || bitmap_lds + (1024u / 8u) * per_env > kLdsBytes)) bitmap_block = 512u;
+        if (args.actions == nullptr) bitmap_block = 512u;           // (in-kernel policy behind 8-byte rows: that instance is built for 512 threads)
+        // ... behind 4-byte delta rows where the map's ids allow them (six columns in 79 KB on the 64x64 maps: 128 bitmaps fit, no
+        // STAY row to make up, one-instruction action clamp)
+        const size_t delta_lds = kMoveAt + delta_table_words(args.c.n_cells) * kDeltaEntry;   // (the host-built image, zero-padded to 16 bytes)
+        unsigned delta_block = (tune.bitmap_block == 1024u || (tune.bitmap_block == 0u && args.n_envs * 8u >= uint64_t(n_cu) * 1024u)) ? 1024u : 512u;
+        if (delta_block == 1024u && (args.n_envs % (1024u / 8u) != 0 || delta_lds + (1024u / 8u) * per_env > kLdsBytes)) delta_block = 512u;
+        if (tune.bitmap_pairs && tune.bitmap_delta_rows && args.mv_delta8 && args.mv4 && n_agents == 32 && tune.force_k != 8 && tune.force_k != 2 &&
+            layout_fits(n_agents, 4, args, delta_lds, &block, &Q) && args.n_envs % (delta_block / 8u) == 0 &&
+            delta_lds + (delta_block / 8u) * per_env <= kLdsBytes) {
+            block = delta_block;
+            K = 4;
+            bitmap = true;
+            delta_rows = true;
+            lds_bytes = delta_lds;
+        } else
+        if (tune.bitmap_pairs && n_agents == 32 && tune.force_k != 8 && tune.force_k != 2 && layout_fits(n_agents, 4, args, bitmap_lds, &block, &Q) &&
+            args.n_envs % (bitmap_block / 8u) == 0 && bitmap_lds + (bitmap_block / 8u) * per_env <= kLdsBytes) {
+            block = bitmap_block;
+            K = 4;
+            bitmap = true;
+            // where the five-column table (STAY included: four selects per agent-step less) still leaves room for the block's
+            // bitmaps -- 64 of them on the 64x64 maps, not 128 -- it is the one staged (C5's share: profiles/r04_c5_stay_column_ab.txt)
+            stay_column = tune.bitmap_stay_column && lds_bytes + (bitmap_block / 8u) * per_env <= kLdsBytes;
+            if (!stay_column) lds_bytes = bitmap_lds;
+        } else if ((tune.force_k == 0 || tune.force_k == 8) && n_agents == 32 && layout_fits(n_agents, 8, args, lds_bytes, &block, &Q) &&
+                   args.n_envs % (512u / 4u) == 0 && (tune.force_k == 8 || args.n_envs * 4u >= tune.oct_min_lanes)) {
+            block = 512u;
+            K = 8;
+        } else {
+            if (tune.force_k == 8 || !layout_fits(n_agents, 4, args, lds_bytes, &block, &Q) || Q < 4) return false;
+            block = 512u;
+            if (args.n_envs % (1024u / unsigned(Q)) == 0 && args.n_envs * uint64_t(Q) >= uint64_t(n_cu) * 1024u) block = 1024u;
+            if (args.n_envs % (block / unsigned(Q)) != 0) return false;
+            K = 4;
+        }
+        compact = true;
+    }
+    plan->K = K;
+    plan->Q = Q;
+    plan->form = delta_rows ? 5 : (full_rows_bitmap ? 4 : (bitmap ? (stay_column ? 3 : 2) : (compact ? 1 : 0)));
+    plan->block = block;
+    plan->lds_bytes = lds_bytes;
+    plan->lds_total = lds_bytes + (bitmap ? size_t(block / unsigned(Q)) * bitmap_stride(args.c.n_cells) : 0u);   // (as launch_impl adds them)
+    return true;
+}
+
+// ... under the table policy.  Which of the two table forms: the LDS copy whenever image + bitmaps + policy table fit the CU's LDS
+// at the residency the launch would have without it (blocks per CU: what the image alone allows, but no more than the grid
+// gives every CU); MAPF_TUNE policy_table_lds=0 never, =1 whenever one block's segment fits.  DESIGN.md has the measurements.
+bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutTuning &tune_in, const size_t table_bytes, LqPlan *plan,
+                           bool *table_lds, uint32_t *table_at) {
+    RolloutTuning tune = tune_in;
+    const int n_cu = tune.n_cu;
+    *table_lds = false;
+    *table_at = 0u;
+    if (args.actions != nullptr || tune.force_k == 8) return false;
+    if (!plan_rollout_lq(n_agents, args, tune, plan)) return false;
+    if (plan->K == 8) {                                         // (no table instance with eight agents per lane: four)
+        tune.force_k = 4;
+        if (!plan_rollout_lq(n_agents, args, tune, plan)) return false;
+    }
+    if (plan->form != 0 && plan->form != 5) return false;
+    if (plan->K == 4 ? (plan->form == 5 ? plan->Q != 8 : plan->Q > 8) : (plan->K != 2 || plan->Q < 2)) return false;
+    if (plan->block > 512u) {                                   // the table instances are built for 512 threads (delta rows: 64 bitmaps)
+        plan->block = 512u;
+        if (args.n_envs % (512u / unsigned(plan->Q)) != 0) return false;
+        plan->lds_total = plan->lds_bytes + (plan->form == 5 ? size_t(512u / unsigned(plan->Q)) * bitmap_stride(args.c.n_cells) : 0u);
+    }
+    const size_t at16 = (plan->lds_total + 15u) & ~size_t(15), with_table = at16 + ((table_bytes + 15u) & ~size_t(15));
+    const uint64_t grid = args.n_envs / (plan->block / unsigned(plan->Q));
+    uint64_t resident = std::min<uint64_t>(std::min<uint64_t>(kLdsBytes / plan->lds_total, 2048u / plan->block), (grid + uint64_t(n_cu) - 1u) / uint64_t(n_cu));
+    if (resident < 1u) resident = 1u;
+    const bool lds = tune.policy_table_lds == 0 ? false : (tune.policy_table_lds == 1 ? with_table <= kLdsBytes : with_table * resident <= kLdsBytes);
+    if (lds) {
+        *table_lds = true;
+        *table_at = uint32_t(at16);
+        plan->lds_total = with_table;
+    }
+    return true;
+}
+
+// The packed single step (mapf_lq_step.hip): full groups of K = 4 or 2 agents per lane, Q = A / K lanes per env a power of two.
+// The forms are tried in this order, and a form whose divisibility test fails falls through to the next one: eight agents per
+// lane over the LDS table, delta rows (with or without bitmaps), BIG, the plain step.  false = not applicable, use lg_step_kernel.
+bool plan_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, StepPlan *plan) {
+    // top_tie: a three-entry list whose last cumulative sum rounds below 1.0 needs a third compare per agent; the packed
+    // sampling does two (as in the packed rollout), so such a table stays with the lane-group kernel
+    if (!tune.quad_lanes || args.c.top_tie) return false;
+    int K = 0;
+    if (tune.force_k != 2 && n_agents % 4 == 0) K = 4;
+    else if (tune.force_k != 4 && n_agents % 2 == 0 && n_agents >= 4) K = 2;
+    else return false;
+    const int Q = n_agents / K;
+    if (Q > 16 || (Q & (Q - 1)) != 0) return false;
+    const uint64_t lanes = args.n_envs * uint64_t(Q);
+    // The BIG form (resident grid, move table in LDS): batches several times what the device holds at once
+    // (profiles/r04_single_step_scaling.txt), a table that leaves room for two 1024-thread blocks per CU.
+    // MAPF_TUNE step_big=0 never, =2 whenever it fits.
+    const size_t big_lds = kStepMoveAt + size_t(args.c.n_cells) * kBigCols * sizeof(MoveEntry);
+    const int n_cu = tune.n_cu;
+    const uint64_t resident_lanes = uint64_t(n_cu) * 2048u;
+    const bool big_fits = K == 4 && Q <= 8 && tune.step_big != 0 && args.n_envs > 0 && args.n_envs % (1024u / unsigned(Q)) == 0 &&
+                          2u * big_lds <= kLdsBytes;
+    const bool big = big_fits && (tune.step_big == 2 || lanes >= 4u * resident_lanes);
+    // ... with EIGHT agents per lane where the team allows it (8, 16, 32 agents): the large-batch step is bound by its vector
+    // instructions once the gathers are gone, and what a lane does once per env (lane context, flags, outcome row, stores,
+    // the hand-over of the probability product) is then paid for 64 envs per wave instead of 32
+    // (measured, 8 agents: 0.289 against 0.262 at 0.5 M envs, 0.35 / 0.41 / 0.42 at 1 / 2 / 4 M -- this form from TWICE the
+    // device's resident lanes on, the four-agents-per-lane form below from four times)
+    if (big_fits && (tune.step_big == 2 || lanes >= 2u * resident_lanes) && Q >= 2 && args.n_envs % (1024u / unsigned(Q / 2)) == 0 &&
+        tune.force_k != 4) {
+        const int Q8 = Q / 2;
+        const unsigned block = 1024u, n_chunks = unsigned(args.n_envs * uint64_t(Q8) / block), grid = n_chunks < unsigned(n_cu) ? n_chunks : unsigned(n_cu);
+        *plan = StepPlan{8, Q8, 1, block, grid, n_chunks, big_lds, int(kLdsBytes - kLdsReserve)};
+        return true;
+    }
+    // The delta-row forms (BIG == 2, 3): where the 16-byte rows do not fit (64x64 maps) but the 4-byte ones do, from a batch of one
+    // full residency on (65536 envs of 32 agents) -- below that the table copy per block (79 KB through the XCD's L2 for each of
+    // its 32 CUs: 1.8 us in front of the first instruction that needs a row, profiles/r05_step_stamps_c5_share.txt) costs more
+    // than the gathers it replaces: configs[4]'s share of one GPU (16384 envs) runs 4.95 us plain against 5.7-5.9 us.
+    const size_t delta_lds = kStepMoveAt + delta_table_words(args.c.n_cells) * sizeof(uint32_t);
+    if (K == 4 && Q <= 8 && args.mv4 && tune.step_delta != 0 && delta_lds <= kLdsBytes && args.n_envs > 0 &&
+        (tune.step_delta == 2 || (!big_fits && lanes >= resident_lanes))) {
+        // 32 agents: the occupancy bitmaps of a chunk's envs behind the table -- one block per CU then, so 1024 threads as soon as
+        // every CU gets such a block (measured on configs[4]'s map, profiles/r05_step32_forms.txt: 131072 envs 15.6 us with
+        // bitmaps in 1024-thread blocks, 18.0 without, 21.5 for the plain step; at 65536 envs 512-thread blocks with bitmaps
+        // 11.7, without 10.8, plain 11.9)
+        const size_t per_env = bitmap_stride(args.c.n_cells);
+        const bool bitmaps_1024 = Q == 8 && tune.bitmap_pairs && delta_lds + (1024u / 8u) * per_env <= kLdsBytes && args.n_envs % (1024u / 8u) == 0 &&
+                                  lanes >= uint64_t(n_cu) * 1024u;
+        unsigned block = (bitmaps_1024 || lanes >= 2u * resident_lanes) ? 1024u : 512u;
+        if (args.n_envs % (block / unsigned(Q)) != 0) block = 512u;
+        bool bitmaps = Q == 8 && tune.bitmap_pairs && delta_lds + (block / 8u) * per_env <= kLdsBytes;
+        if (!bitmaps && Q == 8 && tune.bitmap_pairs && block == 1024u && delta_lds + (512u / 8u) * per_env <= kLdsBytes) { block = 512u; bitmaps = true; }
+        const size_t form_lds = delta_lds + (bitmaps ? (block / 8u) * per_env : 0u);
+        if (args.n_envs % (block / unsigned(Q)) == 0) {
+            unsigned per_cu = unsigned(kLdsBytes / form_lds);
+            if (per_cu > 2048u / block) per_cu = 2048u / block;
+            const unsigned n_chunks = unsigned(lanes / block), grid = n_chunks < per_cu * unsigned(n_cu) ? n_chunks : per_cu * unsigned(n_cu);
+            *plan = StepPlan{K, Q, bitmaps ? 3 : 2, block, grid, n_chunks, form_lds, int(kLdsBytes)};
+            return true;
+        }
+    }
+    if (big) {
+        const unsigned block = 1024u, n_chunks = unsigned(lanes / block), grid = n_chunks < 2u * unsigned(n_cu) ? n_chunks : 2u * unsigned(n_cu);
+        *plan = StepPlan{K, Q, 1, block, grid, n_chunks, big_lds, int(kLdsBytes - kLdsReserve)};
+        return true;
+    }
+    unsigned block = 256u;
+    while (block > 64u && lanes < 256u * uint64_t(block)) block /= 2u;   // small batches: spread over the CUs
+    // from two 256-thread blocks per CU on, four 128-thread blocks measure 3 % faster (65536 and 131072 envs of 8 agents: 3.22
+    // against 3.33 us, 4.45 against 4.60; equal at 262144; at ONE block per CU -- 32768 envs -- 256 threads are 1 % ahead)
+    if (lanes >= 512u * 256u) block = 128u;
+    if (tune.step_block == 64u || tune.step_block == 128u || tune.step_block == 256u || tune.step_block == 512u) block = tune.step_block;
+    const uint64_t per_block = block / unsigned(Q);
+    if (args.n_envs == 0 || args.n_envs % per_block != 0) return false;
+    const unsigned grid = unsigned(args.n_envs / per_block);
+    *plan = StepPlan{K, Q, 0, block, grid, grid, 0, 0};
+    return true;
+}
+
+}  // namespace mapf

@@ -1,0 +1,96 @@
+// Test shim (tests/test_host_tables.py): a C face on the host-only units of the library -- the table builders
+// (mapf_tables.hip) and the launch planner (mapf_plan.hip) -- so that they can be driven through ctypes without a
+// device.  Test code, compiled into the test's tmp dir; not part of libmapf_hip.so.
+#include "mapf_plan.hpp"
+#include "mapf_tables.hpp"
+
+#include <cstdio>
+#include <cstring>
+
+using namespace mapf;
+
+extern "C" {
+
+// [0] kMvCols, [1] kDeltaCols, [2] kDeltaRowBias, [3] sizeof(SlipRow), [4] sizeof(OutcomeRow), [5] delta_table_words(V)
+void shim_sizes(uint32_t V, uint64_t out[6]) {
+    out[0] = kMvCols; out[1] = kDeltaCols; out[2] = kDeltaRowBias; out[3] = sizeof(SlipRow); out[4] = sizeof(OutcomeRow);
+    out[5] = delta_table_words(V);
+}
+
+// rows: 8 SlipRows; consts: p_cand[3]; flags: need_rng, top_tie.  1 = built, 0 = refused
+int shim_slip_tables(double fail_prob, void *rows, double *p_cand, uint32_t *flags) {
+    SlipRow slip[8];
+    EnvConsts c{};
+    std::string err;
+    if (!build_slip_tables(fail_prob, slip, &c, &err)) return 0;
+    std::memcpy(rows, slip, sizeof(slip));
+    std::memcpy(p_cand, c.p_cand, sizeof(c.p_cand));
+    flags[0] = c.need_rng; flags[1] = c.top_tie;
+    return 1;
+}
+
+void shim_outcome_rows(double r_clash, double r_goal, double r_living, void *rows) {
+    EnvConsts c{};
+    c.r_clash = r_clash; c.r_goal = r_goal; c.r_living = r_living;
+    OutcomeRow out[16];
+    build_outcome_rows(c, out);
+    std::memcpy(rows, out, sizeof(out));
+}
+
+uint32_t shim_outcome_status(uint32_t f) { return outcome_status(f); }
+
+// mv: u32[V * kMvCols * 4], mv8: u32[V * kMvCols * 2], mv4: u32[delta_table_words(V)] (written only when the result is 1)
+int shim_move_tables(const uint16_t *nbr, uint32_t V, double fail_prob, uint32_t *mv, uint32_t *mv8, uint32_t *mv4) {
+    SlipRow slip[8];
+    EnvConsts c{};
+    std::string err;
+    if (!build_slip_tables(fail_prob, slip, &c, &err)) return -1;
+    const MoveTables t = build_move_tables(nbr, V, fail_prob, slip);
+    if (t.mv.size() != size_t(V) * kMvCols || t.mv8.size() != t.mv.size() || t.mv4.size() != (t.delta8 ? delta_table_words(V) : 0u)) return -2;
+    std::memcpy(mv, t.mv.data(), t.mv.size() * sizeof(MoveEntry));
+    std::memcpy(mv8, t.mv8.data(), t.mv8.size() * sizeof(CompactEntry));
+    if (t.delta8) std::memcpy(mv4, t.mv4.data(), t.mv4.size() * sizeof(uint32_t));
+    return t.delta8 ? 1 : 0;
+}
+
+// scen: u8[E], rows: u16[256 * 2 * A]; returns the number of pairs (0 = no table)
+uint32_t shim_scen_table(const uint16_t *start, int start_broadcast, const uint16_t *goal, int goal_broadcast, uint64_t E, uint32_t A, uint8_t *scen,
+                         uint16_t *rows) {
+    const ScenTable t = build_scen_table(start, start_broadcast != 0, goal, goal_broadcast != 0, E, A);
+    if (t.n == 0) return (t.scen.empty() && t.rows.empty()) ? 0u : ~0u;
+    if (t.scen.size() != E || t.rows.size() != size_t(t.n) * 2 * A || t.n > 256u) return ~0u;
+    std::memcpy(scen, t.scen.data(), t.scen.size());
+    std::memcpy(rows, t.rows.data(), t.rows.size() * sizeof(uint16_t));
+    return t.n;
+}
+
+// cells: u32[V * 2] (cell_rc, nine 3-bit actions); 1 = built, 0 = refused (err receives the text)
+int shim_greedy_cells(const uint16_t *nbr, uint32_t V, const uint32_t *cell_rc, uint32_t *cells, char *err, size_t err_cap) {
+    std::vector<uint2> out;
+    std::string why;
+    if (!build_greedy_cells(nbr, V, cell_rc, &out, &why)) {
+        std::snprintf(err, err_cap, "%s", why.c_str());
+        return 0;
+    }
+    std::memcpy(cells, out.data(), out.size() * sizeof(uint2));
+    return 1;
+}
+
+// plan_step_lq over a shape: out = K, Q, big, block, grid, n_chunks, lds_bytes, lds_limit; 1 = a packed form, 0 = none, -1 = bad tune
+int shim_plan_step(uint32_t n_cells, int n_agents, uint64_t n_envs, int has_delta_rows, int n_cu, const char *tune, uint64_t out[8]) {
+    std::string err;
+    const RolloutTuning t = rollout_tuning_for(n_cu, tune, &err);
+    if (!err.empty()) return -1;
+    static const uint32_t present = 0;
+    StepArgs args{};
+    args.c.n_cells = n_cells;
+    args.n_envs = n_envs;
+    args.mv4 = has_delta_rows ? &present : nullptr;
+    StepPlan plan;
+    if (!plan_step_lq(n_agents, args, t, &plan)) return 0;
+    out[0] = uint64_t(plan.K); out[1] = uint64_t(plan.Q); out[2] = uint64_t(plan.big); out[3] = plan.block; out[4] = plan.grid;
+    out[5] = plan.n_chunks; out[6] = plan.lds_bytes; out[7] = uint64_t(plan.lds_limit);
+    return 1;
+}
+
+}  // extern "C"
