@@ -422,10 +422,11 @@ class VecMapfEnv:
             self._ptr(res['collision'], np.uint8, (R,), 'collision')))
         return res
 
-    def transition_rewards(self, prev_local, actions, next_local, env_index=None):
+    def transition_rewards(self, prev_local, actions, next_local, env_index=None, want_done=True, want_collision=True):
         """``calc_transition_reward_from_local_states`` (reference mapf_env.py:225-235) for N given transitions:
         ``prev_local`` / ``next_local`` uint16 [N, A], ``actions`` uint8 [N, A].  Returns ``(reward f64 [N],
-        done u8 [N], collision u8 [N])``."""
+        done u8 [N], collision u8 [N])``; with ``want_done`` / ``want_collision`` False that output is not computed
+        (the C ABI gets NULL for it) and None is returned in its place."""
         A = self.n_agents
         prev_local = np.asarray(prev_local) if not self.device_arrays else prev_local
         N = int(prev_local.shape[0])
@@ -433,7 +434,9 @@ class VecMapfEnv:
         next_local = self._coerce(next_local, np.uint16, (N, A), 'next_local')
         actions = self._coerce(actions, np.uint8, (N, A), 'actions')
         env_index = self._coerce(env_index, np.uint32, (N,), 'env_index')
-        reward, done, coll = self._empty((N,), np.float64), self._empty((N,), np.uint8), self._empty((N,), np.uint8)
+        reward = self._empty((N,), np.float64)
+        done = self._empty((N,), np.uint8) if want_done else None
+        coll = self._empty((N,), np.uint8) if want_collision else None
         nat.check(self._lib.mapf_transition_rewards(
             self._h, N, self._ptr(prev_local, np.uint16, (N, A), 'prev_local'),
             self._ptr(actions, np.uint8, (N, A), 'actions'), self._ptr(next_local, np.uint16, (N, A), 'next_local'),

@@ -137,6 +137,27 @@ def categorical_index(probs, u):
     return 0
 
 
+def transition_reward(prev, actions, nxt, goal, consts, criteria=MAKESPAN):
+    """``calc_transition_reward_from_local_states`` (mapf_env.py:225-235) as a plain function of local cell ids:
+    ``consts`` = (r_clash, r_goal, r_living), ``actions`` one code per agent.  Returns (reward, done, collision,
+    living).  _living_reward (:436-446): an int count times r_living, ONE product; collision (:378-389: swap or shared
+    target over every pair) is tested before the goal; the reward is ONE sum ``r_x + living``."""
+    r_clash, r_goal, r_living = consts
+    n = len(prev)
+    if criteria == MAKESPAN:
+        living = r_living
+    else:
+        stayed = sum(1 for i in range(n) if prev[i] == goal[i] and actions[i] == STAY)
+        living = (n - stayed) * r_living
+    for i in range(n):
+        for j in range(i + 1, n):
+            if (prev[i] == nxt[j] and prev[j] == nxt[i]) or nxt[i] == nxt[j]:
+                return r_clash + living, True, True, living
+    if all(nxt[i] == goal[i] for i in range(n)):
+        return r_goal + living, True, False, living
+    return living, False, False, living
+
+
 class OracleEnv:
     """Scalar restatement of ``MapfEnv`` restricted to the step/reset path.
 

@@ -3,6 +3,8 @@
 reference (read-only at /root/reference) in the build container.
 
 Run from the repo root:   python tests/golden/make_golden.py
+(``--only inexact`` regenerates just the sets recorded with reward constants and slip rates on which float64
+arithmetic rounds: ``inexact_*.npz|json`` and ``inexact_cases.json``.)
 
 The reference needs two third-party modules that are not installed here
 (``gym==0.13.0`` -- requirements.txt:7 -- and ``colorama``).  Before importing
@@ -102,6 +104,7 @@ from gym_mapf.envs import map_name_to_files  # noqa: E402
 CRITERIA = {'Makespan': OptimizationCriteria.Makespan, 'SoC': OptimizationCriteria.SoC}
 R_CLASH, R_GOAL, R_LIVING = -1000.0, 100.0, -1.0
 SEED = 42
+U, R, D, L, S = 'UP', 'RIGHT', 'DOWN', 'LEFT', 'STAY'
 
 
 class InjectedUniforms(object):
@@ -152,9 +155,10 @@ def movement_tables(env):
 
 
 def run_trajectories(name, lines, per_env_locs, n_agents, fail_prob, criteria, env_ids, T,
-                     auto_reset, map_name=None, n_uniform_steps=32, action_fn=None):
+                     auto_reset, map_name=None, n_uniform_steps=32, action_fn=None, rewards=(R_CLASH, R_GOAL, R_LIVING)):
     """Lock-step run of one reference env per env id; returns dict of arrays.  ``action_fn(env, env_id, t)`` ->
-    per-agent action indices, or None for the uniform-random policy stream."""
+    per-agent action indices, or None for the uniform-random policy stream.  ``rewards`` = (clash, goal, living)."""
+    r_clash, r_goal, r_living = rewards
     E, A = len(env_ids), n_agents
     grid = MapfGrid(lines)
     out = dict(
@@ -170,7 +174,7 @@ def run_trajectories(name, lines, per_env_locs, n_agents, fail_prob, criteria, e
     first = None
     for j, env_id in enumerate(env_ids):
         starts, goals = per_env_locs(j, env_id)
-        env = MapfEnv(grid, A, starts, goals, fail_prob, R_CLASH, R_GOAL, R_LIVING, CRITERIA[criteria])
+        env = MapfEnv(grid, A, starts, goals, fail_prob, r_clash, r_goal, r_living, CRITERIA[criteria])
         rng = InjectedUniforms(SEED, int(env_id))
         env.np_random = rng
         if first is None:
@@ -206,8 +210,8 @@ def run_trajectories(name, lines, per_env_locs, n_agents, fail_prob, criteria, e
     out.update(valid_locations=np.asarray(first.valid_locations, np.int32),
                mv_n=mv_n, mv_next=mv_next, mv_prob=mv_prob)
     meta = dict(name=name, map_name=map_name, lines=[l.strip() for l in lines], n_agents=A,
-                fail_prob=fail_prob, criteria=criteria, r_clash=R_CLASH, r_goal=R_GOAL,
-                r_living=R_LIVING, seed=SEED, T=T, auto_reset=auto_reset, V=len(first.valid_locations),
+                fail_prob=fail_prob, criteria=criteria, r_clash=r_clash, r_goal=r_goal,
+                r_living=r_living, seed=SEED, T=T, auto_reset=auto_reset, V=len(first.valid_locations),
                 nS=str(first.nS), nA=str(first.nA), joint_state_first_steps=s_dec)
     if action_fn is not None:   # (key absent = the uniform-random policy stream, as in the round-1 sets)
         meta['actions_from'] = 'towards_goal, every fifth step (t % 5 == 4) the policy stream'  # see main()
@@ -261,7 +265,6 @@ def scripted_cases():
                           goals=[list(x) for x in goals], fail_prob=fail_prob, criteria=criteria,
                           r_clash=rewards[0], r_goal=rewards[1], r_living=rewards[2], steps=rec))
 
-    U, R, D, L, S = 'UP', 'RIGHT', 'DOWN', 'LEFT', 'STAY'
     corridor = ['@.@', '@.@', '@.@', '...']
     # right==left!=main row: cumsum [0.8999999999999999, 0.9999999999999999]; u = 1-2^-53 -> argmax of all-False = 0
     run('corridor_allfalse_argmax0', corridor, [(2, 1)], [(0, 1)], 0.1, 'Makespan',
@@ -304,44 +307,88 @@ def scripted_cases():
     print('scripted cases: %d' % len(cases))
 
 
+# the 'small_soc_three' table: map, starts, goals, queried states, queried joint actions
+SMALL_SOC_THREE = (['..@.', '....', '.@..'], ((0, 0), (2, 3), (1, 1)), ((2, 2), (0, 3), (1, 2)),
+                   [((0, 0), (2, 3), (1, 1)), ((1, 0), (1, 2), (1, 1)), ((2, 2), (0, 3), (1, 1))],
+                   [(R, U, S), (D, L, R), (S, S, S)])
+
+
+def transition_table(name, env, states_locs, actions_list):
+    """env.P[s][a] (mapf_env.py:448-478) for every (state, joint action) pair, as one known-answer table."""
+    rows = []
+    for locs in states_locs:
+        s = env.locations_to_state(tuple(locs))
+        for acts in actions_list:
+            a = vector_action_to_integer(tuple(acts))
+            tr = [dict(prob=float(p), collision=bool(c),
+                       next_local=[env.loc_to_int[l] for l in env.state_to_locations(ns)],
+                       s=str(ns), reward=float(r), done=bool(d))
+                  for ((p, c), ns, r, d) in env.P[s][a]]
+            rows.append(dict(local=[env.loc_to_int[tuple(l)] for l in locs],
+                             actions=[ACTIONS.index(x) for x in acts], transitions=tr))
+    return dict(name=name, lines=[''.join('.' if env.grid[r][c].__name__ == 'EmptyCell' else '@'
+                                          for c in range(len(env.grid[0]))) for r in range(len(env.grid))],
+                starts=[list(l) for l in env.agents_starts], goals=[list(l) for l in env.agents_goals],
+                fail_prob=env.fail_prob, criteria=env.optimization_criteria.value,
+                r_clash=env.reward_of_clash, r_goal=env.reward_of_goal,
+                r_living=env.reward_of_living, rows=rows)
+
+
 def transition_tables():
-    """env.P[s][a] enumerations (mapf_env.py:448-478) as known-answer tables."""
-    tabs = []
-
-    def dump(name, env, states_locs, actions_list):
-        rows = []
-        for locs in states_locs:
-            s = env.locations_to_state(tuple(locs))
-            for acts in actions_list:
-                a = vector_action_to_integer(tuple(acts))
-                tr = [dict(prob=float(p), collision=bool(c),
-                           next_local=[env.loc_to_int[l] for l in env.state_to_locations(ns)],
-                           s=str(ns), reward=float(r), done=bool(d))
-                      for ((p, c), ns, r, d) in env.P[s][a]]
-                rows.append(dict(local=[env.loc_to_int[tuple(l)] for l in locs],
-                                 actions=[ACTIONS.index(x) for x in acts], transitions=tr))
-        tabs.append(dict(name=name, lines=[''.join('.' if env.grid[r][c].__name__ == 'EmptyCell' else '@'
-                                                   for c in range(len(env.grid[0]))) for r in range(len(env.grid))],
-                         starts=[list(l) for l in env.agents_starts], goals=[list(l) for l in env.agents_goals],
-                         fail_prob=env.fail_prob, criteria=env.optimization_criteria.value,
-                         r_clash=env.reward_of_clash, r_goal=env.reward_of_goal,
-                         r_living=env.reward_of_living, rows=rows))
-
-    U, R, D, L, S = 'UP', 'RIGHT', 'DOWN', 'LEFT', 'STAY'
+    """env.P[s][a] enumerations as known-answer tables (transition_tables.json)."""
+    lines3, starts3, goals3, states3, actions3 = SMALL_SOC_THREE
     e88 = MapfGrid(ref_map_lines('empty-8-8'))
+    tabs = []
     env = MapfEnv(e88, 2, ((0, 0), (7, 7)), ((0, 2), (5, 7)), 0.2, R_CLASH, R_GOAL, -1, CRITERIA['Makespan'])
-    dump('empty88_right_up', env, [((0, 0), (7, 7)), ((0, 1), (6, 7))], [(R, U), (S, S), (L, D)])
+    tabs.append(transition_table('empty88_right_up', env, [((0, 0), (7, 7)), ((0, 1), (6, 7))], [(R, U), (S, S), (L, D)]))
     env = MapfEnv(e88, 2, ((0, 0), (0, 2)), ((7, 7), (5, 5)), 0.2, R_CLASH, R_GOAL, -1, CRITERIA['Makespan'])
-    dump('empty88_clash', env, [((0, 0), (0, 2)), ((0, 1), (0, 1))], [(R, L), (U, U)])
+    tabs.append(transition_table('empty88_clash', env, [((0, 0), (0, 2)), ((0, 1), (0, 1))], [(R, L), (U, U)]))
     env = MapfEnv(MapfGrid(['..', '..']), 1, ((0, 0),), ((1, 1),), 0.1, R_CLASH, R_GOAL, -1, CRITERIA['Makespan'])
-    dump('two_by_two_merge', env, [((0, 0),), ((1, 0),), ((1, 1),)], [(S,), (U,), (R,), (D,), (L,)])
-    env = MapfEnv(MapfGrid(['..@.', '....', '.@..']), 3, ((0, 0), (2, 3), (1, 1)), ((2, 2), (0, 3), (1, 2)),
-                  0.2, R_CLASH, R_GOAL, -1.0, CRITERIA['SoC'])
-    dump('small_soc_three', env, [((0, 0), (2, 3), (1, 1)), ((1, 0), (1, 2), (1, 1)), ((2, 2), (0, 3), (1, 1))],
-         [(R, U, S), (D, L, R), (S, S, S)])
+    tabs.append(transition_table('two_by_two_merge', env, [((0, 0),), ((1, 0),), ((1, 1),)], [(S,), (U,), (R,), (D,), (L,)]))
+    env = MapfEnv(MapfGrid(lines3), 3, starts3, goals3, 0.2, R_CLASH, R_GOAL, -1.0, CRITERIA['SoC'])
+    tabs.append(transition_table('small_soc_three', env, states3, actions3))
     with open(os.path.join(HERE, 'transition_tables.json'), 'w') as f:
         json.dump(tabs, f, indent=0)
     print('transition tables: %d envs' % len(tabs))
+
+
+def inexact_transition_tables():
+    """The 'small_soc_three' queries under reward constants and slip rates on which float64 rounds (inexact_cases.json)."""
+    lines3, starts3, goals3, states3, actions3 = SMALL_SOC_THREE
+    tabs = []
+    for name, fp, rewards, crit in (('small_soc_three_slip03_soc', 0.3, (-33.3, 7.7, -0.1), 'SoC'),
+                                    ('small_soc_three_slip015_makespan', 0.15, (-0.3, 0.7, -0.1), 'Makespan')):
+        env = MapfEnv(MapfGrid(lines3), 3, starts3, goals3, fp, rewards[0], rewards[1], rewards[2], CRITERIA[crit])
+        tabs.append(transition_table(name, env, states3, actions3))
+    return tabs
+
+
+def transition_reward_helpers(settings):
+    """Hot-path helper methods planners call directly (mapf_env.py:225-235, :378-389, :436-446), on local cell ids: seven
+    (prev, joint action, next) triples under each (criteria, rewards) of ``settings``."""
+    helper = []
+    lines3 = ['..@.', '....', '.@..']
+    for crit, rewards in settings:
+        e = MapfEnv(MapfGrid(lines3), 3, ((0, 0), (1, 2), (2, 3)), ((2, 2), (0, 0), (1, 3)), 0.2,
+                    rewards[0], rewards[1], rewards[2], CRITERIA[crit])
+        l2i = e.loc_to_int
+        trips = []
+        for prev, acts, nxt in ((((0, 0), (1, 2), (2, 3)), ('DOWN', 'LEFT', 'UP'), ((1, 0), (1, 1), (1, 3))),
+                                (((2, 2), (0, 0), (1, 3)), ('STAY', 'STAY', 'STAY'), ((2, 2), (0, 0), (1, 3))),
+                                (((2, 2), (0, 1), (1, 3)), ('STAY', 'LEFT', 'STAY'), ((2, 2), (0, 0), (1, 3))),
+                                (((1, 1), (1, 2), (2, 3)), ('RIGHT', 'LEFT', 'STAY'), ((1, 2), (1, 1), (2, 3))),
+                                (((1, 0), (1, 2), (2, 3)), ('RIGHT', 'LEFT', 'UP'), ((1, 1), (1, 1), (1, 3))),
+                                (((2, 2), (0, 0), (1, 3)), ('STAY', 'RIGHT', 'STAY'), ((2, 2), (0, 1), (1, 3))),
+                                (((2, 3), (0, 0), (2, 2)), ('LEFT', 'STAY', 'RIGHT'), ((2, 2), (0, 0), (2, 3)))):
+            pl, nl = tuple(l2i[x] for x in prev), tuple(l2i[x] for x in nxt)
+            a = vector_action_to_integer(acts)
+            r, d, c = e.calc_transition_reward_from_local_states(pl, a, nl)
+            trips.append(dict(prev_local=list(pl), action=a, next_local=list(nl), reward=float(r), done=bool(d), collision=bool(c),
+                              living=float(e._living_reward(pl, a)),
+                              is_collision=bool(e._is_collision_transition_from_local_states(pl, nl))))
+        helper.append(dict(lines=lines3, starts=[[0, 0], [1, 2], [2, 3]], goals=[[2, 2], [0, 0], [1, 3]], criteria=crit,
+                           rewards=list(rewards), fail_prob=0.2, cases=trips))
+    return helper
 
 
 def host_api_cases():
@@ -425,32 +472,11 @@ def host_api_cases():
     for locs in (((0, 0), (1, 2)), ((2, 2), (0, 0)), ((1, 1), (1, 1)), ((2, 2), (1, 0)), ((0, 3), (0, 3))):
         term.append(dict(locs=[list(l) for l in locs], terminal=bool(e.is_terminal(locs))))
     out['is_terminal'] = dict(lines=['..@.', '....', '.@..'], starts=[[0, 0], [1, 2]], goals=[[2, 2], [0, 0]], cases=term)
-    # hot-path helper methods planners call directly (mapf_env.py:225-235, :378-389, :436-446), on local cell ids
-    helper = []
-    lines3 = ['..@.', '....', '.@..']
-    for crit, rewards in (('SoC', (-1000.0, 100.0, -1.0)), ('Makespan', (-33.25, 7.125, -0.1)), ('SoC', (-5, 3, -2))):
-        e = MapfEnv(MapfGrid(lines3), 3, ((0, 0), (1, 2), (2, 3)), ((2, 2), (0, 0), (1, 3)), 0.2,
-                    rewards[0], rewards[1], rewards[2], CRITERIA[crit])
-        l2i = e.loc_to_int
-        trips = []
-        for prev, acts, nxt in ((((0, 0), (1, 2), (2, 3)), ('DOWN', 'LEFT', 'UP'), ((1, 0), (1, 1), (1, 3))),
-                                (((2, 2), (0, 0), (1, 3)), ('STAY', 'STAY', 'STAY'), ((2, 2), (0, 0), (1, 3))),
-                                (((2, 2), (0, 1), (1, 3)), ('STAY', 'LEFT', 'STAY'), ((2, 2), (0, 0), (1, 3))),
-                                (((1, 1), (1, 2), (2, 3)), ('RIGHT', 'LEFT', 'STAY'), ((1, 2), (1, 1), (2, 3))),
-                                (((1, 0), (1, 2), (2, 3)), ('RIGHT', 'LEFT', 'UP'), ((1, 1), (1, 1), (1, 3))),
-                                (((2, 2), (0, 0), (1, 3)), ('STAY', 'RIGHT', 'STAY'), ((2, 2), (0, 1), (1, 3))),
-                                (((2, 3), (0, 0), (2, 2)), ('LEFT', 'STAY', 'RIGHT'), ((2, 2), (0, 0), (2, 3)))):
-            pl, nl = tuple(l2i[x] for x in prev), tuple(l2i[x] for x in nxt)
-            a = vector_action_to_integer(acts)
-            r, d, c = e.calc_transition_reward_from_local_states(pl, a, nl)
-            trips.append(dict(prev_local=list(pl), action=a, next_local=list(nl), reward=float(r), done=bool(d), collision=bool(c),
-                              living=float(e._living_reward(pl, a)),
-                              is_collision=bool(e._is_collision_transition_from_local_states(pl, nl))))
-        helper.append(dict(lines=lines3, starts=[[0, 0], [1, 2], [2, 3]], goals=[[2, 2], [0, 0], [1, 3]], criteria=crit,
-                           rewards=list(rewards), fail_prob=0.2, cases=trips))
-    out['transition_reward_helpers'] = helper
+    out['transition_reward_helpers'] = transition_reward_helpers(
+        (('SoC', (-1000.0, 100.0, -1.0)), ('Makespan', (-33.25, 7.125, -0.1)), ('SoC', (-5, 3, -2))))
     # the single-location movers (mapf_env.py:43-75)
     import gym_mapf.envs.mapf_env as ref_env
+    lines3 = ['..@.', '....', '.@..']
     g3 = MapfGrid(lines3)
     movers = []
     for name in ('execute_up', 'execute_down', 'execute_right', 'execute_left', 'execute_stay'):
@@ -472,7 +498,49 @@ def reference_selftest():
     return dict(ran=res.testsRun, failures=len(res.failures), errors=len(res.errors))
 
 
+def goal_trajectories(name, A, fp, crit, auto, T, rewards=(R_CLASH, R_GOAL, R_LIVING), n_env=12):
+    """One goal-seeking set (oracle/goal_scenarios.py, seed 7000 + A): see main()."""
+    lines, st, gl = goal_scenarios.goal_scenario(A, n_env, 7000 + A)
+
+    def towards(env, env_id, t):
+        if t % 5 == 4:
+            return None
+        locs = env.state_to_locations(env.s)
+        return [goal_scenarios.towards_goal_action(locs[i], tuple(gl[env_id, i]), len(lines), len(lines[0]))
+                for i in range(len(locs))]
+    run_trajectories(name, lines, lambda j, env_id: (tuple(map(tuple, st[env_id].tolist())), tuple(map(tuple, gl[env_id].tolist()))),
+                     A, fp, crit, list(range(n_env)), T, auto, None, action_fn=towards, rewards=rewards)
+
+
+TINY = ['....', '.@..', '....']
+
+
+def inexact_sets():
+    """Reward constants and slip rates on which float64 arithmetic ROUNDS (every other set uses constants whose products
+    and sums are exact, so a fused multiply-add, a repeated add or a reordered sum would go unnoticed): with
+    (-0.3, 0.7, -0.1) fl(fl(n * living) + goal) differs from the correctly rounded n * living + goal at n = 3, 5, 6, 7, ...,
+    n-fold addition of living differs from n * living from n = 6 on, and ten left-to-right additions of -0.1 are not -1.0.
+    The third set's living reward is the smallest subnormal.  Plus env.P tables and reward-helper triples."""
+    goal_trajectories('inexact_goals_a8_slip03_soc', 8, 0.3, 'SoC', True, 60, rewards=(-33.3, 7.7, -0.1))
+    goal_trajectories('inexact_goals_a32_slip015_makespan', 32, 0.15, 'Makespan', True, 40, rewards=(-0.3, 0.7, -0.1))
+    goal_trajectories('inexact_goals_a16_slip13_soc_noreset', 16, 1.0 / 3.0, 'SoC', False, 12, rewards=(-1e-3, 1e-3, -4.9e-324))
+    goal_trajectories('inexact_goals_a4_slip07_makespan', 4, 0.7, 'Makespan', True, 60, rewards=(-0.3, 0.7, -0.1))
+    run_trajectories('inexact_tiny_a2_slip015', TINY, lambda j, env_id: synth_starts_goals(TINY, 2, int(env_id)), 2, 0.15,
+                     'SoC', list(range(16)), 400, True, None, rewards=(-1.1, 2.3, -0.7))
+    cases = dict(transition_tables=inexact_transition_tables(),
+                 transition_reward_helpers=transition_reward_helpers((('SoC', (-0.3, 0.7, -0.1)),)))
+    with open(os.path.join(HERE, 'inexact_cases.json'), 'w') as f:
+        json.dump(cases, f, indent=0)
+    print('inexact cases: %d tables, %d reward triples' % (len(cases['transition_tables']),
+                                                          len(cases['transition_reward_helpers'][0]['cases'])))
+
+
 def main():
+    if sys.argv[1:] == ['--only', 'inexact']:
+        inexact_sets()
+        return
+    if sys.argv[1:]:
+        sys.exit('usage: make_golden.py [--only inexact]')
     info = dict(reference_tests=reference_selftest())
     rng42, _ = sys.modules['gym.utils.seeding'].np_random(42)
     info['mt19937_seed42_first_draws_UNPINNED'] = [rng42.rand() for _ in range(4)]
@@ -525,18 +593,8 @@ def main():
     # third env lets two agents share a goal cell -> vertex collision with every agent on its goal
     for A, fp, crit, auto, T in ((4, 0.2, 'Makespan', True, 60), (8, 0.2, 'SoC', True, 60), (8, 0.0, 'Makespan', False, 6),
                                  (16, 0.2, 'Makespan', True, 60), (32, 0.2, 'SoC', True, 80), (32, 0.0, 'Makespan', True, 12)):
-        n_env = 12
-        lines, st, gl = goal_scenarios.goal_scenario(A, n_env, 7000 + A)
-
-        def towards(env, env_id, t, gl=gl, lines=lines):
-            if t % 5 == 4:
-                return None
-            locs = env.state_to_locations(env.s)
-            return [goal_scenarios.towards_goal_action(locs[i], tuple(gl[env_id, i]), len(lines), len(lines[0]))
-                    for i in range(len(locs))]
-        run_trajectories('goals_a%d_slip%s_%s%s' % (A, str(fp).replace('.', ''), crit.lower(), '' if auto else '_noreset'),
-                         lines, lambda j, env_id, st=st, gl=gl: (tuple(map(tuple, st[env_id].tolist())), tuple(map(tuple, gl[env_id].tolist()))),
-                         A, fp, crit, list(range(n_env)), T, auto, None, action_fn=towards)
+        goal_trajectories('goals_a%d_slip%s_%s%s' % (A, str(fp).replace('.', ''), crit.lower(), '' if auto else '_noreset'),
+                          A, fp, crit, auto, T)
 
     # the reference's LARGE maps (the only scenario that constructs at 32 agents on maze-128-128-10 is
     # scen 18; Berlin_1_256 -- the map the reference's own grid test opens, mapf_grid_tests.py:22-32 -- constructs at
@@ -549,6 +607,8 @@ def main():
     run_trajectories('berlin256_a2_slip01', ref_map_lines('Berlin_1_256'),
                      scen_locs('Berlin_1_256', [2, 4, 8, 11, 14, 18, 22, 24], 2), 2, 0.1, 'Makespan', list(range(8)), 64, True,
                      'Berlin_1_256')
+
+    inexact_sets()
 
     with open(os.path.join(HERE, 'generation_info.json'), 'w') as f:
         json.dump(info, f, indent=1)

@@ -1,6 +1,9 @@
 """GPU parity: the HIP path (through the C ABI / VecMapfEnv) against the reference's recorded
 outputs (tests/golden) and against the pinned CPU oracles.  Bit-exact: integers, flags and the
 float64 reward/prob bit patterns.  All tests here need a real MI355X (-m gpu)."""
+import math
+from fractions import Fraction
+
 import numpy as np
 import pytest
 
@@ -13,6 +16,12 @@ from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
 
 pytestmark = pytest.mark.gpu
 KERNELS = ('thread_per_env', 'lane_group')
+# reward constants (clash, goal, living): EXACT -- every product n * living and every sum of rewards is exact in float64, in
+# any order; INEXACT -- they round: fl(fl(n * living) + goal) differs from the correctly rounded n * living + goal at
+# n = 3, 5, 6, 7, 9, 10, 12, 15, 20, 23..26, 28, 30, 31 (the same with clash), n-fold addition of living differs from n * living
+# from n = 6 on, ten left-to-right additions of -0.1 give -0.9999999999999999: a fused multiply-add, a repeated add, a
+# reordered or re-associated sum each change bits (tests/golden/inexact_* were recorded from the reference with such constants)
+EXACT, INEXACT = (-1000.0, 100.0, -1.0), (-0.3, 0.7, -0.1)
 
 
 def _families(n_agents):
@@ -408,8 +417,11 @@ def test_recorded_rollout_with_eight_agents_per_lane(n_agents, n_envs, monkeypat
     env.close()
 
 
-@pytest.mark.parametrize('n_agents,n_envs', [(4, 16384), (8, 8192), (8, 16448), (16, 4096)])
-def test_dense_rollout_split_launches_accumulate_and_single_steps(n_agents, n_envs):
+DENSE_SPLIT_SHAPES = [(4, 16384), (8, 8192), (8, 16448), (16, 4096)]
+
+
+@pytest.mark.parametrize('n_agents,n_envs', DENSE_SPLIT_SHAPES)
+def test_dense_rollout_split_launches_accumulate_and_single_steps(n_agents, n_envs, rewards=EXACT):
     """Quad-lane and pair layouts: a rollout split into launches of 1, 4 and 7 steps that accumulate into the same
     totals equals one 12-step launch (returns bit for bit, episode and collision counts, final state), starting at a
     step index that is not a multiple of 4 (the slip stream's call granularity)."""
@@ -419,7 +431,7 @@ def test_dense_rollout_split_launches_accumulate_and_single_steps(n_agents, n_en
     V, E, A = len(valid), n_envs, n_agents
     start = np.argsort(rs.rand(E, V), axis=1)[:, :A].astype(np.uint16)
     goal = np.argsort(rs.rand(E, V), axis=1)[:, :A].astype(np.uint16)
-    mk = lambda: VecMapfEnv(grid, A, None, None, 0.25, -1000.0, 100.0, -1.0, OptimizationCriteria.Makespan, seed=3,  # noqa: E731
+    mk = lambda: VecMapfEnv(grid, A, None, None, 0.25, *rewards, OptimizationCriteria.Makespan, seed=3,  # noqa: E731
                             start_local=start, goal_local=goal)
     one, parts = mk(), mk()
     for env in (one, parts):
@@ -432,11 +444,18 @@ def test_dense_rollout_split_launches_accumulate_and_single_steps(n_agents, n_en
     assert np.array_equal(full['episodes'], acc['episodes']) and np.array_equal(full['collisions'], acc['collisions'])
     (s1, t1), (s2, t2) = one.get_state(), parts.get_state()
     assert t1 == t2 == 15 and np.array_equal(s1, s2)
-    co = c_oracle.COracle(nbr, A, start, goal, 0.25, -1000.0, 100.0, -1.0, mo.MAKESPAN, seed=3)
+    co = c_oracle.COracle(nbr, A, start, goal, 0.25, *rewards, mo.MAKESPAN, seed=3)
     co.t = 3
     ref = co.rollout(12, auto_reset=True)
     assert np.array_equal(_bits(full['returns']), _bits(ref['returns'])) and np.array_equal(s1, co.state)
     one.close(), parts.close()
+
+
+@pytest.mark.parametrize('n_agents,n_envs', DENSE_SPLIT_SHAPES)
+def test_dense_rollout_split_launches_with_inexact_constants(n_agents, n_envs):
+    """The same with the INEXACT constants: a launch that summed its own rewards from zero and added the earlier total at the
+    end (instead of continuing the left-to-right chain) would differ in the last bits."""
+    test_dense_rollout_split_launches_accumulate_and_single_steps(n_agents, n_envs, rewards=INEXACT)
 
 
 @pytest.mark.parametrize('n_agents,n_envs,k,streamed', [(8, 8192, None, True), (16, 4096, None, True), (32, 2048, None, True), (8, 8192, '8', True),
@@ -534,6 +553,101 @@ def _goal_scenario_tables(n_agents, n_envs, seed):
     return grid, nbr, rc, start, goal
 
 
+def _goal_passes(slip, soc_policy=(0.0, 4)):
+    """(fail_prob, criteria, oracle criteria, auto_reset, mode, T): Makespan streamed; SoC policy without auto-reset
+    (`soc_policy` = its slip and T); SoC single steps; Makespan policy without auto-reset; no slip, streamed."""
+    return ((slip, OptimizationCriteria.Makespan, mo.MAKESPAN, True, 'streamed', 10),
+            (soc_policy[0], OptimizationCriteria.SoC, mo.SOC, False, 'policy', soc_policy[1]),
+            (slip, OptimizationCriteria.SoC, mo.SOC, True, 'single', 8),
+            (slip, OptimizationCriteria.Makespan, mo.MAKESPAN, False, 'policy', 10),
+            (0.0, OptimizationCriteria.Makespan, mo.MAKESPAN, True, 'streamed', 3))
+
+
+def _assert_a_wrong_rounding_would_show(refs, prevs, acts, goal, rewards, soc, fail_prob, tag):
+    """On the ORACLE's output alone: this pass would not equally accept a reordered return or a fused / re-associated
+    ``n * r_living + r_x``.  ``prevs[t]`` = the oracle's cells before step t, ``acts[t]`` its actions, ``refs[t]`` its results."""
+    r_clash, r_goal, r_living = rewards
+    T, (E, A) = len(refs), goal.shape
+    rew = np.stack([ref['reward'] for ref in refs])
+    ret = np.zeros(E)
+    for t in range(T):
+        ret = ret + rew[t]                                        # the reference's order: left to right
+    reordered = sum(1 for e in range(E) if math.fsum(rew[:, e].tolist()) != ret[e])
+    # waived without slip: every agent starts one move from its goal, so every episode ends at its first step and the
+    # three-step pass sums three terms from {r_goal + living, r_clash + living}
+    assert fail_prob == 0.0 or reordered > 0, tag
+    if not soc:
+        return
+    counts, two_roundings = set(), 0
+    for t in range(T):
+        fresh = refs[t]['was_terminal'] == 0
+        n = A - ((prevs[t] == goal) & (acts[t] == 0)).sum(axis=1)                 # A - stayed, from the oracle's state
+        counts.update(n[fresh].tolist())
+        on_goal = fresh & (refs[t]['done'] == 1) & (refs[t]['collision'] == 0)
+        for base, sel in ((r_clash, fresh & (refs[t]['collision'] == 1)), (r_goal, on_goal)):
+            for k in np.unique(n[sel]).tolist():
+                exact = float(Fraction(k) * Fraction(r_living) + Fraction(base))   # n * r_living + r_x, rounded once
+                got = refs[t]['reward'][sel & (n == k)]
+                assert np.array_equal(_bits(got), _bits(np.full(got.shape, base + float(k) * r_living))), (tag, t, k)   # n is the oracle's n
+                two_roundings += int((got != exact).sum())
+    assert two_roundings > 0 and len(counts) >= 3, (tag, two_roundings, sorted(counts))       # (no waiver: see the caller)
+
+
+def _goal_reaching_episodes(n_agents, n_envs, layout, env_vars, monkeypatch, rewards, slip, rounding_must_show, soc_policy=(0.0, 4)):
+    """Body of the two tests below: five passes of goal-seeking episodes in the kernel form `layout` names, every recorded step
+    against the C oracle."""
+    set_tune(monkeypatch, **env_vars)
+    A, E = n_agents, n_envs
+    grid, nbr, rc, start, goal = _goal_scenario_tables(A, E, 8100 + A)
+    for fail_prob, crit, ocrit, auto, mode, T in _goal_passes(slip, soc_policy):
+        env = VecMapfEnv(grid, A, None, None, fail_prob, *rewards, crit, seed=31, env_id_offset=5,
+                         start_local=start, goal_local=goal,
+                         kernel='thread_per_env' if layout.startswith('rollout_kernel') else 'auto')
+        co = c_oracle.COracle(nbr, A, start, goal, fail_prob, *rewards, ocrit, seed=31, env_id_offset=5)
+        acts, refs, prevs = [], [], []
+        for t in range(T):
+            prevs.append(co.state.copy())
+            acts.append(co.greedy_actions(rc))
+            refs.append(co.step(acts[-1], auto_reset=auto))
+        if mode == 'single':
+            got = []
+            for t in range(T):
+                local, reward, done, info = env.step(acts[t], auto_reset=auto)
+                got.append((local, reward, info['prob'], done, info['collision']))
+            assert 'step_kernel' in env.last_kernel('step')
+        else:
+            if mode == 'policy':
+                env.set_policy('greedy')
+            res = env.rollout(T, actions=np.stack(acts) if mode == 'streamed' else None, auto_reset=auto, record=True)
+            got = [(res['local'][t], res['reward'][t], res['prob'][t], res['done'][t], res['collision'][t]) for t in range(T)]
+            seen = env.last_kernel('rollout')
+            wanted = layout if (mode == 'streamed' and crit == OptimizationCriteria.Makespan) else layout.split(',RECORD')[0]
+            assert wanted in seen, seen
+            assert ('BITMAP' in seen) == ('BITMAP' in layout), seen
+            ret = np.zeros(E)
+            for t in range(T):
+                ret = ret + refs[t]['reward']                      # the reference's order: left to right, from zero
+            assert np.array_equal(_bits(res['returns']), _bits(ret)), (A, E, mode, fail_prob)
+            assert np.array_equal(res['episodes'], np.sum([ref['done'] for ref in refs], axis=0)), (A, E, mode, fail_prob)
+            assert np.array_equal(res['collisions'], np.sum([ref['collision'] for ref in refs], axis=0)), (A, E, mode, fail_prob)
+        goals = clash_on_goal = 0
+        for t in range(T):
+            ref, (local, reward, prob, done, coll) = refs[t], got[t]
+            tag = (A, E, mode, fail_prob, t)
+            assert np.array_equal(local, ref['local']), tag
+            assert np.array_equal(_bits(reward), _bits(ref['reward'])) and np.array_equal(_bits(prob), _bits(ref['prob'])), tag
+            assert np.array_equal(done, ref['done']) and np.array_equal(coll, ref['collision']), tag
+            fresh = ref['was_terminal'] == 0
+            on_goal = (ref['local'] == goal).all(axis=1)
+            goals += int((fresh & (ref['done'] == 1) & (ref['collision'] == 0)).sum())
+            clash_on_goal += int((fresh & (ref['collision'] == 1) & on_goal).sum())
+        assert np.array_equal(env.get_state()[0], co.state)
+        assert goals > 0 and clash_on_goal > 0, (A, E, mode, fail_prob, goals, clash_on_goal)
+        if rounding_must_show:
+            _assert_a_wrong_rounding_would_show(refs, prevs, acts, goal, rewards, ocrit == mo.SOC, fail_prob, (A, E, mode, fail_prob))
+        env.close()
+
+
 @pytest.mark.parametrize('n_agents,n_envs,layout,env_vars', [
     (4, 16384, 'lq_rollout_kernel<Q=1,K=4', {'k': '4'}), (4, 16512, 'lq_rollout_kernel<Q=2,K=2', {'k': '2'}),
     (8, 8192, 'lq_rollout_kernel<Q=2,K=4', {'k': '4'}), (8, 16448, 'lq_rollout_kernel<Q=4,K=2', {'k': '2'}),
@@ -572,61 +686,45 @@ def test_goal_reaching_episodes_against_c_oracle(n_agents, n_envs, layout, env_v
     open map and are driven towards them (oracle/goal_scenarios.py -- the family the reference itself stepped for
     tests/golden/goals_*).  Every recorded step against the C oracle; each pass must actually contain both outcomes,
     and the library must report the kernel this case is meant to reach."""
-    set_tune(monkeypatch, **env_vars)
-    A, E = n_agents, n_envs
-    grid, nbr, rc, start, goal = _goal_scenario_tables(A, E, 8100 + A)
-    for fail_prob, crit, ocrit, auto, mode, T in (
-            (0.2, OptimizationCriteria.Makespan, mo.MAKESPAN, True, 'streamed', 10),
-            (0.0, OptimizationCriteria.SoC, mo.SOC, False, 'policy', 4),
-            (0.2, OptimizationCriteria.SoC, mo.SOC, True, 'single', 8),
-            (0.2, OptimizationCriteria.Makespan, mo.MAKESPAN, False, 'policy', 10),
-            (0.0, OptimizationCriteria.Makespan, mo.MAKESPAN, True, 'streamed', 3)):
-        env = VecMapfEnv(grid, A, None, None, fail_prob, -1000.0, 100.0, -1.0, crit, seed=31, env_id_offset=5,
-                         start_local=start, goal_local=goal,
-                         kernel='thread_per_env' if layout.startswith('rollout_kernel') else 'auto')
-        co = c_oracle.COracle(nbr, A, start, goal, fail_prob, -1000.0, 100.0, -1.0, ocrit, seed=31, env_id_offset=5)
-        acts, refs = [], []
-        for t in range(T):
-            acts.append(co.greedy_actions(rc))
-            refs.append(co.step(acts[-1], auto_reset=auto))
-        if mode == 'single':
-            got = []
-            for t in range(T):
-                local, reward, done, info = env.step(acts[t], auto_reset=auto)
-                got.append((local, reward, info['prob'], done, info['collision']))
-            assert 'step_kernel' in env.last_kernel('step')
-        else:
-            if mode == 'policy':
-                env.set_policy('greedy')
-            res = env.rollout(T, actions=np.stack(acts) if mode == 'streamed' else None, auto_reset=auto, record=True)
-            got = [(res['local'][t], res['reward'][t], res['prob'][t], res['done'][t], res['collision'][t]) for t in range(T)]
-            seen = env.last_kernel('rollout')
-            wanted = layout if (mode == 'streamed' and crit == OptimizationCriteria.Makespan) else layout.split(',RECORD')[0]
-            assert wanted in seen, seen
-            assert ('BITMAP' in seen) == ('BITMAP' in layout), seen
-        goals = clash_on_goal = 0
-        for t in range(T):
-            ref, (local, reward, prob, done, coll) = refs[t], got[t]
-            tag = (A, E, mode, fail_prob, t)
-            assert np.array_equal(local, ref['local']), tag
-            assert np.array_equal(_bits(reward), _bits(ref['reward'])) and np.array_equal(_bits(prob), _bits(ref['prob'])), tag
-            assert np.array_equal(done, ref['done']) and np.array_equal(coll, ref['collision']), tag
-            fresh = ref['was_terminal'] == 0
-            on_goal = (ref['local'] == goal).all(axis=1)
-            goals += int((fresh & (ref['done'] == 1) & (ref['collision'] == 0)).sum())
-            clash_on_goal += int((fresh & (ref['collision'] == 1) & on_goal).sum())
-        assert np.array_equal(env.get_state()[0], co.state)
-        assert goals > 0 and clash_on_goal > 0, (A, E, mode, fail_prob, goals, clash_on_goal)
-        env.close()
+    _goal_reaching_episodes(n_agents, n_envs, layout, env_vars, monkeypatch, EXACT, 0.2, False)
 
 
-@pytest.mark.parametrize('env_vars,want', [
+@pytest.mark.parametrize('n_agents,n_envs,layout,env_vars', [
+    # packed layout: four, two and eight agents per lane; 8-byte rows; 32 agents with the systolic probability chain
+    (8, 8192, 'lq_rollout_kernel<Q=2,K=4', {'k': '4'}), (8, 16448, 'lq_rollout_kernel<Q=4,K=2', {'k': '2'}),
+    (8, 8192, 'lq_rollout_kernel<Q=1,K=8', {'k': '8'}),
+    (16, 4096, 'lq_rollout_kernel<Q=4,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL> block=512', {'mv_lds_max_bytes': '2048'}),
+    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,NO_TERMINAL,BITMAP> block=', {'k': '4'}),
+    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,NO_TERMINAL> block=', {'k': '4', 'bitmap_pairs': '0'}),
+    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL,BITMAPD> block=512', {'mv_lds_max_bytes': '2048'}),
+    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL,BITMAP5> block=1024', {'mv_lds_max_bytes': '2048', 'bitmap_block': '1024', 'bitmap_delta': '0'}),
+    (32, 1024, 'lq_rollout_kernel<Q=16,K=2', {'k': '2'}),
+    # lane-group layout: LDS and global table, dense and guarded; thread-per-env
+    (8, 16448, 'lg_rollout_kernel<L=4,FULL,MV_LDS', {'quad_lanes': '0'}), (8, 300, 'lg_rollout_kernel<L=4,FULL,MV_GLOBAL', {}),
+    (5, 600, 'lg_rollout_kernel<L=4,RAGGED', {}), (32, 1024, 'lg_rollout_kernel<L=16,FULL,MV_GLOBAL', {'mv_lds_max_bytes': '0'}),
+    (6, 512, 'rollout_kernel<A=6>', {})])
+def test_inexact_constants_in_every_kernel_form(n_agents, n_envs, layout, env_vars, monkeypatch):
+    """The same five passes with reward constants (-0.3, 0.7, -0.1) and slip 0.15, at the smallest batch that reaches each
+    rollout kernel form (and the single-step kernel behind it): the outcome rows staged in LDS, the SoC branches
+    ``r_x + (A - stayed) * r_living`` and the left-to-right return chains have ONE admissible rounding each, and with these
+    constants any other shows.  Each pass proves that on the oracle's output (_assert_a_wrong_rounding_would_show): some
+    env's return differs from the correctly rounded sum of its rewards, some SoC goal / clash reward differs from the
+    correctly rounded n * r_living + r_x, and at least three counts n occur.  The SoC policy pass -- the only one that runs
+    the ROLLOUT kernels under SoC -- has slip 0.15 and eight steps here: without slip every episode ends at its first
+    step with A - stayed == A, one count only, where (A = 8, 16, 32) one rounding and two agree."""
+    _goal_reaching_episodes(n_agents, n_envs, layout, env_vars, monkeypatch, INEXACT, 0.15, True, soc_policy=(0.15, 8))
+
+
+SYSTOLIC_FORMS = [
     ({'mv_lds_max_bytes': '2048'}, 'COMPACT,NO_TERMINAL,BITMAPD> block=512'),
     ({'mv_lds_max_bytes': '2048', 'bitmap_delta': '0'}, 'COMPACT,NO_TERMINAL,BITMAP5> block=512'),
     ({'mv_lds_max_bytes': '2048', 'bitmap_block': '1024', 'bitmap_staycol': '0', 'bitmap_delta': '0'}, 'COMPACT,NO_TERMINAL,BITMAP> block=1024'),
     ({'k': '4'}, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,NO_TERMINAL,BITMAP> block='),
-    ({'k': '4', 'bitmap_pairs': '0'}, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,NO_TERMINAL> block=')])
-def test_systolic_probability_chain_over_short_and_split_launches(env_vars, want, monkeypatch):
+    ({'k': '4', 'bitmap_pairs': '0'}, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,NO_TERMINAL> block=')]
+
+
+@pytest.mark.parametrize('env_vars,want', SYSTOLIC_FORMS)
+def test_systolic_probability_chain_over_short_and_split_launches(env_vars, want, monkeypatch, rewards=EXACT, slip=0.2):
     """32 agents in eight lanes: the ordered probability product is a systolic chain -- one hand-over per step, the last lane
     completing a step's product seven steps later and every launch ending with seven draining rounds.  Launches SHORTER than
     the chain (1, 2, 7 steps), of its length, and longer ones, issued back to back: every recorded probability (and
@@ -634,22 +732,31 @@ def test_systolic_probability_chain_over_short_and_split_launches(env_vars, want
     set_tune(monkeypatch, **env_vars)
     A, E = 32, 2048
     grid, nbr, rc, start, goal = _goal_scenario_tables(A, E, 8100 + A)
-    for fail_prob in (0.2, 0.0):
-        env = VecMapfEnv(grid, A, None, None, fail_prob, -1000.0, 100.0, -1.0, OptimizationCriteria.Makespan, seed=77, env_id_offset=9,
+    for fail_prob in (slip, 0.0):
+        env = VecMapfEnv(grid, A, None, None, fail_prob, *rewards, OptimizationCriteria.Makespan, seed=77, env_id_offset=9,
                          start_local=start, goal_local=goal)
-        co = c_oracle.COracle(nbr, A, start, goal, fail_prob, -1000.0, 100.0, -1.0, mo.MAKESPAN, seed=77, env_id_offset=9)
+        co = c_oracle.COracle(nbr, A, start, goal, fail_prob, *rewards, mo.MAKESPAN, seed=77, env_id_offset=9)
         rs = np.random.RandomState(5)
         for T in (1, 2, 7, 8, 9, 1, 13, 3, 16):
             acts = rs.randint(0, 5, size=(T, E, A)).astype(np.uint8)
             res = env.rollout(T, actions=acts, auto_reset=True, record=True)
             assert want in env.last_kernel('rollout'), env.last_kernel('rollout')
+            ret = np.zeros(E)
             for t in range(T):
                 ref = co.step(acts[t], auto_reset=True)
                 assert np.array_equal(_bits(res['prob'][t]), _bits(ref['prob'])), (fail_prob, T, t)
                 assert np.array_equal(res['local'][t], ref['local']) and np.array_equal(_bits(res['reward'][t]), _bits(ref['reward']))
                 assert np.array_equal(res['done'][t], ref['done']) and np.array_equal(res['collision'][t], ref['collision'])
+                ret = ret + ref['reward']
+            assert np.array_equal(_bits(res['returns']), _bits(ret)), (fail_prob, T)     # this launch's rewards, left to right
         assert np.array_equal(env.get_state()[0], co.state)
         env.close()
+
+
+@pytest.mark.parametrize('env_vars,want', SYSTOLIC_FORMS)
+def test_systolic_probability_chain_with_inexact_constants(env_vars, want, monkeypatch):
+    """The same at slip 0.15 (factors 0.85 and 0.075) with the INEXACT constants."""
+    test_systolic_probability_chain_over_short_and_split_launches(env_vars, want, monkeypatch, rewards=INEXACT, slip=0.15)
 
 
 # ----------------------------------------------------------------------- BASELINE.json full sizes
@@ -947,7 +1054,19 @@ def test_config5_random64_32agents_16384_envs():
 def test_transition_tables_match_reference_on_device():
     """env.P[s][a] from the mapf_transitions kernel == the lists the reference enumerated (order, float64
     bits of prob and reward, flags, next cells)."""
-    for tab in load_json('transition_tables.json'):
+    _check_transition_tables_on_device(load_json('transition_tables.json'))
+
+
+def test_transition_tables_inexact_match_reference_on_device():
+    """The same for the tables the reference enumerated under constants on which float64 rounds (inexact_cases.json: SoC at
+    slip 0.3 with (-33.3, 7.7, -0.1), Makespan at slip 0.15 with (-0.3, 0.7, -0.1))."""
+    tabs = load_json('inexact_cases.json')['transition_tables']
+    assert [(t['criteria'], t['fail_prob'], t['r_living']) for t in tabs] == [('SoC', 0.3, -0.1), ('Makespan', 0.15, -0.1)]
+    _check_transition_tables_on_device(tabs)
+
+
+def _check_transition_tables_on_device(tabs):
+    for tab in tabs:
         A = len(tab['starts'])
         env = VecMapfEnv(MapfGrid(tab['lines']), A, tab['starts'], tab['goals'], tab['fail_prob'], tab['r_clash'],
                          tab['r_goal'], tab['r_living'], CRIT[tab['criteria']], n_envs=1)
@@ -1055,7 +1174,7 @@ def test_compacted_transitions_across_the_scan_block_boundaries(n_agents):
     env.close()
 
 
-def test_transitions_of_large_teams_come_in_windows():
+def test_transitions_of_large_teams_come_in_windows(slip=0.2, rewards=EXACT):
     """env.P for more than 8 agents (reference mapf_env.py:448-478 has no limit): the 3^A branches of a query are
     fetched window by window (mapf_transitions_window); the concatenation equals the pinned Python oracle's
     enumeration, whatever the window size, and MapfEnv.P pages through them by itself."""
@@ -1067,8 +1186,8 @@ def test_transitions_of_large_teams_come_in_windows():
     V, A = len(valid), 9
     start = rs.choice(V, A, replace=False).astype(np.uint16)
     goal = rs.choice(V, A, replace=False).astype(np.uint16)
-    env = VecMapfEnv(grid, A, None, None, 0.2, -1000.0, 100.0, -1.0, OptimizationCriteria.SoC, start_local=start, goal_local=goal)
-    orc = mo.OracleEnv(lines, A, [valid[c] for c in start], [valid[c] for c in goal], 0.2, -1000.0, 100.0, -1.0, mo.SOC)
+    env = VecMapfEnv(grid, A, None, None, slip, *rewards, OptimizationCriteria.SoC, start_local=start, goal_local=goal)
+    orc = mo.OracleEnv(lines, A, [valid[c] for c in start], [valid[c] for c in goal], slip, *rewards, mo.SOC)
     acts = rs.randint(0, 5, size=(1, A)).astype(np.uint8)
     exp = orc.transitions(tuple(int(c) for c in start), acts[0].tolist())
     assert len(exp) > 2000                                   # several windows below
@@ -1088,8 +1207,8 @@ def test_transitions_of_large_teams_come_in_windows():
     lines = ['......', '......', '......']
     starts = tuple((r, c) for r in range(2) for c in range(6))
     goals = tuple((2 - r, 5 - c) for r in range(2) for c in range(6))
-    menv = MapfEnv(MapfGrid(lines), 12, starts, goals, 0.1, -1000.0, 100.0, -1.0, OptimizationCriteria.Makespan)
-    orc = mo.OracleEnv(lines, 12, list(starts), list(goals), 0.1, -1000.0, 100.0, -1.0, mo.MAKESPAN)
+    menv = MapfEnv(MapfGrid(lines), 12, starts, goals, slip / 2, *rewards, OptimizationCriteria.Makespan)
+    orc = mo.OracleEnv(lines, 12, list(starts), list(goals), slip / 2, *rewards, mo.MAKESPAN)
     digits = [2] * 11 + [0]
     joint = sum(d * 5 ** i for i, d in enumerate(digits))
     got = menv.P[menv.s][joint]
@@ -1103,8 +1222,13 @@ def test_transitions_of_large_teams_come_in_windows():
     menv.close()
 
 
+def test_transitions_in_windows_with_inexact_constants():
+    """The same at slip 0.15 (0.075 through MapfEnv.P) with the INEXACT constants."""
+    test_transitions_of_large_teams_come_in_windows(slip=0.15, rewards=INEXACT)
+
+
 @pytest.mark.parametrize('n_agents', list(range(7, 17)))
-def test_every_transitions_kernel_instance_against_oracle(n_agents):
+def test_every_transitions_kernel_instance_against_oracle(n_agents, slip=0.2, rewards=EXACT):
     """mapf_transitions dispatches transitions_rows_kernel<2|4|6|8> up to 8 agents (the 1..6-agent instances: the test
     above) and an exact-size transitions_kernel instance for each of 9..16 (mapf_transitions.hip launch_transitions), each
     with reserved and with compacted rows: every one of them against the pinned Python oracle's enumeration
@@ -1120,8 +1244,8 @@ def test_every_transitions_kernel_instance_against_oracle(n_agents):
     start = np.stack([rs.choice(V, A, replace=False) for _ in range(E)]).astype(np.uint16)
     goal = np.stack([rs.choice(V, A, replace=False) for _ in range(E)]).astype(np.uint16)
     criteria = 'SoC' if A % 2 else 'Makespan'
-    env = VecMapfEnv(grid, A, None, None, 0.2, -1000.0, 100.0, -1.0, CRIT[criteria], start_local=start, goal_local=goal)
-    oracles = [mo.OracleEnv(lines, A, [valid[c] for c in start[e]], [valid[c] for c in goal[e]], 0.2, -1000.0, 100.0, -1.0,
+    env = VecMapfEnv(grid, A, None, None, slip, *rewards, CRIT[criteria], start_local=start, goal_local=goal)
+    oracles = [mo.OracleEnv(lines, A, [valid[c] for c in start[e]], [valid[c] for c in goal[e]], slip, *rewards,
                             OCRIT[criteria]) for e in range(E)]
     env_index = (np.arange(N) % E).astype(np.uint32)
     local = np.stack([rs.choice(V, A, replace=False) for _ in range(N)]).astype(np.uint16)
@@ -1156,6 +1280,103 @@ def test_every_transitions_kernel_instance_against_oracle(n_agents):
     assert name.startswith('transitions_rows_kernel<8>' if A <= 8 else 'transitions_kernel<%d,EXACT>' % A) and 'compacted' in name, name
     env.transitions(local, acts, max_branches=257, env_index=env_index)
     assert 'reserved' in env.last_kernel('transitions')
+    env.close()
+
+
+@pytest.mark.parametrize('n_agents', list(range(7, 17)))
+def test_every_transitions_kernel_instance_with_inexact_constants(n_agents):
+    """The same instances, reserved and compacted rows, at slip 0.15 with the INEXACT constants."""
+    test_every_transitions_kernel_instance_against_oracle(n_agents, slip=0.15, rewards=INEXACT)
+
+
+# ----------------------------------------------------------------------- mapf_transition_rewards as a batch
+def _reward_queries(rs, nbr, goal, env_index, N, A):
+    """N (prev, actions, next) triples: random distinct cells moved by random actions, then by turns -- k agents that sit on
+    their goal and STAY (k = 0 .. 6), a shared target cell, a swapped pair, everybody arriving on the goals, a swapped pair
+    among agents that all arrive on their goals, and action codes above 4 on agents that sit on their goal."""
+    V = nbr.shape[0]
+    prev = np.argsort(rs.rand(N, V), axis=1)[:, :A].astype(np.uint16)
+    acts = rs.randint(0, 5, size=(N, A)).astype(np.uint8)
+    for q in range(N):
+        g = goal[env_index[q]]
+        k = q % 7                                                 # agents on their goal that STAY (fewer where A is smaller)
+        on = rs.choice(A, min(k, A), replace=False)
+        free = [c for c in rs.permutation(V) if c not in set(g[on].tolist())][:A]
+        prev[q] = free
+        prev[q, on] = g[on]
+        acts[q, on] = 0
+        if q % 5 == 4 and len(on):
+            acts[q, on[0]] = rs.randint(5, 256)                   # out of range: read as STAY
+    nxt = nbr[prev.astype(np.int64), acts.clip(0, 4) * (acts <= 4)].astype(np.uint16)
+    for q in range(N):
+        g = goal[env_index[q]]
+        kind = (q // 7) % 6
+        if A >= 2:
+            i, j = rs.choice(A, 2, replace=False)
+        if kind == 1 and A >= 2:
+            nxt[q, j] = nxt[q, i]                                 # vertex collision
+        elif kind == 2 and A >= 2:
+            nxt[q, i], nxt[q, j] = prev[q, j], prev[q, i]         # swap
+        elif kind == 3:
+            nxt[q] = g                                            # everybody on its goal
+        elif kind == 4 and A >= 2:
+            nxt[q] = g                                            # ... and a swap among them: the collision wins
+            prev[q, i], prev[q, j] = g[j], g[i]
+    return prev, acts, nxt
+
+
+@pytest.mark.parametrize('per_env_goals', [True, False], ids=['env_index', 'broadcast_goal'])
+@pytest.mark.parametrize('criteria', ['Makespan', 'SoC'])
+@pytest.mark.parametrize('n_agents', [1, 2, 5, 16, 33])
+def test_transition_rewards_of_a_batch_against_oracle(n_agents, criteria, per_env_goals):
+    """mapf_transition_rewards with N = 1000 queries a call (three full blocks of 256 threads and a ragged fourth), 1 .. 33
+    agents, both criteria, constants (-0.3, 0.7, -0.1) on which ``(A - stayed) * r_living`` and ``r_x + living`` round;
+    goals per env through env_index (E = 7; the last env has two agents SHARE a goal cell) and one broadcast goal row without
+    env_index.  Every query's reward bits, done and collision against the plain restatement mo.transition_reward, which
+    tests/test_oracle_golden.py pins to the reference's recorded triples.  The batch must contain every outcome."""
+    A, N, E = n_agents, 1000, 7
+    rs = np.random.RandomState(3300 + A)
+    grid = MapfGrid([''.join('@' if rs.rand() < 0.15 else '.' for _ in range(12)) for _ in range(12)])
+    nbr = grid.tables()[2]
+    V = nbr.shape[0]
+    goals = np.argsort(rs.rand(E, V), axis=1)[:, :A].astype(np.uint16)
+    starts = np.argsort(rs.rand(E, V), axis=1)[:, :A].astype(np.uint16)
+    if A >= 2:
+        goals[E - 1, 1] = goals[E - 1, 0]
+    if per_env_goals:
+        env_index = rs.randint(0, E, size=N).astype(np.uint32)
+        start_arg, goal_arg, goal = starts, goals, goals
+    else:
+        env_index = None
+        start_arg, goal_arg, goal = starts[0].copy(), goals[0].copy(), goals[:1]
+    which = env_index if per_env_goals else np.zeros(N, np.int64)
+    prev, acts, nxt = _reward_queries(rs, nbr, goal, which, N, A)
+    env = VecMapfEnv(grid, A, None, None, 0.15, *INEXACT, CRIT[criteria], start_local=start_arg, goal_local=goal_arg, n_envs=E)
+    reward, done, coll = env.transition_rewards(prev, acts, nxt, env_index=env_index)
+    read = np.where(acts > 4, 0, acts)                            # include/mapf_hip.h: an action code above 4 is STAY
+    seen = dict(vertex=0, swap=0, goal=0, clash_on_goal=0, above4=int((acts > 4).sum()))
+    stayed_counts = set()
+    for q in range(N):
+        g = goal[which[q]].tolist()
+        p, n = prev[q].tolist(), nxt[q].tolist()
+        r, d, c, _ = mo.transition_reward(p, read[q].tolist(), n, g, INEXACT, OCRIT[criteria])
+        assert _bits(reward[q]) == _bits(r) and (bool(done[q]), bool(coll[q])) == (d, c), (A, criteria, q)
+        vertex = len(set(n)) < A
+        swap = any(p[i] == n[j] and p[j] == n[i] for i in range(A) for j in range(i + 1, A))
+        assert c == (vertex or swap)
+        seen['vertex'] += vertex
+        seen['swap'] += swap and not vertex
+        seen['goal'] += n == g and not c
+        seen['clash_on_goal'] += n == g and c
+        stayed_counts.add(sum(1 for i in range(A) if p[i] == g[i] and read[q, i] == 0))
+    assert seen['goal'] > 0 and seen['above4'] > 0, seen
+    assert A < 2 or (seen['vertex'] > 0 and seen['swap'] > 0 and seen['clash_on_goal'] > 0), seen
+    assert stayed_counts >= set(range(min(A, 6) + 1)), stayed_counts
+    # no query at all; reward only (include/mapf_hip.h: any out_* may be NULL)
+    r0, d0, c0 = env.transition_rewards(prev[:0], acts[:0], nxt[:0], env_index=None if env_index is None else env_index[:0])
+    assert r0.shape == d0.shape == c0.shape == (0,)
+    only, d1, c1 = env.transition_rewards(prev, acts, nxt, env_index=env_index, want_done=False, want_collision=False)
+    assert d1 is None and c1 is None and np.array_equal(_bits(only), _bits(reward))
     env.close()
 
 
@@ -1301,7 +1522,7 @@ def test_mixed_map_batch_in_one_launch_through_the_union_table():
     dev.close(), ref.close()
 
 
-def test_rollout_beyond_one_launch_is_issued_in_slices(monkeypatch):
+def test_rollout_beyond_one_launch_is_issued_in_slices(monkeypatch, rewards=EXACT):
     """The C ABI rejects a launch whose largest array exceeds 4 GiB or that has more than 65535 steps; VecMapfEnv.rollout
     then issues the steps as several launches over consecutive slices of the same arrays.  Forced here with a limit of
     five steps per launch: 13 recorded steps in three launches == the same 13 steps in one, and == the C oracle."""
@@ -1312,7 +1533,7 @@ def test_rollout_beyond_one_launch_is_issued_in_slices(monkeypatch):
     V, E, A, T = len(valid), 256, 8, 13
     start = np.argsort(rs.rand(E, V), axis=1)[:, :A].astype(np.uint16)
     goal = np.argsort(rs.rand(E, V), axis=1)[:, :A].astype(np.uint16)
-    mk = lambda: VecMapfEnv(grid, A, None, None, 0.2, -1000.0, 100.0, -1.0, OptimizationCriteria.SoC, seed=4, start_local=start, goal_local=goal)
+    mk = lambda: VecMapfEnv(grid, A, None, None, 0.2, *rewards, OptimizationCriteria.SoC, seed=4, start_local=start, goal_local=goal)
     one, sliced = mk(), mk()
     acts = np.stack([philox.random_actions_np(4, np.arange(E), t, A) for t in range(T)])
     whole = one.rollout(T, actions=acts, auto_reset=True, record=True)
@@ -1322,7 +1543,7 @@ def test_rollout_beyond_one_launch_is_issued_in_slices(monkeypatch):
         assert np.array_equal(whole[k], parts[k]), k
     for k in ('reward', 'prob', 'returns'):
         assert np.array_equal(_bits(whole[k]), _bits(parts[k])), k
-    co = c_oracle.COracle(nbr, A, start, goal, 0.2, -1000.0, 100.0, -1.0, mo.SOC, seed=4)
+    co = c_oracle.COracle(nbr, A, start, goal, 0.2, *rewards, mo.SOC, seed=4)
     ref = co.rollout(T, actions=acts, auto_reset=True)
     assert np.array_equal(_bits(parts['returns']), _bits(ref['returns'])) and np.array_equal(parts['episodes'], ref['episodes'])
     assert sliced.t == one.t == T and np.array_equal(sliced.get_state()[0], co.state)
@@ -1330,6 +1551,11 @@ def test_rollout_beyond_one_launch_is_issued_in_slices(monkeypatch):
     ref2 = co.rollout(7, auto_reset=True)
     assert np.array_equal(more['episodes'], ref['episodes'] + ref2['episodes'])
     one.close(), sliced.close()
+
+
+def test_rollout_in_slices_with_inexact_constants(monkeypatch):
+    """The same (SoC) with the INEXACT constants: the returns' chain runs on through the slices."""
+    test_rollout_beyond_one_launch_is_issued_in_slices(monkeypatch, rewards=INEXACT)
 
 
 def test_mapf_tune_is_the_one_override_and_rejects_what_it_does_not_know(monkeypatch):

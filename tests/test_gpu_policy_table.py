@@ -15,6 +15,9 @@ from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
 
 pytestmark = pytest.mark.gpu
 R = (-1000.0, 100.0, -1.0)
+# constants on which float64 rounds (see tests/test_gpu_parity.py): n * living, r_x + living and the returns' sums have one
+# admissible operation order each, and any other changes bits
+INEXACT = (-0.3, 0.7, -0.1)
 CRIT = {'Makespan': (OptimizationCriteria.Makespan, mo.MAKESPAN), 'SoC': (OptimizationCriteria.SoC, mo.SOC)}
 
 
@@ -78,13 +81,13 @@ def _check_totals(res, refs, tag, base=None):
 
 
 def _run_parity(grid, nbr, start, goal, A, table, rows, criteria='Makespan', kernel='auto', T=24, fail_prob=0.2, seed=21,
-                expect=None, device_arrays=False, offset=0):
+                expect=None, device_arrays=False, offset=0, rewards=R):
     """record rollout + totals-only rollout + accumulate, all against the oracle; returns (goal episodes, collision episodes)."""
     crit, ocrit = CRIT[criteria]
     E = max(start.shape[0], goal.shape[0]) if start.ndim == 2 else 1
-    env = VecMapfEnv(grid, A, None, None, fail_prob, *R, crit, seed=seed, start_local=start, goal_local=goal, kernel=kernel,
+    env = VecMapfEnv(grid, A, None, None, fail_prob, *rewards, crit, seed=seed, start_local=start, goal_local=goal, kernel=kernel,
                      device_arrays=device_arrays, env_id_offset=offset)
-    co = c_oracle.COracle(nbr, A, start, goal, fail_prob, *R, ocrit, seed=seed, env_id_offset=offset)
+    co = c_oracle.COracle(nbr, A, start, goal, fail_prob, *rewards, ocrit, seed=seed, env_id_offset=offset)
     E = env.n_envs
     env.set_policy('table', table=table, rows=rows)
     assert env.policy == 'table'
@@ -127,26 +130,43 @@ def _random_case(A, E, seed, broadcast_rows=False, n_rows=9):
     return grid, nbr, start, goal, table, rows
 
 
-@pytest.mark.parametrize('n_agents,n_envs,kernel,criteria,expect', [
+TABLE_CASES = [
     (2, 300, 'thread_per_env', 'Makespan', 'rollout_kernel_table<A=2'), (5, 300, 'thread_per_env', 'SoC', 'rollout_kernel_table<A=5'),
     (3, 257, 'lane_group', 'Makespan', 'lg_rollout_kernel_table<L=2,RAGGED'), (40, 64, 'lane_group', 'SoC', 'lg_rollout_kernel_table<L=32'),
     (128, 16, 'lane_group', 'Makespan', 'lg_rollout_kernel_table<L=64'), (7, 1000, 'auto', 'SoC', 'lg_rollout_kernel_table<L=4,RAGGED'),
-])
-def test_random_table_in_the_thread_per_env_and_lane_group_kernels(n_agents, n_envs, kernel, criteria, expect):
+]
+
+
+@pytest.mark.parametrize('n_agents,n_envs,kernel,criteria,expect', TABLE_CASES)
+def test_random_table_in_the_thread_per_env_and_lane_group_kernels(n_agents, n_envs, kernel, criteria, expect, rewards=R):
     grid, nbr, start, goal, table, rows = _random_case(n_agents, n_envs, 800 + n_agents, broadcast_rows=(n_agents == 5))
-    _run_parity(grid, nbr, start, goal, n_agents, table, rows, criteria=criteria, kernel=kernel, expect=expect, T=20)
+    _run_parity(grid, nbr, start, goal, n_agents, table, rows, criteria=criteria, kernel=kernel, expect=expect, T=20, rewards=rewards)
+
+
+@pytest.mark.parametrize('n_agents,n_envs,kernel,criteria,expect', TABLE_CASES)
+def test_random_table_with_inexact_constants_in_the_thread_per_env_and_lane_group_kernels(n_agents, n_envs, kernel, criteria, expect):
+    test_random_table_in_the_thread_per_env_and_lane_group_kernels(n_agents, n_envs, kernel, criteria, expect, rewards=INEXACT)
+
+
+PACKED_TABLE_CASES = [
+    (8, 8192, 'Makespan', 'lq_rollout_kernel_table<Q=4,K=2'), (8, 16448, 'SoC', 'lq_rollout_kernel_table<Q=4,K=2'),
+    (16, 4096, 'Makespan', 'lq_rollout_kernel_table<Q=8,K=2'),
+]
 
 
 @pytest.mark.parametrize('lds', [0, 1])
-@pytest.mark.parametrize('n_agents,n_envs,criteria,expect', [
-    (8, 8192, 'Makespan', 'lq_rollout_kernel_table<Q=4,K=2'), (8, 16448, 'SoC', 'lq_rollout_kernel_table<Q=4,K=2'),
-    (16, 4096, 'Makespan', 'lq_rollout_kernel_table<Q=8,K=2'),
-])
-def test_random_table_in_the_packed_kernels_both_table_forms(monkeypatch, n_agents, n_envs, criteria, expect, lds):
+@pytest.mark.parametrize('n_agents,n_envs,criteria,expect', PACKED_TABLE_CASES)
+def test_random_table_in_the_packed_kernels_both_table_forms(monkeypatch, n_agents, n_envs, criteria, expect, lds, rewards=R):
     set_tune(monkeypatch, policy_table_lds=lds)
     grid, nbr, start, goal, table, rows = _random_case(n_agents, n_envs, 820 + n_agents, broadcast_rows=(n_envs == 16448))
-    _, _, name = _run_parity(grid, nbr, start, goal, n_agents, table, rows, criteria=criteria, expect=expect, T=20)
+    _, _, name = _run_parity(grid, nbr, start, goal, n_agents, table, rows, criteria=criteria, expect=expect, T=20, rewards=rewards)
     assert ('TABLE_LDS' if lds else 'TABLE_GLOBAL') in name, name
+
+
+@pytest.mark.parametrize('lds', [0, 1])
+@pytest.mark.parametrize('n_agents,n_envs,criteria,expect', PACKED_TABLE_CASES)
+def test_random_table_with_inexact_constants_in_the_packed_kernels_both_table_forms(monkeypatch, n_agents, n_envs, criteria, expect, lds):
+    test_random_table_in_the_packed_kernels_both_table_forms(monkeypatch, n_agents, n_envs, criteria, expect, lds, rewards=INEXACT)
 
 
 @pytest.mark.parametrize('k', [2, 4])

@@ -14,6 +14,9 @@ from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
 
 pytestmark = pytest.mark.gpu
 R = (-1000.0, 100.0, -1.0)
+# constants on which float64 rounds (see tests/test_gpu_parity.py): a fused or re-associated r_x + (A - stayed) * r_living
+# changes bits with these, never with R
+INEXACT = (-0.3, 0.7, -0.1)
 
 
 def _bits(x):
@@ -36,16 +39,16 @@ def _check(out, ref, tag, local=True):
 
 
 @pytest.mark.parametrize('criteria', ['Makespan', 'SoC'])
-def test_graph_replay_of_recorded_steps_matches_the_oracle(criteria):
+def test_graph_replay_of_recorded_steps_matches_the_oracle(criteria, rewards=R):
     """16 mapf_step calls recorded once, replayed 6 times = 96 env-steps of 2048 room-32-32-4 envs (the bench workload's
     tables, six scenarios -> scenario table): every step of every replay against the C oracle.  The odd nodes leave
     out_local out and are checked through the state view the next node would read."""
     E, A, N = 2048, 8, 16
     grid, _, nbr, start, goal = _c3_tables(E, 4096)
     crit, ocrit = (OptimizationCriteria.SoC, mo.SOC) if criteria == 'SoC' else (OptimizationCriteria.Makespan, mo.MAKESPAN)
-    env = VecMapfEnv(grid, A, None, None, 0.2, *R, crit, seed=7, env_id_offset=4096, device_arrays=True,
+    env = VecMapfEnv(grid, A, None, None, 0.2, *rewards, crit, seed=7, env_id_offset=4096, device_arrays=True,
                      start_local=start, goal_local=goal)
-    co = c_oracle.COracle(nbr, A, start, goal, 0.2, *R, ocrit, seed=7, env_id_offset=4096)
+    co = c_oracle.COracle(nbr, A, start, goal, 0.2, *rewards, ocrit, seed=7, env_id_offset=4096)
     actions = env.fill_random_actions(0, N)
     env.sync()
     acts_host = actions.cpu().numpy()
@@ -88,6 +91,11 @@ def test_graph_replay_of_recorded_steps_matches_the_oracle(criteria):
     _check(dict(local=local, reward=reward, done=done, **info), co.step(acts_host[5], auto_reset=True), 'plain after graph')
     graph.close()
     env.close()
+
+
+@pytest.mark.parametrize('criteria', ['Makespan', 'SoC'])
+def test_graph_replay_of_recorded_steps_with_inexact_constants(criteria):
+    test_graph_replay_of_recorded_steps_matches_the_oracle(criteria, rewards=INEXACT)
 
 
 def test_graph_of_rollout_and_steps_and_host_side_index_moves():
@@ -168,7 +176,7 @@ def test_scenario_table_step_equals_plain_rows(monkeypatch, n_agents, n_envs):
 
 
 @pytest.mark.parametrize('big', ['2', '2k4', '0'])
-def test_single_step_at_a_batch_larger_than_the_device_holds(monkeypatch, big):
+def test_single_step_at_a_batch_larger_than_the_device_holds(monkeypatch, big, rewards=R):
     """393216 envs x 8 agents: more than an MI355X holds at once.  MAPF_TUNE step_big=2 forces the form the library uses from
     1 M envs on -- a resident grid of 512 blocks of 1024 threads with the move table in LDS, walking 768 chunks (half
     of the blocks take two) -- step_big=0 the one-block-per-256-lanes form.  Six steps against the C oracle, the
@@ -181,8 +189,8 @@ def test_single_step_at_a_batch_larger_than_the_device_holds(monkeypatch, big):
     grid, _, nbr, start, goal = _c3_tables(E)
     import philox
     ids = np.arange(E)
-    env = VecMapfEnv(grid, A, None, None, 0.2, *R, OptimizationCriteria.SoC, seed=3, start_local=start, goal_local=goal)
-    co = c_oracle.COracle(nbr, A, start, goal, 0.2, *R, mo.SOC, seed=3)
+    env = VecMapfEnv(grid, A, None, None, 0.2, *rewards, OptimizationCriteria.SoC, seed=3, start_local=start, goal_local=goal)
+    co = c_oracle.COracle(nbr, A, start, goal, 0.2, *rewards, mo.SOC, seed=3)
     env.set_state(np.ascontiguousarray(start))            # (same cells; the library no longer knows they are not terminal)
     for t in range(6):
         acts = philox.random_actions_np(3, ids, t, A)
@@ -196,6 +204,13 @@ def test_single_step_at_a_batch_larger_than_the_device_holds(monkeypatch, big):
         assert ('NO_TERMINAL' in name) == (t > 0), name
     assert np.array_equal(env.get_state()[0], co.state)
     env.close()
+
+
+@pytest.mark.parametrize('big', ['2', '2k4', '0'])
+def test_single_step_at_a_large_batch_with_inexact_constants(monkeypatch, big):
+    """The same three forms under SoC with the INEXACT constants: the living reward (A - stayed) * r_living and its sum with
+    r_clash / r_goal round, once each."""
+    test_single_step_at_a_batch_larger_than_the_device_holds(monkeypatch, big, rewards=INEXACT)
 
 
 @pytest.mark.parametrize('n_agents,n_envs', [(4, 4096), (16, 1024), (32, 512)])

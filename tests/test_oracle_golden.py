@@ -52,6 +52,71 @@ def test_transition_tables_match_reference():
                 assert str(mo.encode_mixed_radix(nxt, env.V)) == exp['s']
 
 
+def test_inexact_transition_tables_match_reference():
+    """The same env.P queries as 'small_soc_three' above, recorded under constants on which float64 rounds: SoC at slip 0.3
+    with (-33.3, 7.7, -0.1), Makespan at slip 0.15 with (-0.3, 0.7, -0.1) -- the product chain of the probabilities and
+    ``r_x + (A - stayed) * r_living`` have one admissible operation order each."""
+    tabs = load_json('inexact_cases.json')['transition_tables']
+    assert [(t['criteria'], t['fail_prob'], t['r_clash'], t['r_goal'], t['r_living']) for t in tabs] == [
+        ('SoC', 0.3, -33.3, 7.7, -0.1), ('Makespan', 0.15, -0.3, 0.7, -0.1)]
+    for tab in tabs:
+        env = mo.OracleEnv(tab['lines'], len(tab['starts']), tab['starts'], tab['goals'],
+                           tab['fail_prob'], tab['r_clash'], tab['r_goal'], tab['r_living'],
+                           CRIT[tab['criteria']])
+        assert len(tab['rows']) == 9
+        for row in tab['rows']:
+            got = env.transitions(tuple(row['local']), row['actions'])
+            assert len(got) == len(row['transitions']), tab['name']
+            for ((p, c), nxt, r, d), exp in zip(got, row['transitions']):
+                assert _bits(p) == _bits(exp['prob'])
+                assert c == exp['collision'] and d == exp['done']
+                assert list(nxt) == exp['next_local']
+                assert _bits(r) == _bits(exp['reward'])
+                assert str(mo.encode_mixed_radix(nxt, env.V)) == exp['s']
+
+
+def _reward_helper_cases():
+    return load_json('host_api_cases.json')['transition_reward_helpers'] + load_json('inexact_cases.json')['transition_reward_helpers']
+
+
+def test_transition_reward_restatement_matches_reference():
+    """mo.transition_reward (the plain function the batched mapf_transition_rewards test compares against) on the
+    reference's recorded (prev, joint action, next) triples: exact and inexact constants, both criteria."""
+    cases = _reward_helper_cases()
+    assert [(c['criteria'], c['rewards']) for c in cases][-1] == ('SoC', [-0.3, 0.7, -0.1]) and len(cases) == 4
+    for case in cases:
+        env = mo.OracleEnv(case['lines'], 3, case['starts'], case['goals'], case['fail_prob'], *case['rewards'],
+                           CRIT[case['criteria']])
+        assert len(case['cases']) == 7
+        for c in case['cases']:
+            acts = mo.decode_mixed_radix(c['action'], mo.N_ACTIONS, 3)             # vector_action_to_integer: first agent least significant
+            r, d, coll, living = mo.transition_reward(c['prev_local'], acts, c['next_local'], env.goal, case['rewards'],
+                                                      CRIT[case['criteria']])
+            assert _bits(r) == _bits(c['reward']) and _bits(living) == _bits(c['living']), (case['rewards'], c)
+            assert (d, coll) == (c['done'], c['collision']) and coll == c['is_collision']
+            assert (r, d, coll) == env.transition_reward(tuple(c['prev_local']), acts, tuple(c['next_local']))
+
+
+def test_inexact_constants_survive_the_json_round_trip():
+    """The constants the inexact sets were recorded with, bit for bit after json.dump / json.load: in particular the
+    subnormal living reward is -2^-1074 (not zero) and the slip rate of the 1/3 set is the double 1.0 / 3.0."""
+    want = {'inexact_goals_a8_slip03_soc': (0.3, 'SoC', -33.3, 7.7, -0.1),
+            'inexact_goals_a32_slip015_makespan': (0.15, 'Makespan', -0.3, 0.7, -0.1),
+            'inexact_goals_a16_slip13_soc_noreset': (1.0 / 3.0, 'SoC', -1e-3, 1e-3, -2.0 ** -1074),
+            'inexact_goals_a4_slip07_makespan': (0.7, 'Makespan', -0.3, 0.7, -0.1),
+            'inexact_tiny_a2_slip015': (0.15, 'SoC', -1.1, 2.3, -0.7)}
+    for name, (fp, crit, rc, rg, rl) in want.items():
+        meta = load_json(name + '.json')
+        assert meta['criteria'] == crit, name
+        for key, value in (('fail_prob', fp), ('r_clash', rc), ('r_goal', rg), ('r_living', rl)):
+            assert isinstance(meta[key], float) and _bits(meta[key]) == _bits(value), (name, key, meta[key])
+    sub = load_json('inexact_goals_a16_slip13_soc_noreset.json')
+    assert sub['r_living'] != 0.0 and sub['r_living'] == -2.0 ** -1074 and sub['r_living'] / 2 == 0.0
+    assert sub['fail_prob'] == 1.0 / 3.0 and sub['auto_reset'] is False
+    helper = load_json('inexact_cases.json')['transition_reward_helpers']
+    assert len(helper) == 1 and helper[0]['criteria'] == 'SoC' and [_bits(x) for x in helper[0]['rewards']] == [_bits(x) for x in (-0.3, 0.7, -0.1)]
+
+
 def test_trajectories_match_reference(trajectory_set):
     meta, g = trajectory_set
     A, T = meta['n_agents'], meta['T']
