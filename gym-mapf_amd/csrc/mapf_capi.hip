@@ -321,7 +321,7 @@ int mapf_debug_rollout_plan(uint32_t n_cells, int n_agents, uint64_t n_envs, uin
     args.mv4 = delta_rows ? reinterpret_cast<const uint32_t *>(&present) : nullptr;
     mapf::LqPlan plan;
     const bool packed = mapf::plan_rollout_lq(n_agents, args, t, &plan);
-    out[0] = uint64_t(plan.K); out[1] = uint64_t(plan.Q); out[2] = uint64_t(plan.form);
+    out[0] = uint64_t(plan.K); out[1] = uint64_t(plan.Q); out[2] = uint64_t(int(plan.form));
     out[3] = plan.block; out[4] = plan.lds_bytes; out[5] = plan.lds_total;
     return packed ? 1 : 0;
 }

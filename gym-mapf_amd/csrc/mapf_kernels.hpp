@@ -254,9 +254,9 @@ hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const Rollou
 // holds its instance (mapf_dispatch.hip); true when it took the launch (*err = its status)
 bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy *table = nullptr);
 // ... the launchers of those objects: mapf_lq_rollout.hip compiled once per (agents per lane, recording) pair; form, block, lds_bytes,
-// table_lds, table_at: the plan's answers
+enum class TableForm : int;   // table_lds, table_at: the plan's answers (TableForm: mapf_layout.hpp)
 #define MAPF_LQ_LAUNCHER(name)                                                                                                          \
-    hipError_t name(int Q, int form, const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream, \
+    hipError_t name(int Q, TableForm form, const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream, \
                     const TablePolicy *table, bool table_lds, uint32_t table_at);
 MAPF_LQ_LAUNCHER(launch_rollout_lq_k8_r1) MAPF_LQ_LAUNCHER(launch_rollout_lq_k8_r0) MAPF_LQ_LAUNCHER(launch_rollout_lq_k4_r1)
 MAPF_LQ_LAUNCHER(launch_rollout_lq_k4_r0) MAPF_LQ_LAUNCHER(launch_rollout_lq_k2_r1) MAPF_LQ_LAUNCHER(launch_rollout_lq_k2_r0)

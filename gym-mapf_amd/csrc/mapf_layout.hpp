@@ -13,9 +13,9 @@ static_assert(sizeof(SlipRow) * 8 + sizeof(OutcomeRow) * 16 <= kLdsReserve, "sta
 
 // packed rollout (mapf_lq_rollout.hip): slip rows at 0, outcome rows behind them, move table at 1024 with SIX columns per cell
 constexpr uint32_t kSlipAt = 0, kOutcomeAt = sizeof(SlipRow) * 8, kMoveAt = kLdsReserve, kMoveCols = 6;
-constexpr uint32_t kCompactCols = 5, kCompactEntry = 8;   // COMPACT: cells + code only, no sixth column
-constexpr uint32_t kBitmapCols = 4;                       // COMPACT + BITMAP == 1: no STAY column either
-constexpr uint32_t kDeltaEntry = 4;                       // COMPACT + BITMAP == 3: 4-byte delta rows, six columns (kDeltaCols, mapf_kernels.hpp: STAY twice, as the full table)
+constexpr uint32_t kCompactCols = 5, kCompactEntry = 8;   // 8-byte rows: cells + code only, no sixth column
+constexpr uint32_t kBitmapCols = 4;                       // ... in front of 128 bitmaps: no STAY column either
+constexpr uint32_t kDeltaEntry = 4;                       // 4-byte delta rows, six columns (kDeltaCols, mapf_kernels.hpp: STAY twice, as the full table)
 static_assert(kOutcomeAt + sizeof(OutcomeRow) * 16 <= kMoveAt, "LDS image: slip rows, outcome rows, then the move table");
 
 // packed single step, LDS-table forms (mapf_lq_step.hip BIG): the same image, the table at the same place
@@ -25,6 +25,65 @@ static_assert(kOutcomeAt + sizeof(OutcomeRow) * 16 <= kMoveAt, "LDS image: slip 
 constexpr uint32_t kStepMoveAt = kMoveAt, kBigCols = MAPF_BIG_COLS;
 
 // bytes of one env's occupancy bitmap (BITMAP instances): one bit per cell, padded to 16 bytes
-inline size_t bitmap_stride(uint32_t n_cells) { return (size_t((n_cells + 31u) / 32u) * 4u + 15u) & ~size_t(15); }
+constexpr size_t bitmap_stride(uint32_t n_cells) { return (size_t((n_cells + 31u) / 32u) * 4u + 15u) & ~size_t(15); }
+
+// The six forms in which the packed rollout keeps the move table in LDS -- ONE description for the planner, the launcher and the
+// kernels (DESIGN.md 4.1 has the table).  The values are the ABI's `form` numbers (mapf_debug_rollout_plan's out[2]).
+enum class TableForm : int { FullRows = 0, Rows8 = 1, Rows8x4Bitmap = 2, Rows8x5Bitmap = 3, FullRowsBitmap = 4, DeltaRowsBitmap = 5 };
+constexpr int kTableForms = 6;
+struct TableFormTraits {
+    bool compact; int bitmap;        // the kernel's (COMPACT, BITMAP) template arguments (BITMAP != 0: per-env occupancy bitmaps follow the table)
+    uint32_t cols, entry_bytes;      // columns per cell, bytes per entry
+    const char *tag, *note;          // what the kernel's name (mapf_last_kernel) says about the form: the tag among its arguments, the note in its parentheses
+};
+constexpr TableFormTraits table_form_traits(TableForm form) {
+    switch (form) {
+        case TableForm::Rows8:           return {true, 0, kCompactCols, kCompactEntry, "", ", 8-byte table rows"};
+        case TableForm::Rows8x4Bitmap:   return {true, 1, kBitmapCols, kCompactEntry, ",BITMAP", ", 8-byte table rows without the STAY column"};
+        case TableForm::Rows8x5Bitmap:   return {true, 2, kCompactCols, kCompactEntry, ",BITMAP5", ", 8-byte table rows"};
+        case TableForm::FullRowsBitmap:  return {false, 2, kMoveCols, uint32_t(sizeof(MoveEntry)), ",BITMAP", ""};
+        case TableForm::DeltaRowsBitmap: return {true, 3, kDeltaCols, kDeltaEntry, ",BITMAPD", ", 4-byte delta rows"};
+        default:                         return {false, 0, kMoveCols, uint32_t(sizeof(MoveEntry)), "", ""};   // FullRows
+    }
+}
+// ... and back: the form a kernel instance <COMPACT, BITMAP> reads
+constexpr int find_table_form(bool compact, int bitmap) {
+    for (int f = 0; f < kTableForms; ++f)
+        if (table_form_traits(TableForm(f)).compact == compact && table_form_traits(TableForm(f)).bitmap == bitmap) return f;
+    return -1;
+}
+template <bool COMPACT, int BITMAP>
+constexpr TableForm table_form_of() {
+    static_assert(find_table_form(COMPACT, BITMAP) >= 0, "(COMPACT, BITMAP) names none of the six table forms");
+    return TableForm(find_table_form(COMPACT, BITMAP));
+}
+// the kernel's LDS image up to the table's end (delta rows: the host-built image, zero-padded to 16 bytes), and the dynamic LDS
+// segment of a launch: the image, then one bitmap per env of the block where the form has them
+constexpr size_t table_image_bytes(TableForm form, uint32_t n_cells) {
+    const TableFormTraits f = table_form_traits(form);
+    return kMoveAt + (form == TableForm::DeltaRowsBitmap ? delta_table_words(n_cells) : size_t(n_cells) * f.cols) * f.entry_bytes;
+}
+constexpr size_t launch_lds_bytes(TableForm form, uint32_t n_cells, unsigned block, int Q) {
+    return table_image_bytes(form, n_cells) + (table_form_traits(form).bitmap ? size_t(block / unsigned(Q)) * bitmap_stride(n_cells) : 0u);
+}
+
+// Which instances of the packed rollout kernels exist: X(K, Q, form) per family (each: streamed actions and the in-kernel policies, every criteria /
+// terminal variant, recording or not).  mapf_lq_rollout.hip generates its dispatch from these lists, in this order; mapf_plan.hip plans nothing else.
+#define MAPF_LQ_ROLLOUT_INSTANCES(X)                                                                                       \
+    X(8, 4, Rows8) X(8, 1, FullRows) X(8, 2, FullRows) X(8, 4, FullRows)                                                   \
+    X(4, 8, DeltaRowsBitmap) X(4, 8, FullRowsBitmap) X(4, 8, Rows8x5Bitmap) X(4, 8, Rows8x4Bitmap)                         \
+    X(4, 4, Rows8) X(4, 8, Rows8) X(4, 16, Rows8)                                                                          \
+    X(4, 1, FullRows) X(4, 2, FullRows) X(4, 4, FullRows) X(4, 8, FullRows) X(4, 16, FullRows)                             \
+    X(2, 2, FullRows) X(2, 4, FullRows) X(2, 8, FullRows) X(2, 16, FullRows)
+// ... of lq_rollout_kernel_table (the table policy): full rows with two or four agents per lane, the 32-agent delta-row form
+#define MAPF_LQ_ROLLOUT_TABLE_INSTANCES(X)                                                                                 \
+    X(4, 8, DeltaRowsBitmap) X(4, 1, FullRows) X(4, 2, FullRows) X(4, 4, FullRows) X(4, 8, FullRows)                       \
+    X(2, 2, FullRows) X(2, 4, FullRows) X(2, 8, FullRows) X(2, 16, FullRows)
+constexpr bool lq_rollout_instance_exists(int K, int Q, TableForm form, bool table_policy) {
+#define X(KK, QQ, FF) if (K == KK && Q == QQ && form == TableForm::FF) return true;
+    if (table_policy) { MAPF_LQ_ROLLOUT_TABLE_INSTANCES(X) } else { MAPF_LQ_ROLLOUT_INSTANCES(X) }
+#undef X
+    return false;
+}
 
 }  // namespace mapf

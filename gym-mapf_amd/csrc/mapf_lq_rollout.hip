@@ -86,15 +86,20 @@ static_assert(offsetof(SlipRow, thr) % 8 == 0 && kZeroFactor < 128u, "a zero fac
 
 #undef env_id
 
-template <int Q, int K, bool RECORD, bool STREAM, bool COMPACT = false, int BITMAP = 0>
+constexpr const char *kBitmapNote = ", collisions through per-env occupancy bitmaps";
+// One family of instances, launched as planned: FORM's traits (mapf_layout.hpp) give the kernel's (COMPACT, BITMAP), the LDS segment
+// and what the kernel's name says; lds_bytes: the image up to the table's end
+template <int Q, int K, bool RECORD, bool STREAM, TableForm FORM>
 hipError_t launch_impl(const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream) {
+    constexpr TableFormTraits form = table_form_traits(FORM);
+    constexpr bool COMPACT = form.compact; constexpr int BITMAP = form.bitmap;   // the kernel's template arguments
     // (criteria, may-be-terminal): the instance without terminal handling exists for Makespan only
     const bool term = !(args.auto_reset && !args.start_terminal_any);
     auto kern = args.c.criteria != 0u ? lq_rollout_kernel<Q, K, RECORD, STREAM, true, COMPACT, true, BITMAP>
                 : term            ? lq_rollout_kernel<Q, K, RECORD, STREAM, false, COMPACT, true, BITMAP>
                                   : lq_rollout_kernel<Q, K, RECORD, STREAM, false, COMPACT, false, BITMAP>;
     const uint32_t bitmap_base = uint32_t(lds_bytes);           // the bitmaps follow the table
-    if (BITMAP) lds_bytes += size_t(block / unsigned(Q)) * bitmap_stride(args.c.n_cells);
+    lds_bytes = launch_lds_bytes(FORM, args.c.n_cells, block, Q);
     if (lds_bytes > 32 * 1024) {
         // (this kernel has no static LDS object: its dynamic segment may be the CU's whole 160 KB -- the limit every form's
         // "does it fit" test in plan_rollout_lq compares against)
@@ -103,18 +108,17 @@ hipError_t launch_impl(const RolloutArgs &args, uint32_t A, unsigned block, size
     const unsigned grid = unsigned(args.n_envs / (block / unsigned(Q)));
     note_kernel("lq_rollout_kernel<Q=%d,K=%d,%s,%s,%s%s%s%s> block=%u (packed layout: %d agents per lane%s%s)", Q, K, RECORD ? "RECORD" : "TOTALS",
                 STREAM ? "STREAM" : "POLICY", args.c.criteria != 0u ? "SOC" : "MAKESPAN", COMPACT ? ",COMPACT" : "",
-                (args.c.criteria == 0u && !term) ? ",NO_TERMINAL" : "", (BITMAP == 2 && COMPACT) ? ",BITMAP5" : (BITMAP == 3 ? ",BITMAPD" : (BITMAP ? ",BITMAP" : "")), block, K,
-                COMPACT ? (BITMAP == 3 ? ", 4-byte delta rows" : (BITMAP == 1 ? ", 8-byte table rows without the STAY column" : ", 8-byte table rows")) : "",
-                BITMAP ? ", collisions through per-env occupancy bitmaps" : "");
+                (args.c.criteria == 0u && !term) ? ",NO_TERMINAL" : "", form.tag, block, K, form.note, BITMAP ? kBitmapNote : "");
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds_bytes, stream, args, A, bitmap_base);
     return hipGetLastError();
 }
 
-#if MAPF_LQ_K != 8
 // the launcher of the table instances; table_lds / table_at / lds_total: plan_rollout_lq_table's answers
-template <int Q, int K, bool RECORD, bool COMPACT = false, int BITMAP = 0>
+template <int Q, int K, bool RECORD, TableForm FORM>
 hipError_t launch_impl_table(const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream, const TablePolicy &tp, bool table_lds,
                              uint32_t table_at) {
+    constexpr TableFormTraits form = table_form_traits(FORM);
+    constexpr bool COMPACT = form.compact; constexpr int BITMAP = form.bitmap;
     const bool term = !(args.auto_reset && !args.start_terminal_any);
     auto pick = [&](auto tag) {
         constexpr int T = decltype(tag)::value;
@@ -124,7 +128,7 @@ hipError_t launch_impl_table(const RolloutArgs &args, uint32_t A, unsigned block
     };
     auto kern = table_lds ? pick(std::integral_constant<int, 2>{}) : pick(std::integral_constant<int, 1>{});
     const uint32_t bitmap_base = uint32_t(lds_bytes);           // the bitmaps follow the image, the policy table follows them
-    if (BITMAP) lds_bytes += size_t(block / unsigned(Q)) * bitmap_stride(args.c.n_cells);
+    lds_bytes = launch_lds_bytes(FORM, args.c.n_cells, block, Q);
     if (table_lds) {
         if (table_at < lds_bytes || (table_at & 15u) != 0u) return hipErrorInvalidValue;
         lds_bytes = size_t(table_at) + ((size_t(tp.table_bytes) + 15u) & ~size_t(15));
@@ -136,13 +140,36 @@ hipError_t launch_impl_table(const RolloutArgs &args, uint32_t A, unsigned block
     const unsigned grid = unsigned(args.n_envs / (block / unsigned(Q)));
     note_kernel("lq_rollout_kernel_table<Q=%d,K=%d,%s,TABLE,%s%s%s%s,%s> block=%u (packed layout: %d agents per lane%s%s; table policy: %u action bytes %s)", Q, K,
                 RECORD ? "RECORD" : "TOTALS", args.c.criteria != 0u ? "SOC" : "MAKESPAN", COMPACT ? ",COMPACT" : "",
-                (args.c.criteria == 0u && !term) ? ",NO_TERMINAL" : "", BITMAP == 3 ? ",BITMAPD" : "", table_lds ? "TABLE_LDS" : "TABLE_GLOBAL", block, K,
-                BITMAP == 3 ? ", 4-byte delta rows" : "", BITMAP ? ", collisions through per-env occupancy bitmaps" : "", tp.table_bytes,
-                table_lds ? "staged into LDS behind the image" : "gathered from global memory");
+                (args.c.criteria == 0u && !term) ? ",NO_TERMINAL" : "", form.tag, table_lds ? "TABLE_LDS" : "TABLE_GLOBAL", block, K,
+                form.note, BITMAP ? kBitmapNote : "", tp.table_bytes, table_lds ? "staged into LDS behind the image" : "gathered from global memory");
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds_bytes, stream, args, A, bitmap_base, tp, table_lds ? table_at : 0u);
     return hipGetLastError();
 }
-#endif
+
+// The instances of one object -- K agents per lane, recording or not -- by the lists of mapf_layout.hpp (what lq_rollout_instance_exists
+// answers from): a launch whose (Q, form) is in none of this K's lines is refused.  (A template, so that the lines of the other
+// K's are discarded, not instantiated.)
+template <int K, bool R>
+hipError_t launch_planned(int Q, TableForm form, const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream,
+                          const TablePolicy *table, bool table_lds, uint32_t table_at) {
+    if (table && !args.actions) {
+#define X(KK, QQ, FF)                                                                                                                        \
+    if constexpr (KK == K) {                                                                                                                 \
+        if (Q == QQ && form == TableForm::FF) return launch_impl_table<QQ, K, R, TableForm::FF>(args, A, block, lds_bytes, stream, *table, table_lds, table_at); \
+    }
+        MAPF_LQ_ROLLOUT_TABLE_INSTANCES(X)
+#undef X
+        return hipErrorInvalidValue;
+    }
+#define X(KK, QQ, FF)                                                                                                                        \
+    if constexpr (KK == K) {                                                                                                                 \
+        if (Q == QQ && form == TableForm::FF) return args.actions ? launch_impl<QQ, K, R, true, TableForm::FF>(args, A, block, lds_bytes, stream)     \
+                                                                  : launch_impl<QQ, K, R, false, TableForm::FF>(args, A, block, lds_bytes, stream);   \
+    }
+    MAPF_LQ_ROLLOUT_INSTANCES(X)
+#undef X
+    return hipErrorInvalidValue;
+}
 
 }  // namespace
 
@@ -154,90 +181,9 @@ hipError_t launch_impl_table(const RolloutArgs &args, uint32_t A, unsigned block
 #define MAPF_LQ_CAT3(a, b, c) a##b##_r##c
 #define MAPF_LQ_NAME(k, r) MAPF_LQ_CAT3(launch_rollout_lq_k, k, r)
 
-hipError_t MAPF_LQ_NAME(MAPF_LQ_K, MAPF_LQ_RECORD)(int Q, int form, const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream,
+hipError_t MAPF_LQ_NAME(MAPF_LQ_K, MAPF_LQ_RECORD)(int Q, TableForm form, const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream,
                                                    const TablePolicy *table, bool table_lds, uint32_t table_at) {
-    constexpr int K = MAPF_LQ_K;
-    constexpr bool R = MAPF_LQ_RECORD != 0;
-    const bool stream_actions = args.actions != nullptr;
-    if (table && !stream_actions) {
-        // the table instances: what plan_rollout_lq_table plans, nothing else is instantiated
-#if MAPF_LQ_K == 8
-        return hipErrorInvalidValue;
-#else
-#if MAPF_LQ_K == 4
-        if (form == 5 && Q == 8) return launch_impl_table<8, K, R, true, 3>(args, A, block, lds_bytes, stream, *table, table_lds, table_at);
-#endif
-        if (form != 0) return hipErrorInvalidValue;
-        switch (Q) {
-#define X(QQ) case QQ: return launch_impl_table<QQ, K, R>(args, A, block, lds_bytes, stream, *table, table_lds, table_at);
-#if MAPF_LQ_K == 4
-            X(1) X(2) X(4) X(8)
-#else
-            X(2) X(4) X(8) X(16)
-#endif
-#undef X
-            default: return hipErrorInvalidValue;
-        }
-#endif
-    }
-    // form: 0 full table rows, 1 8-byte rows, 2 / 3 8-byte rows + occupancy bitmaps (four / five columns), 4 full rows + bitmaps,
-    // 5 4-byte delta rows + bitmaps
-    const bool compact = (form >= 1 && form <= 3) || form == 5, bitmap = form >= 2;
-    (void)bitmap;
-#if MAPF_LQ_K == 8
-    // eight agents per lane: 8, 16 and 32 agents (Q = 1, 2, 4); 8-byte table rows for the 32-agent maps only
-    if (compact) {
-        if (Q != 4 || bitmap) return hipErrorInvalidValue;
-        return stream_actions ? launch_impl<4, K, R, true, true>(args, A, block, lds_bytes, stream)
-                              : launch_impl<4, K, R, false, true>(args, A, block, lds_bytes, stream);
-    }
-    switch (Q) {
-#define X(QQ)                                                                                                        \
-    case QQ: return stream_actions ? launch_impl<QQ, K, R, true>(args, A, block, lds_bytes, stream)                        \
-                                   : launch_impl<QQ, K, R, false>(args, A, block, lds_bytes, stream);
-        X(1) X(2) X(4)
-#undef X
-        default: return hipErrorInvalidValue;
-    }
+    return launch_planned<MAPF_LQ_K, MAPF_LQ_RECORD != 0>(Q, form, args, A, block, lds_bytes, stream, table, table_lds, table_at);
 }
-#else
-#if MAPF_LQ_K == 4
-    if (bitmap) {    // 32 agents only (that is where the 496 pairs dominate)
-        if (Q != 8) return hipErrorInvalidValue;
-        if (form == 5) return stream_actions ? launch_impl<8, K, R, true, true, 3>(args, A, block, lds_bytes, stream)
-                                             : launch_impl<8, K, R, false, true, 3>(args, A, block, lds_bytes, stream);
-        if (form == 4) return stream_actions ? launch_impl<8, K, R, true, false, 2>(args, A, block, lds_bytes, stream)
-                                             : launch_impl<8, K, R, false, false, 2>(args, A, block, lds_bytes, stream);
-        if (form == 3) return stream_actions ? launch_impl<8, K, R, true, true, 2>(args, A, block, lds_bytes, stream)
-                                             : launch_impl<8, K, R, false, true, 2>(args, A, block, lds_bytes, stream);
-        return stream_actions ? launch_impl<8, K, R, true, true, 1>(args, A, block, lds_bytes, stream)
-                              : launch_impl<8, K, R, false, true, 1>(args, A, block, lds_bytes, stream);
-    }
-    if (compact) {   // instantiated for the group sizes whose maps need it: 16, 32 and 64 agents
-        switch (Q) {
-#define X(QQ)                                                                                                        \
-    case QQ: return stream_actions ? launch_impl<QQ, K, R, true, true>(args, A, block, lds_bytes, stream)                  \
-                                   : launch_impl<QQ, K, R, false, true>(args, A, block, lds_bytes, stream);
-            X(4) X(8) X(16)
-#undef X
-            default: return hipErrorInvalidValue;
-        }
-    }
-#else
-    if (compact) return hipErrorInvalidValue;
-#endif
-    switch (Q) {
-#define X(QQ)                                                                                                        \
-    case QQ: return stream_actions ? launch_impl<QQ, K, R, true>(args, A, block, lds_bytes, stream)                        \
-                                   : launch_impl<QQ, K, R, false>(args, A, block, lds_bytes, stream);
-#if MAPF_LQ_K == 4
-        X(1)
-#endif
-        X(2) X(4) X(8) X(16)
-#undef X
-        default: return hipErrorInvalidValue;
-    }
-}
-#endif
 
 }  // namespace mapf

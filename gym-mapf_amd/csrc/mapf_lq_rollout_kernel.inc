@@ -21,6 +21,11 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
 #endif
     constexpr int P = K / 2;   // packed dwords per lane
     static_assert(K == 2 || K == 4 || K == 8, "two, four or eight agents per lane");
+    constexpr TableFormTraits kForm = table_form_traits(table_form_of<COMPACT, BITMAP>());   // the table form this instance reads (mapf_layout.hpp)
+    constexpr uint32_t kCols = kForm.cols;
+    constexpr bool kDeltaRows = COMPACT && BITMAP == 3;       // 4-byte rows: candidates as deltas against the row's own cell
+    constexpr bool kNoStayColumn = COMPACT && BITMAP == 1;    // four columns: a STAY row is made up in registers
+    constexpr bool kStayTwice = kCols == 6;                   // column 5 = STAY again: an action byte is clamped to it
     // the kernel's LDS image is its dynamic segment, used as a raw scratchpad from LDS address 0 (LdsAbsolute, mapf_lq.hpp: no
     // static LDS object exists in this kernel): every offset below is an instruction immediate
     const LdsAbsolute lds;
@@ -101,7 +106,7 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
             }
         }
     }
-    if constexpr (COMPACT && BITMAP == 3) {
+    if constexpr (kDeltaRows) {
         // the host-built delta rows (RolloutArgs::mv4) as they are: 16 bytes per thread and load, ten loads in flight (the
         // 16-byte rows this form was first staged from are 13 times the bytes: 263 KB per block against 79 KB on a 64x64 map)
         const uint32_t n_vec = uint32_t(delta_table_words(p.c.n_cells) / 4u);
@@ -119,9 +124,8 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
     {   // move table -> LDS with six columns per cell (0..4 = the actions, 5 = STAY again: where out-of-range action
         // bytes are clamped to), batches of eight independent loads per thread
         // (COMPACT: five columns, the first 8 bytes of every row)
-        // (COMPACT + BITMAP == 1: FOUR columns -- the moves; a STAY row is (cell, cell, cell) with the all-equal code and is made
+        // (kNoStayColumn: FOUR columns -- the moves; a STAY row is (cell, cell, cell) with the all-equal code and is made
         // up in registers -- which leaves room for the occupancy bitmaps behind the table)
-        constexpr uint32_t kCols = !COMPACT ? kMoveCols : (BITMAP == 1 ? kBitmapCols : (BITMAP == 3 ? kDeltaCols : kCompactCols));
         const uint32_t n_words = p.c.n_cells * kCols;
         constexpr uint32_t kInFlight = 8;                          // (room-32-32-4's 65 KB: one round trip for a 512-thread block)
         for (uint32_t w0 = threadIdx.x; w0 < n_words; w0 += kInFlight * blockDim.x) {
@@ -130,19 +134,14 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
             for (uint32_t k = 0; k < kInFlight; ++k) {
                 const uint32_t w = min(w0 + k * blockDim.x, n_words - 1u);
                 const uint32_t cell = w / kCols, col = w - cell * kCols;
-                part[k] = p.mv[(!COMPACT || BITMAP == 3) ? cell * kMvCols + (col < kMvCols ? col : 0u) : cell * kMvCols + col + (BITMAP == 1 ? 1u : 0u)];
+                part[k] = p.mv[!COMPACT ? cell * kMvCols + (col < kMvCols ? col : 0u) : cell * kMvCols + col + (kNoStayColumn ? 1u : 0u)];
             }
 #pragma unroll
             for (uint32_t k = 0; k < kInFlight; ++k) {
                 const uint32_t w = w0 + k * blockDim.x;
                 if (w < n_words) {
                     // COMPACT rows: {c0 | c1 << 16, c2 | byte offset of the code's slip row << 16}
-                    if (COMPACT && BITMAP == 3) {
-                        // {c0 - cell, c1 - cell, c2 - cell (low bytes: a slot past the list's end is never sampled), (row offset + bias) / 8}
-                        const uint32_t cell = w / kCols;
-                        reinterpret_cast<uint32_t *>(lds_mv)[w] = ((part[k].x - cell) & 0xFFu) | ((((part[k].x >> 16) - cell) & 0xFFu) << 8) |
-                                                                  (((part[k].y - cell) & 0xFFu) << 16) | (((part[k].w + kRowBias) >> 3) << 24);
-                    } else if (COMPACT) reinterpret_cast<u32x2 *>(lds_mv)[w] = u32x2{part[k].x, (part[k].y & 0xFFFFu) | ((part[k].w + kRowBias) << 16)};
+                    if (COMPACT) reinterpret_cast<u32x2 *>(lds_mv)[w] = u32x2{part[k].x, (part[k].y & 0xFFFFu) | ((part[k].w + kRowBias) << 16)};
                     else lds_mv[w] = make_uint4(part[k].x, part[k].y, part[k].z ^ kHalfBias, part[k].w + kRowBias);   // thresholds: see sample_slot_packed
                 }
             }
@@ -343,10 +342,10 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
 
     // In-kernel policy stream (!STREAM, no greedy table): the words of the current four-step block, one call per agent quad
     constexpr int kPolicyCalls = K == 8 ? 2 : 1;
-    constexpr uint32_t kColShift = COMPACT ? (BITMAP == 3 ? 2u : 3u) : 4u;     // log2 of a table row's bytes
+    constexpr uint32_t kColShift = kForm.entry_bytes == 16u ? 4u : (kForm.entry_bytes == 8u ? 3u : 2u);   // log2 of a table row's bytes
     // the policy word's bytes go straight into the table address (no action integer is formed) where nothing else asks for
     // the action: not in the SoC instances (_living_reward counts STAY) nor behind the four-column table (STAY has no row there)
-    constexpr bool FAST_POLICY = !STREAM && !SOC && !(COMPACT && BITMAP == 1);
+    constexpr bool FAST_POLICY = !STREAM && !SOC && !kNoStayColumn;
     Words4 pol[kPolicyCalls];
 #pragma unroll
     for (int j = 0; j < kPolicyCalls; ++j) pol[j] = Words4{0u, 0u, 0u, 0u};
@@ -392,9 +391,9 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
     // steps, so the prefetch address is clamped; 2: no prefetch (the first step of a WORD_SLOTS launch, whose register is its
     // own).  `raw` is the register that holds this step's action word.
     // (delta rows: the slot selects a byte -- steps of one, the row's byte 2 down to 0, zeros above it)
-    uint32_t pk_eights = 0x00080008u, pk_steps = BITMAP == 3 ? 0x00010001u : 0x02020202u, sel_base = BITMAP == 3 ? 0x0C0C0C02u : 0x0C0C0504u;   // sample_slot_packed's constants,
+    uint32_t pk_eights = 0x00080008u, pk_steps = kDeltaRows ? 0x00010001u : 0x02020202u, sel_base = kDeltaRows ? 0x0C0C0C02u : 0x0C0C0504u;   // sample_slot_packed's constants,
     asm volatile("" : "+v"(pk_eights), "+v"(pk_steps), "+v"(sel_base));                   // one vector register each
-    uint32_t row_bytes = COMPACT ? (BITMAP == 3 ? kDeltaCols * kDeltaEntry : (BITMAP == 1 ? kBitmapCols : kCompactCols) * kCompactEntry) : kMoveCols * uint32_t(sizeof(MoveEntry));
+    uint32_t row_bytes = kCols * kForm.entry_bytes;
     asm volatile("" : "+v"(row_bytes));   // (one register for the whole loop; as an SGPR operand the assembler rejects the SDWA form)
     auto one_step = [&](const uint32_t s, RawWord &raw, auto w_tag, auto first_tag, auto tail_tag) __attribute__((always_inline)) {
         constexpr int W = decltype(w_tag)::value;
@@ -423,7 +422,7 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 const uint32_t byte = uint32_t(raw >> (8 * k)) & 0xFFu;
-                act[k] = (COMPACT && BITMAP != 3) ? (byte > 4u ? 0u : byte) : min(byte, 5u);   // six columns: extract + clamp is one v_min_u32 (byte select)
+                act[k] = kStayTwice ? min(byte, 5u) : (byte > 4u ? 0u : byte);   // six columns: extract + clamp is one v_min_u32 (byte select)
             }
 #pragma unroll
             for (int k = 0; k < K; ++k) asm volatile("" : "+v"(act[k]));   // the wait for `raw` sits here
@@ -488,8 +487,8 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
         uint32_t delta_row[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            if (COMPACT && BITMAP == 3) delta_row[k] = lds_at<uint32_t>(lds, kMoveAt + col_at[k]);
-            else if (COMPACT && BITMAP == 1) cells_code[k] = lds_at<u32x2>(lds, kMoveAt - kCompactEntry + col_at[k]);   // column act - 1 (STAY: see below)
+            if (kDeltaRows) delta_row[k] = lds_at<uint32_t>(lds, kMoveAt + col_at[k]);
+            else if (kNoStayColumn) cells_code[k] = lds_at<u32x2>(lds, kMoveAt - kCompactEntry + col_at[k]);   // column act - 1 (STAY: see below)
             else if (COMPACT) cells_code[k] = lds_at<u32x2>(lds, kMoveAt + col_at[k]);
             else entry[k] = lds_entry_at(lds, kMoveAt + col_at[k]);
         }
@@ -511,7 +510,7 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
         STAMP(1);   // previous step: probability chain, totals, trajectory stores
         if (COMPACT) {   // the code's thresholds: a second LDS read that depends on the first; the row completes to a MoveEntry
             uint32_t row_off[K], th[K];
-            if (BITMAP == 1) {   // a STAY row: the cell itself, the all-equal code (one entry: candidates m = r = l)
+            if (kNoStayColumn) {   // a STAY row: the cell itself, the all-equal code (one entry: candidates m = r = l)
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
                     const bool stay = act[k] == 0u;
@@ -521,12 +520,12 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
             }
 #pragma unroll
             for (int k = 0; k < K; ++k) {
-                if (BITMAP == 3) asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(row_off[k]) : "v"(delta_row[k]), "v"(eight));
+                if (kDeltaRows) asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(row_off[k]) : "v"(delta_row[k]), "v"(eight));
                 else row_off[k] = cells_code[k].y >> 16;
                 th[k] = lds_at<uint32_t>(lds, kSlipAt + uint32_t(offsetof(SlipRow, th_biased)) - kRowBias + row_off[k]);   // (th[0] | th[1] << 16) ^ bias
             }
 #pragma unroll
-            for (int k = 0; k < K; ++k) entry[k] = BITMAP == 3 ? make_uint4(delta_row[k], 0u, th[k], row_off[k]) : make_uint4(cells_code[k].x, cells_code[k].y, th[k], row_off[k]);
+            for (int k = 0; k < K; ++k) entry[k] = kDeltaRows ? make_uint4(delta_row[k], 0u, th[k], row_off[k]) : make_uint4(cells_code[k].x, cells_code[k].y, th[k], row_off[k]);
         }
         // A slip-stream call serves an agent quad for two steps: every four steps a lane refreshes the two calls of the
         // block (h0, h0 + 1) for each of its quads, in lockstep, and files their words per pair in step order (rng[i] =
@@ -561,7 +560,7 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
             word[i] = W == 0 ? rng[i].w0 : W == 1 ? rng[i].w1 : W == 2 ? rng[i].w2 : W == 3 ? rng[i].w3 : step_word(rng[i], t);
             const uint32_t biased = word[i] ^ kHalfBias;             // low half: agent 2i's uniform, high half: agent 2i+1's
             uint32_t cell[2];
-            if constexpr (BITMAP == 3) {
+            if constexpr (kDeltaRows) {
                 d[2 * i] = sample_slot_delta<0>(entry[2 * i].x, entry[2 * i].z, entry[2 * i].w, __builtin_amdgcn_perm(biased, biased, 0x01000100u),
                                                 pk_eights, pk_steps, sel_base, c[i], q_at[2 * i], cell[0]);
                 d[2 * i + 1] = sample_slot_delta<1>(entry[2 * i + 1].x, entry[2 * i + 1].z, entry[2 * i + 1].w,
@@ -588,7 +587,7 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
             for (int k = 0; k < K; ++k) {
                 if (__any(zero_half(d[k]) != 0u)) {
                     MoveEntry full = entry[k];
-                    if (COMPACT && BITMAP == 3) {   // the candidates' cells back from their deltas
+                    if (kDeltaRows) {   // the candidates' cells back from their deltas
                         const uint32_t mine = (k & 1) ? c[k / 2] >> 16 : c[k / 2] & 0xFFFFu, row = full.x;
                         const uint32_t c0 = (mine + uint32_t(int32_t(int8_t(row)))) & 0xFFFFu, c1 = (mine + uint32_t(int32_t(int8_t(row >> 8)))) & 0xFFFFu,
                                        c2 = (mine + uint32_t(int32_t(int8_t(row >> 16)))) & 0xFFFFu;
@@ -654,7 +653,7 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 const uint32_t goal_k = (k & 1) ? g[k / 2] >> 16 : g[k / 2] & 0xFFFFu;
-                mine += (cur[k] == goal_k && (act[k] == 0u || ((!COMPACT || BITMAP == 3) && act[k] == 5u))) ? 1u : 0u;
+                mine += (cur[k] == goal_k && (act[k] == 0u || (kStayTwice && act[k] == 5u))) ? 1u : 0u;
             }
             const int stayed = int(group_reduce<Q, true>(mine, x));
             const double living = __dmul_rn(double(int(n_agents) - stayed), p.c.r_living);

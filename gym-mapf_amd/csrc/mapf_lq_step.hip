@@ -109,15 +109,17 @@ __global__ void __launch_bounds__(BIG ? 1024 : 512) lq_step_kernel(uint16_t *con
                                                       const uint32_t agents_block, const uint32_t t_lo, const uint32_t seed_lo,
                                                       const uint32_t seed_hi, const StepArgs p_block, const uint32_t n_chunks) {
     constexpr int P = K / 2;
+    // BIG is a StepForm's number (mapf_plan.hpp): resident grid with the move table in LDS; ... as 4-byte delta rows; ... with per-env bitmaps behind them
+    constexpr bool kResident = BIG != 0, kDeltaRows = BIG >= 2, kBitmaps = BIG == 3;
 #ifdef MAPF_STEP_STAMPS
     unsigned long long stamp_[8] = {}, real0_, cyc0_;
     asm volatile("s_memrealtime %0\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(real0_), "=s"(cyc0_) :: "memory");
 #endif
     // the kernel's LDS image (mapf_lq.hpp): 1 KB static (the table image: slip rows, outcome rows) reached through the
     // object; the BIG form's image is the dynamic segment -- the move table behind those 1 KB -- used as a raw scratchpad
-    using Image = std::conditional_t<BIG != 0, LdsAbsolute, LdsObject>;
+    using Image = std::conditional_t<kResident, LdsAbsolute, LdsObject>;
     Image lds;
-    if constexpr (!BIG) {
+    if constexpr (!kResident) {
         __shared__ __attribute__((aligned(16))) unsigned char lds_static[kStepLds];
         lds.base = (lds_ptr)lds_static;
     }
@@ -142,16 +144,16 @@ __global__ void __launch_bounds__(BIG ? 1024 : 512) lq_step_kernel(uint16_t *con
             for (uint32_t k = 0; k < kInFlight; ++k)
                 if (w0 + k * block_threads < n_vec) *(__attribute__((address_space(3))) u32x4 *)lds_addr(lds, kStepMoveAt + 16u * (w0 + k * block_threads)) = part[k];
         }
-        if constexpr (BIG == 3) {   // the block's occupancy bitmaps (one per env of a chunk; every use clears what it set)
+        if constexpr (kBitmaps) {   // the block's occupancy bitmaps (one per env of a chunk; every use clears what it set)
             const uint32_t n_words = (block_threads / uint32_t(Q)) * (bitmap_stride >> 2);
             for (uint32_t w = threadIdx.x; w < n_words; w += block_threads) *(lds_u32)lds_addr(lds, bitmap_base + 4u * w) = 0u;
         }
         stage_outcome_table(p_block.c, lds_generic<OutcomeRow>(lds, kStepOutcomeAt));
         stage_slip_table(slip_rows, lds_generic<SlipRow>(lds, kStepSlipAt));   // ends with __syncthreads()
     };
-    if constexpr (BIG >= 2) {
+    if constexpr (kDeltaRows) {
     } else
-    if (BIG) {   // move table -> LDS: 16-byte rows, SIX columns per cell (kBigCols: column 5 = STAY again, so that an action byte is
+    if (kResident) {   // move table -> LDS: 16-byte rows, SIX columns per cell (kBigCols: column 5 = STAY again, so that an action byte is
         // extracted and clamped by one v_min_u32 -- in LDS the sixth column costs room, not gather traffic); four independent
         // loads per thread and round; the thresholds bias-shifted as the packed sampling compares them
         const uint32_t n_rows = p_block.c.n_cells * kBigCols;
@@ -196,14 +198,14 @@ __global__ void __launch_bounds__(BIG ? 1024 : 512) lq_step_kernel(uint16_t *con
     // CU); the fields are re-read from the kernarg segment through a pointer the optimiser cannot see through, so that they
     // are fetched where an iteration uses them, as in the straight-line form (scalar cache hits).
     union { StepArgs args; uint32_t words[sizeof(StepArgs) / 4]; } reread;
-    if constexpr (BIG) {
+    if constexpr (kResident) {
         using KernWord = const __attribute__((address_space(4))) uint32_t;
         KernWord *ka = (KernWord *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + kStepArgsOffset);
         asm volatile("" : "+s"(ka));
 #pragma unroll
         for (uint32_t i = 0; i < sizeof(StepArgs) / 4; ++i) reread.words[i] = ka[i];
     }
-    const StepArgs &p = BIG ? reread.args : p_block;
+    const StepArgs &p = kResident ? reread.args : p_block;
     constexpr bool first_pass = decltype(first_tag)::value;   // !BIG: the LDS image is written behind the chunk's first loads
     LaneCtx<Q> x;
     x.lane = threadIdx.x & 63u;
@@ -274,7 +276,7 @@ __global__ void __launch_bounds__(BIG ? 1024 : 512) lq_step_kernel(uint16_t *con
     CompactEntry compact[K];
     uint32_t delta_row[K];
     const uint32_t last_cell = p.c.n_cells - 1u;
-    constexpr uint32_t kCols = BIG ? kBigCols : kMvCols;
+    constexpr uint32_t kCols = kResident ? kBigCols : kMvCols;
     uint32_t row_bytes = kDeltaCols * 4u, eight = 8u;
     asm volatile("" : "+v"(row_bytes), "+v"(eight));   // (SDWA operands must be vector registers)
     // the LDS image first (it arrived with the first trip): the plain form reads its thresholds from it right behind the gathers
@@ -292,8 +294,8 @@ __global__ void __launch_bounds__(BIG ? 1024 : 512) lq_step_kernel(uint16_t *con
         // bound by the texture path's line rate and every launch re-fetches the table into eight L2s, so half the bytes is
         // what counts; the code's thresholds then come from the slip row in LDS (profiles/r04_step_table_forms.txt)
         // BIG == 2: 4-byte delta rows from the LDS copy, cell * 24 + action * 4 (an out-of-range LDS address reads zeros: no clamp)
-        if (BIG >= 2) delta_row[k] = lds_at<uint32_t>(lds, kStepMoveAt + (act[k] << 2) + ((k & 1) ? half_times<1>(c[k / 2], row_bytes) : half_times<0>(c[k / 2], row_bytes)));
-        else if (BIG) entry[k] = lds_entry_at(lds, kStepMoveAt + row * 16u);
+        if (kDeltaRows) delta_row[k] = lds_at<uint32_t>(lds, kStepMoveAt + (act[k] << 2) + ((k & 1) ? half_times<1>(c[k / 2], row_bytes) : half_times<0>(c[k / 2], row_bytes)));
+        else if (kResident) entry[k] = lds_entry_at(lds, kStepMoveAt + row * 16u);
         else compact[k] = p.mv8[row];
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -311,7 +313,7 @@ __global__ void __launch_bounds__(BIG ? 1024 : 512) lq_step_kernel(uint16_t *con
 #pragma unroll
         for (int i = 0; i < P; ++i) asm volatile("" : "+v"(sc[i]));
     }
-    if constexpr (BIG >= 2) {   // the code's thresholds: a second LDS read that depends on the first; the row completes to a MoveEntry
+    if constexpr (kDeltaRows) {   // the code's thresholds: a second LDS read that depends on the first; the row completes to a MoveEntry
         uint32_t row_off[K], th[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -321,7 +323,7 @@ __global__ void __launch_bounds__(BIG ? 1024 : 512) lq_step_kernel(uint16_t *con
 #pragma unroll
         for (int k = 0; k < K; ++k) entry[k] = make_uint4(delta_row[k], 0u, th[k], row_off[k]);
     }
-    if constexpr (!BIG) {   // complete the rows: thresholds (bias-shifted, as the packed sampling compares them) by the code's row offset
+    if constexpr (!kResident) {   // complete the rows: thresholds (bias-shifted, as the packed sampling compares them) by the code's row offset
         uint32_t th[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) th[k] = lds_at<uint32_t>(lds, kStepSlipAt + uint32_t(offsetof(SlipRow, th_biased)) + (compact[k].y >> 16));
@@ -333,7 +335,7 @@ __global__ void __launch_bounds__(BIG ? 1024 : 512) lq_step_kernel(uint16_t *con
     // ---- sampling (the fused rollout's packed form): both threshold compares of an agent in one saturating packed
     // subtract, the slot's probability address and cell selector from one dot product each
     // (delta rows: the slot selects a byte -- steps of one, the row's byte 2 down to 0, zeros above it)
-    uint32_t pk_eights = 0x00080008u, pk_steps = BIG >= 2 ? 0x00010001u : 0x02020202u, sel_base = BIG >= 2 ? 0x0C0C0C02u : 0x0C0C0504u;
+    uint32_t pk_eights = 0x00080008u, pk_steps = kDeltaRows ? 0x00010001u : 0x02020202u, sel_base = kDeltaRows ? 0x0C0C0C02u : 0x0C0C0504u;
     asm volatile("" : "+v"(pk_eights), "+v"(pk_steps), "+v"(sel_base));
     double q[K];
     uint32_t n[P], word[P], d[K], tie_all = 0u;
@@ -348,7 +350,7 @@ __global__ void __launch_bounds__(BIG ? 1024 : 512) lq_step_kernel(uint16_t *con
         uint32_t q_at[2], cell[2];
         MoveEntry e0 = entry[2 * i], e1 = entry[2 * i + 1];
         // (the thresholds are bias-shifted already: th_biased / the BIG form's LDS copy of the table)
-        if constexpr (BIG >= 2) {
+        if constexpr (kDeltaRows) {
             d[2 * i] = sample_slot_delta<0>(e0.x, e0.z, e0.w, __builtin_amdgcn_perm(biased, biased, 0x01000100u), pk_eights, pk_steps, sel_base, c[i], q_at[0], cell[0]);
             d[2 * i + 1] = sample_slot_delta<1>(e1.x, e1.z, e1.w, __builtin_amdgcn_perm(biased, biased, 0x03020302u), pk_eights, pk_steps, sel_base, c[i], q_at[1], cell[1]);
             q[2 * i] = lds_at<double>(lds, kStepSlipAt + 16u - kDeltaRowBias + q_at[0]);
@@ -375,8 +377,8 @@ __global__ void __launch_bounds__(BIG ? 1024 : 512) lq_step_kernel(uint16_t *con
                 uint32_t nx;
                 MoveEntry full = entry[k];
                 // (8-byte rows: the list's members, where slip_move_exact_members looks for them, from the code's slip row)
-                if (!BIG) full.y = (full.y & 0xFFFFu) | (lds_at<uint32_t>(lds, kStepSlipAt + uint32_t(offsetof(SlipRow, members)) + full.w) << 19);
-                if (BIG >= 2) {   // the candidates' cells back from their deltas, the members from the slip row
+                if (!kResident) full.y = (full.y & 0xFFFFu) | (lds_at<uint32_t>(lds, kStepSlipAt + uint32_t(offsetof(SlipRow, members)) + full.w) << 19);
+                if (kDeltaRows) {   // the candidates' cells back from their deltas, the members from the slip row
                     const uint32_t mine = (k & 1) ? c[k / 2] >> 16 : c[k / 2] & 0xFFFFu, row = full.x;
                     const uint32_t c0 = (mine + uint32_t(int32_t(int8_t(row)))) & 0xFFFFu, c1 = (mine + uint32_t(int32_t(int8_t(row >> 8)))) & 0xFFFFu,
                                    c2 = (mine + uint32_t(int32_t(int8_t(row >> 16)))) & 0xFFFFu;
@@ -392,7 +394,7 @@ __global__ void __launch_bounds__(BIG ? 1024 : 512) lq_step_kernel(uint16_t *con
     // ---- is_terminal(prev) and the collision tests in one pass over the agent pairs; the per-env facts as ONE integer
     // code = vertex | swap << 1 | off_goal << 2 | was_terminal << 3 (mapf_env.py:210-223, :225-235, :378-389)
     PairAcc<true> acc;
-    if constexpr (BIG == 3) {
+    if constexpr (kBitmaps) {
         acc = bitmap_pair_tests<Q, K>(x, lds, bitmap_at, c, n);   // (a terminal env's bits are set and cleared like any other's: its outcome row ignores them)
         if (TERM) {                                                // is_terminal(prev)'s duplicate test stays with the agent pairs
             const uint32_t none[P] = {};
@@ -486,12 +488,12 @@ __global__ void __launch_bounds__(BIG ? 1024 : 512) lq_step_kernel(uint16_t *con
     }
 #endif
     };   // one_chunk
-    if constexpr (BIG) {
+    if constexpr (kResident) {
         // Two chunks per iteration, their first trips in two sets of registers that take turns: "cur = next" would be a
         // register move of values still in flight, i.e. a wait for the very loads the prefetch is there to hide.
         const uint32_t stride = gridDim.x;
         FirstTrip a = first_trip(blockIdx.x);
-        if constexpr (BIG >= 2) {
+        if constexpr (kDeltaRows) {
             __builtin_amdgcn_sched_barrier(0);                           // (the first trip's requests go out ahead of the table's)
             stage_delta_table();
         }
@@ -541,21 +543,22 @@ bool try_launch_step_lq(int n_agents, const StepArgs &args, const RolloutTuning 
     const char *const scen_tag = scen ? ",SCEN" : "", *const term_tag = term ? "" : ",NO_TERMINAL",
                *const scen_note = scen ? ", start / goal rows from the scenario table" : "";
     const int Q = plan.Q, K = plan.K;
-    if (plan.big == 1)
+    const bool bitmaps = plan.big == StepForm::DeltaRowsBitmap;
+    if (plan.big == StepForm::FullRows)
         note_kernel("lq_step_kernel<Q=%d,K=%d%s%s,BIG> block=1024 resident grid (packed layout: %d agents per lane, move table in LDS%s)", Q, K, scen_tag, term_tag, K, scen_note);
-    else if (plan.big >= 2)
+    else if (plan.big != StepForm::Plain)
         note_kernel("lq_step_kernel<Q=%d,K=%d%s%s,DELTA%s> block=%u resident grid (packed layout: 4 agents per lane, 4-byte delta rows of the move table in LDS%s%s)", Q, K,
-                    scen_tag, term_tag, plan.big == 3 ? ",BITMAP" : "", plan.block, plan.big == 3 ? ", collisions through per-env occupancy bitmaps" : "", scen_note);
+                    scen_tag, term_tag, bitmaps ? ",BITMAP" : "", plan.block, bitmaps ? ", collisions through per-env occupancy bitmaps" : "", scen_note);
     else
         note_kernel("lq_step_kernel<Q=%d,K=%d%s%s> block=%u (packed layout: %d agents per lane%s)", Q, K, scen_tag, term_tag, plan.block, K, scen_note);
     // the instances that exist, in the order plan_step_lq tries their forms
-#define X(QQ, KK, BB) if (Q == QQ && K == KK && plan.big == BB) { *err = launch_step_instance<QQ, KK, BB>(plan, args, uint32_t(n_agents), stream); return true; }
-    X(1, 8, 1) X(2, 8, 1) X(4, 8, 1)
-    X(8, 4, 3)
-    X(1, 4, 2) X(2, 4, 2) X(4, 4, 2) X(8, 4, 2)
-    X(1, 4, 1) X(2, 4, 1) X(4, 4, 1) X(8, 4, 1)
-    X(1, 4, 0) X(2, 4, 0) X(4, 4, 0) X(8, 4, 0) X(16, 4, 0)
-    X(2, 2, 0) X(4, 2, 0) X(8, 2, 0) X(16, 2, 0)
+#define X(QQ, KK, FF) if (Q == QQ && K == KK && plan.big == StepForm::FF) { *err = launch_step_instance<QQ, KK, int(StepForm::FF)>(plan, args, uint32_t(n_agents), stream); return true; }
+    X(1, 8, FullRows) X(2, 8, FullRows) X(4, 8, FullRows)
+    X(8, 4, DeltaRowsBitmap)
+    X(1, 4, DeltaRows) X(2, 4, DeltaRows) X(4, 4, DeltaRows) X(8, 4, DeltaRows)
+    X(1, 4, FullRows) X(2, 4, FullRows) X(4, 4, FullRows) X(8, 4, FullRows)
+    X(1, 4, Plain) X(2, 4, Plain) X(4, 4, Plain) X(8, 4, Plain) X(16, 4, Plain)
+    X(2, 2, Plain) X(4, 2, Plain) X(8, 2, Plain) X(16, 2, Plain)
 #undef X
     *err = hipErrorInvalidValue;   // (plan_step_lq plans no other instance)
     return true;

@@ -1,6 +1,5 @@
 // Launch planning of the packed kernels (mapf_plan.hpp): host-only integer arithmetic, no kernel and no runtime call.
 #include "mapf_plan.hpp"
-#include "mapf_layout.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -56,12 +55,14 @@ RolloutTuning rollout_tuning_for(int n_cu, const char *text, std::string *err) {
     return t;
 }
 
-// does the K-agents-per-lane form apply to this launch?  (full groups, power-of-two group size, full blocks)
-static bool layout_fits(int n_agents, int K, const RolloutArgs &args, size_t lds_bytes, unsigned *block_out, int *q_out) {
+// does the K-agents-per-lane layout apply to this launch?  (full groups, power-of-two group size, full blocks; `image`: the
+// LDS image that decides how many blocks share a CU)
+static bool layout_fits(int n_agents, int K, const RolloutArgs &args, size_t image, unsigned *block_out, int *q_out) {
     if (n_agents < K || n_agents % K != 0) return false;
     const int Q = n_agents / K;
-    if (Q > 16 || (Q & (Q - 1)) != 0 || (K == 2 && Q < 2) || (K == 8 && Q > 4)) return false;
-    const size_t copies = kLdsBytes / lds_bytes;   // blocks per CU by LDS
+    // (eight per lane exist up to Q = 4: asked HERE, so that larger teams go on to four per lane; all other existence: first_candidate)
+    if (Q > 16 || (Q & (Q - 1)) != 0 || (K == 8 && Q > 4)) return false;
+    const size_t copies = kLdsBytes / image;       // blocks per CU by LDS
     unsigned block = copies >= 4 ? 256u : 512u;
     // a small batch is spread over the CUs in smaller blocks (down to one wave): every block stages its own table copy,
     // which is cheap next to a rollout's steps, and an idle CU is not
@@ -74,95 +75,88 @@ static bool layout_fits(int n_agents, int K, const RolloutArgs &args, size_t lds
     return true;
 }
 
+// One block per CU (a table that fills most of its LDS): 1024 threads -- four waves per SIMD -- once the batch gives every CU a
+// block of that size and the launch fits, else 512 (two waves per SIMD).  `pinned`: MAPF_TUNE's say (0 = by batch).
+static unsigned one_block_per_cu(TableForm form, int Q, const RolloutArgs &args, const RolloutTuning &tune, unsigned pinned) {
+    if (Q < 1 || Q > 16) return 512u;                               // (no such layout: layout_fits refuses it)
+    const bool want = pinned == 1024u || (pinned == 0u && args.n_envs * uint64_t(Q) >= uint64_t(tune.n_cu) * 1024u);
+    return want && args.n_envs % (1024u / unsigned(Q)) == 0 && launch_lds_bytes(form, args.c.n_cells, 1024u, Q) <= kLdsBytes ? 1024u : 512u;
+}
+
+// One entry of the planner's ordered list: the first candidate that applies takes the launch.
+struct Candidate {
+    TableForm form; int K;  // the form, agents per lane
+    bool admitted;          // the tuning and the launch's shape allow it
+    uint64_t min_lanes;     // ... from this many lanes (n_envs * Q) on
+    TableForm rule_image;   // the form whose image layout_fits looks at (its own, but for the five 8-byte columns)
+    unsigned block;         // its block rule: 0 = what layout_fits picks, else this many threads
+};
+
+// the first candidate of `list` that applies: its layout fits, the batch is large enough, its block rule leaves whole blocks and
+// its launch fits the CU's LDS.  What is planned must be an instance the launcher holds.
+static bool first_candidate(const Candidate *list, size_t n, int n_agents, const RolloutArgs &args, LqPlan *plan) {
+    for (const Candidate *c = list; c != list + n; ++c) {
+        unsigned block = 0; int Q = 0;
+        if (!c->admitted || !layout_fits(n_agents, c->K, args, table_image_bytes(c->rule_image, args.c.n_cells), &block, &Q) ||
+            args.n_envs * uint64_t(Q) < c->min_lanes) continue;
+        if (c->block) block = c->block;
+        if (args.n_envs % (block / unsigned(Q)) != 0 || launch_lds_bytes(c->form, args.c.n_cells, block, Q) > kLdsBytes) continue;
+        if (!lq_rollout_instance_exists(c->K, Q, c->form, false)) return false;
+        *plan = LqPlan{c->K, Q, c->form, block, table_image_bytes(c->form, args.c.n_cells), launch_lds_bytes(c->form, args.c.n_cells, block, Q)};
+        return true;
+    }
+    return false;
+}
+
 // the dispatch decision (see LqPlan): which packed form, block size and LDS image a launch of this shape takes
 bool plan_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, LqPlan *plan) {
-    const int n_cu = tune.n_cu;
+    using F = TableForm;
     // top_tie: a three-entry list whose last cumulative sum rounds below 1.0 needs a third compare per agent (hi = 65535);
     // the packed sampling does two, so such a table (none arises from fail_prob / 2 splits) stays with the lane-group kernel
     if (!tune.quad_lanes || args.c.top_tie || args.n_steps > 65535u) return false;   // (per-launch counts are 16-bit)
-    unsigned block = 0;
-    int Q = 0, K = 0;
-    bool compact = false, bitmap = false, stay_column = false, full_rows_bitmap = false, delta_rows = false;
-    size_t lds_bytes = kMoveAt + size_t(args.c.n_cells) * kMoveCols * sizeof(MoveEntry);   // the kernel's whole LDS image
-    if (lds_bytes <= tune.mv_lds_max_bytes && lds_bytes <= kLdsBytes - kLdsReserve) {
-        // Four agents per lane halve the waves: that form needs tune.quad_min_lanes lanes (default: enough to put one
-        // wave on every SIMD); below that the two-agents-per-lane form of the same kernel runs.
-        // Eight agents per lane halve them again (at 8 agents nothing crosses lanes any more): worth it from two waves
-        // per SIMD of THAT form on, i.e. 131072 envs at 8 agents.
-        // 32 agents: four per lane with the occupancy bitmaps behind the full table (O(A) collision tests, see below) wherever that
-        // form applies -- 496 agent pairs per env are most of either all-pairs form's step
-        if (tune.bitmap_pairs && n_agents == 32 && (tune.force_k == 0 || tune.force_k == 4) && layout_fits(n_agents, 4, args, lds_bytes, &block, &Q) &&
-            lds_bytes + (block / 8u) * bitmap_stride(args.c.n_cells) <= kLdsBytes &&
-            (tune.force_k == 4 || args.n_envs * uint64_t(Q) >= tune.quad_min_lanes)) {
-            K = 4;
-            bitmap = true;
-            full_rows_bitmap = true;
-        } else
-        if ((tune.force_k == 0 || tune.force_k == 8) && layout_fits(n_agents, 8, args, lds_bytes, &block, &Q) &&
-            (tune.force_k == 8 || args.n_envs * uint64_t(Q) >= tune.oct_min_lanes) && block <= 512u) K = 8;
-        else if (tune.force_k != 2 && tune.force_k != 8 && layout_fits(n_agents, 4, args, lds_bytes, &block, &Q) &&
-                 (tune.force_k == 4 || args.n_envs * uint64_t(Q) >= tune.quad_min_lanes)) K = 4;
-        else if (tune.force_k != 4 && tune.force_k != 8 && layout_fits(n_agents, 2, args, lds_bytes, &block, &Q)) K = 2;
-        else return false;
-    } else {
-        // the full table is too large: 8-byte rows, one block per CU (512 threads = two waves per SIMD; 1024 when the
-        // batch gives every CU a block of that size), four agents per lane, group sizes 4 / 8 / 16 only
-        lds_bytes = kMoveAt + size_t(args.c.n_cells) * kCompactCols * kCompactEntry;
-        if (tune.mv_lds_max_bytes == 0 || lds_bytes > kLdsBytes - kLdsReserve) return false;
-        const size_t bitmap_lds = kMoveAt + size_t(args.c.n_cells) * kBitmapCols * kCompactEntry;   // (no STAY column in that form)
-        // 32 agents: four per lane, collisions through per-env occupancy bitmaps behind the table (one bit per cell) -- O(A)
-        // instead of 496 pair tests per env.  64 envs per 512-thread block; 128 per 1024-thread block (four waves per SIMD)
-        // once the batch gives every CU a block of that size and 128 bitmaps fit (C5's share of one GPU: 481 G against 377 G
-        // for the all-pairs form; C5 whole: profiles/r04_c5_one_bit_bitmap_ab.txt).  MAPF_TUNE k=8 / bitmap_pairs=0 keep the
-        // all-pairs forms reachable (eight agents per lane, Q = 4, one 512-thread block per CU; four per lane below).
-        const size_t per_env = bitmap_stride(args.c.n_cells);
-        unsigned bitmap_block = 512u;
-        if (tune.bitmap_block == 1024u || (tune.bitmap_block == 0u && args.n_envs * 8u >= uint64_t(n_cu) * 1024u)) bitmap_block = 1024u;
-        if (bitmap_block == 1024u && (args.n_envs % (1024u / 8u) != 0 || bitmap_lds + (1024u / 8u) * per_env > kLdsBytes)) bitmap_block = 512u;
-        if (args.actions == nullptr) bitmap_block = 512u;           // (in-kernel policy behind 8-byte rows: that instance is built for 512 threads)
+    const uint32_t V = args.c.n_cells;
+    const int k = tune.force_k;                                    // MAPF_TUNE k=2|4|8 pins the agents per lane
+    const bool team32 = n_agents == 32, bitmaps = tune.bitmap_pairs && team32 && k != 8 && k != 2;
+    const uint64_t quad_min = k == 4 ? 0u : tune.quad_min_lanes, oct_min = k == 8 ? 0u : tune.oct_min_lanes;
+    const size_t full = table_image_bytes(F::FullRows, V);
+    if (full <= tune.mv_lds_max_bytes && full <= kLdsBytes - kLdsReserve) {
+        const Candidate list[] = {
+            // 32 agents: four per lane with the occupancy bitmaps behind the full table (O(A) collision tests, see below) wherever that
+            // form applies -- 496 agent pairs per env are most of either all-pairs form's step
+            {F::FullRowsBitmap, 4, tune.bitmap_pairs && team32 && (k == 0 || k == 4), quad_min, F::FullRows, 0u},
+            // Eight agents per lane halve the waves again (at 8 agents nothing crosses lanes any more): worth it from two waves
+            // per SIMD of THAT form on, i.e. 131072 envs at 8 agents.
+            {F::FullRows, 8, k == 0 || k == 8, oct_min, F::FullRows, 0u},
+            // Four agents per lane halve the waves: that form needs tune.quad_min_lanes lanes (default: enough to put one
+            // wave on every SIMD); below that the two-agents-per-lane form of the same kernel runs.
+            {F::FullRows, 4, k != 2 && k != 8, quad_min, F::FullRows, 0u},
+            {F::FullRows, 2, k != 4 && k != 8, 0u, F::FullRows, 0u},
+        };
+        return first_candidate(list, sizeof(list) / sizeof(list[0]), n_agents, args, plan);
+    }
+    // the full table is too large: 8-byte rows (or 4-byte ones), one block per CU, four agents per lane, group sizes 4 / 8 / 16 only
+    if (tune.mv_lds_max_bytes == 0 || table_image_bytes(F::Rows8, V) > kLdsBytes - kLdsReserve) return false;
+    // 32 agents: four per lane, collisions through per-env occupancy bitmaps behind the table (one bit per cell) -- O(A)
+    // instead of 496 pair tests per env.  64 envs per 512-thread block; 128 per 1024-thread block (four waves per SIMD)
+    // once the batch gives every CU a block of that size and 128 bitmaps fit (C5's share of one GPU: 481 G against 377 G
+    // for the all-pairs form; C5 whole: profiles/r04_c5_one_bit_bitmap_ab.txt).  MAPF_TUNE k=8 / bitmap_pairs=0 keep the
+    // all-pairs forms reachable (eight agents per lane, Q = 4, one 512-thread block per CU; four per lane below).
+    // (in-kernel policy behind 8-byte rows: that instance is built for 512 threads)
+    const unsigned rows8_bitmap_block = args.actions == nullptr ? 512u : one_block_per_cu(F::Rows8x4Bitmap, 8, args, tune, tune.bitmap_block);
+    const Candidate list[] = {
         // ... behind 4-byte delta rows where the map's ids allow them (six columns in 79 KB on the 64x64 maps: 128 bitmaps fit, no
         // STAY row to make up, one-instruction action clamp)
-        const size_t delta_lds = kMoveAt + delta_table_words(args.c.n_cells) * kDeltaEntry;   // (the host-built image, zero-padded to 16 bytes)
-        unsigned delta_block = (tune.bitmap_block == 1024u || (tune.bitmap_block == 0u && args.n_envs * 8u >= uint64_t(n_cu) * 1024u)) ? 1024u : 512u;
-        if (delta_block == 1024u && (args.n_envs % (1024u / 8u) != 0 || delta_lds + (1024u / 8u) * per_env > kLdsBytes)) delta_block = 512u;
-        if (tune.bitmap_pairs && tune.bitmap_delta_rows && args.mv_delta8 && args.mv4 && n_agents == 32 && tune.force_k != 8 && tune.force_k != 2 &&
-            layout_fits(n_agents, 4, args, delta_lds, &block, &Q) && args.n_envs % (delta_block / 8u) == 0 &&
-            delta_lds + (delta_block / 8u) * per_env <= kLdsBytes) {
-            block = delta_block;
-            K = 4;
-            bitmap = true;
-            delta_rows = true;
-            lds_bytes = delta_lds;
-        } else
-        if (tune.bitmap_pairs && n_agents == 32 && tune.force_k != 8 && tune.force_k != 2 && layout_fits(n_agents, 4, args, bitmap_lds, &block, &Q) &&
-            args.n_envs % (bitmap_block / 8u) == 0 && bitmap_lds + (bitmap_block / 8u) * per_env <= kLdsBytes) {
-            block = bitmap_block;
-            K = 4;
-            bitmap = true;
-            // where the five-column table (STAY included: four selects per agent-step less) still leaves room for the block's
-            // bitmaps -- 64 of them on the 64x64 maps, not 128 -- it is the one staged (C5's share: profiles/r04_c5_stay_column_ab.txt)
-            stay_column = tune.bitmap_stay_column && lds_bytes + (bitmap_block / 8u) * per_env <= kLdsBytes;
-            if (!stay_column) lds_bytes = bitmap_lds;
-        } else if ((tune.force_k == 0 || tune.force_k == 8) && n_agents == 32 && layout_fits(n_agents, 8, args, lds_bytes, &block, &Q) &&
-                   args.n_envs % (512u / 4u) == 0 && (tune.force_k == 8 || args.n_envs * 4u >= tune.oct_min_lanes)) {
-            block = 512u;
-            K = 8;
-        } else {
-            if (tune.force_k == 8 || !layout_fits(n_agents, 4, args, lds_bytes, &block, &Q) || Q < 4) return false;
-            block = 512u;
-            if (args.n_envs % (1024u / unsigned(Q)) == 0 && args.n_envs * uint64_t(Q) >= uint64_t(n_cu) * 1024u) block = 1024u;
-            if (args.n_envs % (block / unsigned(Q)) != 0) return false;
-            K = 4;
-        }
-        compact = true;
-    }
-    plan->K = K;
-    plan->Q = Q;
-    plan->form = delta_rows ? 5 : (full_rows_bitmap ? 4 : (bitmap ? (stay_column ? 3 : 2) : (compact ? 1 : 0)));
-    plan->block = block;
-    plan->lds_bytes = lds_bytes;
-    plan->lds_total = lds_bytes + (bitmap ? size_t(block / unsigned(Q)) * bitmap_stride(args.c.n_cells) : 0u);   // (as launch_impl adds them)
-    return true;
+        {F::DeltaRowsBitmap, 4, bitmaps && tune.bitmap_delta_rows && args.mv_delta8 && args.mv4, 0u, F::DeltaRowsBitmap,
+         one_block_per_cu(F::DeltaRowsBitmap, 8, args, tune, tune.bitmap_block)},
+        // where the five-column table (STAY included: four selects per agent-step less) still leaves room for the block's
+        // bitmaps -- 64 of them on the 64x64 maps, not 128 -- it is the one staged (C5's share: profiles/r04_c5_stay_column_ab.txt);
+        // it takes the block the four-column table would
+        {F::Rows8x5Bitmap, 4, bitmaps && tune.bitmap_stay_column, 0u, F::Rows8x4Bitmap, rows8_bitmap_block},
+        {F::Rows8x4Bitmap, 4, bitmaps, 0u, F::Rows8x4Bitmap, rows8_bitmap_block},
+        {F::Rows8, 8, (k == 0 || k == 8) && team32, oct_min, F::Rows8, 512u},
+        {F::Rows8, 4, k != 8, 0u, F::Rows8, one_block_per_cu(F::Rows8, n_agents / 4, args, tune, 0u)},
+    };
+    return first_candidate(list, sizeof(list) / sizeof(list[0]), n_agents, args, plan);
 }
 
 // ... under the table policy.  Which of the two table forms: the LDS copy whenever image + bitmaps + policy table fit the CU's LDS
@@ -180,12 +174,11 @@ bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutT
         tune.force_k = 4;
         if (!plan_rollout_lq(n_agents, args, tune, plan)) return false;
     }
-    if (plan->form != 0 && plan->form != 5) return false;
-    if (plan->K == 4 ? (plan->form == 5 ? plan->Q != 8 : plan->Q > 8) : (plan->K != 2 || plan->Q < 2)) return false;
+    if (!lq_rollout_instance_exists(plan->K, plan->Q, plan->form, true)) return false;
     if (plan->block > 512u) {                                   // the table instances are built for 512 threads (delta rows: 64 bitmaps)
         plan->block = 512u;
         if (args.n_envs % (512u / unsigned(plan->Q)) != 0) return false;
-        plan->lds_total = plan->lds_bytes + (plan->form == 5 ? size_t(512u / unsigned(plan->Q)) * bitmap_stride(args.c.n_cells) : 0u);
+        plan->lds_total = launch_lds_bytes(plan->form, args.c.n_cells, 512u, plan->Q);
     }
     const size_t at16 = (plan->lds_total + 15u) & ~size_t(15), with_table = at16 + ((table_bytes + 15u) & ~size_t(15));
     const uint64_t grid = args.n_envs / (plan->block / unsigned(plan->Q));
@@ -232,10 +225,10 @@ bool plan_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune,
         tune.force_k != 4) {
         const int Q8 = Q / 2;
         const unsigned block = 1024u, n_chunks = unsigned(args.n_envs * uint64_t(Q8) / block), grid = n_chunks < unsigned(n_cu) ? n_chunks : unsigned(n_cu);
-        *plan = StepPlan{8, Q8, 1, block, grid, n_chunks, big_lds, int(kLdsBytes - kLdsReserve)};
+        *plan = StepPlan{8, Q8, StepForm::FullRows, block, grid, n_chunks, big_lds, int(kLdsBytes - kLdsReserve)};
         return true;
     }
-    // The delta-row forms (BIG == 2, 3): where the 16-byte rows do not fit (64x64 maps) but the 4-byte ones do, from a batch of one
+    // The delta-row forms (StepForm::DeltaRows, DeltaRowsBitmap): where the 16-byte rows do not fit (64x64 maps) but the 4-byte ones do, from a batch of one
     // full residency on (65536 envs of 32 agents) -- below that the table copy per block (79 KB through the XCD's L2 for each of
     // its 32 CUs: 1.8 us in front of the first instruction that needs a row, profiles/r05_step_stamps_c5_share.txt) costs more
     // than the gathers it replaces: configs[4]'s share of one GPU (16384 envs) runs 4.95 us plain against 5.7-5.9 us.
@@ -258,13 +251,13 @@ bool plan_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune,
             unsigned per_cu = unsigned(kLdsBytes / form_lds);
             if (per_cu > 2048u / block) per_cu = 2048u / block;
             const unsigned n_chunks = unsigned(lanes / block), grid = n_chunks < per_cu * unsigned(n_cu) ? n_chunks : per_cu * unsigned(n_cu);
-            *plan = StepPlan{K, Q, bitmaps ? 3 : 2, block, grid, n_chunks, form_lds, int(kLdsBytes)};
+            *plan = StepPlan{K, Q, bitmaps ? StepForm::DeltaRowsBitmap : StepForm::DeltaRows, block, grid, n_chunks, form_lds, int(kLdsBytes)};
             return true;
         }
     }
     if (big) {
         const unsigned block = 1024u, n_chunks = unsigned(lanes / block), grid = n_chunks < 2u * unsigned(n_cu) ? n_chunks : 2u * unsigned(n_cu);
-        *plan = StepPlan{K, Q, 1, block, grid, n_chunks, big_lds, int(kLdsBytes - kLdsReserve)};
+        *plan = StepPlan{K, Q, StepForm::FullRows, block, grid, n_chunks, big_lds, int(kLdsBytes - kLdsReserve)};
         return true;
     }
     unsigned block = 256u;
@@ -276,7 +269,7 @@ bool plan_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune,
     const uint64_t per_block = block / unsigned(Q);
     if (args.n_envs == 0 || args.n_envs % per_block != 0) return false;
     const unsigned grid = unsigned(args.n_envs / per_block);
-    *plan = StepPlan{K, Q, 0, block, grid, grid, 0, 0};
+    *plan = StepPlan{K, Q, StepForm::Plain, block, grid, grid, 0, 0};
     return true;
 }
 

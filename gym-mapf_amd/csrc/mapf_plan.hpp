@@ -2,7 +2,7 @@
 // integer arithmetic over the launch's shape, the tuning and the LDS layout (mapf_layout.hpp) -- no kernel, no runtime
 // call -- so it can be swept without a device (mapf_debug_rollout_plan, tests/test_cabi_and_host.py).
 #pragma once
-#include "mapf_kernels.hpp"
+#include "mapf_layout.hpp"
 
 namespace mapf {
 
@@ -13,11 +13,10 @@ RolloutTuning rollout_tuning_for(int n_cu, const char *text, std::string *err);
 // actions / mv4 / mv_delta8 present or not) and the tuning (its n_cu included): false = no packed form applies.
 struct LqPlan {
     int K = 0, Q = 0;                // agents per lane, lanes per env
-    int form = 0;                    // 0 full 16-byte rows, 1 8-byte rows, 2 / 3 bitmaps behind four / five 8-byte columns, 4 bitmaps behind
-                                     // full rows, 5 bitmaps behind 4-byte delta rows
+    TableForm form = TableForm::FullRows;   // how the move table lies in LDS (mapf_layout.hpp; DESIGN.md 4.1 lists the six forms)
     unsigned block = 0;              // threads per block
-    size_t lds_bytes = 0;            // the kernel's LDS image without the bitmaps (what the launcher is handed)
-    size_t lds_total = 0;            // ... with them: the dynamic LDS segment of the launch, <= 160 KB
+    size_t lds_bytes = 0;            // table_image_bytes(form): the kernel's LDS image without the bitmaps (what the launcher is handed)
+    size_t lds_total = 0;            // launch_lds_bytes(form, ...): with them -- the dynamic LDS segment of the launch, <= 160 KB
 };
 bool plan_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, LqPlan *plan);
 // ... under the table policy (args.actions == null): the packed table instances exist for two and four agents per lane over full
@@ -26,11 +25,12 @@ bool plan_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning 
 bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, size_t table_bytes, LqPlan *plan,
                            bool *table_lds, uint32_t *table_at);
 
-// What try_launch_step_lq (mapf_lq_step.hip) launches: the instance lq_step_kernel<Q, K, ., ., big> and its geometry.
+// The forms of the packed single step: the plain step, or a resident grid with the move table in LDS (the values: the kernel's BIG)
+enum class StepForm : int { Plain = 0, FullRows = 1, DeltaRows = 2, DeltaRowsBitmap = 3 };   // (16-byte rows; 4-byte delta rows; ... + per-env occupancy bitmaps)
+// What try_launch_step_lq (mapf_lq_step.hip) launches: the instance lq_step_kernel<Q, K, ., ., form> and its geometry.
 struct StepPlan {
     int K = 0, Q = 0;                // agents per lane (2, 4; 8 in the large-batch form), lanes per env
-    int big = 0;                     // 0 plain step; resident grid with the move table in LDS: 1 16-byte rows, 2 4-byte delta rows,
-                                     // 3 delta rows + per-env occupancy bitmaps
+    StepForm big = StepForm::Plain;   // the form (the name of the kernel's template argument)
     unsigned block = 0, grid = 0;
     unsigned n_chunks = 0;           // the kernel's last argument: chunks of `block` lanes the resident grid walks (plain step: the grid)
     size_t lds_bytes = 0;            // dynamic LDS segment (0 for the plain step: its 1 KB image is static)

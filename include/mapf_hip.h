@@ -350,9 +350,9 @@ int mapf_abi_version(void);
  * n_cells = cells of the map incl. the blocked id; streamed = actions given (1) or drawn in the kernel (0); delta_rows = the
  * map admits 4-byte delta rows (every neighbour id within +-127 of its cell); tune = a MAPF_TUNE string or NULL for the
  * defaults (the MAPF_TUNE environment variable is NOT read).
- * out[0..5] = {agents per lane K, lanes per env Q, form (0 full 16-byte rows, 1 8-byte rows, 2 / 3 bitmaps behind four /
- * five 8-byte columns, 4 bitmaps behind full rows, 5 bitmaps behind delta rows), threads per block, LDS bytes of the table
- * image, LDS bytes of the launch}.  Returns 1 when a packed form applies, 0 when the lane-group kernel takes the launch,
+ * out[0..5] = {agents per lane K, lanes per env Q, form (0..5: how the move table lies in LDS -- the table of the six forms
+ * in DESIGN.md 4.1, TableForm in csrc/mapf_layout.hpp), threads per block, LDS bytes of the table image, LDS bytes of the
+ * launch}.  Returns 1 when a packed form applies, 0 when the lane-group kernel takes the launch,
  * MAPF_EINVAL (< 0) for a malformed tune string or null out. */
 int mapf_debug_rollout_plan(uint32_t n_cells, int n_agents, uint64_t n_envs, uint32_t n_steps, int streamed, int delta_rows,
                             int n_cu, const char *tune, uint64_t out[6]);

@@ -76,7 +76,7 @@ int shim_greedy_cells(const uint16_t *nbr, uint32_t V, const uint32_t *cell_rc, 
     return 1;
 }
 
-// plan_step_lq over a shape: out = K, Q, big, block, grid, n_chunks, lds_bytes, lds_limit; 1 = a packed form, 0 = none, -1 = bad tune
+// plan_step_lq over a shape: out = K, Q, form (StepForm's number), block, grid, n_chunks, lds_bytes, lds_limit; 1 = a packed form, 0 = none, -1 = bad tune
 int shim_plan_step(uint32_t n_cells, int n_agents, uint64_t n_envs, int has_delta_rows, int n_cu, const char *tune, uint64_t out[8]) {
     std::string err;
     const RolloutTuning t = rollout_tuning_for(n_cu, tune, &err);
@@ -88,9 +88,37 @@ int shim_plan_step(uint32_t n_cells, int n_agents, uint64_t n_envs, int has_delt
     args.mv4 = has_delta_rows ? &present : nullptr;
     StepPlan plan;
     if (!plan_step_lq(n_agents, args, t, &plan)) return 0;
-    out[0] = uint64_t(plan.K); out[1] = uint64_t(plan.Q); out[2] = uint64_t(plan.big); out[3] = plan.block; out[4] = plan.grid;
+    out[0] = uint64_t(plan.K); out[1] = uint64_t(plan.Q); out[2] = uint64_t(int(plan.big)); out[3] = plan.block; out[4] = plan.grid;
     out[5] = plan.n_chunks; out[6] = plan.lds_bytes; out[7] = uint64_t(plan.lds_limit);
     return 1;
+}
+
+// plan_rollout_lq_table over a shape (a launch without streamed actions, under a policy table of table_bytes): out = K, Q, form,
+// block, lds_bytes, lds_total, table_lds, table_at; 1 = a packed table instance, 0 = none, -1 = bad tune
+int shim_plan_rollout_table(uint32_t n_cells, int n_agents, uint64_t n_envs, uint32_t n_steps, int has_delta_rows, uint64_t table_bytes, int n_cu,
+                            const char *tune, uint64_t out[8]) {
+    std::string err;
+    const RolloutTuning t = rollout_tuning_for(n_cu, tune, &err);
+    if (!err.empty()) return -1;
+    static const uint32_t present = 0;
+    RolloutArgs args{};
+    args.c.n_cells = n_cells;
+    args.n_envs = n_envs;
+    args.n_steps = n_steps;
+    args.mv_delta8 = has_delta_rows != 0;
+    args.mv4 = has_delta_rows ? &present : nullptr;
+    LqPlan plan;
+    bool table_lds = false;
+    uint32_t table_at = 0;
+    if (!plan_rollout_lq_table(n_agents, args, t, size_t(table_bytes), &plan, &table_lds, &table_at)) return 0;
+    out[0] = uint64_t(plan.K); out[1] = uint64_t(plan.Q); out[2] = uint64_t(int(plan.form)); out[3] = plan.block; out[4] = plan.lds_bytes;
+    out[5] = plan.lds_total; out[6] = table_lds ? 1u : 0u; out[7] = table_at;
+    return 1;
+}
+
+// does the launcher hold the packed rollout instance (K, Q, form)?  (table: of lq_rollout_kernel_table)
+int shim_rollout_instance_exists(int K, int Q, int form, int table) {
+    return form >= 0 && form < kTableForms && lq_rollout_instance_exists(K, Q, TableForm(form), table != 0) ? 1 : 0;
 }
 
 }  // extern "C"

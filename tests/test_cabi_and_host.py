@@ -2,6 +2,7 @@
 the product fails loudly without a GPU (no CPU fallback), and the kernels that can be dispatched
 compile without register spills.  No compute is launched here."""
 import ctypes
+import functools
 import os
 import re
 import subprocess
@@ -13,6 +14,7 @@ from conftest import ROOT
 from gym_mapf_amd import _native as nat
 from gym_mapf_amd.envs.grid import MapfGrid
 from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
+from test_host_tables import shim  # noqa: F401  (the host shim, built once per run)
 
 HEADER = os.path.join(ROOT, 'include', 'mapf_hip.h')
 CSRC = os.path.join(ROOT, 'gym-mapf_amd', 'csrc')
@@ -200,12 +202,22 @@ def test_packed_kernels_layout_assumptions_hold_in_the_compiled_objects(device_l
         assert '__builtin_trap' not in open(os.path.join(CSRC, unit)).read(), unit
 
 
-def test_packed_rollout_dispatch_never_plans_past_the_lds_or_launch_bounds():
+# the sweep of plan_rollout_lq (tests/test_plan_decisions.py digests the same one, and more)
+ROLLOUT_PLAN_CELLS = sorted(set(list(range(2, 200, 7)) + list(range(600, 760, 3)) + list(range(800, 1800, 11)) + list(range(1650, 1720)) +
+                                list(range(3000, 3400, 5)) + list(range(4000, 20500, 61)) + list(range(19700, 20300, 3)) + [683, 3278, 4097, 65535]))
+ROLLOUT_PLAN_TUNES = [None, b'k=8', b'k=4', b'k=2', b'bitmap_block=1024', b'bitmap_block=512', b'bitmap_pairs=0', b'bitmap_delta=0',
+                      b'bitmap_staycol=0', b'mv_lds_max_bytes=163840', b'mv_lds_max_bytes=0', b'quad_min_lanes=0,oct_min_lanes=0']
+ROLLOUT_PLAN_AGENTS = (2, 4, 8, 16, 32, 64, 128)
+ROLLOUT_PLAN_ENVS = (64, 1000, 1024, 4096, 16384, 16448, 65536, 131072, 262144)
+
+
+def test_packed_rollout_dispatch_never_plans_past_the_lds_or_launch_bounds(shim):
     """mapf_debug_rollout_plan is the arithmetic try_launch_rollout_lq runs before every packed rollout launch (no device
     involved).  Swept over map sizes across every form's LDS boundary, agent counts, batch sizes, streamed / in-kernel policy,
     delta rows or not, and the MAPF_TUNE overrides the tests use: whatever form is planned fits the CU's 160 KB of LDS (the limit
     the launcher raises the kernel's dynamic segment to), fills whole blocks, and stays within its instance's launch bounds;
-    and the forms end exactly where the next cell would not fit."""
+    and the forms end exactly where the next cell would not fit.  Every planned (K, Q, form) is an instance the launcher holds
+    (lq_rollout_instance_exists, asked through the host shim)."""
     from gym_mapf_amd import _native
     import ctypes
     lib = _native.load()
@@ -217,14 +229,12 @@ def test_packed_rollout_dispatch_never_plans_past_the_lds_or_launch_bounds():
         assert rc in (0, 1), (rc, lib.mapf_last_error())
         return rc, tuple(out)
 
-    cells = sorted(set(list(range(2, 200, 7)) + list(range(600, 760, 3)) + list(range(800, 1800, 11)) + list(range(1650, 1720)) +
-                       list(range(3000, 3400, 5)) + list(range(4000, 20500, 61)) + list(range(19700, 20300, 3)) + [683, 3278, 4097, 65535]))
-    tunes = [None, b'k=8', b'k=4', b'k=2', b'bitmap_block=1024', b'bitmap_block=512', b'bitmap_pairs=0', b'bitmap_delta=0',
-             b'bitmap_staycol=0', b'mv_lds_max_bytes=163840', b'mv_lds_max_bytes=0', b'quad_min_lanes=0,oct_min_lanes=0']
+    cells, tunes = ROLLOUT_PLAN_CELLS, ROLLOUT_PLAN_TUNES
+    exists = functools.lru_cache(maxsize=None)(lambda K, Q, form: shim.shim_rollout_instance_exists(K, Q, form, 0) == 1)
     seen_forms, n_packed = set(), 0
     for tune in tunes:
-        for A in (2, 4, 8, 16, 32, 64, 128):
-            for E in (64, 1000, 1024, 4096, 16384, 16448, 65536, 131072, 262144):
+        for A in ROLLOUT_PLAN_AGENTS:
+            for E in ROLLOUT_PLAN_ENVS:
                 for streamed in (1, 0):
                     for delta in (0, 1):
                         for V in cells:
@@ -235,6 +245,7 @@ def test_packed_rollout_dispatch_never_plans_past_the_lds_or_launch_bounds():
                             seen_forms.add(form)
                             ctx = (tune, A, E, streamed, delta, V, K, Q, form, block, table, total)
                             assert K in (2, 4, 8) and K * Q == A and Q in (1, 2, 4, 8, 16), ctx
+                            assert exists(K, Q, form), ctx
                             assert block in (64, 128, 256, 512, 1024) and E % (block // Q) == 0, ctx
                             assert 1024 < table <= total <= LDS, ctx
                             assert (total > table) == (form in (2, 3, 4, 5)), ctx          # bitmaps behind the table

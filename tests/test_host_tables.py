@@ -21,15 +21,28 @@ OUTCOME = np.dtype([('reward', '<f8'), ('status', '<u4'), ('pad', '<u4')])
 LDS = 160 * 1024
 
 
+_SHIM = []      # built once per run: tests/test_cabi_and_host.py and tests/test_plan_decisions.py use the fixture too
+
+
 @pytest.fixture(scope='module')
 def shim(tmp_path_factory):
-    out = tmp_path_factory.mktemp('host_tables') / 'libhost_tables_shim.so'
+    if not _SHIM:
+        _SHIM.append(load_shim(build_shim(tmp_path_factory.mktemp('host_tables'))))
+    return _SHIM[0]
+
+
+def build_shim(out_dir, csrc=CSRC):
+    out = os.path.join(str(out_dir), 'libhost_tables_shim.so')
     cmd = ['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-shared', '-I' + os.path.join(ROOT, 'include'),
-           '-I' + CSRC, os.path.join(ROOT, 'tests', 'host_tables_shim.hip'), os.path.join(CSRC, 'mapf_tables.hip'),
-           os.path.join(CSRC, 'mapf_plan.hip'), '-o', str(out)]                     # (the Makefile's flags: no FMA contraction)
+           '-I' + csrc, os.path.join(ROOT, 'tests', 'host_tables_shim.hip'), os.path.join(csrc, 'mapf_tables.hip'),
+           os.path.join(csrc, 'mapf_plan.hip'), '-o', out]                          # (the Makefile's flags: no FMA contraction)
     proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     assert proc.returncode == 0, proc.stdout.decode('utf-8', 'replace')[-3000:]
-    lib = ctypes.CDLL(str(out))
+    return out
+
+
+def load_shim(path):
+    lib = ctypes.CDLL(path)
     lib.shim_slip_tables.argtypes = [ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.shim_outcome_rows.argtypes = [ctypes.c_double] * 3 + [ctypes.c_void_p]
     lib.shim_outcome_status.argtypes = [ctypes.c_uint32]
@@ -40,6 +53,10 @@ def shim(tmp_path_factory):
     lib.shim_scen_table.restype = ctypes.c_uint32
     lib.shim_greedy_cells.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
     lib.shim_plan_step.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p]
+    lib.shim_plan_rollout_table.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int,
+                                            ctypes.c_char_p, ctypes.c_void_p]
+    if hasattr(lib, 'shim_rollout_instance_exists'):
+        lib.shim_rollout_instance_exists.argtypes = [ctypes.c_int] * 4
     return lib
 
 
@@ -260,23 +277,30 @@ def test_greedy_policy_cells(shim):
     assert b'cell_rc does not match the neighbour table' in err.value
 
 
+# the sweep of plan_step_lq (tests/test_plan_decisions.py digests the same one)
+STEP_PLAN_CELLS = sorted(set(list(range(2, 200, 13)) + list(range(600, 900, 17)) + list(range(3000, 3400, 23)) + list(range(4000, 7200, 97)) +
+                             [682, 683, 852, 853, 3294, 3648, 6783, 6784, 6785, 14818, 47540, 65535]))
+STEP_PLAN_TUNES = [None, b'step_big=2', b'step_big=0', b'step_delta=2', b'step_delta=0', b'step_big=2,step_delta=2', b'k=2', b'k=4',
+                   b'step_block=512', b'step_block=64', b'bitmap_pairs=0', b'quad_lanes=0']
+STEP_PLAN_CUS = (256, 8)
+STEP_PLAN_AGENTS = (2, 3, 4, 6, 8, 16, 32, 64, 128)
+STEP_PLAN_ENVS = (0, 1, 64, 1000, 1024, 4096, 16384, 65536, 131072, 262144, 1 << 20, 1 << 22)
+
+
 def test_packed_step_plan_stays_within_the_lds_and_its_residency(shim):
     """plan_step_lq swept like the rollout plan (tests/test_cabi_and_host.py): whatever instance is planned exists, fills whole
     blocks, keeps its LDS image within the CU's 160 KB (and within the limit the launcher raises the kernel to), and its
     resident grid within what the LDS image and 2048 threads per CU allow."""
     out = np.zeros(8, np.uint64)
     stride = lambda V: (((V + 31) // 32) * 4 + 15) & ~15                                   # noqa: E731  (bytes of one env's bitmap)
-    cells = sorted(set(list(range(2, 200, 13)) + list(range(600, 900, 17)) + list(range(3000, 3400, 23)) + list(range(4000, 7200, 97)) +
-                       [682, 683, 852, 853, 3294, 3648, 6783, 6784, 6785, 14818, 47540, 65535]))
-    tunes = [None, b'step_big=2', b'step_big=0', b'step_delta=2', b'step_delta=0', b'step_big=2,step_delta=2', b'k=2', b'k=4',
-             b'step_block=512', b'step_block=64', b'bitmap_pairs=0', b'quad_lanes=0']
+    cells, tunes = STEP_PLAN_CELLS, STEP_PLAN_TUNES
     instances = {(Q, 8, 1) for Q in (1, 2, 4)} | {(8, 4, 3)} | {(Q, 4, b) for Q in (1, 2, 4, 8) for b in (1, 2)} | \
                 {(Q, 4, 0) for Q in (1, 2, 4, 8, 16)} | {(Q, 2, 0) for Q in (2, 4, 8, 16)}          # mapf_lq_step.hip's instance switch
     seen, n_planned = set(), 0
     for tune in tunes:
-        for n_cu in (256, 8):
-            for A in (2, 3, 4, 6, 8, 16, 32, 64, 128):
-                for E in (0, 1, 64, 1000, 1024, 4096, 16384, 65536, 131072, 262144, 1 << 20, 1 << 22):
+        for n_cu in STEP_PLAN_CUS:
+            for A in STEP_PLAN_AGENTS:
+                for E in STEP_PLAN_ENVS:
                     for delta in (0, 1):
                         for V in cells:
                             rc = shim.shim_plan_step(V, A, E, delta, n_cu, tune, out.ctypes.data)
