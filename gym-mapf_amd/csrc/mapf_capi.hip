@@ -20,7 +20,7 @@
 namespace {
 
 thread_local std::string g_last_error;
-thread_local char g_noted_kernel[160] = "";
+thread_local char g_noted_kernel[mapf::kKernelNameBytes] = "";
 
 int fail(int code, const std::string &msg) {
     g_last_error = msg;
@@ -620,7 +620,8 @@ int mapf_rollout(mapf_handle_t h, const mapf_rollout_io *io) {
     a.t = h->capturing ? h->cap_steps : h->t;
     a.t_dev = h->capturing ? h->t_dev : nullptr;
     a.policy_cells = h->policy_cells;
-    // (the table policy travels beside the argument block: its kernels are instances of their own)
+    // (the table policy travels beside the argument block: its kernels are instances of their own; streamed actions take
+    // precedence over it, as over the other policies -- the ONE place that rule is applied: no launcher sees both)
     const mapf::TablePolicy *table = (h->table.table && !io->actions) ? &h->table : nullptr;
     a.start_broadcast = h->start_broadcast; a.goal_broadcast = h->goal_broadcast;
     a.auto_reset = io->step_flags & MAPF_STEP_AUTO_RESET;

@@ -36,22 +36,12 @@ hipError_t launch_rollout(int n_agents, const RolloutArgs &args, hipStream_t str
 // true when a packed layout took the launch (*err = its status); false = not applicable, use the lane-group kernel
 bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy *table) {
     LqPlan plan;
-    bool table_lds = false;
-    uint32_t table_at = 0u;
-    if (table && args.actions) table = nullptr;
-    if (table ? !plan_rollout_lq_table(n_agents, args, tune, table->table_bytes, &plan, &table_lds, &table_at)
-              : !plan_rollout_lq(n_agents, args, tune, &plan)) return false;
+    if (table ? !plan_rollout_lq_table(n_agents, args, tune, table->table_bytes, &plan) : !plan_rollout_lq(n_agents, args, tune, &plan)) return false;
     const bool record = args.rec_local != nullptr;
-    const int K = plan.K;
-    if (record && !(args.rec_reward && args.rec_prob && args.rec_done && args.rec_collision)) {
-        *err = hipErrorInvalidValue;
-        return true;
-    }
-#define LQ_ARGS plan.Q, plan.form, args, uint32_t(n_agents), plan.block, plan.lds_bytes, stream, table, table_lds, table_at
-    if (K == 8) *err = record ? launch_rollout_lq_k8_r1(LQ_ARGS) : launch_rollout_lq_k8_r0(LQ_ARGS);
-    else if (K == 4) *err = record ? launch_rollout_lq_k4_r1(LQ_ARGS) : launch_rollout_lq_k4_r0(LQ_ARGS);
-    else *err = record ? launch_rollout_lq_k2_r1(LQ_ARGS) : launch_rollout_lq_k2_r0(LQ_ARGS);
-#undef LQ_ARGS
+    const uint32_t A = uint32_t(n_agents);
+    if (plan.K == 8) *err = record ? launch_rollout_lq_k8_r1(plan, args, A, stream, table) : launch_rollout_lq_k8_r0(plan, args, A, stream, table);
+    else if (plan.K == 4) *err = record ? launch_rollout_lq_k4_r1(plan, args, A, stream, table) : launch_rollout_lq_k4_r0(plan, args, A, stream, table);
+    else *err = record ? launch_rollout_lq_k2_r1(plan, args, A, stream, table) : launch_rollout_lq_k2_r0(plan, args, A, stream, table);
     return true;
 }
 

@@ -204,7 +204,6 @@ static hipError_t launch_tpe_rollout(const RolloutArgs &args, unsigned grid, uns
 
 hipError_t MAPF_G(launch_rollout_g)(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table) {
     if (args.n_envs == 0) return hipSuccess;
-    if (table && args.actions) table = nullptr;                  // (streamed actions take precedence, as over the other policies)
     const unsigned block = pick_block(args.n_envs), grid = grid_for(args.n_envs, block);
     if (table) note_kernel("rollout_kernel_table<A=%d,TABLE> block=%u (thread per env, table policy: action bytes gathered from global memory)", n_agents, block);
     else note_kernel("rollout_kernel<A=%d> block=%u (thread per env)", n_agents, block);

@@ -161,6 +161,7 @@ struct TablePolicy {
 
 // Every launcher names the kernel instance (and block size) that took the launch; the C ABI keeps the name of a
 // handle's last step / rollout launch (mapf_last_kernel) so a benchmark labels its numbers with what actually ran.
+constexpr size_t kKernelNameBytes = 160;   // what is kept of a name, the terminator included
 void note_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 
 // routed by agent count (mapf_dispatch.hip)
@@ -199,8 +200,10 @@ uint64_t transitions_scan_blocks(uint64_t n_queries);
 hipError_t launch_transition_rewards(const TransitionsArgs &args, const uint16_t *next, hipStream_t stream);
 
 hipError_t launch_step(int n_agents, const StepArgs &args, hipStream_t stream);
-// (table: the table policy of an actions == null launch, or null -- a launcher whose family has no table instance for the
-// launch's shape returns hipErrorInvalidValue: a missing kernel is an error, never another policy)
+// (table: the table policy of an actions == null launch, or null: streamed actions take precedence over it as over the other
+// policies, and the C ABI, which applies that rule, never passes both -- a launcher whose family has no table instance for the
+// launch's shape returns hipErrorInvalidValue: a missing kernel is an error, never another policy.  A recording launch names
+// all five rec_* arrays: the C ABI substitutes scratch for absent ones)
 hipError_t launch_rollout(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table = nullptr);
 hipError_t launch_reset(int n_agents, uint16_t *state, const uint16_t *start, bool start_broadcast,
                         const uint8_t *mask, uint64_t n_envs, hipStream_t stream);
@@ -253,15 +256,15 @@ hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const Rollou
 // packed layout of the fused rollout (2, 4 or 8 agents per lane): plans the launch (mapf_plan.hpp) and routes it to the object that
 // holds its instance (mapf_dispatch.hip); true when it took the launch (*err = its status)
 bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy *table = nullptr);
-// ... the launchers of those objects: mapf_lq_rollout.hip compiled once per (agents per lane, recording) pair; form, block, lds_bytes,
-enum class TableForm : int;   // table_lds, table_at: the plan's answers (TableForm: mapf_layout.hpp)
-#define MAPF_LQ_LAUNCHER(name)                                                                                                          \
-    hipError_t name(int Q, TableForm form, const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream, \
-                    const TablePolicy *table, bool table_lds, uint32_t table_at);
-MAPF_LQ_LAUNCHER(launch_rollout_lq_k8_r1) MAPF_LQ_LAUNCHER(launch_rollout_lq_k8_r0) MAPF_LQ_LAUNCHER(launch_rollout_lq_k4_r1)
-MAPF_LQ_LAUNCHER(launch_rollout_lq_k4_r0) MAPF_LQ_LAUNCHER(launch_rollout_lq_k2_r1) MAPF_LQ_LAUNCHER(launch_rollout_lq_k2_r0)
-#undef MAPF_LQ_LAUNCHER
-int lg_group_size(int n_agents);
+// ... the launchers of those objects: mapf_lq_rollout.hip compiled once per (agents per lane, recording) pair; each launches the
+// instance the plan names (table: the table policy, or null)
+struct LqPlan;   // mapf_plan.hpp
+hipError_t launch_rollout_lq_k8_r1(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table);
+hipError_t launch_rollout_lq_k8_r0(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table);
+hipError_t launch_rollout_lq_k4_r1(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table);
+hipError_t launch_rollout_lq_k4_r0(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table);
+hipError_t launch_rollout_lq_k2_r1(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table);
+hipError_t launch_rollout_lq_k2_r0(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table);
 
 // per-group entry points: group g holds the kernels specialised for A in 4g+1 .. 4g+4
 hipError_t launch_step_g0(int n_agents, const StepArgs &args, hipStream_t stream);

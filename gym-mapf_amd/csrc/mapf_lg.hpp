@@ -12,7 +12,8 @@
 // factor 1.0; FULL specialisations (A == 2L) drop all ghost bookkeeping.
 //
 // Same semantics, arguments and outputs as step_kernel / rollout_kernel in mapf_kernels.hip.
-// This header holds the device code shared by mapf_lg_kernels.hip (step + helpers) and mapf_lg_rollout.hip.
+// This header holds the device code shared by mapf_lg_kernels.hip (step + helpers) and mapf_lg_rollout.hip; the geometry of
+// their launches is planned in mapf_plan.hip (plan_step_lg, plan_rollout_lg).
 #pragma once
 #include "mapf_kernels.hpp"
 #include "mapf_device.hpp"
@@ -505,15 +506,6 @@ static inline hipError_t allow_large_lds(const void *kernel, int bytes) {
     if (hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)) return e;
     done.insert({dev, kernel});
     return hipSuccess;
-}
-
-static inline void lg_geometry(int L, uint64_t n_envs, unsigned &grid, unsigned &block) {
-    const uint64_t threads = n_envs * uint64_t(L);
-    // one-wave blocks keep >= ~2 blocks per CU at small sizes; from two waves per SIMD upward four-wave blocks launch
-    // faster (measured at 65536 envs x 8 agents: 5.29 us per step instead of 5.67)
-    block = threads < (uint64_t(1) << 17) ? 64u : 256u;
-    const uint64_t per_block = block / unsigned(L);
-    grid = unsigned((n_envs + per_block - 1) / per_block);
 }
 
 #define MAPF_FOR_EACH_L(X) X(1) X(2) X(4) X(8) X(16) X(32) X(64)

@@ -1,5 +1,6 @@
 // Lane-group family: single-step kernel, run-time-A helper kernels and their launchers (device code: mapf_lg.hpp).
 #include "mapf_lg.hpp"
+#include "mapf_plan.hpp"
 
 namespace mapf {
 
@@ -165,38 +166,28 @@ hipError_t launch_fill_actions(int n_agents, uint8_t *actions, const EnvConsts &
 }
 
 // ------------------------------------------------------------------- launchers
-int lg_group_size(int n_agents) {
-    int pairs = (n_agents + 1) / 2, L = 1;
-    while (L < pairs) L <<= 1;
-    return L;
-}
-
+// launches the instance plan_step_lg names (mapf_plan.hip), unless the packed single step takes the launch
 hipError_t launch_step_lg(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream) {
     if (args.n_envs == 0) return hipSuccess;
     hipError_t packed_status;
     if (try_launch_step_lq(n_agents, args, tune, stream, &packed_status)) return packed_status;
-    const int L = lg_group_size(n_agents);
-    const bool full = n_agents == 2 * L;
-    unsigned grid, block;
-    lg_geometry(L, args.n_envs, grid, block);
-    const uint32_t A = uint32_t(n_agents);
-    note_kernel("lg_step_kernel<L=%d,%s,%s> block=%u (pair layout: 2 agents per lane)", L, full ? "FULL" : "RAGGED",
-                args.uniforms ? "EXT_UNIFORMS" : "PHILOX", block);
-    switch (L) {
+    const LgStepPlan plan = plan_step_lg(n_agents, args);
+    const bool ext = args.uniforms != nullptr;
+    void (*kern)(const StepArgs, const uint32_t) = nullptr;
+    switch (plan.L) {
 #define X(N)                                                                                                         \
     case N:                                                                                                          \
-        if (args.uniforms) {                                                                                         \
-            if (full) hipLaunchKernelGGL((lg_step_kernel<N, true, true>), dim3(grid), dim3(block), 0, stream, args, A);   \
-            else hipLaunchKernelGGL((lg_step_kernel<N, false, true>), dim3(grid), dim3(block), 0, stream, args, A);       \
-        } else {                                                                                                     \
-            if (full) hipLaunchKernelGGL((lg_step_kernel<N, true, false>), dim3(grid), dim3(block), 0, stream, args, A);  \
-            else hipLaunchKernelGGL((lg_step_kernel<N, false, false>), dim3(grid), dim3(block), 0, stream, args, A);      \
-        }                                                                                                            \
+        kern = ext ? (plan.full ? lg_step_kernel<N, true, true> : lg_step_kernel<N, false, true>)                    \
+                   : (plan.full ? lg_step_kernel<N, true, false> : lg_step_kernel<N, false, false>);                 \
         break;
         MAPF_FOR_EACH_L(X)
 #undef X
         default: return hipErrorInvalidValue;
     }
+    char name[kKernelNameBytes];
+    lg_step_kernel_name(name, plan, ext);
+    note_kernel("%s", name);
+    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(plan.block), 0, stream, args, uint32_t(n_agents));
     return hipGetLastError();
 }
 

@@ -44,7 +44,7 @@
 // beyond the LDS budget, single steps) stays with mapf_lg_rollout.hip; launch_rollout_lg() picks.  Same stream,
 // same arithmetic, same outputs: the parity tests run all layouts against the oracle.
 #include "mapf_lq.hpp"
-#include "mapf_layout.hpp"
+#include "mapf_plan.hpp"
 
 #include <type_traits>
 
@@ -87,10 +87,10 @@ static_assert(offsetof(SlipRow, thr) % 8 == 0 && kZeroFactor < 128u, "a zero fac
 #undef env_id
 
 constexpr const char *kBitmapNote = ", collisions through per-env occupancy bitmaps";
-// One family of instances, launched as planned: FORM's traits (mapf_layout.hpp) give the kernel's (COMPACT, BITMAP), the LDS segment
-// and what the kernel's name says; lds_bytes: the image up to the table's end
+// One family of instances, launched as planned: FORM's traits (mapf_layout.hpp) give the kernel's (COMPACT, BITMAP) and what the
+// kernel's name says; the plan (mapf_plan.hpp) gives the block, where the bitmaps begin (lds_bytes) and the launch's dynamic LDS segment (lds_total)
 template <int Q, int K, bool RECORD, bool STREAM, TableForm FORM>
-hipError_t launch_impl(const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream) {
+hipError_t launch_impl(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream) {
     constexpr TableFormTraits form = table_form_traits(FORM);
     constexpr bool COMPACT = form.compact; constexpr int BITMAP = form.bitmap;   // the kernel's template arguments
     // (criteria, may-be-terminal): the instance without terminal handling exists for Makespan only
@@ -98,28 +98,25 @@ hipError_t launch_impl(const RolloutArgs &args, uint32_t A, unsigned block, size
     auto kern = args.c.criteria != 0u ? lq_rollout_kernel<Q, K, RECORD, STREAM, true, COMPACT, true, BITMAP>
                 : term            ? lq_rollout_kernel<Q, K, RECORD, STREAM, false, COMPACT, true, BITMAP>
                                   : lq_rollout_kernel<Q, K, RECORD, STREAM, false, COMPACT, false, BITMAP>;
-    const uint32_t bitmap_base = uint32_t(lds_bytes);           // the bitmaps follow the table
-    lds_bytes = launch_lds_bytes(FORM, args.c.n_cells, block, Q);
-    if (lds_bytes > 32 * 1024) {
+    if (plan.lds_total > 32 * 1024) {
         // (this kernel has no static LDS object: its dynamic segment may be the CU's whole 160 KB -- the limit every form's
         // "does it fit" test in plan_rollout_lq compares against)
         if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(kLdsBytes))) return e;
     }
-    const unsigned grid = unsigned(args.n_envs / (block / unsigned(Q)));
+    const unsigned block = plan.block, grid = unsigned(args.n_envs / (block / unsigned(Q)));
     note_kernel("lq_rollout_kernel<Q=%d,K=%d,%s,%s,%s%s%s%s> block=%u (packed layout: %d agents per lane%s%s)", Q, K, RECORD ? "RECORD" : "TOTALS",
                 STREAM ? "STREAM" : "POLICY", args.c.criteria != 0u ? "SOC" : "MAKESPAN", COMPACT ? ",COMPACT" : "",
                 (args.c.criteria == 0u && !term) ? ",NO_TERMINAL" : "", form.tag, block, K, form.note, BITMAP ? kBitmapNote : "");
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds_bytes, stream, args, A, bitmap_base);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), plan.lds_total, stream, args, A, uint32_t(plan.lds_bytes));   // (the bitmaps follow the table)
     return hipGetLastError();
 }
 
-// the launcher of the table instances; table_lds / table_at / lds_total: plan_rollout_lq_table's answers
+// the launcher of the table instances (plan_rollout_lq_table's plan: the bitmaps follow the image, the policy table follows them at table_at)
 template <int Q, int K, bool RECORD, TableForm FORM>
-hipError_t launch_impl_table(const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream, const TablePolicy &tp, bool table_lds,
-                             uint32_t table_at) {
+hipError_t launch_impl_table(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy &tp) {
     constexpr TableFormTraits form = table_form_traits(FORM);
     constexpr bool COMPACT = form.compact; constexpr int BITMAP = form.bitmap;
-    const bool term = !(args.auto_reset && !args.start_terminal_any);
+    const bool term = !(args.auto_reset && !args.start_terminal_any), table_lds = plan.table_lds;
     auto pick = [&](auto tag) {
         constexpr int T = decltype(tag)::value;
         return args.c.criteria != 0u ? lq_rollout_kernel_table<Q, K, RECORD, true, COMPACT, true, BITMAP, T>
@@ -127,14 +124,9 @@ hipError_t launch_impl_table(const RolloutArgs &args, uint32_t A, unsigned block
                                  : lq_rollout_kernel_table<Q, K, RECORD, false, COMPACT, false, BITMAP, T>;
     };
     auto kern = table_lds ? pick(std::integral_constant<int, 2>{}) : pick(std::integral_constant<int, 1>{});
-    const uint32_t bitmap_base = uint32_t(lds_bytes);           // the bitmaps follow the image, the policy table follows them
-    lds_bytes = launch_lds_bytes(FORM, args.c.n_cells, block, Q);
-    if (table_lds) {
-        if (table_at < lds_bytes || (table_at & 15u) != 0u) return hipErrorInvalidValue;
-        lds_bytes = size_t(table_at) + ((size_t(tp.table_bytes) + 15u) & ~size_t(15));
-    }
-    if (lds_bytes > kLdsBytes || block > 512u) return hipErrorInvalidValue;
-    if (lds_bytes > 32 * 1024) {
+    const unsigned block = plan.block;
+    if (plan.lds_total > kLdsBytes || block > 512u) return hipErrorInvalidValue;   // (the table instances are built for 512 threads)
+    if (plan.lds_total > 32 * 1024) {
         if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(kLdsBytes))) return e;
     }
     const unsigned grid = unsigned(args.n_envs / (block / unsigned(Q)));
@@ -142,7 +134,7 @@ hipError_t launch_impl_table(const RolloutArgs &args, uint32_t A, unsigned block
                 RECORD ? "RECORD" : "TOTALS", args.c.criteria != 0u ? "SOC" : "MAKESPAN", COMPACT ? ",COMPACT" : "",
                 (args.c.criteria == 0u && !term) ? ",NO_TERMINAL" : "", form.tag, table_lds ? "TABLE_LDS" : "TABLE_GLOBAL", block, K,
                 form.note, BITMAP ? kBitmapNote : "", tp.table_bytes, table_lds ? "staged into LDS behind the image" : "gathered from global memory");
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds_bytes, stream, args, A, bitmap_base, tp, table_lds ? table_at : 0u);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), plan.lds_total, stream, args, A, uint32_t(plan.lds_bytes), tp, plan.table_at);
     return hipGetLastError();
 }
 
@@ -150,12 +142,11 @@ hipError_t launch_impl_table(const RolloutArgs &args, uint32_t A, unsigned block
 // answers from): a launch whose (Q, form) is in none of this K's lines is refused.  (A template, so that the lines of the other
 // K's are discarded, not instantiated.)
 template <int K, bool R>
-hipError_t launch_planned(int Q, TableForm form, const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream,
-                          const TablePolicy *table, bool table_lds, uint32_t table_at) {
-    if (table && !args.actions) {
+hipError_t launch_planned(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table) {
+    if (table) {
 #define X(KK, QQ, FF)                                                                                                                        \
     if constexpr (KK == K) {                                                                                                                 \
-        if (Q == QQ && form == TableForm::FF) return launch_impl_table<QQ, K, R, TableForm::FF>(args, A, block, lds_bytes, stream, *table, table_lds, table_at); \
+        if (plan.Q == QQ && plan.form == TableForm::FF) return launch_impl_table<QQ, K, R, TableForm::FF>(plan, args, A, stream, *table);    \
     }
         MAPF_LQ_ROLLOUT_TABLE_INSTANCES(X)
 #undef X
@@ -163,8 +154,8 @@ hipError_t launch_planned(int Q, TableForm form, const RolloutArgs &args, uint32
     }
 #define X(KK, QQ, FF)                                                                                                                        \
     if constexpr (KK == K) {                                                                                                                 \
-        if (Q == QQ && form == TableForm::FF) return args.actions ? launch_impl<QQ, K, R, true, TableForm::FF>(args, A, block, lds_bytes, stream)     \
-                                                                  : launch_impl<QQ, K, R, false, TableForm::FF>(args, A, block, lds_bytes, stream);   \
+        if (plan.Q == QQ && plan.form == TableForm::FF) return args.actions ? launch_impl<QQ, K, R, true, TableForm::FF>(plan, args, A, stream)     \
+                                                                            : launch_impl<QQ, K, R, false, TableForm::FF>(plan, args, A, stream);   \
     }
     MAPF_LQ_ROLLOUT_INSTANCES(X)
 #undef X
@@ -181,9 +172,8 @@ hipError_t launch_planned(int Q, TableForm form, const RolloutArgs &args, uint32
 #define MAPF_LQ_CAT3(a, b, c) a##b##_r##c
 #define MAPF_LQ_NAME(k, r) MAPF_LQ_CAT3(launch_rollout_lq_k, k, r)
 
-hipError_t MAPF_LQ_NAME(MAPF_LQ_K, MAPF_LQ_RECORD)(int Q, TableForm form, const RolloutArgs &args, uint32_t A, unsigned block, size_t lds_bytes, hipStream_t stream,
-                                                   const TablePolicy *table, bool table_lds, uint32_t table_at) {
-    return launch_planned<MAPF_LQ_K, MAPF_LQ_RECORD != 0>(Q, form, args, A, block, lds_bytes, stream, table, table_lds, table_at);
+hipError_t MAPF_LQ_NAME(MAPF_LQ_K, MAPF_LQ_RECORD)(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table) {
+    return launch_planned<MAPF_LQ_K, MAPF_LQ_RECORD != 0>(plan, args, A, stream, table);
 }
 
 }  // namespace mapf

@@ -1,6 +1,7 @@
-// Launch planning of the packed kernels: which form, block, grid and LDS image a launch of a given shape takes.  Pure
-// integer arithmetic over the launch's shape, the tuning and the LDS layout (mapf_layout.hpp) -- no kernel, no runtime
-// call -- so it can be swept without a device (mapf_debug_rollout_plan, tests/test_cabi_and_host.py).
+// Launch planning of the packed and the lane-group kernels: which form, block, grid and LDS image a launch of a given shape
+// takes.  Pure integer arithmetic over the launch's shape, the tuning and the LDS layout (mapf_layout.hpp) -- no kernel, no
+// runtime call -- so it can be swept without a device (mapf_debug_rollout_plan, tests/test_plan_decisions.py).  A launcher
+// takes ONE plan and launches the instance it names; it decides nothing itself.
 #pragma once
 #include "mapf_layout.hpp"
 
@@ -10,20 +11,28 @@ namespace mapf {
 RolloutTuning rollout_tuning_for(int n_cu, const char *text, std::string *err);
 
 // What try_launch_rollout_lq decides before it launches, from the launch's shape (args.c.n_cells, n_envs, n_steps, c.top_tie,
-// actions / mv4 / mv_delta8 present or not) and the tuning (its n_cu included): false = no packed form applies.
+// actions / mv4 / mv_delta8 present or not) and the tuning (its n_cu included): false = no packed form applies.  The whole plan:
+// the launchers of mapf_lq_rollout.hip are handed nothing else.
 struct LqPlan {
     int K = 0, Q = 0;                // agents per lane, lanes per env
     TableForm form = TableForm::FullRows;   // how the move table lies in LDS (mapf_layout.hpp; DESIGN.md 4.1 lists the six forms)
     unsigned block = 0;              // threads per block
-    size_t lds_bytes = 0;            // table_image_bytes(form): the kernel's LDS image without the bitmaps (what the launcher is handed)
-    size_t lds_total = 0;            // launch_lds_bytes(form, ...): with them -- the dynamic LDS segment of the launch, <= 160 KB
+    size_t lds_bytes = 0;            // table_image_bytes(form): the kernel's LDS image without the bitmaps, i.e. where the bitmaps begin
+    size_t lds_total = 0;            // the dynamic LDS segment of the launch, <= 160 KB: launch_lds_bytes(form, ...), with the bitmaps (and the policy table)
+    bool table_lds = false;          // table policy: the action bytes are staged into LDS behind the image (and the bitmaps) ...
+    uint32_t table_at = 0;           // ... at this byte, a multiple of 16 (lds_total then includes them)
 };
 bool plan_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, LqPlan *plan);
 // ... under the table policy (args.actions == null): the packed table instances exist for two and four agents per lane over full
-// 16-byte rows and for the 32-agent bitmap form over delta rows, in blocks of at most 512 threads; *table_lds = the action bytes are
-// staged into LDS behind the image (and the bitmaps) at byte *table_at, plan->lds_total then includes them.  false = lane-group kernel.
-bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, size_t table_bytes, LqPlan *plan,
-                           bool *table_lds, uint32_t *table_at);
+// 16-byte rows and for the 32-agent bitmap form over delta rows, in blocks of at most 512 threads.  false = lane-group kernel.
+bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, size_t table_bytes, LqPlan *plan);
+// (the earlier signature, for host shims written against it: no launcher keeps the two table fields apart)
+inline bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, size_t table_bytes, LqPlan *plan,
+                                  bool *table_lds, uint32_t *table_at) {
+    const bool packed = plan_rollout_lq_table(n_agents, args, tune, table_bytes, plan);
+    *table_lds = packed && plan->table_lds; *table_at = *table_lds ? plan->table_at : 0u;
+    return packed;
+}
 
 // The forms of the packed single step: the plain step, or a resident grid with the move table in LDS (the values: the kernel's BIG)
 enum class StepForm : int { Plain = 0, FullRows = 1, DeltaRows = 2, DeltaRowsBitmap = 3 };   // (16-byte rows; 4-byte delta rows; ... + per-env occupancy bitmaps)
@@ -37,5 +46,27 @@ struct StepPlan {
     int lds_limit = 0;               // what the launcher raises the instance's dynamic-LDS limit to when lds_bytes > 32 KB
 };
 bool plan_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, StepPlan *plan);
+
+// The lane-group family (mapf_lg.hpp) takes every launch the packed kernels decline: odd teams, ragged batches, large maps,
+// caller-supplied uniforms.  L lanes per env: the power of two >= ceil(A / 2) (two agents per lane).
+int lg_group_size(int n_agents);
+// Largest block of a rollout kernel: groups of 16 lanes unroll 8 rotation rounds and need more than the 128 registers a
+// 1024-thread block leaves per lane.  The kernels' __launch_bounds__ (rollout_max_block, mapf_lg_rollout.hip) read it too.
+constexpr unsigned kLgRolloutMaxBlock = 1024u, kLgRolloutMaxBlock16 = 512u;
+// The instance lg_rollout_kernel<L, full, mv_lds, ., ., dense> (or lg_rollout_kernel_table<L, full, mv_lds, ., dense>) and its geometry
+struct LgRolloutPlan {
+    int L = 0;                       // lanes per env
+    bool full = false;               // A == 2L: no ghost slots
+    bool mv_lds = false;             // the whole move table is staged into LDS once per block
+    bool dense = false;              // full groups and the env count fills every block: no per-lane predicates
+    unsigned block = 0, grid = 0;
+    size_t lds_bytes = 0;            // dynamic LDS segment: the move table, or 0 (the launcher raises the limit beyond 32 KB)
+};
+LgRolloutPlan plan_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune);
+struct LgStepPlan { int L = 0; bool full = false; unsigned block = 0, grid = 0; };
+LgStepPlan plan_step_lg(int n_agents, const StepArgs &args);
+// The names the launchers note for these plans (mapf_last_kernel; at most kKernelNameBytes with the terminator)
+void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy);
+void lg_step_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms);
 
 }  // namespace mapf

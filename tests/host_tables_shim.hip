@@ -108,11 +108,35 @@ int shim_plan_rollout_table(uint32_t n_cells, int n_agents, uint64_t n_envs, uin
     args.mv_delta8 = has_delta_rows != 0;
     args.mv4 = has_delta_rows ? &present : nullptr;
     LqPlan plan;
-    bool table_lds = false;
-    uint32_t table_at = 0;
-    if (!plan_rollout_lq_table(n_agents, args, t, size_t(table_bytes), &plan, &table_lds, &table_at)) return 0;
+    if (!plan_rollout_lq_table(n_agents, args, t, size_t(table_bytes), &plan)) return 0;
     out[0] = uint64_t(plan.K); out[1] = uint64_t(plan.Q); out[2] = uint64_t(int(plan.form)); out[3] = plan.block; out[4] = plan.lds_bytes;
-    out[5] = plan.lds_total; out[6] = table_lds ? 1u : 0u; out[7] = table_at;
+    out[5] = plan.lds_total; out[6] = plan.table_lds ? 1u : 0u; out[7] = plan.table_at;
+    return 1;
+}
+
+// plan_rollout_lg over a shape (policy: 0 streamed actions, 1 the in-kernel policy stream, 2 the table policy): out = L, full, mv_lds, dense,
+// block, grid, lds_bytes; name (kKernelNameBytes) = what the launcher notes for that plan; 1 = planned, -1 = bad tune
+int shim_plan_rollout_lg(uint32_t n_cells, int n_agents, uint64_t n_envs, int record, int policy, const char *tune, uint64_t out[7], char *name) {
+    std::string err;
+    const RolloutTuning t = rollout_tuning_for(256, tune, &err);
+    if (!err.empty()) return -1;
+    RolloutArgs args{};
+    args.c.n_cells = n_cells;
+    args.n_envs = n_envs;
+    const LgRolloutPlan plan = plan_rollout_lg(n_agents, args, t);
+    out[0] = uint64_t(plan.L); out[1] = plan.full ? 1u : 0u; out[2] = plan.mv_lds ? 1u : 0u; out[3] = plan.dense ? 1u : 0u; out[4] = plan.block;
+    out[5] = plan.grid; out[6] = plan.lds_bytes;
+    lg_rollout_kernel_name(name, plan, record != 0, policy == 0, policy == 2);
+    return 1;
+}
+
+// plan_step_lg: out = L, full, block, grid; name as above
+int shim_plan_step_lg(int n_agents, uint64_t n_envs, int ext_uniforms, uint64_t out[4], char *name) {
+    StepArgs args{};
+    args.n_envs = n_envs;
+    const LgStepPlan plan = plan_step_lg(n_agents, args);
+    out[0] = uint64_t(plan.L); out[1] = plan.full ? 1u : 0u; out[2] = plan.block; out[3] = plan.grid;
+    lg_step_kernel_name(name, plan, ext_uniforms != 0);
     return 1;
 }
 

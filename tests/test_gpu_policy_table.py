@@ -29,6 +29,14 @@ def _np(x):
     return x.cpu().numpy() if hasattr(x, 'cpu') else np.asarray(x)
 
 
+def _state(env):
+    """the handle's state on the host: in device mode get_state only ENQUEUES its copy on the env's stream, which the reader's stream
+    does not wait for"""
+    local = env.get_state()[0]
+    env.sync()
+    return _np(local)
+
+
 def _random_map(seed, size=20, p=0.15):
     rs = np.random.RandomState(seed)
     return MapfGrid([''.join('@' if rs.rand() < p else '.' for _ in range(size)) for _ in range(size)])
@@ -101,7 +109,7 @@ def _run_parity(grid, nbr, start, goal, A, table, rows, criteria='Makespan', ker
     refs, goals, colls = _oracle_steps(co, table, full, T)
     _check_record(res, refs, name)
     totals = _check_totals(res, refs, name)
-    assert np.array_equal(_np(env.get_state()[0]), co.state), name
+    assert np.array_equal(_state(env), co.state), name
     # totals only, then accumulated into the same arrays
     res2 = env.rollout(T // 2, auto_reset=True)
     env.sync()
@@ -113,7 +121,7 @@ def _run_parity(grid, nbr, start, goal, A, table, rows, criteria='Makespan', ker
     env.sync()
     refs3, g3, c3 = _oracle_steps(co, table, full, 5)
     _check_totals(res3, refs3, 'accumulate ' + name, base=base)
-    assert np.array_equal(_np(env.get_state()[0]), co.state) and env.t == co.t
+    assert np.array_equal(_state(env), co.state) and env.t == co.t
     env.close()
     del totals
     return goals + g2 + g3, colls + c2 + c3, name
@@ -262,7 +270,7 @@ def test_full_bench_shape_65536_envs_recording():
     refs, goals, colls = _oracle_steps(co, table, _full_rows(rows, E, A), T)
     _check_record(res, refs, name)
     _check_totals(res, refs, name)
-    assert np.array_equal(_np(env.get_state()[0]), co.state)
+    assert np.array_equal(_state(env), co.state)
     assert goals > 0 and colls > 0, (goals, colls)
     env.close()
 
@@ -352,7 +360,7 @@ def test_step_graph_with_a_table_rollout_replays_with_fresh_slip_numbers():
         env.sync()
         refs, _, _ = _oracle_steps(co, table, _full_rows(rows, E, A), T)
         _check_record(res, refs, 'replay %d' % rep)
-        assert np.array_equal(_np(env.get_state()[0]), co.state)
+        assert np.array_equal(_state(env), co.state)
     assert env.t == co.t == K * T
     graph.close()
     env.set_policy('random')                                      # allowed again once the graph is gone

@@ -1,16 +1,26 @@
-"""Every decision of the three launch planners (csrc/mapf_plan.hip), pinned: plan_rollout_lq, plan_rollout_lq_table and
-plan_step_lq are swept over shapes and MAPF_TUNE overrides, and the SHA-256 of each group's concatenated results ("no packed
-form" is one of the results) is compared with tests/golden/plan_decisions.json -- recorded from the commit before the planner
-was rewritten as ordered candidate lists, so a change of any decision names its group here.  No GPU involved.
+"""Every decision of the launch planners (csrc/mapf_plan.hip), pinned.
 
-    python tests/test_plan_decisions.py --record [OUT.json]
+The packed planners -- plan_rollout_lq, plan_rollout_lq_table and plan_step_lq -- are swept over shapes and MAPF_TUNE overrides, and
+the SHA-256 of each group's concatenated results ("no packed form" is one of the results) is compared with
+tests/golden/plan_decisions.json -- recorded from the commit before the planner was rewritten as ordered candidate lists, so a
+change of any decision names its group here.
+
+The lane-group planners -- plan_rollout_lg and plan_step_lg -- take every launch the packed kernels decline.  Their recorded
+decisions are those of the commit before they existed, when the launchers decided inline and only mapf_last_kernel showed what
+they decided: every shape of the sweep below was launched once on an MI355X (a one-step rollout, a step) and the kernel's name
+parsed into the fields a plan holds.  The fixture keeps them per shape ('-' = a packed kernel took the launch), and the full name
+of one shape per distinct name.  The comparison involves no GPU; one GPU test launches a shape of every kind.
+
+    python tests/test_plan_decisions.py --record [OUT.json] [packed] [lane_group]
 
 writes the fixture from the library MAPF_HIP_LIB names (default: the tree's) and the host shim MAPF_HOST_SHIM names (default:
-built from the tree's sources)."""
+built from the tree's sources); `packed` / `lane_group` alone re-records those groups only and keeps the others of OUT.json.
+`lane_group` needs a GPU."""
 import ctypes
 import hashlib
 import json
 import os
+import re
 import sys
 import tempfile
 
@@ -28,6 +38,20 @@ NOT_PACKED = b'-'
 TABLE_AGENTS, TABLE_ENVS = (4, 8, 16, 32, 64), (1024, 16384, 65536, 262144)
 TABLE_BYTES = (1, 8, 64)                                               # policy tables of V, 8 V and 64 V action bytes
 TABLE_TUNES = (None, b'policy_table_lds=0', b'policy_table_lds=1')
+# the lane-group sweep: the smallest shapes at which each rule can go wrong -- odd teams and every group size; batches around one
+# wave, the 64 * 256 threads the LDS table needs, the 2^17 threads of the four-wave block and whole / ragged blocks; maps whose
+# move table leaves >= 4, 2, 2 and 1 copies per CU (the last only with the limit lifted)
+LG_AGENTS = (1, 2, 3, 5, 8, 16, 17, 31, 32, 33, 128)
+LG_ENVS = (1, 63, 64, 257, 4096, 8191, 8192, 16384, 65536)
+LG_MAPS = ((10, 10), (22, 31), (25, 40), (30, 50))                     # empty maps of 100, 682, 1000 and 1500 free cells
+LG_TUNES = (None, b'quad_lanes=0', b'quad_lanes=0,mv_lds_max_bytes=163840', b'mv_lds_max_bytes=0')
+LG_ROLLOUTS = tuple((record, policy) for record in (0, 1) for policy in (0, 1, 2))   # policy: streamed actions, policy stream, table policy
+LG_STEPS = (0, 1)                                                      # caller uniforms
+LG_PACKED = '-'
+LG_ROLLOUT_NAME = re.compile(r'^lg_rollout_kernel(_table)?<L=(\d+),(FULL|RAGGED),(MV_LDS|MV_GLOBAL),(RECORD|TOTALS),(STREAM|POLICY|TABLE),(DENSE|GUARDED)> block=(\d+) ')
+LG_STEP_NAME = re.compile(r'^lg_step_kernel<L=(\d+),(FULL|RAGGED),(EXT_UNIFORMS|PHILOX)> block=(\d+) ')
+LG_ROLLOUT_CODE, LG_STEP_CODE = re.compile(r'^(\d+)([FR])([LG])([DG])(\d+)$'), re.compile(r'^(\d+)([FR])(\d+)$')   # (lg_rollout_code, lg_step_code)
+KERNEL_NAME_BYTES = 160                                                # what mapf_last_kernel keeps of a name (the terminator included)
 
 
 def _name(tune):
@@ -96,6 +120,128 @@ def step_digests(shim_lib):
     return digests
 
 
+def lg_key(tune, V, A, E):
+    return '%s V=%d A=%d E=%d' % (_name(tune), V, A, E)
+
+
+def lg_shapes():
+    for tune in LG_TUNES:
+        for rows, cols in LG_MAPS:
+            for A in LG_AGENTS:
+                for E in LG_ENVS:
+                    yield tune, rows, cols, A, E
+
+
+def lg_rollout_code(name, record, policy):
+    """a rollout kernel's name as the fields of a plan: '<L><F|R><L|G><D|G><block>' (full or ragged groups, move table in LDS or
+    global memory, dense or guarded), '-' for a packed kernel; what the name says about recording and the policy must be what
+    the launch asked for"""
+    if name.startswith('lq_rollout_kernel'):
+        return LG_PACKED
+    m = LG_ROLLOUT_NAME.match(name)
+    assert m, name
+    table, L, full, mv, rec, pol, dense, block = m.groups()
+    assert rec == ('RECORD' if record else 'TOTALS') and pol == ('STREAM', 'POLICY', 'TABLE')[policy] and (table is not None) == (policy == 2), name
+    return '%s%s%s%s%s' % (L, full[0], 'L' if mv == 'MV_LDS' else 'G', dense[0], block)
+
+
+def lg_step_code(name, uniforms):
+    """... of a step kernel: '<L><F|R><block>'"""
+    if name.startswith('lq_step_kernel'):
+        return LG_PACKED
+    m = LG_STEP_NAME.match(name)
+    assert m, name
+    L, full, ext, block = m.groups()
+    assert ext == ('EXT_UNIFORMS' if uniforms else 'PHILOX'), name
+    return '%s%s%s' % (L, full[0], block)
+
+
+def planned_rollout_lg(shim_lib, tune, V, A, E, record, policy):
+    """plan_rollout_lg through the shim: (code, grid, lds_bytes, the name the launcher notes)"""
+    out, name = (ctypes.c_uint64 * 7)(), ctypes.create_string_buffer(2 * KERNEL_NAME_BYTES)
+    rc = shim_lib.shim_plan_rollout_lg(V, A, E, record, policy, tune, out, name)
+    assert rc == 1, (rc, tune)
+    L, full, mv_lds, dense, block, grid, lds_bytes = out
+    return '%d%s%s%s%d' % (L, 'F' if full else 'R', 'L' if mv_lds else 'G', 'D' if dense else 'G', block), grid, lds_bytes, name.value.decode()
+
+
+def planned_step_lg(shim_lib, A, E, uniforms):
+    out, name = (ctypes.c_uint64 * 4)(), ctypes.create_string_buffer(2 * KERNEL_NAME_BYTES)
+    assert shim_lib.shim_plan_step_lg(A, E, uniforms, out, name) == 1
+    L, full, block, grid = out
+    return '%d%s%d' % (L, 'F' if full else 'R', block), grid, name.value.decode()
+
+
+class LaneGroupLauncher:
+    """Launches the shapes of the lane-group sweep on the GPU and reads mapf_last_kernel: device-mode handles of the lane-group
+    family on empty maps, rows broadcast, inputs shared by all shapes."""
+
+    def __init__(self):
+        import numpy as np
+        import torch
+        from gym_mapf_amd.envs.grid import MapfGrid
+        from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
+        self.np, self.torch, self.make_grid, self.make_env, self.criteria = np, torch, MapfGrid, VecMapfEnv, OptimizationCriteria.Makespan
+        n = max(LG_ENVS) * max(LG_AGENTS)
+        self.actions = torch.zeros(n, dtype=torch.uint8, device='cuda')
+        self.uniforms = torch.full((n,), 0.5, dtype=torch.float64, device='cuda')
+        self.grids = {}
+
+    def names(self, tune, rows, cols, A, E):
+        """the kernel names of the shape's six one-step rollouts (LG_ROLLOUTS) and two steps (LG_STEPS)"""
+        np, outer_tune = self.np, os.environ.pop('MAPF_TUNE', None)
+        if tune:
+            os.environ['MAPF_TUNE'] = tune.decode()             # (read when the handle is created)
+        if (rows, cols) not in self.grids:
+            self.grids[rows, cols] = self.make_grid(['.' * cols] * rows)
+        V = rows * cols
+        env = self.make_env(self.grids[rows, cols], A, None, None, 0.2, -1000.0, 100.0, -1.0, self.criteria, n_envs=E, device_arrays=True,
+                            start_local=np.arange(A) % V, goal_local=(np.arange(A) + 1) % V, kernel='lane_group')
+        try:
+            rollouts = {}
+            for table in (False, True):
+                if table:
+                    env.set_policy('table', table=np.zeros((1, V), dtype=np.uint8), rows=np.zeros(A, dtype=np.uint16))
+                for record, policy in LG_ROLLOUTS:
+                    if (policy == 2) == table:
+                        env.rollout(1, actions=self.actions[:E * A].view(1, E, A) if policy == 0 else None, record=bool(record))
+                        rollouts[record, policy] = env.last_kernel('rollout')
+            steps = []
+            for uniforms in LG_STEPS:
+                env.step(self.actions[:E * A].view(E, A), uniforms=self.uniforms[:E * A].view(E, A) if uniforms else None)
+                steps.append(env.last_kernel('step'))
+            env.sync()
+        finally:
+            env.close()
+            os.environ.pop('MAPF_TUNE', None)
+            if outer_tune is not None:
+                os.environ['MAPF_TUNE'] = outer_tune
+        return [rollouts[r] for r in LG_ROLLOUTS], steps
+
+
+def record_lane_group():
+    """the two lane-group groups and the kept names: of every distinct name, the smallest shape that printed it"""
+    launcher = LaneGroupLauncher()
+    rollouts, steps, kept = {}, {}, {}
+    for tune, rows, cols, A, E in lg_shapes():
+        key = lg_key(tune, rows * cols, A, E)
+        rollout_names, step_names = launcher.names(tune, rows, cols, A, E)
+        rollouts[key] = ' '.join(lg_rollout_code(name, *LG_ROLLOUTS[i]) for i, name in enumerate(rollout_names))
+        steps[key] = ' '.join(lg_step_code(name, LG_STEPS[i]) for i, name in enumerate(step_names))
+        for planner, names in (('rollout', rollout_names), ('step', step_names)):
+            for i, name in enumerate(names):
+                if name.startswith('lg_') and (name not in kept or E * A < kept[name][0]):
+                    kept[name] = (E * A, '%s|%d|%s' % (planner, i, key))
+        if E == LG_ENVS[-1] and A == LG_AGENTS[-1]:
+            print('launched %s V=%d' % (_name(tune), rows * cols), flush=True)
+    return rollouts, steps, {name: where for name, (_, where) in kept.items()}
+
+
+def parse_lg_key(key):
+    tune, V, A, E = key.split(' ')
+    return (None if tune == 'default' else tune.encode()), int(V[2:]), int(A[2:]), int(E[2:])
+
+
 def _compare(planner, found):
     with open(FIXTURE) as f:
         recorded = json.load(f)[planner]
@@ -134,15 +280,113 @@ def test_step_plan_decisions_are_the_recorded_ones(shim):  # noqa: F811
     _compare('plan_step_lq', step_digests(shim))
 
 
+def _fixture():
+    with open(FIXTURE) as f:
+        return json.load(f)
+
+
+def test_lane_group_plans_are_the_recorded_ones(shim):  # noqa: F811
+    """plan_rollout_lg and plan_step_lg decide what the inline launchers decided on the GPU, shape by shape; the grid follows from
+    block, L and E, the dynamic LDS segment is the move table or nothing; the kept names are formatted byte for byte.  Shapes a
+    packed kernel took are skipped: none with the packed layout off, and no more than half of the sweep in all."""
+    recorded = _fixture()
+    rollouts, steps, names = recorded['plan_rollout_lg'], recorded['plan_step_lg'], recorded['lg_kernel_names']
+    keys = [lg_key(tune, rows * cols, A, E) for tune, rows, cols, A, E in lg_shapes()]
+    assert len(keys) == 4 * 4 * 11 * 9 and sorted(keys) == sorted(rollouts) == sorted(steps)
+    sizes = (ctypes.c_uint64 * 6)()
+    shim.shim_sizes(2, sizes)
+    mv_cols = sizes[0]                                           # (16-byte entries per cell of the move table)
+    n, skipped, skipped_unpacked, wrong = 0, 0, 0, []
+    for key in keys:
+        tune, V, A, E = parse_lg_key(key)
+        unpacked = tune is not None and b'quad_lanes=0' in tune
+        rollout_codes, step_codes = rollouts[key].split(' '), steps[key].split(' ')
+        assert len(rollout_codes) == len(LG_ROLLOUTS) and len(step_codes) == len(LG_STEPS), key
+        for (record, policy), want in zip(LG_ROLLOUTS, rollout_codes):
+            n += 1
+            if want == LG_PACKED:
+                skipped += 1
+                skipped_unpacked += unpacked
+                continue
+            code, grid, lds_bytes, _ = planned_rollout_lg(shim, tune, V, A, E, record, policy)
+            L, _, mv, _, block = LG_ROLLOUT_CODE.match(want).groups()
+            if (code, grid, lds_bytes) != (want, -(-E // (int(block) // int(L))), V * mv_cols * 16 if mv == 'L' else 0):
+                wrong.append((key, record, policy, want, code, grid, lds_bytes))
+        for uniforms, want in zip(LG_STEPS, step_codes):
+            n += 1
+            if want == LG_PACKED:
+                skipped += 1
+                skipped_unpacked += unpacked
+                continue
+            code, grid, _ = planned_step_lg(shim, A, E, uniforms)
+            L, _, block = LG_STEP_CODE.match(want).groups()
+            if (code, grid) != (want, -(-E // (int(block) // int(L)))):
+                wrong.append((key, 'step', uniforms, want, code, grid))
+    assert not wrong, '%d of %d lane-group launches are planned differently: %s' % (len(wrong), n, wrong[:12])
+    assert n == len(keys) * 8 and skipped_unpacked == 0 and 2 * skipped <= n, (n, skipped, skipped_unpacked)
+    assert len(names) > 100
+    for name, where in names.items():
+        planner, i, key = where.split('|')
+        tune, V, A, E = parse_lg_key(key)
+        found = planned_rollout_lg(shim, tune, V, A, E, *LG_ROLLOUTS[int(i)])[3] if planner == 'rollout' else planned_step_lg(shim, A, E, LG_STEPS[int(i)])[2]
+        assert found == name and len(name) < KERNEL_NAME_BYTES, (where, found, name)
+
+
+def lg_kinds(recorded):
+    """{kind: (shape's key, index into LG_ROLLOUTS, recorded name)}: the smallest shape of every combination that exists of full /
+    ragged groups, move table in LDS / global memory, dense / guarded and table policy or not; plus the smallest one whose block
+    the 16-lane cap cut to 512 threads (V = 1500 leaves one table copy per CU: 1024 threads for every other group size).  A name
+    is a function of the recorded fields, recording and policy, and the fixture keeps every distinct name once."""
+    kinds, size, name_of = {}, {}, {}
+    for name, where in recorded['lg_kernel_names'].items():
+        planner, i, key = where.split('|')
+        if planner == 'rollout':
+            name_of[lg_rollout_code(name, *LG_ROLLOUTS[int(i)]), int(i)] = name
+    for key, codes in recorded['plan_rollout_lg'].items():
+        _, V, A, E = parse_lg_key(key)
+        for i, code in enumerate(codes.split(' ')):
+            if code == LG_PACKED:
+                continue
+            L, full, mv, dense, block = LG_ROLLOUT_CODE.match(code).groups()
+            capped = (L, mv, block) == ('16', 'L', '512') and V == 1500
+            for kind in [(full, mv, dense, LG_ROLLOUTS[i][1] == 2)] + ([('the L = 16 cap',)] if capped else []):
+                if kind not in kinds or E * A < size[kind]:
+                    kinds[kind], size[kind] = (key, i, name_of[code, i]), E * A
+    return kinds
+
+
+@pytest.mark.gpu
+def test_lane_group_launches_print_the_recorded_names():
+    """the launcher that takes a plan launches the instance the plan names: a shape of every kind of the sweep, each compared with
+    the name recorded for it"""
+    kinds = lg_kinds(_fixture())
+    assert len(kinds) == 13, sorted(kinds, key=str)              # FULL: 2 x 2 x 2, RAGGED (never dense): 2 x 2, the cap
+    launcher = LaneGroupLauncher()
+    for kind, (key, i, name) in sorted(kinds.items(), key=str):
+        tune, V, A, E = parse_lg_key(key)
+        rows, cols = [m for m in LG_MAPS if m[0] * m[1] == V][0]
+        assert launcher.names(tune, rows, cols, A, E)[0][i] == name, (kind, key, i)
+
+
 if __name__ == '__main__':
     if len(sys.argv) < 2 or sys.argv[1] != '--record':
         sys.exit(__doc__)
     from gym_mapf_amd import _native
-    shim_path = os.environ.get('MAPF_HOST_SHIM') or build_shim(tempfile.mkdtemp(prefix='host_tables_'))
-    shim_lib = load_shim(shim_path)
-    record = {'plan_rollout_lq': rollout_digests(_native.load()), 'plan_rollout_lq_table': table_digests(shim_lib),
-              'plan_step_lq': step_digests(shim_lib)}
-    with open(sys.argv[2] if len(sys.argv) > 2 else FIXTURE, 'w') as f:
+    out_path = sys.argv[2] if len(sys.argv) > 2 else FIXTURE
+    groups = sys.argv[3:] or ['packed', 'lane_group']
+    assert set(groups) <= {'packed', 'lane_group'}, __doc__
+    record = {}
+    if os.path.exists(out_path):
+        with open(out_path) as f:
+            record = json.load(f)
+    if 'lane_group' in groups:
+        record['plan_rollout_lg'], record['plan_step_lg'], record['lg_kernel_names'] = record_lane_group()
+    if 'packed' in groups:
+        shim_path = os.environ.get('MAPF_HOST_SHIM') or build_shim(tempfile.mkdtemp(prefix='host_tables_'))
+        shim_lib = load_shim(shim_path)
+        record.update({'plan_rollout_lq': rollout_digests(_native.load()), 'plan_rollout_lq_table': table_digests(shim_lib),
+                       'plan_step_lq': step_digests(shim_lib)})
+    with open(out_path, 'w') as f:
         json.dump(record, f, indent=0, sort_keys=True)
         f.write('\n')
-    print('recorded %s groups from %s and %s' % ({k: len(v) for k, v in record.items()}, _native.LIB_PATH, shim_path))
+    print('recorded %s of %s from %s' % (groups, {k: len(v) for k, v in record.items()}, _native.LIB_PATH))
