@@ -1,9 +1,6 @@
 """GPU parity: the HIP path (through the C ABI / VecMapfEnv) against the reference's recorded
 outputs (tests/golden) and against the pinned CPU oracles.  Bit-exact: integers, flags and the
 float64 reward/prob bit patterns.  All tests here need a real MI355X (-m gpu)."""
-import math
-from fractions import Fraction
-
 import numpy as np
 import pytest
 
@@ -13,6 +10,7 @@ import philox
 from conftest import set_tune, load_json
 from gym_mapf_amd.envs.grid import MapfGrid
 from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
+from totals_cases import _assert_a_wrong_rounding_would_show, _goal_scenario_tables   # (shared with the totals-only sweep)
 
 pytestmark = pytest.mark.gpu
 KERNELS = ('thread_per_env', 'lane_group')
@@ -539,20 +537,6 @@ def test_greedy_policy_rollout_against_c_oracle(n_agents, n_envs, kernel):
 
 
 # ----------------------------------------------------------------------- episodes that end on goals
-def _goal_scenario_tables(n_agents, n_envs, seed):
-    import goal_scenarios
-    lines, start_loc, goal_loc = goal_scenarios.goal_scenario(n_agents, n_envs, seed)
-    grid = MapfGrid(lines)
-    valid, l2i, nbr = grid.tables()
-    ids = np.zeros((len(lines), len(lines[0])), np.uint16)
-    for loc, k in l2i.items():
-        ids[loc] = k
-    start = np.ascontiguousarray(ids[start_loc[..., 0], start_loc[..., 1]])
-    goal = np.ascontiguousarray(ids[goal_loc[..., 0], goal_loc[..., 1]])
-    rc = np.asarray([r | (c << 16) for r, c in valid], np.uint32)
-    return grid, nbr, rc, start, goal
-
-
 def _goal_passes(slip, soc_policy=(0.0, 4)):
     """(fail_prob, criteria, oracle criteria, auto_reset, mode, T): Makespan streamed; SoC policy without auto-reset
     (`soc_policy` = its slip and T); SoC single steps; Makespan policy without auto-reset; no slip, streamed."""
@@ -561,36 +545,6 @@ def _goal_passes(slip, soc_policy=(0.0, 4)):
             (slip, OptimizationCriteria.SoC, mo.SOC, True, 'single', 8),
             (slip, OptimizationCriteria.Makespan, mo.MAKESPAN, False, 'policy', 10),
             (0.0, OptimizationCriteria.Makespan, mo.MAKESPAN, True, 'streamed', 3))
-
-
-def _assert_a_wrong_rounding_would_show(refs, prevs, acts, goal, rewards, soc, fail_prob, tag):
-    """On the ORACLE's output alone: this pass would not equally accept a reordered return or a fused / re-associated
-    ``n * r_living + r_x``.  ``prevs[t]`` = the oracle's cells before step t, ``acts[t]`` its actions, ``refs[t]`` its results."""
-    r_clash, r_goal, r_living = rewards
-    T, (E, A) = len(refs), goal.shape
-    rew = np.stack([ref['reward'] for ref in refs])
-    ret = np.zeros(E)
-    for t in range(T):
-        ret = ret + rew[t]                                        # the reference's order: left to right
-    reordered = sum(1 for e in range(E) if math.fsum(rew[:, e].tolist()) != ret[e])
-    # waived without slip: every agent starts one move from its goal, so every episode ends at its first step and the
-    # three-step pass sums three terms from {r_goal + living, r_clash + living}
-    assert fail_prob == 0.0 or reordered > 0, tag
-    if not soc:
-        return
-    counts, two_roundings = set(), 0
-    for t in range(T):
-        fresh = refs[t]['was_terminal'] == 0
-        n = A - ((prevs[t] == goal) & (acts[t] == 0)).sum(axis=1)                 # A - stayed, from the oracle's state
-        counts.update(n[fresh].tolist())
-        on_goal = fresh & (refs[t]['done'] == 1) & (refs[t]['collision'] == 0)
-        for base, sel in ((r_clash, fresh & (refs[t]['collision'] == 1)), (r_goal, on_goal)):
-            for k in np.unique(n[sel]).tolist():
-                exact = float(Fraction(k) * Fraction(r_living) + Fraction(base))   # n * r_living + r_x, rounded once
-                got = refs[t]['reward'][sel & (n == k)]
-                assert np.array_equal(_bits(got), _bits(np.full(got.shape, base + float(k) * r_living))), (tag, t, k)   # n is the oracle's n
-                two_roundings += int((got != exact).sum())
-    assert two_roundings > 0 and len(counts) >= 3, (tag, two_roundings, sorted(counts))       # (no waiver: see the caller)
 
 
 def _goal_reaching_episodes(n_agents, n_envs, layout, env_vars, monkeypatch, rewards, slip, rounding_must_show, soc_policy=(0.0, 4)):
