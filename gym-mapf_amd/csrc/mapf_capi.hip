@@ -183,6 +183,9 @@ struct mapf_handle_s : StreamAndEvents {
     std::vector<mapf_graph_s *> graphs;   // recordings that are still alive (destroyed with the handle at the latest)
 
     const mapf::SlipRow *slip_rows() const { return slip.ptr ? slip.ptr->slip : nullptr; }
+    // what a step / rollout / reset advances, reads and writes: the recording's own counter and flag while a graph is recorded
+    uint64_t &steps() { return capturing ? cap_steps : t; }
+    bool &terminal_possible() { return capturing ? cap_may_be_terminal : may_be_terminal; }
     void drop_policy_table() {
         table_bytes.reset();
         table_rows.reset();
@@ -284,13 +287,36 @@ int fetch_arrays(mapf_handle_t h, const CallArray *arrays, size_t n) {
 template <size_t N> int stage_arrays(mapf_handle_t h, const CallArray (&arrays)[N]) { return stage_arrays(h, arrays, N); }
 template <size_t N> int fetch_arrays(mapf_handle_t h, const CallArray (&arrays)[N]) { return fetch_arrays(h, arrays, N); }
 
-// launch one step, then the bookkeeping every path of mapf_step shares: kernel name, step index, may-be-terminal
+// a recorded launch: offset inside the recording + the device-side index (see StepArgs::t_dev)
+template <typename Args> void fill_step_index(mapf_handle_t h, Args &a) { a.t = h->steps(); a.t_dev = h->capturing ? h->t_dev.ptr : nullptr; }
+
+// The handle's part of an argument block.  What StepArgs, RolloutArgs and TransitionsArgs share by name -- the tables and the
+// goals -- is all a query block takes ...
+template <typename Args> Args query_args_from_handle(mapf_handle_t h) {
+    Args a{};
+    a.c = h->c; a.mv = h->mv; a.slip = h->slip_rows(); a.goal = h->goal; a.goal_broadcast = h->goal_broadcast;
+    return a;
+}
+// ... a launch that moves the batch (StepArgs, RolloutArgs) also takes its state, its ids and the step index
+template <typename Args> Args args_from_handle(mapf_handle_t h) {
+    Args a = query_args_from_handle<Args>(h);
+    a.mv4 = h->mv4; a.state = h->state; a.start = h->start; a.start_broadcast = h->start_broadcast;
+    a.n_envs = h->E; a.env_id_offset = h->env_id_offset;
+    fill_step_index(h, a);
+    return a;
+}
+
+// after a state-changing launch of n steps: the kernel that took it, the step index, and may-be-terminal -- every finished
+// episode is back on its start cells (auto-reset), or anything goes
+void after_launch(mapf_handle_t h, std::string &last_kernel, uint64_t n_steps, bool auto_reset) {
+    if (last_kernel != g_noted_kernel) last_kernel = g_noted_kernel;
+    h->steps() += n_steps;
+    if (n_steps) h->terminal_possible() = auto_reset ? h->start_terminal_any : true;
+}
+
 int launch_step_and_advance(mapf_handle_t h, const mapf::StepArgs &a) {
     HIP_TRY(h->lane_group ? mapf::launch_step_lg(int(h->A), a, h->tune, h->stream) : mapf::launch_step(int(h->A), a, h->stream));
-    if (h->last_step_kernel != g_noted_kernel) h->last_step_kernel = g_noted_kernel;
-    if (h->capturing) h->cap_steps += 1; else h->t += 1;
-    // after this step: every finished episode is back on its start cells (auto-reset), or anything goes
-    (h->capturing ? h->cap_may_be_terminal : h->may_be_terminal) = a.auto_reset ? h->start_terminal_any : true;
+    after_launch(h, h->last_step_kernel, 1, a.auto_reset);
     return MAPF_OK;
 }
 }  // namespace
@@ -499,7 +525,7 @@ int mapf_reset(mapf_handle_t h, const uint8_t *mask) {
     const CallArray io[] = {input(h->s_mask, mask, size_t(h->E), &d_mask, "mask")};
     if (int rc = stage_arrays(h, io)) return rc;
     HIP_TRY(mapf::launch_reset(int(h->A), h->state, h->start, h->start_broadcast, d_mask, h->E, h->stream));
-    if (!mask) (h->capturing ? h->cap_may_be_terminal : h->may_be_terminal) = h->start_terminal_any;
+    if (!mask) h->terminal_possible() = h->start_terminal_any;
     if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
     return MAPF_OK;
 }
@@ -513,37 +539,31 @@ int mapf_step(mapf_handle_t h, const uint8_t *actions, const double *uniforms, u
     if (int rc = check_foreign_capture(h, "mapf_step")) return rc;
     if (int rc = check_extent(h, h->E, uniforms != nullptr)) return rc;
     const size_t E = size_t(h->E), EA = E * h->A;
-    mapf::StepArgs a{};
-    a.c = h->c; a.mv = h->mv; a.mv8 = h->mv8; a.mv4 = h->mv4; a.slip = h->slip_rows(); a.state = h->state; a.start = h->start; a.goal = h->goal;
-    a.n_envs = h->E; a.env_id_offset = h->env_id_offset;
-    // a recorded launch: offset inside the recording + the device-side index (see StepArgs::t_dev)
-    a.t = h->capturing ? h->cap_steps : h->t;
-    a.t_dev = h->capturing ? h->t_dev : nullptr;
-    a.scen = h->scen; a.scen_rows = h->scen_rows;
-    a.start_broadcast = h->start_broadcast; a.goal_broadcast = h->goal_broadcast;
+    mapf::StepArgs a = args_from_handle<mapf::StepArgs>(h);
+    a.mv8 = h->mv8; a.scen = h->scen; a.scen_rows = h->scen_rows;
     a.auto_reset = step_flags & MAPF_STEP_AUTO_RESET;
-    a.state_not_terminal = !(h->capturing ? h->cap_may_be_terminal : h->may_be_terminal);
+    a.state_not_terminal = !h->terminal_possible();
+    const CallArray io[] = {input(h->s_actions, actions, EA, &a.actions, "actions"), input(h->s_uniforms, uniforms, EA, &a.uniforms, "uniforms"),
+                            output(h->s_local, out_local, EA, &a.out_local, "out_local"), output(h->s_reward, out_reward, E, &a.out_reward, "out_reward"),
+                            output(h->s_prob, out_prob, E, &a.out_prob, "out_prob"), output(h->s_done, out_done, E, &a.out_done, "out_done"),
+                            output(h->s_coll, out_collision, E, &a.out_collision, "out_collision"),
+                            output(h->s_term, out_was_terminal, E, &a.out_was_terminal, "out_was_terminal")};
     if (!h->device_ptrs) {
-        // tiny host-mode call: inputs and outputs live in one pinned, device-mapped block (16-byte aligned slots)
-        auto slot = [](size_t &off, size_t bytes) { const size_t at = off; off += (bytes + 15u) & ~size_t(15); return at; };
-        size_t total = 0;
-        const size_t o_act = slot(total, EA), o_uni = slot(total, uniforms ? EA * sizeof(double) : 0),
-                     o_loc = slot(total, out_local ? EA * sizeof(uint16_t) : 0), o_rew = slot(total, out_reward ? E * sizeof(double) : 0),
-                     o_prob = slot(total, out_prob ? E * sizeof(double) : 0), o_done = slot(total, out_done ? E : 0),
-                     o_coll = slot(total, out_collision ? E : 0), o_term = slot(total, out_was_terminal ? E : 0),
-                     o_flag = slot(total, sizeof(uint32_t));
+        // tiny host-mode call: inputs and outputs live in one pinned, device-mapped block -- a 16-byte aligned slot per array
+        // of the list (none for an absent one), then the flag word
+        constexpr size_t n_io = sizeof(io) / sizeof(io[0]);
+        const auto slot = [](size_t &off, size_t bytes) { const size_t at = off; off += (bytes + 15u) & ~size_t(15); return at; };
+        size_t total = 0, at[n_io];
+        for (size_t i = 0; i < n_io; ++i) at[i] = slot(total, io[i].user ? io[i].bytes : 0);
+        const size_t o_flag = slot(total, sizeof(uint32_t));
         if (total <= kZeroCopyMaxBytes && E > 0) {
             HIP_TRY(h->pinned.reserve(kZeroCopyMaxBytes));
             char *hp = h->pinned.host, *dp = h->pinned.dev;
-            std::memcpy(hp + o_act, actions, EA);
-            a.actions = reinterpret_cast<const uint8_t *>(dp + o_act);
-            if (uniforms) { std::memcpy(hp + o_uni, uniforms, EA * sizeof(double)); a.uniforms = reinterpret_cast<const double *>(dp + o_uni); }
-            if (out_local) a.out_local = reinterpret_cast<uint16_t *>(dp + o_loc);
-            if (out_reward) a.out_reward = reinterpret_cast<double *>(dp + o_rew);
-            if (out_prob) a.out_prob = reinterpret_cast<double *>(dp + o_prob);
-            if (out_done) a.out_done = reinterpret_cast<uint8_t *>(dp + o_done);
-            if (out_collision) a.out_collision = reinterpret_cast<uint8_t *>(dp + o_coll);
-            if (out_was_terminal) a.out_was_terminal = reinterpret_cast<uint8_t *>(dp + o_term);
+            for (size_t i = 0; i < n_io; ++i) {
+                if (io[i].user && io[i].upload) std::memcpy(hp + at[i], io[i].user, io[i].bytes);
+                void *dev = io[i].user ? dp + at[i] : nullptr;
+                std::memcpy(io[i].slot, &dev, sizeof(dev));
+            }
             const uint64_t launch_threads = h->lane_group ? E * uint64_t(mapf::lg_group_size(int(h->A))) : E;
             const bool flagged = launch_threads <= 64;             // one wave: see below
             const uint32_t seq = uint32_t(h->t) + 1u;
@@ -562,20 +582,11 @@ int mapf_step(mapf_handle_t h, const uint8_t *actions, const double *uniforms, u
                 for (int spin = 0; spin < 200000 && !signalled; ++spin) signalled = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq;
             }
             if (!signalled) HIP_TRY(hipStreamSynchronize(h->stream));
-            if (out_local) std::memcpy(out_local, hp + o_loc, EA * sizeof(uint16_t));
-            if (out_reward) std::memcpy(out_reward, hp + o_rew, E * sizeof(double));
-            if (out_prob) std::memcpy(out_prob, hp + o_prob, E * sizeof(double));
-            if (out_done) std::memcpy(out_done, hp + o_done, E);
-            if (out_collision) std::memcpy(out_collision, hp + o_coll, E);
-            if (out_was_terminal) std::memcpy(out_was_terminal, hp + o_term, E);
+            for (size_t i = 0; i < n_io; ++i)
+                if (io[i].user && io[i].download) std::memcpy(const_cast<void *>(io[i].user), hp + at[i], io[i].bytes);
             return MAPF_OK;
         }
     }
-    const CallArray io[] = {input(h->s_actions, actions, EA, &a.actions, "actions"), input(h->s_uniforms, uniforms, EA, &a.uniforms, "uniforms"),
-                            output(h->s_local, out_local, EA, &a.out_local, "out_local"), output(h->s_reward, out_reward, E, &a.out_reward, "out_reward"),
-                            output(h->s_prob, out_prob, E, &a.out_prob, "out_prob"), output(h->s_done, out_done, E, &a.out_done, "out_done"),
-                            output(h->s_coll, out_collision, E, &a.out_collision, "out_collision"),
-                            output(h->s_term, out_was_terminal, E, &a.out_was_terminal, "out_was_terminal")};
     if (int rc = stage_arrays(h, io)) return rc;
     if (int rc = launch_step_and_advance(h, a)) return rc;
     if (int rc = fetch_arrays(h, io)) return rc;
@@ -598,11 +609,17 @@ int reserve_stand_in(mapf_handle_t h, DeviceBuf &buf, size_t bytes, const char *
 }
 int complete_recording(mapf_handle_t h, mapf::RolloutArgs &a, size_t TE, size_t TEA) {
     if (!(a.rec_local || a.rec_reward || a.rec_prob || a.rec_done || a.rec_collision)) return MAPF_OK;
-    if (!a.rec_local) { if (int rc = reserve_stand_in(h, h->x_local, TEA * sizeof(uint16_t), "rec_local")) return rc; a.rec_local = static_cast<uint16_t *>(h->x_local.ptr); }
-    if (!a.rec_reward) { if (int rc = reserve_stand_in(h, h->x_reward, TE * sizeof(double), "rec_reward")) return rc; a.rec_reward = static_cast<double *>(h->x_reward.ptr); }
-    if (!a.rec_prob) { if (int rc = reserve_stand_in(h, h->x_prob, TE * sizeof(double), "rec_prob")) return rc; a.rec_prob = static_cast<double *>(h->x_prob.ptr); }
-    if (!a.rec_done) { if (int rc = reserve_stand_in(h, h->x_done, TE, "rec_done")) return rc; a.rec_done = static_cast<uint8_t *>(h->x_done.ptr); }
-    if (!a.rec_collision) { if (int rc = reserve_stand_in(h, h->x_coll, TE, "rec_collision")) return rc; a.rec_collision = static_cast<uint8_t *>(h->x_coll.ptr); }
+    const struct { void *field; DeviceBuf *buf; size_t bytes; const char *name; } rows[] = {
+        {&a.rec_local, &h->x_local, TEA * sizeof(uint16_t), "rec_local"}, {&a.rec_reward, &h->x_reward, TE * sizeof(double), "rec_reward"},
+        {&a.rec_prob, &h->x_prob, TE * sizeof(double), "rec_prob"}, {&a.rec_done, &h->x_done, TE, "rec_done"},
+        {&a.rec_collision, &h->x_coll, TE, "rec_collision"}};
+    for (const auto &r : rows) {
+        void *given = nullptr;
+        std::memcpy(&given, r.field, sizeof(given));   // (typed pointer fields: memcpy, where a void ** cast would alias)
+        if (given) continue;
+        if (int rc = reserve_stand_in(h, *r.buf, r.bytes, r.name)) return rc;
+        std::memcpy(r.field, &r.buf->ptr, sizeof(void *));
+    }
     return MAPF_OK;
 }
 }  // namespace
@@ -614,16 +631,12 @@ int mapf_rollout(mapf_handle_t h, const mapf_rollout_io *io) {
     if (int rc = check_foreign_capture(h, "mapf_rollout")) return rc;
     if (int rc = check_extent(h, uint64_t(h->E) * io->n_steps, false)) return rc;
     const size_t E = size_t(h->E), T = io->n_steps, TE = T * E, TEA = TE * h->A;
-    mapf::RolloutArgs a{};
-    a.c = h->c; a.mv = h->mv; a.mv4 = h->mv4; a.slip = h->slip_rows(); a.state = h->state; a.start = h->start; a.goal = h->goal;
-    a.n_envs = h->E; a.env_id_offset = h->env_id_offset; a.n_steps = io->n_steps;
-    a.t = h->capturing ? h->cap_steps : h->t;
-    a.t_dev = h->capturing ? h->t_dev : nullptr;
+    mapf::RolloutArgs a = args_from_handle<mapf::RolloutArgs>(h);
+    a.n_steps = io->n_steps;
     a.policy_cells = h->policy_cells;
     // (the table policy travels beside the argument block: its kernels are instances of their own; streamed actions take
     // precedence over it, as over the other policies -- the ONE place that rule is applied: no launcher sees both)
     const mapf::TablePolicy *table = (h->table.table && !io->actions) ? &h->table : nullptr;
-    a.start_broadcast = h->start_broadcast; a.goal_broadcast = h->goal_broadcast;
     a.auto_reset = io->step_flags & MAPF_STEP_AUTO_RESET;
     a.accumulate = io->accumulate != 0;
     a.start_terminal_any = h->start_terminal_any;
@@ -636,15 +649,10 @@ int mapf_rollout(mapf_handle_t h, const mapf_rollout_io *io) {
                                 output(h->s_local, io->rec_local, TEA, &a.rec_local, "rec_local"), output(h->s_reward, io->rec_reward, TE, &a.rec_reward, "rec_reward"),
                                 output(h->s_prob, io->rec_prob, TE, &a.rec_prob, "rec_prob"), output(h->s_done, io->rec_done, TE, &a.rec_done, "rec_done"),
                                 output(h->s_coll, io->rec_collision, TE, &a.rec_collision, "rec_collision")};
-    if (h->device_ptrs)
-        for (const CallArray &e : arrays)
-            if (e.user && misaligned(e.user)) return fail(MAPF_EINVAL, "rollout: device pointers must be 16-byte aligned");
     if (int rc = stage_arrays(h, arrays)) return rc;
     if (int rc = complete_recording(h, a, TE, TEA)) return rc;
     HIP_TRY(h->lane_group_rollout ? mapf::launch_rollout_lg(int(h->A), a, h->tune, h->stream, table) : mapf::launch_rollout(int(h->A), a, h->stream, table));
-    if (h->last_rollout_kernel != g_noted_kernel) h->last_rollout_kernel = g_noted_kernel;
-    if (h->capturing) h->cap_steps += io->n_steps; else h->t += io->n_steps;
-    if (io->n_steps) (h->capturing ? h->cap_may_be_terminal : h->may_be_terminal) = a.auto_reset ? h->start_terminal_any : true;
+    after_launch(h, h->last_rollout_kernel, io->n_steps, a.auto_reset);
     if (int rc = fetch_arrays(h, arrays)) return rc;
     if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
     return MAPF_OK;
@@ -752,8 +760,7 @@ int transitions_impl(mapf_handle_t h, bool compact, uint64_t n_queries, const ui
         for (size_t i = 0; i < NA; ++i) if (local[i] >= h->V) return fail(MAPF_EINVAL, "transitions: cell out of range");
         if (env_index) for (size_t i = 0; i < N; ++i) if (env_index[i] >= h->E) return fail(MAPF_EINVAL, "transitions: env_index out of range");
     }
-    mapf::TransitionsArgs a{};
-    a.c = h->c; a.mv = h->mv; a.slip = h->slip_rows(); a.goal = h->goal; a.goal_broadcast = h->goal_broadcast;
+    mapf::TransitionsArgs a = query_args_from_handle<mapf::TransitionsArgs>(h);
     a.n_queries = n_queries; a.max_branches = max_branches; a.n_agents = h->A; a.first_branch = first_branch;
     a.capacity = compact ? capacity_rows : ~uint64_t(0);
     enum { kOffset = 3, kCount, kNext, kProb, kReward, kDone, kColl };
@@ -817,8 +824,7 @@ int mapf_transition_rewards(mapf_handle_t h, uint64_t n_queries, const uint16_t 
             if (prev_local[i] >= h->V || next_local[i] >= h->V) return fail(MAPF_EINVAL, "transition_rewards: cell out of range");
         if (env_index) for (size_t i = 0; i < N; ++i) if (env_index[i] >= h->E) return fail(MAPF_EINVAL, "transition_rewards: env_index out of range");
     }
-    mapf::TransitionsArgs a{};
-    a.c = h->c; a.mv = h->mv; a.slip = h->slip_rows(); a.goal = h->goal; a.goal_broadcast = h->goal_broadcast;
+    mapf::TransitionsArgs a = query_args_from_handle<mapf::TransitionsArgs>(h);
     a.n_queries = n_queries; a.max_branches = 1; a.n_agents = h->A; a.capacity = ~uint64_t(0);
     const uint16_t *d_next = nullptr;
     const CallArray io[] = {input(h->q_local, prev_local, NA, &a.local, "prev_local"), input(h->q_actions, actions, NA, &a.actions, "actions"),

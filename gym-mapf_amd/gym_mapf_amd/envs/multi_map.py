@@ -23,10 +23,26 @@ There is no CPU implementation behind either.
 """
 import numpy as np
 
-from gym_mapf_amd.envs.vec_env import VecMapfEnv
+from gym_mapf_amd.envs.vec_env import STEP_OUTPUTS, VecMapfEnv, array_ptr, checked_ptr
 
-_STEP_SPEC = (('local', np.uint16, True), ('reward', np.float64, False), ('done', np.uint8, False),
-              ('collision', np.uint8, False), ('prob', np.float64, False), ('was_terminal', np.uint8, False))
+
+def _distinct(grids):
+    """(the distinct grids, which of them every env lives on); MapfGrid.__eq__ compares cell contents (reference grid.py:42-46)"""
+    distinct, which = [], np.empty(len(grids), np.int64)
+    for e, g in enumerate(grids):
+        for k, d in enumerate(distinct):
+            if g is d or g == d:
+                which[e] = k
+                break
+        else:
+            which[e] = len(distinct)
+            distinct.append(g)
+    return distinct, which
+
+
+def _on_stream(torch, stream):
+    """context: torch work (allocations, copies, arithmetic) goes on the HIP stream with this integer handle"""
+    return torch.cuda.stream(torch.cuda.ExternalStream(stream))
 
 
 class MultiMapVecEnv:
@@ -39,17 +55,7 @@ class MultiMapVecEnv:
         self.device_arrays = bool(device_arrays)
         if len(start_locations) != self.n_envs or len(goal_locations) != self.n_envs:
             raise ValueError('one start / goal row per env')
-        distinct = []                                   # [grid]; MapfGrid.__eq__ compares cell contents (reference grid.py:42-46)
-        which = np.empty(self.n_envs, np.int64)
-        for e, g in enumerate(grids):
-            for k, d in enumerate(distinct):
-                if g is d or g == d:
-                    which[e] = k
-                    break
-            else:
-                which[e] = len(distinct)
-                distinct.append(g)
-        self.grids = distinct
+        self.grids, which = _distinct(grids)
         self._parts = []                                # (env indices of the run, VecMapfEnv)
         self._stream = stream
         e = 0
@@ -60,7 +66,7 @@ class MultiMapVecEnv:
             idx = np.arange(e, run_end)
             starts = np.asarray([start_locations[i] for i in idx]).reshape(len(idx), self.n_agents, 2)
             goals = np.asarray([goal_locations[i] for i in idx]).reshape(len(idx), self.n_agents, 2)
-            env = VecMapfEnv(distinct[which[e]], self.n_agents, starts, goals, fail_prob, reward_of_collision, reward_of_goal,
+            env = VecMapfEnv(self.grids[which[e]], self.n_agents, starts, goals, fail_prob, reward_of_collision, reward_of_goal,
                              reward_of_living, optimization_criteria, seed=seed, env_id_offset=int(env_id_offset) + e,
                              device=device, device_arrays=self.device_arrays, stream=self._stream)
             if self.device_arrays and self._stream is None:
@@ -79,20 +85,9 @@ class MultiMapVecEnv:
         return self._stream
 
     # ------------------------------------------------------------------ device-mode plumbing
-    def _torch_stream(self):
-        return self._torch.cuda.stream(self._torch.cuda.ExternalStream(self._stream))
-
     @staticmethod
     def _aligned(tensor):
         return tensor.data_ptr() % 16 == 0
-
-    def _check(self, tensor, dtype, shape, name):
-        t = self._torch
-        want = {np.uint8: t.uint8, np.uint16: t.uint16, np.float64: t.float64, np.uint32: t.uint32}[dtype]
-        if not (isinstance(tensor, t.Tensor) and tensor.is_cuda and tensor.dtype == want and tensor.is_contiguous()
-                and tuple(tensor.shape) == tuple(shape)):
-            raise ValueError('%s must be a contiguous CUDA %s tensor of shape %r' % (name, want, tuple(shape)))
-        return tensor
 
     def prepare_step(self, actions, uniforms=None, auto_reset=False, out=None, write_local=True):
         """Device mode: validate once, call many times (``VecMapfEnv.prepare_step`` for the whole batch).  Returns
@@ -101,25 +96,23 @@ class MultiMapVecEnv:
         if not self.device_arrays:
             raise ValueError('prepare_step() needs device_arrays=True')
         E, A, t = self.n_envs, self.n_agents, self._torch
-        self._check(actions, np.uint8, (E, A), 'actions')
-        if uniforms is not None:
-            self._check(uniforms, np.float64, (E, A), 'uniforms')
+        checked_ptr(t, actions, np.uint8, (E, A), 'actions')
+        array_ptr(t, uniforms, np.float64, (E, A), 'uniforms')
         out = dict(out) if out else {}
         any_env = self._parts[0][1]
-        ctx = self._torch_stream
         # Everything this method allocates -- missing outputs, staging copies -- is only ever used on self.stream, so it is
         # allocated UNDER that stream: the caching allocator then orders a later reuse of the blocks behind the work queued
         # there (allocated on the caller's current stream they could be handed out again while self.stream still writes them).
         # The caller's own tensors (actions, uniforms, a supplied `out`) must be produced and consumed on self.stream, or be
         # synchronised with it (`torch.cuda.stream(env.torch_stream)` / `sync()`): the calls below only enqueue.
-        with ctx():
-            for name, dt, per_agent in _STEP_SPEC:
+        with _on_stream(t, self._stream):
+            for name, dt, per_agent in STEP_OUTPUTS:
                 if name == 'local' and not write_local:
                     continue
                 shape = (E, A) if per_agent else (E,)
                 if name not in out:
                     out[name] = any_env._empty(shape, dt)
-                self._check(out[name], dt, shape, name)
+                checked_ptr(t, out[name], dt, shape, name)
         calls, copies_in, copies_out, staged_runs = [], [], [], 0
         for idx, env in self._parts:
             lo, hi = int(idx[0]), int(idx[-1]) + 1
@@ -129,20 +122,20 @@ class MultiMapVecEnv:
                 part = batch[lo:hi]
                 if self._aligned(part):
                     return part                                      # in place
-                with ctx():
+                with _on_stream(t, self._stream):
                     stage = t.empty_like(part)
                 (copies_in if inputs else copies_out).append((stage, part))
                 return stage
             a = view(actions, True)
             u = view(uniforms, True) if uniforms is not None else None
-            o = {name: view(out[name], False) for name, _, _ in _STEP_SPEC if name in out}
+            o = {name: view(out[name], False) for name, _, _ in STEP_OUTPUTS if name in out}
             call, _ = env.prepare_step(a, uniforms=u, auto_reset=auto_reset, out=o, write_local=write_local)
             calls.append(call)
             staged_runs += (len(copies_in) + len(copies_out)) > n_before
 
         def call_all():
             if copies_in or copies_out:
-                with ctx():
+                with _on_stream(t, self._stream):
                     for stage, part in copies_in:
                         stage.copy_(part, non_blocking=True)
                     for c in calls:
@@ -163,7 +156,7 @@ class MultiMapVecEnv:
             if mask is None:
                 env.reset(None)
             elif self.device_arrays:
-                with self._torch_stream():
+                with _on_stream(self._torch, self._stream):
                     env.reset(mask[int(idx[0]):int(idx[-1]) + 1].clone())   # (an aligned, owned copy of the run's mask bytes)
             else:
                 env.reset(np.ascontiguousarray(np.asarray(mask, np.uint8)[idx]))
@@ -195,7 +188,7 @@ class MultiMapVecEnv:
         if self.device_arrays:
             t = self._torch
             parts = []
-            with self._torch_stream():
+            with _on_stream(self._torch, self._stream):
                 for idx, env in self._parts:
                     lo, hi = int(idx[0]), int(idx[-1]) + 1
                     a = None if actions is None else actions[:, lo:hi].contiguous()
@@ -213,7 +206,7 @@ class MultiMapVecEnv:
         """(cells [E, A] of each env's own map, step index).  Device mode: a CUDA tensor gathered from the runs' state views
         on ``self.stream`` (the runs' buffers are separate allocations: this is a copy)."""
         if self.device_arrays:
-            with self._torch_stream():
+            with _on_stream(self._torch, self._stream):
                 local = self._torch.cat([env.state_view() for _, env in self._parts])
             return local, self._parts[-1][1].t
         local = np.empty((self.n_envs, self.n_agents), np.uint16)
@@ -270,19 +263,10 @@ class UnionMapVecEnv:
         self.device_arrays = bool(device_arrays)
         if len(start_locations) != self.n_envs or len(goal_locations) != self.n_envs:
             raise ValueError('one start / goal row per env')
-        distinct, which = [], np.empty(self.n_envs, np.int64)
-        for e, g in enumerate(grids):
-            for k, d in enumerate(distinct):
-                if g is d or g == d:
-                    which[e] = k
-                    break
-            else:
-                which[e] = len(distinct)
-                distinct.append(g)
-        self.grids = distinct
-        self.union = UnionGrid(distinct)
+        self.grids, which = _distinct(grids)
+        self.union = UnionGrid(self.grids)
         base = np.asarray(self.union.base, np.int64)[which]
-        l2i = [g.tables()[1] for g in distinct]
+        l2i = [g.tables()[1] for g in self.grids]
         A = self.n_agents
 
         def to_union(locations, what):
@@ -310,22 +294,18 @@ class UnionMapVecEnv:
     def stream(self):
         return self._env.stream
 
-    def _on_stream(self):
-        t = self._torch
-        return t.cuda.stream(t.cuda.ExternalStream(self._env.stream))
-
     def _own(self, local):
         """union ids -> each env's own map's ids (any leading step axis)"""
         if self.device_arrays:
             t = self._torch
-            with self._on_stream():
+            with _on_stream(t, self._env.stream):
                 return (local.view(t.int16) - self._base).view(t.uint16)        # (mod 2^16: the same bits as unsigned subtraction)
         return (local - self._base_host).astype(np.uint16)
 
     def _union(self, local):
         if self.device_arrays:
             t = self._torch
-            with self._on_stream():
+            with _on_stream(t, self._env.stream):
                 return (local.view(t.int16) + self._base).view(t.uint16)
         return (np.asarray(local, np.uint16) + self._base_host).astype(np.uint16)
 

@@ -12,6 +12,7 @@ results are env-major arrays (``x[e, i]`` = agent i of env e) and the work happe
 There is no CPU implementation behind this class: without the library or a GPU the
 constructor raises ``MapfNativeError``.
 """
+import collections
 import ctypes
 import enum
 
@@ -27,6 +28,46 @@ class OptimizationCriteria(enum.Enum):
 
 
 _CRITERIA_CODE = {OptimizationCriteria.Makespan: nat.MAPF_MAKESPAN, OptimizationCriteria.SoC: nat.MAPF_SOC}
+
+
+# One step's outputs, in the argument order of mapf_step: (name, dtype, one value per agent -- else one per env).  The first
+# five are also what a recording rollout keeps per step (mapf_rollout_io's rec_<name>); ROLLOUT_TOTALS are its out_<name>.
+STEP_OUTPUTS = (('local', np.uint16, True), ('reward', np.float64, False), ('done', np.uint8, False),
+                ('collision', np.uint8, False), ('prob', np.float64, False), ('was_terminal', np.uint8, False))
+ROLLOUT_TOTALS = (('returns', np.float64), ('episodes', np.uint32), ('collisions', np.uint32))
+_TORCH_DTYPE = {np.uint8: 'uint8', np.uint16: 'uint16', np.uint32: 'uint32', np.uint64: 'uint64', np.float64: 'float64'}
+# rollout(out=...): the argument block of the last such call, with what it was made from
+_RolloutIO = collections.namedtuple('_RolloutIO', 'out call arrays actions io')
+
+
+def checked_ptr(torch, arr, dtype, shape, name):
+    """Raw pointer of a caller-supplied array after checking dtype/shape/contiguity: a CUDA tensor of the ``torch`` module
+    (device mode), a numpy array when ``torch`` is None (host mode)."""
+    if torch is not None:
+        want = getattr(torch, _TORCH_DTYPE[dtype])
+        if not (isinstance(arr, torch.Tensor) and arr.is_cuda and arr.dtype == want and arr.is_contiguous()
+                and tuple(arr.shape) == tuple(shape)):
+            raise ValueError('%s must be a contiguous CUDA %s tensor of shape %r' % (name, want, tuple(shape)))
+        return arr.data_ptr()
+    if not (isinstance(arr, np.ndarray) and arr.dtype == dtype and arr.flags.c_contiguous
+            and tuple(arr.shape) == tuple(shape)):
+        raise ValueError('%s must be a C-contiguous %s array of shape %r' % (name, np.dtype(dtype), tuple(shape)))
+    return arr.ctypes.data
+
+
+def array_ptr(torch, arr, dtype, shape, name):
+    """``checked_ptr`` of an optional array: None stays None (the C ABI's NULL)."""
+    return None if arr is None else checked_ptr(torch, arr, dtype, shape, name)
+
+
+def coerce_array(torch, arr, dtype, shape, name):
+    """Inputs: accept anything array-like in host mode (``torch`` None), strict tensors in device mode."""
+    if arr is None or torch is not None:
+        return arr
+    out = np.ascontiguousarray(arr, dtype=dtype)
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError('%s must have shape %r, got %r' % (name, tuple(shape), tuple(out.shape)))
+    return out
 
 
 def _locs_to_local(loc_to_int, locs):
@@ -130,7 +171,7 @@ class VecMapfEnv:
         nat.check(self._lib.mapf_create(ctypes.byref(desc), ctypes.byref(handle)))
         self._h = handle
         self.policy = 'random'         # on-device policy of rollout(actions=None): see set_policy
-        self._rollout_io = None        # rollout(out=...): the argument block of the last such call, with the arrays it points into
+        self._rollout_io = None        # rollout(out=...): the _RolloutIO of the last such call
 
     # ------------------------------------------------------------------ construction
     def _as_local(self, locations, local_ids, what):
@@ -139,13 +180,14 @@ class VecMapfEnv:
         A = self.n_agents
         if local_ids is not None:
             ids = np.asarray(local_ids)
-            if ids.ndim == 1:
+            broadcast = ids.ndim == 1
+            if broadcast:
                 ids = ids.reshape(1, -1)
             if ids.ndim != 2 or ids.shape[1] != A or not np.issubdtype(ids.dtype, np.integer):
                 raise ValueError('%s_local must be an integer array of shape [A] or [E, A]' % what)
             if ids.size and (ids.min() < 0 or ids.max() >= self.n_cells):
                 raise KeyError('%s_local: local id out of range' % what)
-            return np.ascontiguousarray(ids, dtype=np.uint16), local_ids is not None and np.asarray(local_ids).ndim == 1
+            return np.ascontiguousarray(ids, dtype=np.uint16), broadcast
         if len(locations) != A and not (np.asarray(locations).ndim == 3):
             raise AssertionError('%r locations number is different than the number of agents %d' % (locations, A))
         arr = np.asarray(locations)
@@ -158,36 +200,34 @@ class VecMapfEnv:
 
     # --------------------------------------------------------------------- plumbing
     def _ptr(self, arr, dtype, shape, name):
-        """Raw pointer of a caller-supplied array after checking dtype/shape/contiguity."""
-        if arr is None:
-            return None
-        if self.device_arrays:
-            t = self._torch
-            want = {np.uint8: t.uint8, np.uint16: t.uint16, np.float64: t.float64, np.uint32: t.uint32, np.uint64: t.uint64}[dtype]
-            if not (isinstance(arr, t.Tensor) and arr.is_cuda and arr.dtype == want and arr.is_contiguous()
-                    and tuple(arr.shape) == tuple(shape)):
-                raise ValueError('%s must be a contiguous CUDA %s tensor of shape %r' % (name, want, tuple(shape)))
-            return arr.data_ptr()
-        if not (isinstance(arr, np.ndarray) and arr.dtype == dtype and arr.flags.c_contiguous
-                and tuple(arr.shape) == tuple(shape)):
-            raise ValueError('%s must be a C-contiguous %s array of shape %r' % (name, np.dtype(dtype), tuple(shape)))
-        return arr.ctypes.data
+        return array_ptr(self._torch, arr, dtype, shape, name)
 
     def _empty(self, shape, dtype):
         if self.device_arrays:
-            t = self._torch
-            td = {np.uint8: t.uint8, np.uint16: t.uint16, np.float64: t.float64, np.uint32: t.uint32, np.uint64: t.uint64}[dtype]
-            return t.empty(shape, dtype=td, device=self._tdev)
+            return self._torch.empty(shape, dtype=getattr(self._torch, _TORCH_DTYPE[dtype]), device=self._tdev)
         return np.empty(shape, dtype=dtype)
 
     def _coerce(self, arr, dtype, shape, name):
-        """Inputs: accept anything array-like in host mode, strict tensors in device mode."""
-        if arr is None or self.device_arrays:
-            return arr
-        out = np.ascontiguousarray(arr, dtype=dtype)
-        if tuple(out.shape) != tuple(shape):
-            raise ValueError('%s must have shape %r, got %r' % (name, tuple(shape), tuple(out.shape)))
-        return out
+        return coerce_array(self._torch, arr, dtype, shape, name)
+
+    def _inputs(self, *spec):
+        """The input arrays of a call, each named once as (name, dtype, shape, array): the arrays as the library reads them (the
+        caller keeps them alive across the call) and their pointers."""
+        arrays = [self._coerce(arr, dt, shape, name) for name, dt, shape, arr in spec]
+        return arrays, [self._ptr(arr, dt, shape, name) for arr, (name, dt, shape, _) in zip(arrays, spec)]
+
+    def _outputs(self, spec, given=None, skip=(), fill=False):
+        """The output arrays of a call, each named once as (name, dtype, shape): the dict ``given`` (with ``fill``, completed by new
+        arrays), or a dict of new arrays -- and their pointers in the spec's order, None for the names in ``skip``."""
+        res, ptrs = ({} if given is None else given), []
+        for name, dt, shape in spec:
+            if name in skip:
+                ptrs.append(None)
+                continue
+            if name not in res and (fill or given is None):
+                res[name] = self._empty(shape, dt)
+            ptrs.append(self._ptr(res[name], dt, shape, name))
+        return res, ptrs
 
     # -------------------------------------------------------------------------- API
     def reset(self, mask=None):
@@ -205,23 +245,18 @@ class VecMapfEnv:
         ``collision`` and ``was_terminal`` arrays.  ``out`` may carry preallocated arrays under
         those names (plus ``local``, ``reward``, ``done``).
         """
-        E, A = self.n_envs, self.n_agents
-        actions = self._coerce(actions, np.uint8, (E, A), 'actions')
-        uniforms = self._coerce(uniforms, np.float64, (E, A), 'uniforms')
-        out = dict(out) if out else {}
-        spec = (('local', np.uint16, (E, A)), ('reward', np.float64, (E,)), ('done', np.uint8, (E,)),
-                ('collision', np.uint8, (E,)), ('prob', np.float64, (E,)), ('was_terminal', np.uint8, (E,)))
-        for name, dt, shp in spec:
-            if name not in out:
-                out[name] = self._empty(shp, dt)
-        p = {name: self._ptr(out[name], dt, shp, name) for name, dt, shp in spec}
-        nat.check(self._lib.mapf_step(
-            self._h, self._ptr(actions, np.uint8, (E, A), 'actions'),
-            self._ptr(uniforms, np.float64, (E, A), 'uniforms'),
-            p['local'], p['reward'], p['done'], p['collision'], p['prob'], p['was_terminal'],
-            nat.MAPF_STEP_AUTO_RESET if auto_reset else 0))
+        args, (_, _, out) = self._step_args(actions, uniforms, auto_reset, out)
+        nat.check(self._lib.mapf_step(*args))
         info = {'prob': out['prob'], 'collision': out['collision'], 'was_terminal': out['was_terminal']}
         return out['local'], out['reward'], out['done'], info
+
+    def _step_args(self, actions, uniforms, auto_reset, out, write_local=True):
+        """The argument tuple of one ``mapf_step`` and what it points into: (actions, uniforms, out), ``out`` completed."""
+        E, A = self.n_envs, self.n_agents
+        keep, inputs = self._inputs(('actions', np.uint8, (E, A), actions), ('uniforms', np.float64, (E, A), uniforms))
+        out, outputs = self._outputs([(name, dt, (E, A) if per_agent else (E,)) for name, dt, per_agent in STEP_OUTPUTS],
+                                     dict(out) if out else {}, skip=() if write_local else ('local',), fill=True)
+        return (self._h, *inputs, *outputs, nat.MAPF_STEP_AUTO_RESET if auto_reset else 0), (*keep, out)
 
     def prepare_step(self, actions, uniforms=None, auto_reset=False, out=None, write_local=True):
         """Validate once, call many times: returns ``(call, out)`` where ``call()`` performs
@@ -229,24 +264,8 @@ class VecMapfEnv:
         for device mode, where a training loop refills ``actions`` in place every iteration.
         ``write_local=False`` leaves ``out_local`` out of the call: the next observation is then read from
         ``state_view()`` (the handle's own state buffer, after auto-reset) and the step writes the cells once."""
-        E, A = self.n_envs, self.n_agents
-        actions = self._coerce(actions, np.uint8, (E, A), 'actions')
-        uniforms = self._coerce(uniforms, np.float64, (E, A), 'uniforms')
-        out = dict(out) if out else {}
-        spec = (('local', np.uint16, (E, A)), ('reward', np.float64, (E,)), ('done', np.uint8, (E,)),
-                ('collision', np.uint8, (E,)), ('prob', np.float64, (E,)), ('was_terminal', np.uint8, (E,)))
-        for name, dt, shp in spec:
-            if name not in out and (write_local or name != 'local'):
-                out[name] = self._empty(shp, dt)
-        args = (self._h, self._ptr(actions, np.uint8, (E, A), 'actions'),
-                self._ptr(uniforms, np.float64, (E, A), 'uniforms'),
-                self._ptr(out['local'], np.uint16, (E, A), 'local') if write_local else None,
-                self._ptr(out['reward'], np.float64, (E,), 'reward'),
-                self._ptr(out['done'], np.uint8, (E,), 'done'), self._ptr(out['collision'], np.uint8, (E,), 'collision'),
-                self._ptr(out['prob'], np.float64, (E,), 'prob'),
-                self._ptr(out['was_terminal'], np.uint8, (E,), 'was_terminal'),
-                nat.MAPF_STEP_AUTO_RESET if auto_reset else 0)
-        fn, check, keep = self._lib.mapf_step, nat.check, (actions, uniforms, out)
+        args, keep = self._step_args(actions, uniforms, auto_reset, out, write_local)
+        fn, check, out = self._lib.mapf_step, nat.check, keep[2]
 
         def call():
             rc = fn(*args)
@@ -306,9 +325,9 @@ class VecMapfEnv:
             # or another actions buffer take the full path below) -- slicing, checking and packing nine arrays is ~6 us of host
             # time per call, which is what a T <= 16 launch is bound by (profiles/r05_rollout_T_sweep.txt, column b)
             cached = self._rollout_io
-            if cached is not None and cached[0] is out and cached[1] == (T, bool(auto_reset), bool(record)):
-                arrays, act_ref, io = cached[2], cached[3], cached[4]
-                same = all(out.get(k) is v for k, v in arrays)
+            if cached is not None and cached.out is out and cached.call == (T, bool(auto_reset), bool(record)):
+                act_ref = cached.actions
+                same = all(out.get(k) is v for k, v in cached.arrays)
                 if actions is None:
                     same = same and act_ref is None
                 elif act_ref is not None and self.device_arrays:
@@ -317,21 +336,18 @@ class VecMapfEnv:
                 else:
                     same = False
                 if same:
-                    nat.check(self._lib.mapf_rollout(self._h, ctypes.byref(io)))
+                    nat.check(self._lib.mapf_rollout(self._h, ctypes.byref(cached.io)))
                     return out
         actions = self._coerce(actions, np.uint8, (T, E, A), 'actions')
         if out is not None and accumulate_into is not None:
             raise ValueError('pass either out= (overwrite) or accumulate_into= (add), not both')
         res = accumulate_into if accumulate_into is not None else (out if out is not None else {})
-        for name, dt in (('returns', np.float64), ('episodes', np.uint32), ('collisions', np.uint32)):
-            if name not in res:
-                res[name] = self._empty((E,), dt)
-        if record:
-            for name, dt, shp in (('local', np.uint16, (T, E, A)), ('reward', np.float64, (T, E)),
-                                  ('done', np.uint8, (T, E)), ('collision', np.uint8, (T, E)),
-                                  ('prob', np.float64, (T, E))):
-                if out is None or name not in res or tuple(res[name].shape) != shp:
-                    res[name] = self._empty(shp, dt)
+        trajectory = STEP_OUTPUTS[:5] if record else ()
+        res, totals = self._outputs([(name, dt, (E,)) for name, dt in ROLLOUT_TOTALS], res, fill=True)
+        for name, dt, per_agent in trajectory:
+            shape = (T, E, A) if per_agent else (T, E)
+            if out is None or name not in res or tuple(res[name].shape) != shape:
+                res[name] = self._empty(shape, dt)
         per_step = max(E * A * 2, E * 8) if (record or actions is not None) else 0    # bytes of the widest per-step row
         t_max = min(self._MAX_LAUNCH_STEPS, self._MAX_ARRAY_BYTES // per_step if per_step else self._MAX_LAUNCH_STEPS)
         if T > 0 and t_max < 1:
@@ -340,28 +356,21 @@ class VecMapfEnv:
         while True:
             n = min(T - first, t_max) if T else 0
             sl = slice(first, first + n)
-            part = lambda name: res[name][sl] if record else None
-            io = nat.MapfRolloutIO(
-                struct_size=ctypes.sizeof(nat.MapfRolloutIO), n_steps=n,
-                step_flags=nat.MAPF_STEP_AUTO_RESET if auto_reset else 0, accumulate=1 if accumulate else 0,
-                actions=self._ptr(actions[sl] if actions is not None else None, np.uint8, (n, E, A), 'actions'),
-                out_returns=self._ptr(res['returns'], np.float64, (E,), 'returns'),
-                out_episodes=self._ptr(res['episodes'], np.uint32, (E,), 'episodes'),
-                out_collisions=self._ptr(res['collisions'], np.uint32, (E,), 'collisions'),
-                rec_local=self._ptr(part('local'), np.uint16, (n, E, A), 'local'),
-                rec_reward=self._ptr(part('reward'), np.float64, (n, E), 'reward'),
-                rec_done=self._ptr(part('done'), np.uint8, (n, E), 'done'),
-                rec_collision=self._ptr(part('collision'), np.uint8, (n, E), 'collision'),
-                rec_prob=self._ptr(part('prob'), np.float64, (n, E), 'prob'))
+            fields = {'actions': self._ptr(actions[sl] if actions is not None else None, np.uint8, (n, E, A), 'actions')}
+            fields.update(zip(('out_' + name for name, _ in ROLLOUT_TOTALS), totals))
+            for name, dt, per_agent in trajectory:
+                fields['rec_' + name] = self._ptr(res[name][sl], dt, (n, E, A) if per_agent else (n, E), name)
+            io = nat.MapfRolloutIO(struct_size=ctypes.sizeof(nat.MapfRolloutIO), n_steps=n, step_flags=nat.MAPF_STEP_AUTO_RESET if auto_reset else 0,
+                                   accumulate=1 if accumulate else 0, **fields)
             nat.check(self._lib.mapf_rollout(self._h, ctypes.byref(io)))
             first += n
             if first >= T:
                 if out is not None and accumulate_into is None and n == T and self.device_arrays:
                     # (one launch covered the call: its argument block serves the next call with the same arrays; the arrays are
                     # referenced here, so their memory cannot be handed to anyone else while the block is kept)
-                    keys = ('returns', 'episodes', 'collisions') + (('local', 'reward', 'done', 'collision', 'prob') if record else ())
-                    self._rollout_io = (out, (T, bool(auto_reset), bool(record)), tuple((k, res[k]) for k in keys),
-                                        None if actions is None else (actions.data_ptr(), tuple(actions.shape), actions), io)
+                    keys = [name for name, _ in ROLLOUT_TOTALS] + [name for name, _, _ in trajectory]
+                    self._rollout_io = _RolloutIO(out, (T, bool(auto_reset), bool(record)), tuple((k, res[k]) for k in keys),
+                                                  None if actions is None else (actions.data_ptr(), tuple(actions.shape), actions), io)
                 return res
             accumulate = True
 
@@ -373,23 +382,19 @@ class VecMapfEnv:
         ``first_branch``, ``next`` uint16 [N, M, A], ``prob`` / ``reward`` float64 [N, M], ``done`` / ``collision``
         uint8 [N, M].  Rows whose branch index is >= count[q] are unspecified.  Up to 16 agents."""
         A = self.n_agents
-        local = np.asarray(local) if not self.device_arrays else local
-        N = int(local.shape[0])
+        N, alive, queries = self._queries(local, actions, env_index)    # (alive: the coerced arrays, held across the call)
         M = int(max_branches) if max_branches is not None else 3 ** A
-        local = self._coerce(local, np.uint16, (N, A), 'local')
-        actions = self._coerce(actions, np.uint8, (N, A), 'actions')
-        env_index = self._coerce(env_index, np.uint32, (N,), 'env_index')
-        res = out if out is not None else {
-            'count': self._empty((N,), np.uint32), 'next': self._empty((N, M, A), np.uint16),
-            'prob': self._empty((N, M), np.float64), 'reward': self._empty((N, M), np.float64),
-            'done': self._empty((N, M), np.uint8), 'collision': self._empty((N, M), np.uint8)}
-        nat.check(self._lib.mapf_transitions_window(
-            self._h, N, self._ptr(local, np.uint16, (N, A), 'local'), self._ptr(actions, np.uint8, (N, A), 'actions'),
-            self._ptr(env_index, np.uint32, (N,), 'env_index'), int(first_branch), M, self._ptr(res['count'], np.uint32, (N,), 'count'),
-            self._ptr(res['next'], np.uint16, (N, M, A), 'next'), self._ptr(res['prob'], np.float64, (N, M), 'prob'),
-            self._ptr(res['reward'], np.float64, (N, M), 'reward'), self._ptr(res['done'], np.uint8, (N, M), 'done'),
-            self._ptr(res['collision'], np.uint8, (N, M), 'collision')))
+        res, outputs = self._outputs((('count', np.uint32, (N,)), ('next', np.uint16, (N, M, A)), ('prob', np.float64, (N, M)),
+                                      ('reward', np.float64, (N, M)), ('done', np.uint8, (N, M)), ('collision', np.uint8, (N, M))), out)
+        nat.check(self._lib.mapf_transitions_window(self._h, N, *queries, int(first_branch), M, *outputs))
         return res
+
+    def _queries(self, local, actions, env_index):
+        """The query arrays of both transitions calls: (N, the arrays to keep alive across the call, their pointers)."""
+        A, local = self.n_agents, (local if self.device_arrays else np.asarray(local))
+        N = int(local.shape[0])
+        return (N,) + self._inputs(('local', np.uint16, (N, A), local), ('actions', np.uint8, (N, A), actions),
+                                   ('env_index', np.uint32, (N,), env_index))
 
     def transitions_compact(self, local, actions, env_index=None, first_branch=0, max_branches=None, capacity=None, out=None):
         """``env.P[s][a]`` for N queries with COMPACTED rows (``mapf_transitions_compact``): the branches of query q are
@@ -399,27 +404,12 @@ class VecMapfEnv:
         which always suffices); rows beyond it are not written -- check ``offset[N] <= R`` (after ``sync()`` in device
         mode).  ``out`` reuses the arrays of an earlier call."""
         A = self.n_agents
-        local = np.asarray(local) if not self.device_arrays else local
-        N = int(local.shape[0])
+        N, alive, queries = self._queries(local, actions, env_index)    # (alive: the coerced arrays, held across the call)
         M = min(int(max_branches), 3 ** A) if max_branches is not None else 3 ** A
-        local = self._coerce(local, np.uint16, (N, A), 'local')
-        actions = self._coerce(actions, np.uint8, (N, A), 'actions')
-        env_index = self._coerce(env_index, np.uint32, (N,), 'env_index')
-        if out is not None:
-            res, R = out, int(out['prob'].shape[0])
-        else:
-            R = int(capacity) if capacity is not None else N * M
-            res = {'offset': self._empty((N + 1,), np.uint64), 'count': self._empty((N,), np.uint32),
-                   'next': self._empty((R, A), np.uint16), 'prob': self._empty((R,), np.float64),
-                   'reward': self._empty((R,), np.float64), 'done': self._empty((R,), np.uint8),
-                   'collision': self._empty((R,), np.uint8)}
-        nat.check(self._lib.mapf_transitions_compact(
-            self._h, N, self._ptr(local, np.uint16, (N, A), 'local'), self._ptr(actions, np.uint8, (N, A), 'actions'),
-            self._ptr(env_index, np.uint32, (N,), 'env_index'), int(first_branch), max(1, M), R,
-            self._ptr(res['offset'], np.uint64, (N + 1,), 'offset'), self._ptr(res['count'], np.uint32, (N,), 'count'),
-            self._ptr(res['next'], np.uint16, (R, A), 'next'), self._ptr(res['prob'], np.float64, (R,), 'prob'),
-            self._ptr(res['reward'], np.float64, (R,), 'reward'), self._ptr(res['done'], np.uint8, (R,), 'done'),
-            self._ptr(res['collision'], np.uint8, (R,), 'collision')))
+        R = int(out['prob'].shape[0]) if out is not None else int(capacity) if capacity is not None else N * M
+        res, outputs = self._outputs((('offset', np.uint64, (N + 1,)), ('count', np.uint32, (N,)), ('next', np.uint16, (R, A)), ('prob', np.float64, (R,)),
+                                      ('reward', np.float64, (R,)), ('done', np.uint8, (R,)), ('collision', np.uint8, (R,))), out)
+        nat.check(self._lib.mapf_transitions_compact(self._h, N, *queries, int(first_branch), max(1, M), R, *outputs))
         return res
 
     def transition_rewards(self, prev_local, actions, next_local, env_index=None, want_done=True, want_collision=True):
@@ -427,22 +417,14 @@ class VecMapfEnv:
         ``prev_local`` / ``next_local`` uint16 [N, A], ``actions`` uint8 [N, A].  Returns ``(reward f64 [N],
         done u8 [N], collision u8 [N])``; with ``want_done`` / ``want_collision`` False that output is not computed
         (the C ABI gets NULL for it) and None is returned in its place."""
-        A = self.n_agents
-        prev_local = np.asarray(prev_local) if not self.device_arrays else prev_local
+        A, prev_local = self.n_agents, (prev_local if self.device_arrays else np.asarray(prev_local))
         N = int(prev_local.shape[0])
-        prev_local = self._coerce(prev_local, np.uint16, (N, A), 'prev_local')
-        next_local = self._coerce(next_local, np.uint16, (N, A), 'next_local')
-        actions = self._coerce(actions, np.uint8, (N, A), 'actions')
-        env_index = self._coerce(env_index, np.uint32, (N,), 'env_index')
-        reward = self._empty((N,), np.float64)
-        done = self._empty((N,), np.uint8) if want_done else None
-        coll = self._empty((N,), np.uint8) if want_collision else None
-        nat.check(self._lib.mapf_transition_rewards(
-            self._h, N, self._ptr(prev_local, np.uint16, (N, A), 'prev_local'),
-            self._ptr(actions, np.uint8, (N, A), 'actions'), self._ptr(next_local, np.uint16, (N, A), 'next_local'),
-            self._ptr(env_index, np.uint32, (N,), 'env_index'), self._ptr(reward, np.float64, (N,), 'reward'),
-            self._ptr(done, np.uint8, (N,), 'done'), self._ptr(coll, np.uint8, (N,), 'collision')))
-        return reward, done, coll
+        alive, queries = self._inputs(('prev_local', np.uint16, (N, A), prev_local), ('actions', np.uint8, (N, A), actions),
+                                     ('next_local', np.uint16, (N, A), next_local), ('env_index', np.uint32, (N,), env_index))    # (alive: as above)
+        skip = [name for name, wanted in (('done', want_done), ('collision', want_collision)) if not wanted]
+        res, outputs = self._outputs((('reward', np.float64, (N,)), ('done', np.uint8, (N,)), ('collision', np.uint8, (N,))), skip=skip)
+        nat.check(self._lib.mapf_transition_rewards(self._h, N, *queries, *outputs))
+        return res['reward'], res.get('done'), res.get('collision')
 
     def fill_random_actions(self, t0, n_steps, out=None):
         """Synthetic policy stream: uint8 [n_steps, E, A] uniform over the 5 actions."""

@@ -8,8 +8,9 @@ import c_oracle
 import mapf_oracle as mo
 import philox
 from conftest import set_tune, load_json
+from gym_mapf_amd import _native as nat
 from gym_mapf_amd.envs.grid import MapfGrid
-from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
+from gym_mapf_amd.envs.vec_env import STEP_OUTPUTS, OptimizationCriteria, VecMapfEnv
 from totals_cases import _assert_a_wrong_rounding_would_show, _goal_scenario_tables   # (shared with the totals-only sweep)
 
 pytestmark = pytest.mark.gpu
@@ -1553,7 +1554,65 @@ def test_out_of_range_actions_are_stay_and_device_pointers_must_be_aligned():
     local, reward, done, info = dev.step(buf[:128].view(64, 2))
     dev.sync()
     assert local.shape == (64, 2) and bool((info['was_terminal'] == 0).all())
+    # a rollout names the misaligned array and enqueues nothing
+    streamed = torch.zeros(4 * 64 * 2 + 3, dtype=torch.uint8, device='cuda')
+    t_before = dev.t
+    with pytest.raises(nat.MapfNativeError) as err:
+        dev.rollout(4, actions=streamed[3:].view(4, 64, 2))
+    assert err.value.code == nat.MAPF_EINVAL and '16-byte aligned' in str(err.value) and 'actions' in str(err.value)
+    assert dev.t == t_before == 1
     dev.close()
+
+
+# (agents, envs): the smallest batches that reach each branch of the host-mode step's staging -- see the test
+STAGING_SHAPES = [(2, 1), (2, 64), (2, 65), (4, 32), (4, 33), (2, 398), (2, 399)]
+
+
+@pytest.mark.parametrize('n_agents,n_envs', STAGING_SHAPES)
+def test_host_mode_step_staging_regimes(n_agents, n_envs):
+    """mapf_step on host pointers, called directly, through every way its arrays travel: tiny calls use one pinned,
+    device-mapped block (a 16-byte slot per present array, then a flag word) -- the scalar regime (1 env), a one-wave launch
+    that signals its end through the flag word (thread-per-env: up to 64 envs; lane groups of two lanes at 4 agents: up to
+    32), the first launch beyond one wave (65 / 33 envs: stream wait), the last call that fits the 16 KiB block (2 agents,
+    398 envs with uniforms and all six outputs: 16352 bytes) -- and the first that does not (399 envs: 16400 bytes), which
+    goes through the staging buffers and copies.  Every pattern of absent outputs (none, each one, all but the reward), with
+    and without uniforms and auto-reset, three consecutive steps each (the flag word's sequence number advances): the
+    present arrays equal the C oracle's bit for bit and eight guard elements on either side of every array stay untouched.
+    Which path a call took is not observable: the assertion is that the results do not depend on it."""
+    A, E = n_agents, n_envs
+    grid = MapfGrid(['....', '....'])
+    rs = np.random.RandomState(100 * A + E)
+    start = np.stack([rs.permutation(8)[:A] for _ in range(E)]).astype(np.uint16)
+    goal = np.stack([rs.permutation(8)[:A] for _ in range(E)]).astype(np.uint16)
+    env = VecMapfEnv(grid, A, None, None, 0.2, *INEXACT, OptimizationCriteria.SoC, seed=9, start_local=start, goal_local=goal)
+    co = c_oracle.COracle(grid.tables()[2], A, start, goal, 0.2, *INEXACT, mo.SOC, seed=9)
+    sentinel = {np.uint8: 0xA5, np.uint16: 0xA5A5, np.float64: -12345.678}
+    names = [name for name, _, _ in STEP_OUTPUTS]
+    bufs = {name: np.empty(E * (A if per_agent else 1) + 16, dt) for name, dt, per_agent in STEP_OUTPUTS}
+    n_steps, n_done = 0, 0
+    for present in [set(names)] + [set(names) - {name} for name in names] + [{'reward'}]:
+        for with_uniforms in (True, False):
+            for auto_reset in (True, False):
+                for k in range(3):
+                    acts = rs.randint(0, 5, (E, A)).astype(np.uint8)
+                    uni = rs.rand(E, A) if with_uniforms else None
+                    for name, dt, _ in STEP_OUTPUTS:
+                        bufs[name].fill(sentinel[dt])
+                    nat.check(env._lib.mapf_step(env._h, acts.ctypes.data, None if uni is None else uni.ctypes.data,
+                                                 *[bufs[name][8:].ctypes.data if name in present else None for name in names],
+                                                 nat.MAPF_STEP_AUTO_RESET if auto_reset else 0))
+                    ref = co.step(acts, uni, auto_reset=auto_reset)
+                    n_steps, n_done = n_steps + 1, n_done + int(ref['done'].sum())
+                    tag = (sorted(present), with_uniforms, auto_reset, k)
+                    for name, dt, _ in STEP_OUTPUTS:
+                        buf, want = bufs[name], np.full(8, sentinel[dt], dt)
+                        assert np.array_equal(buf[:8], want) and np.array_equal(buf[-8:], want), (tag, name, 'guard')
+                        if name in present:
+                            assert np.array_equal(buf[8:-8].view(np.uint8), ref[name].ravel().view(np.uint8)), (tag, name)
+                        else:
+                            assert np.all(buf == sentinel[dt]), (tag, name, 'absent')
+    assert env.t == n_steps == 96 and n_done > 0
+    env.close()
 
 
 def test_rollout_with_large_lds_move_table():

@@ -426,6 +426,42 @@ def test_stand_in_trajectory_buffers_cannot_move_under_a_recorded_rollout():
     env.close()
 
 
+REC_ARRAYS = (('local', 'uint16', True), ('reward', 'float64', False), ('prob', 'float64', False), ('done', 'uint8', False), ('collision', 'uint8', False))
+
+
+def test_every_partial_recording_equals_the_same_arrays_of_a_full_one():
+    """Each rec_* array alone, and each one alone left out (the library's stand-ins take the others' writes): the arrays the
+    caller passed hold what a full recording of the same steps holds.  Every rollout runs on an env of its own, all seeded alike."""
+    import ctypes
+    import torch
+    E, A, T = 1024, 8, 8
+    grid, _, nbr, start, goal = _c3_tables(E)
+
+    def fresh_env():
+        return VecMapfEnv(grid, A, None, None, 0.2, *R, OptimizationCriteria.Makespan, seed=5, device_arrays=True,
+                          start_local=start, goal_local=goal)
+
+    env = fresh_env()
+    full = env.rollout(T, record=True)
+    env.sync()
+    full = {name: arr.cpu().numpy() for name, arr in full.items()}
+    assert env.t == T and int(full['episodes'].sum()) > 0
+    env.close()
+    names = [name for name, _, _ in REC_ARRAYS]
+    for present in [{name} for name in names] + [set(names) - {name} for name in names]:
+        env = fresh_env()
+        got = {name: torch.zeros((T, E, A) if per_agent else (T, E), dtype=getattr(torch, dt), device='cuda')
+               for name, dt, per_agent in REC_ARRAYS if name in present}
+        io = nat.MapfRolloutIO(struct_size=ctypes.sizeof(nat.MapfRolloutIO), n_steps=T, step_flags=nat.MAPF_STEP_AUTO_RESET, accumulate=0,
+                               **{'rec_' + name: arr.data_ptr() for name, arr in got.items()})
+        nat.check(env._lib.mapf_rollout(env._h, ctypes.byref(io)))
+        env.sync()
+        assert env.t == T
+        for name, arr in got.items():
+            assert np.array_equal(arr.cpu().numpy().view(np.uint8), full[name].view(np.uint8)), (sorted(present), name)
+        env.close()
+
+
 def test_own_stream_capture_is_refused_once_the_stream_was_handed_out():
     """A handle that created its own stream cannot be captured by anybody else -- until mapf_get_stream hands the stream
     out (torch ExternalStream interop).  From then on a step enqueued under a foreign capture is refused like on a
