@@ -165,6 +165,11 @@ struct mapf_handle_s : StreamAndEvents {
     DevicePtr<uint16_t> table_rows;
     mapf::TablePolicy table{};
     DevicePtr<uint16_t> state, start, goal;
+    // episode step limit (mapf_set_episode_limit): N (0 = none) and the per-env ages, which are all zero while N == 0 -- only the
+    // limit kernels and mapf_episode_steps write them, and only a handle with a limit runs those
+    uint32_t episode_limit = 0;
+    DevicePtr<uint32_t> age;
+    DeviceBuf s_trunc, s_rtrunc, s_age, x_trunc;   // staging of out_truncations / rec_truncated / the ages; stand-in for rec_truncated
     // host-pointer mode staging
     DeviceBuf s_actions, s_uniforms, s_local, s_reward, s_prob, s_done, s_coll, s_term, s_mask, s_ret, s_epi, s_ncoll;
     DeviceBuf x_local, x_reward, x_prob, x_done, x_coll;   // stand-ins for trajectory arrays the caller left out
@@ -314,8 +319,9 @@ void after_launch(mapf_handle_t h, std::string &last_kernel, uint64_t n_steps, b
     if (n_steps) h->terminal_possible() = auto_reset ? h->start_terminal_any : true;
 }
 
-int launch_step_and_advance(mapf_handle_t h, const mapf::StepArgs &a) {
-    HIP_TRY(h->lane_group ? mapf::launch_step_lg(int(h->A), a, h->tune, h->stream) : mapf::launch_step(int(h->A), a, h->stream));
+// (limit: the handle's episode limit, or null -- the limit instances exist in the lane-group family only, which then takes the launch)
+int launch_step_and_advance(mapf_handle_t h, const mapf::StepArgs &a, const mapf::EpisodeLimit *limit) {
+    HIP_TRY((h->lane_group || limit) ? mapf::launch_step_lg(int(h->A), a, h->tune, h->stream, limit) : mapf::launch_step(int(h->A), a, h->stream));
     after_launch(h, h->last_step_kernel, 1, a.auto_reset);
     return MAPF_OK;
 }
@@ -325,7 +331,7 @@ extern "C" {
 
 const char *mapf_last_error(void) { return g_last_error.c_str(); }
 
-const char *mapf_version(void) { return "mapf_hip 0.5.0 (abi 5, gfx950)"; }
+const char *mapf_version(void) { return "mapf_hip 0.6.0 (abi 6, gfx950)"; }
 
 int mapf_abi_version(void) { return MAPF_ABI_VERSION; }
 
@@ -350,6 +356,24 @@ int mapf_debug_rollout_plan(uint32_t n_cells, int n_agents, uint64_t n_envs, uin
     out[0] = uint64_t(plan.K); out[1] = uint64_t(plan.Q); out[2] = uint64_t(int(plan.form));
     out[3] = plan.block; out[4] = plan.lds_bytes; out[5] = plan.lds_total;
     return packed ? 1 : 0;
+}
+
+int mapf_debug_rollout_plan_limited(uint32_t n_cells, int n_agents, uint64_t n_envs, uint32_t n_steps, int streamed, int delta_rows,
+                                    int n_cu, const char *tune, uint32_t max_steps, uint64_t out[6]) {
+    if (max_steps == 0u) return mapf_debug_rollout_plan(n_cells, n_agents, n_envs, n_steps, streamed, delta_rows, n_cu, tune, out);
+    if (!out) return fail(MAPF_EINVAL, "out is null");
+    if (n_agents < 1 || n_cells < 2 || n_cu < 1) return fail(MAPF_EINVAL, "mapf_debug_rollout_plan_limited: n_agents >= 1, n_cells >= 2, n_cu >= 1");
+    std::string tune_error;
+    const mapf::RolloutTuning t = mapf::rollout_tuning_for(n_cu, tune, &tune_error);
+    if (!tune_error.empty()) return fail(MAPF_EINVAL, tune_error);
+    mapf::RolloutArgs args{};   // (the lane-group plan reads the shape only)
+    args.c.n_cells = n_cells;
+    args.n_envs = n_envs;
+    args.n_steps = n_steps;
+    const mapf::LgRolloutPlan plan = mapf::plan_rollout_lg_limit(n_agents, args, t);
+    out[0] = 2; out[1] = uint64_t(plan.L); out[2] = plan.mv_lds ? 1 : 0;
+    out[3] = plan.block; out[4] = plan.lds_bytes; out[5] = plan.grid;
+    return 0;
 }
 
 int mapf_device_count(int *out_count) {
@@ -447,6 +471,8 @@ int mapf_create(const mapf_desc *d, mapf_handle_t *out_handle) {
     if (n_goal) HIP_TRY(hipMemcpy(h->goal, d->goal, n_goal * sizeof(uint16_t), hipMemcpyHostToDevice));
     HIP_TRY(h->t_dev.alloc(1));
     HIP_TRY(hipMemset(h->t_dev, 0, sizeof(uint64_t)));
+    HIP_TRY(h->age.alloc(E ? E : 1));
+    HIP_TRY(hipMemset(h->age, 0, (E ? E : 1) * sizeof(uint32_t)));
     if (scen.n) {
         h->n_scen = scen.n;
         HIP_TRY(h->scen.upload(scen.scen.data(), scen.scen.size()));
@@ -525,16 +551,20 @@ int mapf_reset(mapf_handle_t h, const uint8_t *mask) {
     const CallArray io[] = {input(h->s_mask, mask, size_t(h->E), &d_mask, "mask")};
     if (int rc = stage_arrays(h, io)) return rc;
     HIP_TRY(mapf::launch_reset(int(h->A), h->state, h->start, h->start_broadcast, d_mask, h->E, h->stream));
+    if (h->episode_limit) HIP_TRY(mapf::launch_reset_ages(h->age, d_mask, h->E, h->stream));   // a reset env's episode begins again
     if (!mask) h->terminal_possible() = h->start_terminal_any;
     if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
     return MAPF_OK;
 }
 
-int mapf_step(mapf_handle_t h, const uint8_t *actions, const double *uniforms, uint16_t *out_local,
+namespace {
+// mapf_step and mapf_step_limited (out_truncated: null from mapf_step)
+int step_impl(mapf_handle_t h, const uint8_t *actions, const double *uniforms, uint16_t *out_local,
               double *out_reward, uint8_t *out_done, uint8_t *out_collision, double *out_prob,
-              uint8_t *out_was_terminal, uint32_t step_flags) {
+              uint8_t *out_was_terminal, uint8_t *out_truncated, uint32_t step_flags) {
     if (int rc = check_handle(h)) return rc;
     if (!actions) return fail(MAPF_EINVAL, "actions is null");
+    if (out_truncated && !h->episode_limit) return fail(MAPF_EINVAL, "step_limited: out_truncated on a handle without an episode limit (mapf_set_episode_limit)");
     if (step_flags & ~MAPF_STEP_AUTO_RESET) return fail(MAPF_EINVAL, "unknown step flag");
     if (int rc = check_foreign_capture(h, "mapf_step")) return rc;
     if (int rc = check_extent(h, h->E, uniforms != nullptr)) return rc;
@@ -543,11 +573,14 @@ int mapf_step(mapf_handle_t h, const uint8_t *actions, const double *uniforms, u
     a.mv8 = h->mv8; a.scen = h->scen; a.scen_rows = h->scen_rows;
     a.auto_reset = step_flags & MAPF_STEP_AUTO_RESET;
     a.state_not_terminal = !h->terminal_possible();
+    mapf::EpisodeLimit lim{h->age, h->episode_limit, nullptr, nullptr};
+    const mapf::EpisodeLimit *limit = h->episode_limit ? &lim : nullptr;
     const CallArray io[] = {input(h->s_actions, actions, EA, &a.actions, "actions"), input(h->s_uniforms, uniforms, EA, &a.uniforms, "uniforms"),
                             output(h->s_local, out_local, EA, &a.out_local, "out_local"), output(h->s_reward, out_reward, E, &a.out_reward, "out_reward"),
                             output(h->s_prob, out_prob, E, &a.out_prob, "out_prob"), output(h->s_done, out_done, E, &a.out_done, "out_done"),
                             output(h->s_coll, out_collision, E, &a.out_collision, "out_collision"),
-                            output(h->s_term, out_was_terminal, E, &a.out_was_terminal, "out_was_terminal")};
+                            output(h->s_term, out_was_terminal, E, &a.out_was_terminal, "out_was_terminal"),
+                            output(h->s_rtrunc, out_truncated, E, &lim.rec_truncated, "out_truncated")};
     if (!h->device_ptrs) {
         // tiny host-mode call: inputs and outputs live in one pinned, device-mapped block -- a 16-byte aligned slot per array
         // of the list (none for an absent one), then the flag word
@@ -564,7 +597,7 @@ int mapf_step(mapf_handle_t h, const uint8_t *actions, const double *uniforms, u
                 void *dev = io[i].user ? dp + at[i] : nullptr;
                 std::memcpy(io[i].slot, &dev, sizeof(dev));
             }
-            const uint64_t launch_threads = h->lane_group ? E * uint64_t(mapf::lg_group_size(int(h->A))) : E;
+            const uint64_t launch_threads = (h->lane_group || limit) ? E * uint64_t(mapf::lg_group_size(int(h->A))) : E;
             const bool flagged = launch_threads <= 64;             // one wave: see below
             const uint32_t seq = uint32_t(h->t) + 1u;
             if (flagged) {
@@ -572,7 +605,7 @@ int mapf_step(mapf_handle_t h, const uint8_t *actions, const double *uniforms, u
                 a.done_flag = reinterpret_cast<uint32_t *>(dp + o_flag);
                 a.done_seq = seq;
             }
-            if (int rc = launch_step_and_advance(h, a)) return rc;
+            if (int rc = launch_step_and_advance(h, a, limit)) return rc;
             // A one-wave launch signals its end itself: its last instruction stores the call's sequence number into the
             // pinned block (system-scope release after all outputs), and the host spins on that word instead of paying the
             // sleeping stream wait (~6 us of a ~16 us call).  Anything larger, or a slow launch, uses hipStreamSynchronize.
@@ -588,10 +621,23 @@ int mapf_step(mapf_handle_t h, const uint8_t *actions, const double *uniforms, u
         }
     }
     if (int rc = stage_arrays(h, io)) return rc;
-    if (int rc = launch_step_and_advance(h, a)) return rc;
+    if (int rc = launch_step_and_advance(h, a, limit)) return rc;
     if (int rc = fetch_arrays(h, io)) return rc;
     if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
     return MAPF_OK;
+}
+}  // namespace
+
+int mapf_step(mapf_handle_t h, const uint8_t *actions, const double *uniforms, uint16_t *out_local,
+              double *out_reward, uint8_t *out_done, uint8_t *out_collision, double *out_prob,
+              uint8_t *out_was_terminal, uint32_t step_flags) {
+    return step_impl(h, actions, uniforms, out_local, out_reward, out_done, out_collision, out_prob, out_was_terminal, nullptr, step_flags);
+}
+
+int mapf_step_limited(mapf_handle_t h, const uint8_t *actions, const double *uniforms, uint16_t *out_local,
+                      double *out_reward, uint8_t *out_done, uint8_t *out_collision, double *out_prob,
+                      uint8_t *out_was_terminal, uint8_t *out_truncated, uint32_t step_flags) {
+    return step_impl(h, actions, uniforms, out_local, out_reward, out_done, out_collision, out_prob, out_was_terminal, out_truncated, step_flags);
 }
 
 namespace {
@@ -624,10 +670,14 @@ int complete_recording(mapf_handle_t h, mapf::RolloutArgs &a, size_t TE, size_t 
 }
 }  // namespace
 
-int mapf_rollout(mapf_handle_t h, const mapf_rollout_io *io) {
+namespace {
+// mapf_rollout and mapf_rollout_limited (out_truncations, rec_truncated: null from mapf_rollout)
+int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_truncations, uint8_t *rec_truncated) {
     if (int rc = check_handle(h)) return rc;
     if (!io || io->struct_size != sizeof(mapf_rollout_io)) return fail(MAPF_EINVAL, "bad mapf_rollout_io");
     if (io->step_flags & ~MAPF_STEP_AUTO_RESET) return fail(MAPF_EINVAL, "unknown step flag");
+    if ((out_truncations || rec_truncated) && !h->episode_limit)
+        return fail(MAPF_EINVAL, "rollout_limited: out_truncations / rec_truncated on a handle without an episode limit (mapf_set_episode_limit)");
     if (int rc = check_foreign_capture(h, "mapf_rollout")) return rc;
     if (int rc = check_extent(h, uint64_t(h->E) * io->n_steps, false)) return rc;
     const size_t E = size_t(h->E), T = io->n_steps, TE = T * E, TEA = TE * h->A;
@@ -641,6 +691,9 @@ int mapf_rollout(mapf_handle_t h, const mapf_rollout_io *io) {
     a.accumulate = io->accumulate != 0;
     a.start_terminal_any = h->start_terminal_any;
     a.mv_delta8 = h->mv_delta8;
+    // (the episode limit travels beside the argument block too: its kernels are the lane-group family's limit instances)
+    mapf::EpisodeLimit lim{h->age, h->episode_limit, nullptr, nullptr};
+    const mapf::EpisodeLimit *limit = h->episode_limit ? &lim : nullptr;
     // (the totals are inputs too when the call accumulates)
     const CallArray arrays[] = {input(h->s_actions, io->actions, TEA, &a.actions, "actions"),
                                 output(h->s_ret, io->out_returns, E, &a.out_returns, "out_returns", a.accumulate),
@@ -648,12 +701,57 @@ int mapf_rollout(mapf_handle_t h, const mapf_rollout_io *io) {
                                 output(h->s_ncoll, io->out_collisions, E, &a.out_collisions, "out_collisions", a.accumulate),
                                 output(h->s_local, io->rec_local, TEA, &a.rec_local, "rec_local"), output(h->s_reward, io->rec_reward, TE, &a.rec_reward, "rec_reward"),
                                 output(h->s_prob, io->rec_prob, TE, &a.rec_prob, "rec_prob"), output(h->s_done, io->rec_done, TE, &a.rec_done, "rec_done"),
-                                output(h->s_coll, io->rec_collision, TE, &a.rec_collision, "rec_collision")};
+                                output(h->s_coll, io->rec_collision, TE, &a.rec_collision, "rec_collision"),
+                                output(h->s_trunc, out_truncations, E, &lim.out_truncations, "out_truncations", a.accumulate),
+                                output(h->s_rtrunc, rec_truncated, TE, &lim.rec_truncated, "rec_truncated")};
     if (int rc = stage_arrays(h, arrays)) return rc;
+    if (limit && lim.rec_truncated && !a.rec_local) {   // the truncated bytes alone make the launch a recording one
+        if (int rc = reserve_stand_in(h, h->x_local, TEA * sizeof(uint16_t), "rec_local")) return rc;
+        a.rec_local = static_cast<uint16_t *>(h->x_local.ptr);
+    }
     if (int rc = complete_recording(h, a, TE, TEA)) return rc;
-    HIP_TRY(h->lane_group_rollout ? mapf::launch_rollout_lg(int(h->A), a, h->tune, h->stream, table) : mapf::launch_rollout(int(h->A), a, h->stream, table));
+    if (limit && a.rec_local && !lim.rec_truncated) {   // ... and a recording limit launch writes them: a stand-in when absent
+        if (int rc = reserve_stand_in(h, h->x_trunc, TE, "rec_truncated")) return rc;
+        lim.rec_truncated = static_cast<uint8_t *>(h->x_trunc.ptr);
+    }
+    HIP_TRY((h->lane_group_rollout || limit) ? mapf::launch_rollout_lg(int(h->A), a, h->tune, h->stream, table, limit)
+                                             : mapf::launch_rollout(int(h->A), a, h->stream, table));
     after_launch(h, h->last_rollout_kernel, io->n_steps, a.auto_reset);
     if (int rc = fetch_arrays(h, arrays)) return rc;
+    if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
+    return MAPF_OK;
+}
+
+}  // namespace
+
+int mapf_rollout(mapf_handle_t h, const mapf_rollout_io *io) { return rollout_impl(h, io, nullptr, nullptr); }
+
+int mapf_rollout_limited(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_truncations, uint8_t *rec_truncated) {
+    return rollout_impl(h, io, out_truncations, rec_truncated);
+}
+
+int mapf_set_episode_limit(mapf_handle_t h, uint32_t max_steps) {
+    if (!h) return fail(MAPF_EINVAL, "set_episode_limit: null handle");
+    if (int rc = check_not_recording(h, "mapf_set_episode_limit")) return rc;
+    if (!h->graphs.empty()) return fail(MAPF_EINVAL, "set_episode_limit: recorded graphs hold launches without a limit (destroy them first)");
+    if (int rc = check_handle(h)) return rc;
+    HIP_TRY(hipMemsetAsync(h->age, 0, (h->E ? size_t(h->E) : 1) * sizeof(uint32_t), h->stream));   // every call: new episodes
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->episode_limit = max_steps;
+    return MAPF_OK;
+}
+
+int mapf_episode_steps(mapf_handle_t h, uint32_t *out_age, const uint32_t *set_age) {
+    if (!h) return fail(MAPF_EINVAL, "episode_steps: null handle");
+    if (!out_age && !set_age) return fail(MAPF_EINVAL, "episode_steps: out_age and set_age are both null");
+    if (set_age && !h->episode_limit) return fail(MAPF_EINVAL, "episode_steps: set_age on a handle without an episode limit (mapf_set_episode_limit)");
+    if (int rc = check_not_recording(h, "mapf_episode_steps")) return rc;
+    if (h->device_ptrs && (misaligned(out_age) || misaligned(set_age))) return fail(MAPF_EINVAL, "episode_steps: device pointer must be 16-byte aligned");
+    if (int rc = check_handle(h)) return rc;
+    const size_t bytes = size_t(h->E) * sizeof(uint32_t);
+    // (out_age receives the ages as they are before set_age replaces them)
+    if (out_age && bytes) HIP_TRY(hipMemcpyAsync(out_age, h->age, bytes, h->device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    if (set_age && bytes) HIP_TRY(hipMemcpyAsync(h->age, set_age, bytes, h->device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
     return MAPF_OK;
 }
@@ -874,6 +972,7 @@ int mapf_set_state(mapf_handle_t h, const uint16_t *local, uint64_t t) {
         HIP_TRY(hipMemcpyAsync(h->state, local, n * sizeof(uint16_t),
                                h->device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
         h->may_be_terminal = true;   // (an arbitrary state)
+        if (h->episode_limit) HIP_TRY(hipMemsetAsync(h->age, 0, size_t(h->E) * sizeof(uint32_t), h->stream));   // (... of new episodes)
         if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
     }
     h->t = t;
@@ -899,6 +998,7 @@ int mapf_graph_begin(mapf_handle_t h) {
     if (int rc = check_handle(h)) return rc;
     if (!h->device_ptrs) return fail(MAPF_EINVAL, "graph_begin: only handles created with MAPF_FLAG_DEVICE_PTRS can be recorded (host-pointer calls wait for the stream)");
     if (h->capturing) return fail(MAPF_EINVAL, "graph_begin: already recording");
+    if (h->episode_limit) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with an episode limit cannot be recorded (mapf_set_episode_limit(h, 0) first)");
     HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed));
     h->capturing = true;
     h->cap_steps = 0;

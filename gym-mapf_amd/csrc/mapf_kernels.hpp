@@ -159,6 +159,16 @@ struct TablePolicy {
     uint32_t rows_broadcast;       // rows is [A]
 };
 
+// Episode step limit (include/mapf_hip.h mapf_set_episode_limit): the handle's per-env ages, the limit and where a launch
+// reports its truncations.  Travels beside the argument blocks as the table policy does -- StepArgs, RolloutArgs, and with them
+// every kernel that exists without the limit, stay as they are; the limit instances are kernels of their own (mapf_lg_limit.hip).
+struct EpisodeLimit {
+    uint32_t *age;                 // [E] live steps since the episode began, saturating
+    uint32_t max_steps;            // N >= 1
+    uint32_t *out_truncations;     // rollout: [E] or null (RolloutArgs::accumulate applies)
+    uint8_t *rec_truncated;        // rollout: [T*E], non-null exactly when the launch records; single step: [E] or null
+};
+
 // Every launcher names the kernel instance (and block size) that took the launch; the C ABI keeps the name of a
 // handle's last step / rollout launch (mapf_last_kernel) so a benchmark labels its numbers with what actually ran.
 constexpr size_t kKernelNameBytes = 160;   // what is kept of a name, the terminator included
@@ -249,10 +259,18 @@ struct RolloutTuning {
                                      //   memory / from a copy staged into LDS behind the table image whenever that fits (default: by shape)
 };
 RolloutTuning default_rollout_tuning(int device, std::string *err);   // (asks the device, reads MAPF_TUNE: mapf_dispatch.hip)
-hipError_t launch_step_lg(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream);
+// (limit: the episode limit of a handle that has one, or null -- then the lane-group limit instance takes the launch: no packed
+// form and no thread-per-env kernel is consulted, mapf_lg_limit.hip)
+hipError_t launch_step_lg(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, const EpisodeLimit *limit = nullptr);
 // packed layout of the single step (mapf_lq_step.hip): true when it took the launch (*err = its status)
 bool try_launch_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err);
-hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table = nullptr);
+hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table = nullptr,
+                             const EpisodeLimit *limit = nullptr);
+// the limit instances (mapf_lg_limit.hip): the lane-group kernels with a per-env age, and the masked zeroing of the ages
+hipError_t launch_rollout_lg_limit(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table,
+                                   const EpisodeLimit &limit);
+hipError_t launch_step_lg_limit(int n_agents, const StepArgs &args, hipStream_t stream, const EpisodeLimit &limit);
+hipError_t launch_reset_ages(uint32_t *age, const uint8_t *mask, uint64_t n_envs, hipStream_t stream);
 // packed layout of the fused rollout (2, 4 or 8 agents per lane): plans the launch (mapf_plan.hpp) and routes it to the object that
 // holds its instance (mapf_dispatch.hip); true when it took the launch (*err = its status)
 bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy *table = nullptr);

@@ -17,6 +17,7 @@
 #pragma once
 #include "mapf_kernels.hpp"
 #include "mapf_device.hpp"
+#include "mapf_plan.hpp"
 #include <mutex>
 #include <set>
 #include <utility>
@@ -492,6 +493,27 @@ __device__ __forceinline__ LaneCtx<L> lane_ctx(uint32_t n_agents, uint64_t n_env
     x.v1 = live && 2u * x.g + 1u < n_agents;
     if (!live) x.e = 0;
     return x;
+}
+
+// Largest block a rollout kernel may be launched with (the kernels' __launch_bounds__): what the planner caps its blocks at
+template <int L> constexpr unsigned rollout_max_block() { return L == 16 ? kLgRolloutMaxBlock16 : kLgRolloutMaxBlock; }
+
+// raw (still packed) action bytes of a lane's two slots: byte 0 = agent 2g, byte 1 = agent 2g+1.  Kept packed so
+// that a prefetch issued one step ahead is not forced to complete by an unpack.
+template <bool EVEN>
+__device__ __forceinline__ uint32_t load_actions_raw(const uint8_t *base, uint32_t row, uint32_t n_agents, uint32_t g,
+                                                     bool v0, bool v1) {
+    const uint8_t *p = at(base, row * n_agents + 2u * g);
+    uint32_t raw = 0u;
+    if (EVEN || (n_agents & 1u) == 0u) {
+        if (v0) raw = *reinterpret_cast<const uint16_t *>(p);
+    } else {
+        uint32_t lo = 0u, hi = 0u;
+        if (v0) lo = p[0];
+        if (v1) hi = p[1];
+        raw = lo | (hi << 8);
+    }
+    return raw;
 }
 
 // Dynamic LDS beyond the 32 KB default needs an explicit opt-in per (device, kernel).  The driver call is made once per

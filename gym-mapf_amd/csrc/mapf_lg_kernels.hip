@@ -167,8 +167,9 @@ hipError_t launch_fill_actions(int n_agents, uint8_t *actions, const EnvConsts &
 
 // ------------------------------------------------------------------- launchers
 // launches the instance plan_step_lg names (mapf_plan.hip), unless the packed single step takes the launch
-hipError_t launch_step_lg(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream) {
+hipError_t launch_step_lg(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, const EpisodeLimit *limit) {
     if (args.n_envs == 0) return hipSuccess;
+    if (limit) return launch_step_lg_limit(n_agents, args, stream, *limit);   // (before the packed single step is consulted)
     hipError_t packed_status;
     if (try_launch_step_lq(n_agents, args, tune, stream, &packed_status)) return packed_status;
     const LgStepPlan plan = plan_step_lg(n_agents, args);

@@ -6,27 +6,6 @@
 
 namespace mapf {
 
-// Largest block a rollout kernel may be launched with (the kernels' __launch_bounds__): what the planner caps its blocks at
-template <int L> constexpr unsigned rollout_max_block() { return L == 16 ? kLgRolloutMaxBlock16 : kLgRolloutMaxBlock; }
-
-// raw (still packed) action bytes of a lane's two slots: byte 0 = agent 2g, byte 1 = agent 2g+1.  Kept packed so
-// that a prefetch issued one step ahead is not forced to complete by an unpack.
-template <bool EVEN>
-__device__ __forceinline__ uint32_t load_actions_raw(const uint8_t *base, uint32_t row, uint32_t n_agents, uint32_t g,
-                                                     bool v0, bool v1) {
-    const uint8_t *p = at(base, row * n_agents + 2u * g);
-    uint32_t raw = 0u;
-    if (EVEN || (n_agents & 1u) == 0u) {
-        if (v0) raw = *reinterpret_cast<const uint16_t *>(p);
-    } else {
-        uint32_t lo = 0u, hi = 0u;
-        if (v0) lo = p[0];
-        if (v1) hi = p[1];
-        raw = lo | (hi << 8);
-    }
-    return raw;
-}
-
 // MV_LDS: the whole move table (V*6 entries of 16 B) is staged into LDS once per block and the two gathers of
 // every step become ds_read_b128 (a random 64-lane gather through the vector-memory pipe touches up to 64 cache
 // lines).  RECORD: all five trajectory arrays are written every step (the C ABI substitutes scratch for absent
@@ -86,8 +65,10 @@ static hipError_t launch_planned(const LgRolloutPlan &plan, const RolloutArgs &a
     }
 }
 
-hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table) {
+hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table,
+                             const EpisodeLimit *limit) {
     if (args.n_envs == 0) return hipSuccess;
+    if (limit) return launch_rollout_lg_limit(n_agents, args, tune, stream, table, *limit);   // (before any packed plan is consulted)
     hipError_t packed_status;
     if (try_launch_rollout_lq(n_agents, args, tune, stream, &packed_status, table)) return packed_status;
     const LgRolloutPlan plan = plan_rollout_lg(n_agents, args, tune);

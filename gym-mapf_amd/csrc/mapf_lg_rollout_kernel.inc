@@ -5,7 +5,20 @@
 //     greedy policy's goal coordinates do.
 // Textual inclusion, not a shared function template: the first kernel's token stream is what it was before the table policy
 // existed, so its instances compile to the same code.
-#if MAPF_ROLLOUT_TABLE_KERNEL
+// mapf_lg_limit.hip includes it twice more with MAPF_ROLLOUT_LIMIT 1 (the episode step limit, include/mapf_hip.h
+// mapf_set_episode_limit): lg_rollout_kernel_limit_guarded and lg_rollout_kernel_table_limit_guarded carry the env's age in a
+// register beside `terminal`, count truncations like episodes, store the truncated byte with the delayed flag bytes and go
+// back to the start cells on done OR truncated.  They have no DENSE form (the name says so): always the guarded one.
+#if MAPF_ROLLOUT_LIMIT && MAPF_ROLLOUT_TABLE_KERNEL
+template <int L, bool FULL, bool MV_LDS, bool RECORD, bool TABLE = true>
+__global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel_table_limit_guarded(const RolloutArgs p, const uint32_t n_agents, const TablePolicy tp,
+                                                                                                const EpisodeLimit lim) {
+    constexpr bool STREAM = false, DENSE = false;
+#elif MAPF_ROLLOUT_LIMIT
+template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM>
+__global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel_limit_guarded(const RolloutArgs p, const uint32_t n_agents, const EpisodeLimit lim) {
+    constexpr bool DENSE = false;
+#elif MAPF_ROLLOUT_TABLE_KERNEL
 template <int L, bool FULL, bool MV_LDS, bool RECORD, bool DENSE, bool TABLE = true>
 __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel_table(const RolloutArgs p, const uint32_t n_agents, const TablePolicy tp) {
     constexpr bool STREAM = false;   // (a table instance runs the launches without streamed actions)
@@ -70,6 +83,17 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
     double ret = (p.accumulate && ret_p && leader) ? *ret_p : 0.0;
     uint32_t episodes = (p.accumulate && epi_p && leader) ? *epi_p : 0u;
     uint32_t collisions = (p.accumulate && col_p && leader) ? *col_p : 0u;
+#if MAPF_ROLLOUT_LIMIT
+    // the env's age: read once by every lane of the group (one address per group: each lane decides `back` itself), written
+    // back once by the leader; lanes past the last env read env 0's and write nothing
+    gu32 age_p = (gu32)at(lim.age, e);
+    gu32 trn_p = (gu32)(lim.out_truncations ? at(lim.out_truncations, e) : nullptr);
+    gu8 trunc_lane = (gu8)(RECORD ? lim.rec_truncated : nullptr) + e;      // the delayed step's row
+    asm volatile("" : "+v"(age_p), "+v"(trn_p), "+v"(trunc_lane));
+    uint32_t age = *age_p;
+    uint32_t truncations = (p.accumulate && trn_p && leader) ? *trn_p : 0u;
+    const uint32_t max_steps = lim.max_steps;
+#endif
     const uint64_t env_id = p.env_id_offset + e;
     const uint32_t n_envs = uint32_t(p.n_envs);
 
@@ -128,6 +152,9 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
                 *reward_lane = d_reward;
                 *done_lane = uint8_t(d_flags & 1u);
                 *coll_lane = uint8_t(d_flags >> 8);
+#if MAPF_ROLLOUT_LIMIT
+                *trunc_lane = uint8_t(d_flags >> 24);          // byte 3 truncated
+#endif
             }
         }
     };
@@ -136,6 +163,9 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
         reward_lane += step_rows;
         done_lane += step_rows;
         if (!(DENSE && L > 1)) { prob_lane += step_rows; coll_lane += step_rows; }
+#if MAPF_ROLLOUT_LIMIT
+        trunc_lane += step_rows;
+#endif
     };
     const uint8_t *act_lane = STREAM ? p.actions + lane_cell : nullptr;   // the row being prefetched
 
@@ -200,7 +230,18 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
             d_next0 = next0; d_next1 = next1; d_reward = o.reward; d_prob = o.prob;
             d_flags = o.status;                            // byte 0 done, byte 1 collision
         }
+#if MAPF_ROLLOUT_LIMIT
+        // a live step ages the episode (saturating); it is truncated when it did not end the episode and the age has reached
+        // the limit.  A step from a terminal state (a no-op) leaves the age alone and is never truncated.
+        const uint32_t aged = terminal != 0u ? age : (age + (age != 0xFFFFFFFFu ? 1u : 0u));
+        const uint32_t truncated = (terminal == 0u && (o.status & 0xFFu) == 0u && aged >= max_steps) ? 1u : 0u;
+        truncations += truncated;
+        if (RECORD) d_flags |= truncated << 24;
+        const bool back = p.auto_reset && ((o.status & 0xFFu) != 0u || truncated != 0u);   // done or truncated: start cells, age 0
+        age = back ? 0u : aged;
+#else
         const bool back = p.auto_reset && (o.status & 0xFFu) != 0u;   // MapfEnv.reset(): start cells, no reseed
+#endif
         cur0 = back ? start0 : next0;
         cur1 = back ? start1 : next1;
         terminal = back ? start_terminal : (o.status >> 16);
@@ -219,6 +260,10 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
         if (ret_p) *ret_p = ret;
         if (epi_p) *epi_p = episodes;
         if (col_p) *col_p = collisions;
+#if MAPF_ROLLOUT_LIMIT
+        *age_p = age;
+        if (trn_p) *trn_p = truncations;
+#endif
     }
 }
 

@@ -312,6 +312,12 @@ LgRolloutPlan plan_rollout_lg(int n_agents, const RolloutArgs &args, const Rollo
     return plan;
 }
 
+LgRolloutPlan plan_rollout_lg_limit(int n_agents, const RolloutArgs &args, const RolloutTuning &tune) {
+    LgRolloutPlan plan = plan_rollout_lg(n_agents, args, tune);
+    plan.dense = false;
+    return plan;
+}
+
 LgStepPlan plan_step_lg(int n_agents, const StepArgs &args) {
     LgStepPlan plan;
     plan.L = lg_group_size(n_agents);
@@ -325,6 +331,17 @@ void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, 
              plan.full ? "FULL" : "RAGGED", plan.mv_lds ? "MV_LDS" : "MV_GLOBAL", record ? "RECORD" : "TOTALS",
              table_policy ? "TABLE" : (streamed ? "STREAM" : "POLICY"), plan.dense ? "DENSE" : "GUARDED", plan.block,
              table_policy ? "; table policy: action bytes gathered from global memory" : "");
+}
+
+void lg_rollout_limit_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy) {
+    snprintf(name, kKernelNameBytes, "lg_rollout_kernel%s_limit_guarded<L=%d,%s,%s,%s,%s,LIMIT> block=%u (pair layout: 2 agents per lane; episode step limit%s)",
+             table_policy ? "_table" : "", plan.L, plan.full ? "FULL" : "RAGGED", plan.mv_lds ? "MV_LDS" : "MV_GLOBAL", record ? "RECORD" : "TOTALS",
+             table_policy ? "TABLE" : (streamed ? "STREAM" : "POLICY"), plan.block, table_policy ? "; table policy: action bytes gathered from global memory" : "");
+}
+
+void lg_step_limit_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms) {
+    snprintf(name, kKernelNameBytes, "lg_step_kernel_limit<L=%d,%s,%s,LIMIT> block=%u (pair layout: 2 agents per lane; episode step limit)", plan.L,
+             plan.full ? "FULL" : "RAGGED", ext_uniforms ? "EXT_UNIFORMS" : "PHILOX", plan.block);
 }
 
 void lg_step_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms) {

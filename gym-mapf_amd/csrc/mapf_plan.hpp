@@ -63,10 +63,17 @@ struct LgRolloutPlan {
     size_t lds_bytes = 0;            // dynamic LDS segment: the move table, or 0 (the launcher raises the limit beyond 32 KB)
 };
 LgRolloutPlan plan_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune);
+// ... under an episode step limit (EpisodeLimit, mapf_kernels.hpp): the limit instances exist in the lane-group family only, so no
+// packed plan and no thread-per-env kernel is consulted and this plan takes the launch -- plan_rollout_lg's, never dense (the
+// limit instances have the guarded form only)
+LgRolloutPlan plan_rollout_lg_limit(int n_agents, const RolloutArgs &args, const RolloutTuning &tune);
 struct LgStepPlan { int L = 0; bool full = false; unsigned block = 0, grid = 0; };
 LgStepPlan plan_step_lg(int n_agents, const StepArgs &args);
 // The names the launchers note for these plans (mapf_last_kernel; at most kKernelNameBytes with the terminator)
 void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy);
 void lg_step_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms);
+// ... and for the limit instances (mapf_lg_limit.hip): the same fields, and LIMIT
+void lg_rollout_limit_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy);
+void lg_step_limit_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms);
 
 }  // namespace mapf

@@ -9,7 +9,7 @@ from ctypes import POINTER, Structure, byref, c_char_p, c_double, c_int, c_int32
 
 LIB_PATH = os.environ.get('MAPF_HIP_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib', 'libmapf_hip.so')
 
-MAPF_ABI_VERSION = 5            # include/mapf_hip.h: the version this binding was written against (checked at load)
+MAPF_ABI_VERSION = 6            # include/mapf_hip.h: the version this binding was written against (checked at load)
 MAPF_OK, MAPF_EINVAL, MAPF_EHIP, MAPF_ENODEVICE, MAPF_EUNSUPPORTED = 0, -1, -2, -3, -4
 MAPF_MAX_AGENTS = 128
 MAPF_MAKESPAN, MAPF_SOC = 0, 1
@@ -49,7 +49,11 @@ SIGNATURES = {
     'mapf_destroy': (c_int, [c_void_p]),
     'mapf_reset': (c_int, [c_void_p, c_void_p]),
     'mapf_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
+    'mapf_step_limited': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
     'mapf_rollout': (c_int, [c_void_p, POINTER(MapfRolloutIO)]),
+    'mapf_rollout_limited': (c_int, [c_void_p, POINTER(MapfRolloutIO), c_void_p, c_void_p]),
+    'mapf_set_episode_limit': (c_int, [c_void_p, c_uint32]),
+    'mapf_episode_steps': (c_int, [c_void_p, c_void_p, c_void_p]),
     'mapf_fill_random_actions': (c_int, [c_void_p, c_void_p, c_uint64, c_uint32]),
     'mapf_set_policy': (c_int, [c_void_p, c_int, c_void_p]),
     'mapf_set_policy_table': (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
@@ -80,6 +84,7 @@ SIGNATURES = {
     'mapf_version': (c_char_p, []),
     'mapf_abi_version': (c_int, []),
     'mapf_debug_rollout_plan': (c_int, [c_uint32, c_int, c_uint64, c_uint32, c_int, c_int, c_int, c_char_p, POINTER(c_uint64)]),
+    'mapf_debug_rollout_plan_limited': (c_int, [c_uint32, c_int, c_uint64, c_uint32, c_int, c_int, c_int, c_char_p, c_uint32, POINTER(c_uint64)]),
 }
 
 _lib = None

@@ -35,9 +35,13 @@ _CRITERIA_CODE = {OptimizationCriteria.Makespan: nat.MAPF_MAKESPAN, Optimization
 STEP_OUTPUTS = (('local', np.uint16, True), ('reward', np.float64, False), ('done', np.uint8, False),
                 ('collision', np.uint8, False), ('prob', np.float64, False), ('was_terminal', np.uint8, False))
 ROLLOUT_TOTALS = (('returns', np.float64), ('episodes', np.uint32), ('collisions', np.uint32))
+# ... and what an env with an episode limit (set_episode_limit) reports on top: mapf_step_limited's out_truncated, a recording
+# rollout's rec_truncated, the rollout's out_truncations
+STEP_TRUNCATED = ('truncated', np.uint8, False)
+ROLLOUT_TRUNCATIONS = ('truncations', np.uint32)
 _TORCH_DTYPE = {np.uint8: 'uint8', np.uint16: 'uint16', np.uint32: 'uint32', np.uint64: 'uint64', np.float64: 'float64'}
 # rollout(out=...): the argument block of the last such call, with what it was made from
-_RolloutIO = collections.namedtuple('_RolloutIO', 'out call arrays actions io')
+_RolloutIO = collections.namedtuple('_RolloutIO', 'out call arrays actions io call_args')
 
 
 def checked_ptr(torch, arr, dtype, shape, name):
@@ -172,6 +176,7 @@ class VecMapfEnv:
         self._h = handle
         self.policy = 'random'         # on-device policy of rollout(actions=None): see set_policy
         self._rollout_io = None        # rollout(out=...): the _RolloutIO of the last such call
+        self.episode_limit = 0         # set_episode_limit: steps per episode, 0 = no limit
 
     # ------------------------------------------------------------------ construction
     def _as_local(self, locations, local_ids, what):
@@ -243,18 +248,26 @@ class VecMapfEnv:
         device Philox stream.  Returns ``(local, reward, done, info)`` with ``local`` uint16
         [E, A], ``reward`` float64 [E], ``done`` uint8 [E] and ``info`` holding ``prob``,
         ``collision`` and ``was_terminal`` arrays.  ``out`` may carry preallocated arrays under
-        those names (plus ``local``, ``reward``, ``done``).
+        those names (plus ``local``, ``reward``, ``done``).  With an episode limit (``set_episode_limit``) ``info`` also
+        holds ``truncated`` uint8 [E].
         """
         args, (_, _, out) = self._step_args(actions, uniforms, auto_reset, out)
-        nat.check(self._lib.mapf_step(*args))
+        nat.check(self._step_fn()(*args))
         info = {'prob': out['prob'], 'collision': out['collision'], 'was_terminal': out['was_terminal']}
+        if self.episode_limit:
+            info['truncated'] = out['truncated']
         return out['local'], out['reward'], out['done'], info
+
+    def _step_fn(self):
+        """``mapf_step``, or ``mapf_step_limited`` (one more output, ``truncated``) for an env with an episode limit."""
+        return self._lib.mapf_step_limited if self.episode_limit else self._lib.mapf_step
 
     def _step_args(self, actions, uniforms, auto_reset, out, write_local=True):
         """The argument tuple of one ``mapf_step`` and what it points into: (actions, uniforms, out), ``out`` completed."""
         E, A = self.n_envs, self.n_agents
         keep, inputs = self._inputs(('actions', np.uint8, (E, A), actions), ('uniforms', np.float64, (E, A), uniforms))
-        out, outputs = self._outputs([(name, dt, (E, A) if per_agent else (E,)) for name, dt, per_agent in STEP_OUTPUTS],
+        spec = STEP_OUTPUTS + ((STEP_TRUNCATED,) if self.episode_limit else ())
+        out, outputs = self._outputs([(name, dt, (E, A) if per_agent else (E,)) for name, dt, per_agent in spec],
                                      dict(out) if out else {}, skip=() if write_local else ('local',), fill=True)
         return (self._h, *inputs, *outputs, nat.MAPF_STEP_AUTO_RESET if auto_reset else 0), (*keep, out)
 
@@ -265,7 +278,7 @@ class VecMapfEnv:
         ``write_local=False`` leaves ``out_local`` out of the call: the next observation is then read from
         ``state_view()`` (the handle's own state buffer, after auto-reset) and the step writes the cells once."""
         args, keep = self._step_args(actions, uniforms, auto_reset, out, write_local)
-        fn, check, out = self._lib.mapf_step, nat.check, keep[2]
+        fn, check, out = self._step_fn(), nat.check, keep[2]
 
         def call():
             rc = fn(*args)
@@ -317,7 +330,9 @@ class VecMapfEnv:
         launches over consecutive slices of the same arrays (totals accumulate, the trajectory is identical).
         ``out``: the dict an earlier call of the same shape returned -- its arrays are written again instead of allocating
         eight new ones per call (totals overwritten, unlike ``accumulate_into``); a training loop that calls
-        ``rollout(T=16..64)`` thousands of times wants this (profiles/r05_rollout_T_sweep.txt)."""
+        ``rollout(T=16..64)`` thousands of times wants this (profiles/r05_rollout_T_sweep.txt).
+        With an episode limit (``set_episode_limit``) the dict also has ``truncations`` u32 [E] and, when ``record``,
+        ``truncated`` u8 [T, E]; ``out`` and ``accumulate_into`` cover them."""
         E, A, T = self.n_envs, self.n_agents, int(n_steps)
         if out is not None and accumulate_into is None:
             # the repeat call of a training loop: the same dict of arrays, the same shape.  The argument block of the earlier call
@@ -336,14 +351,18 @@ class VecMapfEnv:
                 else:
                     same = False
                 if same:
-                    nat.check(self._lib.mapf_rollout(self._h, ctypes.byref(cached.io)))
+                    nat.check(cached.call_args[0](*cached.call_args[1:]))
                     return out
         actions = self._coerce(actions, np.uint8, (T, E, A), 'actions')
         if out is not None and accumulate_into is not None:
             raise ValueError('pass either out= (overwrite) or accumulate_into= (add), not both')
         res = accumulate_into if accumulate_into is not None else (out if out is not None else {})
-        trajectory = STEP_OUTPUTS[:5] if record else ()
-        res, totals = self._outputs([(name, dt, (E,)) for name, dt in ROLLOUT_TOTALS], res, fill=True)
+        limited = bool(self.episode_limit)
+        trajectory = (STEP_OUTPUTS[:5] + ((STEP_TRUNCATED,) if limited else ())) if record else ()
+        total_spec = ROLLOUT_TOTALS + ((ROLLOUT_TRUNCATIONS,) if limited else ())
+        if limited and accumulate_into is not None and 'truncations' not in res:   # (totals of a call without the limit: count from 0)
+            res['truncations'] = self._torch.zeros((E,), dtype=self._torch.uint32, device=self._tdev) if self.device_arrays else np.zeros((E,), np.uint32)
+        res, totals = self._outputs([(name, dt, (E,)) for name, dt in total_spec], res, fill=True)
         for name, dt, per_agent in trajectory:
             shape = (T, E, A) if per_agent else (T, E)
             if out is None or name not in res or tuple(res[name].shape) != shape:
@@ -357,20 +376,23 @@ class VecMapfEnv:
             n = min(T - first, t_max) if T else 0
             sl = slice(first, first + n)
             fields = {'actions': self._ptr(actions[sl] if actions is not None else None, np.uint8, (n, E, A), 'actions')}
-            fields.update(zip(('out_' + name for name, _ in ROLLOUT_TOTALS), totals))
+            fields.update(zip(('out_' + name for name, _ in total_spec), totals))
             for name, dt, per_agent in trajectory:
                 fields['rec_' + name] = self._ptr(res[name][sl], dt, (n, E, A) if per_agent else (n, E), name)
+            # (the truncation outputs are mapf_rollout_limited's two arguments behind the block, which stays mapf_rollout's)
+            beside = (fields.pop('out_truncations'), fields.pop('rec_truncated', None)) if limited else ()
             io = nat.MapfRolloutIO(struct_size=ctypes.sizeof(nat.MapfRolloutIO), n_steps=n, step_flags=nat.MAPF_STEP_AUTO_RESET if auto_reset else 0,
                                    accumulate=1 if accumulate else 0, **fields)
-            nat.check(self._lib.mapf_rollout(self._h, ctypes.byref(io)))
+            call_args = (self._lib.mapf_rollout_limited if limited else self._lib.mapf_rollout, self._h, ctypes.byref(io)) + beside
+            nat.check(call_args[0](*call_args[1:]))
             first += n
             if first >= T:
                 if out is not None and accumulate_into is None and n == T and self.device_arrays:
                     # (one launch covered the call: its argument block serves the next call with the same arrays; the arrays are
                     # referenced here, so their memory cannot be handed to anyone else while the block is kept)
-                    keys = [name for name, _ in ROLLOUT_TOTALS] + [name for name, _, _ in trajectory]
+                    keys = [name for name, _ in total_spec] + [name for name, _, _ in trajectory]
                     self._rollout_io = _RolloutIO(out, (T, bool(auto_reset), bool(record)), tuple((k, res[k]) for k in keys),
-                                                  None if actions is None else (actions.data_ptr(), tuple(actions.shape), actions), io)
+                                                  None if actions is None else (actions.data_ptr(), tuple(actions.shape), actions), io, call_args)
                 return res
             accumulate = True
 
@@ -472,6 +494,31 @@ class VecMapfEnv:
             raise ValueError("policy must be 'random', 'greedy' or 'table'")
         self._rollout_io = None            # (a cached argument block must not outlive a policy change)
         self.policy = policy
+
+    def set_episode_limit(self, n):
+        """Episode step limit: an episode that has taken ``n`` steps without ending is TRUNCATED -- with ``auto_reset`` the env goes
+        back to its start cells as after ``done``, without it the env lives on and reports ``truncated`` on every later step.
+        ``None`` or 0 switches the limit off (the default).  Truncation changes no reward, no ``done`` and no random number; every
+        call zeroes the per-env step counts (``episode_steps``).  With a limit ``rollout`` also returns ``truncations`` (and
+        ``truncated`` when recording), ``step``'s ``info`` gains ``truncated``, and the launches run the lane-group kernels' limit
+        instances (``last_kernel`` says LIMIT).  The reference has no limit: this is the caller-side ``TimeLimit`` / "n episodes of
+        at most max_steps" loop around ``MapfEnv.step`` (mapf_env.py:237-266), done inside the launch."""
+        n = 0 if n is None else n
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= 0xFFFFFFFF:
+            raise ValueError('the episode limit must be None or an integer 0 .. 2**32 - 1, got %r' % (n,))
+        nat.check(self._lib.mapf_set_episode_limit(self._h, int(n)))
+        self._rollout_io = None            # (a cached argument block names the arrays of the other mode)
+        self.episode_limit = int(n)
+
+    def episode_steps(self, out=None, set=None):
+        """The steps every env's current episode has taken since it began, uint32 [E] (all zero without a limit); ``set`` uint32 [E]
+        replaces them afterwards (needs a limit).  Host arrays, or CUDA tensors in device mode (then only enqueued)."""
+        shape = (self.n_envs,)
+        set = self._coerce(set, np.uint32, shape, 'set')
+        if out is None:
+            out = self._empty(shape, np.uint32)
+        nat.check(self._lib.mapf_episode_steps(self._h, self._ptr(out, np.uint32, shape, 'out'), self._ptr(set, np.uint32, shape, 'set')))
+        return out
 
     @staticmethod
     def _host_ints(a, name):

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MAPF_ABI_VERSION 5
+#define MAPF_ABI_VERSION 6
 
 /* status codes */
 #define MAPF_OK            0
@@ -171,6 +171,46 @@ typedef struct mapf_rollout_io {
     double   *rec_prob;
 } mapf_rollout_io;
 int mapf_rollout(mapf_handle_t h, const mapf_rollout_io *io);
+
+/*
+ * Episode step limit (ABI 6): "n episodes of at most max_steps steps" inside the fused rollout and the single step -- what a
+ * planner's evaluation loop or gym's TimeLimit wrapper does around MapfEnv.step (mapf_env.py:237-266) on the host; the
+ * reference itself has no limit.  THE DEFINITION.  A handle has a limit N (u32; 0 = none, the default) and a per-env age a
+ * (u32[E], device memory, all zero at mapf_create).  For every env and every step taken while N > 0:
+ *   1. the env is terminal on entry (the no-op of mapf_env.py:239-240): outputs as without a limit, truncated = 0, a unchanged;
+ *   2. otherwise a' = a + 1, saturating at 2^32 - 1; transition, reward, prob, done and collision are exactly those without a
+ *      limit; truncated = !done && a' >= N;
+ *   3. with MAPF_STEP_AUTO_RESET and done || truncated: the state becomes the start cells (as the reset on done) and a' = 0;
+ *   4. without auto-reset the state is the next state and a' is kept: a truncated env goes on living and reports
+ *      truncated = 1 on every later live step until someone resets it.
+ * Truncation changes no reward, no done, no collision, no returns / episodes / collisions total and no Philox counter (the
+ * streams are keyed by (env, step index, agent), not by episode).  The ages go back to zero: for the envs a mapf_reset(mask)
+ * resets; for all envs in mapf_set_state with cells (with only t they stay) and in EVERY mapf_set_episode_limit call.
+ * With N == 0 every launch, kernel instance and output is what it is without this feature.
+ *
+ * mapf_set_episode_limit: refused (MAPF_EINVAL) while recording and while recorded graphs live, as mapf_set_policy_table is;
+ *   a handle with a limit refuses mapf_graph_begin with MAPF_EUNSUPPORTED.
+ * mapf_episode_steps: out_age u32[E] receives the ages, then set_age u32[E] replaces them (either may be NULL, not both; set_age
+ *   needs a limit); HOST pointers, or DEVICE pointers on a MAPF_FLAG_DEVICE_PTRS handle (then only enqueued).
+ * mapf_rollout keeps its argument block (mapf_rollout_io stays as it is, its struct_size check an equality): on a handle with a
+ *   limit it applies the limit and reports no truncation.  mapf_rollout_limited is mapf_rollout plus out_truncations u32[E]
+ *   (counts the truncated steps per env; io->accumulate applies to it) and rec_truncated u8[T*E] (the flag per step, step-major,
+ *   recorded like rec_done); either may be NULL, non-NULL on a handle without a limit is MAPF_EINVAL.
+ * mapf_step keeps its signature: on a handle with a limit it applies the limit and reports no flag; mapf_step_limited is
+ *   mapf_step plus out_truncated u8[E] (NULL allowed; non-NULL on a handle without a limit: MAPF_EINVAL).
+ * Everything is validated on the host before any device work.  Limit launches run the lane-group kernels' limit instances
+ * whatever the handle's family flag, and mapf_last_kernel says LIMIT.
+ * Out of scope: limit forms of the packed (lq_*) rollout and step kernels and of the thread-per-env family (a handle with a
+ * limit gives up their speed: README has the numbers), recorded graphs, the multi-map / union-map wrappers and the scalar
+ * MapfEnv of the Python package, a "time-out reward".
+ */
+int mapf_set_episode_limit(mapf_handle_t h, uint32_t max_steps);
+int mapf_episode_steps(mapf_handle_t h, uint32_t *out_age, const uint32_t *set_age);
+int mapf_rollout_limited(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_truncations, uint8_t *rec_truncated);
+int mapf_step_limited(mapf_handle_t h, const uint8_t *actions, const double *uniforms,
+                      uint16_t *out_local, double *out_reward, uint8_t *out_done,
+                      uint8_t *out_collision, double *out_prob, uint8_t *out_was_terminal,
+                      uint8_t *out_truncated, uint32_t step_flags);
 
 /* Synthetic policy used by bench/rollout: fills actions u8[n_steps*E*A] for step indices
  * t0 .. t0+n_steps-1 from the policy stream (oracle/philox.py random_actions_np; ABI 5: key seed + 1, ONE Philox
@@ -356,6 +396,11 @@ int mapf_abi_version(void);
  * MAPF_EINVAL (< 0) for a malformed tune string or null out. */
 int mapf_debug_rollout_plan(uint32_t n_cells, int n_agents, uint64_t n_envs, uint32_t n_steps, int streamed, int delta_rows,
                             int n_cu, const char *tune, uint64_t out[6]);
+/* The same question for a handle with an episode limit of max_steps (0: exactly the call above).  With a limit no packed form
+ * is consulted: returns 0 and out[0..5] = {agents per lane (2), lanes per env L, move table in LDS (0 | 1), threads per block,
+ * LDS bytes of the launch, blocks} of the lane-group limit instance that takes the launch. */
+int mapf_debug_rollout_plan_limited(uint32_t n_cells, int n_agents, uint64_t n_envs, uint32_t n_steps, int streamed, int delta_rows,
+                                    int n_cu, const char *tune, uint32_t max_steps, uint64_t out[6]);
 
 #ifdef __cplusplus
 }
