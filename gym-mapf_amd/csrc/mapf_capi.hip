@@ -325,20 +325,12 @@ int launch_step_and_advance(mapf_handle_t h, const mapf::StepArgs &a, const mapf
     after_launch(h, h->last_step_kernel, 1, a.auto_reset);
     return MAPF_OK;
 }
-}  // namespace
-
-extern "C" {
-
-const char *mapf_last_error(void) { return g_last_error.c_str(); }
-
-const char *mapf_version(void) { return "mapf_hip 0.6.0 (abi 6, gfx950)"; }
-
-int mapf_abi_version(void) { return MAPF_ABI_VERSION; }
-
-int mapf_debug_rollout_plan(uint32_t n_cells, int n_agents, uint64_t n_envs, uint32_t n_steps, int streamed, int delta_rows,
-                            int n_cu, const char *tune, uint64_t out[6]) {
+// The two mapf_debug_rollout_plan* entries (`who`: the one the shape message names): the null / shape checks, the tuning parse, and
+// the plan a launch of that shape takes -- under an episode limit (max_steps != 0) the lane-group limit plan, else the packed one
+int debug_rollout_plan(const char *who, uint32_t n_cells, int n_agents, uint64_t n_envs, uint32_t n_steps, int streamed, int delta_rows, int n_cu,
+                       const char *tune, uint32_t max_steps, uint64_t out[6]) {
     if (!out) return fail(MAPF_EINVAL, "out is null");
-    if (n_agents < 1 || n_cells < 2 || n_cu < 1) return fail(MAPF_EINVAL, "mapf_debug_rollout_plan: n_agents >= 1, n_cells >= 2, n_cu >= 1");
+    if (n_agents < 1 || n_cells < 2 || n_cu < 1) return fail(MAPF_EINVAL, std::string(who) + ": n_agents >= 1, n_cells >= 2, n_cu >= 1");
     std::string tune_error;
     const mapf::RolloutTuning t = mapf::rollout_tuning_for(n_cu, tune, &tune_error);
     if (!tune_error.empty()) return fail(MAPF_EINVAL, tune_error);
@@ -351,29 +343,37 @@ int mapf_debug_rollout_plan(uint32_t n_cells, int n_agents, uint64_t n_envs, uin
     args.actions = streamed ? &present : nullptr;
     args.mv_delta8 = delta_rows != 0;
     args.mv4 = delta_rows ? reinterpret_cast<const uint32_t *>(&present) : nullptr;
+    if (max_steps != 0u) {   // (the lane-group plan reads the shape only)
+        const mapf::LgRolloutPlan plan = mapf::plan_rollout_lg(n_agents, args, t, true);
+        out[0] = 2; out[1] = uint64_t(plan.L); out[2] = plan.mv_lds ? 1 : 0;
+        out[3] = plan.block; out[4] = plan.lds_bytes; out[5] = plan.grid;
+        return 0;
+    }
     mapf::LqPlan plan;
     const bool packed = mapf::plan_rollout_lq(n_agents, args, t, &plan);
     out[0] = uint64_t(plan.K); out[1] = uint64_t(plan.Q); out[2] = uint64_t(int(plan.form));
     out[3] = plan.block; out[4] = plan.lds_bytes; out[5] = plan.lds_total;
     return packed ? 1 : 0;
 }
+}  // namespace
+
+extern "C" {
+
+const char *mapf_last_error(void) { return g_last_error.c_str(); }
+
+const char *mapf_version(void) { return "mapf_hip 0.6.0 (abi 6, gfx950)"; }
+
+int mapf_abi_version(void) { return MAPF_ABI_VERSION; }
+
+int mapf_debug_rollout_plan(uint32_t n_cells, int n_agents, uint64_t n_envs, uint32_t n_steps, int streamed, int delta_rows,
+                            int n_cu, const char *tune, uint64_t out[6]) {
+    return debug_rollout_plan("mapf_debug_rollout_plan", n_cells, n_agents, n_envs, n_steps, streamed, delta_rows, n_cu, tune, 0u, out);
+}
 
 int mapf_debug_rollout_plan_limited(uint32_t n_cells, int n_agents, uint64_t n_envs, uint32_t n_steps, int streamed, int delta_rows,
                                     int n_cu, const char *tune, uint32_t max_steps, uint64_t out[6]) {
-    if (max_steps == 0u) return mapf_debug_rollout_plan(n_cells, n_agents, n_envs, n_steps, streamed, delta_rows, n_cu, tune, out);
-    if (!out) return fail(MAPF_EINVAL, "out is null");
-    if (n_agents < 1 || n_cells < 2 || n_cu < 1) return fail(MAPF_EINVAL, "mapf_debug_rollout_plan_limited: n_agents >= 1, n_cells >= 2, n_cu >= 1");
-    std::string tune_error;
-    const mapf::RolloutTuning t = mapf::rollout_tuning_for(n_cu, tune, &tune_error);
-    if (!tune_error.empty()) return fail(MAPF_EINVAL, tune_error);
-    mapf::RolloutArgs args{};   // (the lane-group plan reads the shape only)
-    args.c.n_cells = n_cells;
-    args.n_envs = n_envs;
-    args.n_steps = n_steps;
-    const mapf::LgRolloutPlan plan = mapf::plan_rollout_lg_limit(n_agents, args, t);
-    out[0] = 2; out[1] = uint64_t(plan.L); out[2] = plan.mv_lds ? 1 : 0;
-    out[3] = plan.block; out[4] = plan.lds_bytes; out[5] = plan.grid;
-    return 0;
+    return debug_rollout_plan(max_steps ? "mapf_debug_rollout_plan_limited" : "mapf_debug_rollout_plan", n_cells, n_agents, n_envs, n_steps, streamed, delta_rows,
+                              n_cu, tune, max_steps, out);
 }
 
 int mapf_device_count(int *out_count) {

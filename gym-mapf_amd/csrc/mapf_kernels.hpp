@@ -266,7 +266,8 @@ hipError_t launch_step_lg(int n_agents, const StepArgs &args, const RolloutTunin
 bool try_launch_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err);
 hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table = nullptr,
                              const EpisodeLimit *limit = nullptr);
-// the limit instances (mapf_lg_limit.hip): the lane-group kernels with a per-env age, and the masked zeroing of the ages
+// the limit instances (mapf_lg_limit.hip): the lane-group kernels with a per-env age, and the masked zeroing of the ages.  These
+// two and the two above check their launch, plan it and hand the plan to the family's one launcher (mapf_lg_launch.hpp)
 hipError_t launch_rollout_lg_limit(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table,
                                    const EpisodeLimit &limit);
 hipError_t launch_step_lg_limit(int n_agents, const StepArgs &args, hipStream_t stream, const EpisodeLimit &limit);

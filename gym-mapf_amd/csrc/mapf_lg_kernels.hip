@@ -1,59 +1,18 @@
-// Lane-group family: single-step kernel, run-time-A helper kernels and their launchers (device code: mapf_lg.hpp).
-#include "mapf_lg.hpp"
-#include "mapf_plan.hpp"
+// Lane-group family: single-step kernel, run-time-A helper kernels and their launchers (device code: mapf_lg.hpp; the step's
+// launcher proper: mapf_lg_launch.hpp).
+#include "mapf_lg_launch.hpp"
 
 namespace mapf {
 
-template <int L, bool FULL, bool EXT_UNIFORMS>
-__global__ void __launch_bounds__(256) lg_step_kernel(const StepArgs p, const uint32_t n_agents) {
-    bool live;
-    const LaneCtx<L> x = lane_ctx<L>(n_agents, p.n_envs, live);
-    const uint32_t e = x.e;
+// lg_step_kernel: the body of the single-step kernels without its limit sections
+#define MAPF_STEP_LIMIT 0
+#include "mapf_lg_step_kernel.inc"
+#undef MAPF_STEP_LIMIT
 
-    uint32_t cur0, cur1, goal0, goal1, act0, act1;
-    load_pair<uint16_t>(p.state, e, n_agents, x.g, x.v0, x.v1, cur0, cur1);
-    load_pair<uint16_t>(p.goal, p.goal_broadcast ? 0 : e, n_agents, x.g, x.v0, x.v1, goal0, goal1);
-    load_pair<uint8_t>(p.actions, e, n_agents, x.g, x.v0, x.v1, act0, act1);
-    double u0 = 0.0, u1 = 0.0;
-    if (EXT_UNIFORMS) {
-        const double *up = at(p.uniforms, e * n_agents + 2u * x.g);
-        if (x.v0) u0 = up[0];
-        if (x.v1) u1 = up[1];
-    }
-    // A single step is launch-latency bound: the sampled probability is rebuilt from its members (no third dependent
-    // memory round trip); the 8 slip rows are only read on the exact-tie path and for caller-supplied uniforms,
-    // straight from global memory (they stay in L1/L2) rather than staged into LDS behind a barrier.
-    const SlipRow *rows = p.slip;
-
-    uint32_t next0, next1;
-    EnvOut o;
-#ifdef MAPF_STAMPS
-    StampCtx st{};
-#endif
-    uint32_t word = 0u;   // this step's slip word of my pair: the call of my quad (g >> 1), word 2 * (t & 1) + (g & 1)
-    const uint64_t t = first_step_index(p);
-    if (!EXT_UNIFORMS && p.c.need_rng) word = quad_step_word(slip_words(p.c, p.env_id_offset + e, t >> 1, x.g >> 1, 0u, 0u), t, x.g & 1u);
-    lg_transition<L, FULL, EXT_UNIFORMS, false, false, false, !EXT_UNIFORMS>(p.c, p.mv, rows, nullptr, x, n_agents, cur0, cur1, goal0, goal1, act0, act1,
-                                                u0, u1, p.env_id_offset + e, t, word, false, next0, next1, o STAMP_ARG);
-    if (!live) return;
-
-    if (p.out_local) store_cells(p.out_local, e, n_agents, x.g, x.v0, x.v1, next0, next1);
-    if (x.g == uint32_t(L - 1) && p.out_prob) *at(p.out_prob, e) = o.prob;   // the product chain ends in the last lane
-    if (x.g == 0u) {
-        if (p.out_reward) *at(p.out_reward, e) = o.reward;
-        if (p.out_done) *at(p.out_done, e) = o.done() ? 1 : 0;
-        if (p.out_collision) *at(p.out_collision, e) = o.collision() ? 1 : 0;
-        if (p.out_was_terminal) *at(p.out_was_terminal, e) = o.was_terminal ? 1 : 0;
-    }
-    if (p.auto_reset && o.done()) {
-        uint32_t s0, s1;
-        load_pair<uint16_t>(p.start, p.start_broadcast ? 0 : e, n_agents, x.g, x.v0, x.v1, s0, s1);
-        store_cells(p.state, e, n_agents, x.g, x.v0, x.v1, s0, s1);
-    } else if (!o.was_terminal) {
-        store_cells(p.state, e, n_agents, x.g, x.v0, x.v1, next0, next1);
-    }
-    signal_step_done(p.done_flag, p.done_seq);
-}
+struct LgStepFamily {
+    template <int L, bool FULL, bool EXT_UNIFORMS>
+    static auto kernel() { return lg_step_kernel<L, FULL, EXT_UNIFORMS>; }
+};
 
 // ------------------------------------------------------- run-time-A helper kernels
 // masked MapfEnv.reset (mapf_env.py:290-293): one thread per cell
@@ -172,24 +131,7 @@ hipError_t launch_step_lg(int n_agents, const StepArgs &args, const RolloutTunin
     if (limit) return launch_step_lg_limit(n_agents, args, stream, *limit);   // (before the packed single step is consulted)
     hipError_t packed_status;
     if (try_launch_step_lq(n_agents, args, tune, stream, &packed_status)) return packed_status;
-    const LgStepPlan plan = plan_step_lg(n_agents, args);
-    const bool ext = args.uniforms != nullptr;
-    void (*kern)(const StepArgs, const uint32_t) = nullptr;
-    switch (plan.L) {
-#define X(N)                                                                                                         \
-    case N:                                                                                                          \
-        kern = ext ? (plan.full ? lg_step_kernel<N, true, true> : lg_step_kernel<N, false, true>)                    \
-                   : (plan.full ? lg_step_kernel<N, true, false> : lg_step_kernel<N, false, false>);                 \
-        break;
-        MAPF_FOR_EACH_L(X)
-#undef X
-        default: return hipErrorInvalidValue;
-    }
-    char name[kKernelNameBytes];
-    lg_step_kernel_name(name, plan, ext);
-    note_kernel("%s", name);
-    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(plan.block), 0, stream, args, uint32_t(n_agents));
-    return hipGetLastError();
+    return launch_lg_step<LgStepFamily>(plan_step_lg(n_agents, args), args, uint32_t(n_agents), stream);
 }
 
 }  // namespace mapf

@@ -1,0 +1,73 @@
+// Lane-group family: the launchers of its fused rollout and single-step kernels, once for every family of instances.  A launcher
+// takes ONE plan (mapf_plan.hpp) and launches the instance it names; which kernels those instances are is the including unit's
+// say, through a family type:
+//   rollout -- Family::kernel<L, FULL, MV_LDS, RECORD, STREAM, TABLE>(dense) returns the kernel's address (mapf_lg_rollout.hip:
+//              lg_rollout_kernel / lg_rollout_kernel_table, DENSE for full groups only; mapf_lg_limit.hip: the limit instances,
+//              guarded only);
+//   step    -- Family::kernel<L, FULL, EXT_UNIFORMS>() likewise (mapf_lg_kernels.hip: lg_step_kernel; mapf_lg_limit.hip:
+//              lg_step_kernel_limit).
+// `extra` are the kernel's arguments behind (args, A): nothing, the table policy, the episode limit, or both in that order.
+#pragma once
+#include "mapf_lg.hpp"
+#include "mapf_plan.hpp"
+
+namespace mapf {
+
+// Launches the planned instance: (MV_LDS, dense) pick the kernel, the plan gives its geometry and its LDS segment (the move
+// table, or nothing) and the name the launch notes.
+template <class Family, int L, bool FULL, bool RECORD, bool STREAM, bool TABLE, class... Extra>
+hipError_t launch_lg_rollout_instance(const LgRolloutPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const Extra &...extra) {
+    const auto kern = plan.mv_lds ? Family::template kernel<L, FULL, true, RECORD, STREAM, TABLE>(plan.dense)
+                                  : Family::template kernel<L, FULL, false, RECORD, STREAM, TABLE>(plan.dense);
+    if (plan.lds_bytes > 32 * 1024) {
+        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(kLdsBytes - kLdsReserve))) return e;
+    }
+    char name[kKernelNameBytes];
+    lg_rollout_kernel_name(name, plan, RECORD, STREAM, TABLE);
+    note_kernel("%s", name);
+    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(plan.block), plan.lds_bytes, stream, args, A, extra...);
+    return hipGetLastError();
+}
+
+// the instance's other arguments: the plan's L and FULL, RECORD and STREAM from the arrays the launch names (under TABLE no launch
+// streams its actions, and both arms of P name the one table instance)
+template <class Family, bool TABLE, class... Extra>
+hipError_t launch_lg_rollout(const LgRolloutPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const Extra &...extra) {
+    const bool record = args.rec_local != nullptr, streamed = !TABLE && args.actions != nullptr;
+    switch (plan.L) {
+#define P(N, FULL, RECORD) (streamed ? launch_lg_rollout_instance<Family, N, FULL, RECORD, !TABLE, TABLE>(plan, args, A, stream, extra...)  \
+                                     : launch_lg_rollout_instance<Family, N, FULL, RECORD, false, TABLE>(plan, args, A, stream, extra...))
+#define X(N)                                                                                                         \
+    case N:                                                                                                          \
+        if (plan.full) return record ? P(N, true, true) : P(N, true, false);                                         \
+        return record ? P(N, false, true) : P(N, false, false);
+        MAPF_FOR_EACH_L(X)
+#undef X
+#undef P
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// the single step: the plan's L and FULL, EXT_UNIFORMS from the launch's arrays
+template <class Family, class... Extra>
+hipError_t launch_lg_step(const LgStepPlan &plan, const StepArgs &args, uint32_t A, hipStream_t stream, const Extra &...extra) {
+    const bool ext = args.uniforms != nullptr;
+    void (*kern)(const StepArgs, const uint32_t, const Extra...) = nullptr;
+    switch (plan.L) {
+#define X(N)                                                                                                                       \
+    case N:                                                                                                                        \
+        kern = ext ? (plan.full ? Family::template kernel<N, true, true>() : Family::template kernel<N, false, true>())            \
+                   : (plan.full ? Family::template kernel<N, true, false>() : Family::template kernel<N, false, false>());         \
+        break;
+        MAPF_FOR_EACH_L(X)
+#undef X
+        default: return hipErrorInvalidValue;
+    }
+    char name[kKernelNameBytes];
+    lg_step_kernel_name(name, plan, ext);
+    note_kernel("%s", name);
+    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(plan.block), 0, stream, args, A, extra...);
+    return hipGetLastError();
+}
+
+}  // namespace mapf

@@ -1,8 +1,6 @@
-// Lane-group family: fused T-step rollout kernel and its launcher (device code: mapf_lg.hpp; the launch's plan: mapf_plan.hip).
-#include "mapf_lg.hpp"
-#include "mapf_plan.hpp"
-
-#include <type_traits>
+// Lane-group family: fused T-step rollout kernel and its launcher (device code: mapf_lg.hpp; the launch's plan: mapf_plan.hip; the
+// launcher proper: mapf_lg_launch.hpp).
+#include "mapf_lg_launch.hpp"
 
 namespace mapf {
 
@@ -25,45 +23,15 @@ namespace mapf {
 #include "mapf_lg_rollout_kernel.inc"
 #undef MAPF_ROLLOUT_TABLE_KERNEL
 
-// Launches the planned instance of lg_rollout_kernel, or of lg_rollout_kernel_table (TABLE: then STREAM is false): (MV_LDS,
-// DENSE) pick the kernel, the plan gives its geometry and its LDS segment (the move table, or nothing).
-template <int L, bool FULL, bool RECORD, bool STREAM, bool TABLE>
-static hipError_t launch_instance(const LgRolloutPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table) {
-    auto pick = [&](auto mv_lds) {   // (DENSE exists for full groups only)
-        constexpr bool MV_LDS = decltype(mv_lds)::value;
-        if constexpr (TABLE) return plan.dense ? lg_rollout_kernel_table<L, FULL, MV_LDS, RECORD, FULL> : lg_rollout_kernel_table<L, FULL, MV_LDS, RECORD, false>;
-        else return plan.dense ? lg_rollout_kernel<L, FULL, MV_LDS, RECORD, STREAM, FULL> : lg_rollout_kernel<L, FULL, MV_LDS, RECORD, STREAM, false>;
-    };
-    const auto kern = plan.mv_lds ? pick(std::true_type{}) : pick(std::false_type{});
-    if (plan.lds_bytes > 32 * 1024) {
-        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(kLdsBytes - kLdsReserve))) return e;
+// The instances without an episode limit: lg_rollout_kernel, or lg_rollout_kernel_table (TABLE: then STREAM is false); DENSE
+// exists for full groups only.
+struct LgRolloutFamily {
+    template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM, bool TABLE>
+    static auto kernel(bool dense) {
+        if constexpr (TABLE) return dense ? lg_rollout_kernel_table<L, FULL, MV_LDS, RECORD, FULL> : lg_rollout_kernel_table<L, FULL, MV_LDS, RECORD, false>;
+        else return dense ? lg_rollout_kernel<L, FULL, MV_LDS, RECORD, STREAM, FULL> : lg_rollout_kernel<L, FULL, MV_LDS, RECORD, STREAM, false>;
     }
-    char name[kKernelNameBytes];
-    lg_rollout_kernel_name(name, plan, RECORD, STREAM, TABLE);
-    note_kernel("%s", name);
-    if constexpr (TABLE) hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(plan.block), plan.lds_bytes, stream, args, A, *table);
-    else hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(plan.block), plan.lds_bytes, stream, args, A);
-    return hipGetLastError();
-}
-
-// the instance's other arguments: the plan's L and FULL, RECORD and STREAM from the arrays the launch names (under TABLE no launch
-// streams its actions, and both arms of P name the one table instance)
-template <bool TABLE>
-static hipError_t launch_planned(const LgRolloutPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table) {
-    const bool record = args.rec_local != nullptr, streamed = !TABLE && args.actions != nullptr;
-    switch (plan.L) {
-#define P(N, FULL, RECORD) (streamed ? launch_instance<N, FULL, RECORD, !TABLE, TABLE>(plan, args, A, stream, table)  \
-                                     : launch_instance<N, FULL, RECORD, false, TABLE>(plan, args, A, stream, table))
-#define X(N)                                                                                                         \
-    case N:                                                                                                          \
-        if (plan.full) return record ? P(N, true, true) : P(N, true, false);                                         \
-        return record ? P(N, false, true) : P(N, false, false);
-        MAPF_FOR_EACH_L(X)
-#undef X
-#undef P
-        default: return hipErrorInvalidValue;
-    }
-}
+};
 
 hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table,
                              const EpisodeLimit *limit) {
@@ -72,7 +40,8 @@ hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const Rollou
     hipError_t packed_status;
     if (try_launch_rollout_lq(n_agents, args, tune, stream, &packed_status, table)) return packed_status;
     const LgRolloutPlan plan = plan_rollout_lg(n_agents, args, tune);
-    return table ? launch_planned<true>(plan, args, uint32_t(n_agents), stream, table) : launch_planned<false>(plan, args, uint32_t(n_agents), stream, table);
+    return table ? launch_lg_rollout<LgRolloutFamily, true>(plan, args, uint32_t(n_agents), stream, *table)
+                 : launch_lg_rollout<LgRolloutFamily, false>(plan, args, uint32_t(n_agents), stream);
 }
 
 }  // namespace mapf

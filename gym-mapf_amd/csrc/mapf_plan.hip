@@ -290,10 +290,11 @@ static void lg_geometry(int L, uint64_t n_envs, unsigned &grid, unsigned &block)
 
 // MV_LDS: the move table goes to LDS while the tuning's limit (default: two blocks per CU) and the CU's LDS hold it beside the
 // 1 KB table image, from 256 waves on.  DENSE: full groups and no ragged last block.
-LgRolloutPlan plan_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune) {
+LgRolloutPlan plan_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, bool limited) {
     LgRolloutPlan plan;
     plan.L = lg_group_size(n_agents);
     plan.full = n_agents == 2 * plan.L;
+    plan.limit = limited;
     const size_t mv_bytes = size_t(args.c.n_cells) * kMvCols * sizeof(MoveEntry);
     const uint64_t threads = args.n_envs * uint64_t(plan.L);
     plan.mv_lds = mv_bytes + kLdsReserve <= tune.mv_lds_max_bytes && mv_bytes + kLdsReserve <= kLdsBytes && threads >= 64 * 256;
@@ -308,45 +309,31 @@ LgRolloutPlan plan_rollout_lg(int n_agents, const RolloutArgs &args, const Rollo
     } else {
         lg_geometry(plan.L, args.n_envs, plan.grid, plan.block);
     }
-    plan.dense = plan.full && args.n_envs % (plan.block / unsigned(plan.L)) == 0;
+    plan.dense = !limited && plan.full && args.n_envs % (plan.block / unsigned(plan.L)) == 0;   // (the limit instances: guarded only)
     return plan;
 }
 
-LgRolloutPlan plan_rollout_lg_limit(int n_agents, const RolloutArgs &args, const RolloutTuning &tune) {
-    LgRolloutPlan plan = plan_rollout_lg(n_agents, args, tune);
-    plan.dense = false;
-    return plan;
-}
-
-LgStepPlan plan_step_lg(int n_agents, const StepArgs &args) {
+LgStepPlan plan_step_lg(int n_agents, const StepArgs &args, bool limited) {
     LgStepPlan plan;
     plan.L = lg_group_size(n_agents);
     plan.full = n_agents == 2 * plan.L;
+    plan.limit = limited;
     lg_geometry(plan.L, args.n_envs, plan.grid, plan.block);
     return plan;
 }
 
+// (a limit plan: _limit_guarded and LIMIT where the others say DENSE or GUARDED, and the note)
 void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy) {
-    snprintf(name, kKernelNameBytes, "lg_rollout_kernel%s<L=%d,%s,%s,%s,%s,%s> block=%u (pair layout: 2 agents per lane%s)", table_policy ? "_table" : "", plan.L,
-             plan.full ? "FULL" : "RAGGED", plan.mv_lds ? "MV_LDS" : "MV_GLOBAL", record ? "RECORD" : "TOTALS",
-             table_policy ? "TABLE" : (streamed ? "STREAM" : "POLICY"), plan.dense ? "DENSE" : "GUARDED", plan.block,
-             table_policy ? "; table policy: action bytes gathered from global memory" : "");
-}
-
-void lg_rollout_limit_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy) {
-    snprintf(name, kKernelNameBytes, "lg_rollout_kernel%s_limit_guarded<L=%d,%s,%s,%s,%s,LIMIT> block=%u (pair layout: 2 agents per lane; episode step limit%s)",
-             table_policy ? "_table" : "", plan.L, plan.full ? "FULL" : "RAGGED", plan.mv_lds ? "MV_LDS" : "MV_GLOBAL", record ? "RECORD" : "TOTALS",
-             table_policy ? "TABLE" : (streamed ? "STREAM" : "POLICY"), plan.block, table_policy ? "; table policy: action bytes gathered from global memory" : "");
-}
-
-void lg_step_limit_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms) {
-    snprintf(name, kKernelNameBytes, "lg_step_kernel_limit<L=%d,%s,%s,LIMIT> block=%u (pair layout: 2 agents per lane; episode step limit)", plan.L,
-             plan.full ? "FULL" : "RAGGED", ext_uniforms ? "EXT_UNIFORMS" : "PHILOX", plan.block);
+    snprintf(name, kKernelNameBytes, "lg_rollout_kernel%s%s<L=%d,%s,%s,%s,%s,%s> block=%u (pair layout: 2 agents per lane%s%s)", table_policy ? "_table" : "",
+             plan.limit ? "_limit_guarded" : "", plan.L, plan.full ? "FULL" : "RAGGED", plan.mv_lds ? "MV_LDS" : "MV_GLOBAL", record ? "RECORD" : "TOTALS",
+             table_policy ? "TABLE" : (streamed ? "STREAM" : "POLICY"), plan.limit ? "LIMIT" : (plan.dense ? "DENSE" : "GUARDED"), plan.block,
+             plan.limit ? "; episode step limit" : "", table_policy ? "; table policy: action bytes gathered from global memory" : "");
 }
 
 void lg_step_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms) {
-    snprintf(name, kKernelNameBytes, "lg_step_kernel<L=%d,%s,%s> block=%u (pair layout: 2 agents per lane)", plan.L, plan.full ? "FULL" : "RAGGED",
-             ext_uniforms ? "EXT_UNIFORMS" : "PHILOX", plan.block);
+    snprintf(name, kKernelNameBytes, "lg_step_kernel%s<L=%d,%s,%s%s> block=%u (pair layout: 2 agents per lane%s)", plan.limit ? "_limit" : "", plan.L,
+             plan.full ? "FULL" : "RAGGED", ext_uniforms ? "EXT_UNIFORMS" : "PHILOX", plan.limit ? ",LIMIT" : "", plan.block,
+             plan.limit ? "; episode step limit" : "");
 }
 
 }  // namespace mapf

@@ -1,7 +1,8 @@
 // Launch planning of the packed and the lane-group kernels: which form, block, grid and LDS image a launch of a given shape
 // takes.  Pure integer arithmetic over the launch's shape, the tuning and the LDS layout (mapf_layout.hpp) -- no kernel, no
 // runtime call -- so it can be swept without a device (mapf_debug_rollout_plan, tests/test_plan_decisions.py).  A launcher
-// takes ONE plan and launches the instance it names; it decides nothing itself.
+// takes ONE plan and launches the instance it names; it decides nothing itself (the lane-group plans name their family too: with
+// or without the episode step limit).
 #pragma once
 #include "mapf_layout.hpp"
 
@@ -26,13 +27,6 @@ bool plan_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning 
 // ... under the table policy (args.actions == null): the packed table instances exist for two and four agents per lane over full
 // 16-byte rows and for the 32-agent bitmap form over delta rows, in blocks of at most 512 threads.  false = lane-group kernel.
 bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, size_t table_bytes, LqPlan *plan);
-// (the earlier signature, for host shims written against it: no launcher keeps the two table fields apart)
-inline bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, size_t table_bytes, LqPlan *plan,
-                                  bool *table_lds, uint32_t *table_at) {
-    const bool packed = plan_rollout_lq_table(n_agents, args, tune, table_bytes, plan);
-    *table_lds = packed && plan->table_lds; *table_at = *table_lds ? plan->table_at : 0u;
-    return packed;
-}
 
 // The forms of the packed single step: the plain step, or a resident grid with the move table in LDS (the values: the kernel's BIG)
 enum class StepForm : int { Plain = 0, FullRows = 1, DeltaRows = 2, DeltaRowsBitmap = 3 };   // (16-byte rows; 4-byte delta rows; ... + per-env occupancy bitmaps)
@@ -53,27 +47,26 @@ int lg_group_size(int n_agents);
 // Largest block of a rollout kernel: groups of 16 lanes unroll 8 rotation rounds and need more than the 128 registers a
 // 1024-thread block leaves per lane.  The kernels' __launch_bounds__ (rollout_max_block, mapf_lg_rollout.hip) read it too.
 constexpr unsigned kLgRolloutMaxBlock = 1024u, kLgRolloutMaxBlock16 = 512u;
-// The instance lg_rollout_kernel<L, full, mv_lds, ., ., dense> (or lg_rollout_kernel_table<L, full, mv_lds, ., dense>) and its geometry
+// The instance lg_rollout_kernel<L, full, mv_lds, ., ., dense> (or lg_rollout_kernel_table<L, full, mv_lds, ., dense>) and its geometry;
+// under `limit` the instance of the same fields among the limit kernels (mapf_lg_limit.hip), which are never dense
 struct LgRolloutPlan {
     int L = 0;                       // lanes per env
     bool full = false;               // A == 2L: no ghost slots
     bool mv_lds = false;             // the whole move table is staged into LDS once per block
     bool dense = false;              // full groups and the env count fills every block: no per-lane predicates
+    bool limit = false;              // the family the plan names: the instances under an episode step limit, or those without
     unsigned block = 0, grid = 0;
     size_t lds_bytes = 0;            // dynamic LDS segment: the move table, or 0 (the launcher raises the limit beyond 32 KB)
 };
-LgRolloutPlan plan_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune);
-// ... under an episode step limit (EpisodeLimit, mapf_kernels.hpp): the limit instances exist in the lane-group family only, so no
-// packed plan and no thread-per-env kernel is consulted and this plan takes the launch -- plan_rollout_lg's, never dense (the
-// limit instances have the guarded form only)
-LgRolloutPlan plan_rollout_lg_limit(int n_agents, const RolloutArgs &args, const RolloutTuning &tune);
-struct LgStepPlan { int L = 0; bool full = false; unsigned block = 0, grid = 0; };
-LgStepPlan plan_step_lg(int n_agents, const StepArgs &args);
-// The names the launchers note for these plans (mapf_last_kernel; at most kKernelNameBytes with the terminator)
+// (limited: the launch runs under an episode step limit (EpisodeLimit, mapf_kernels.hpp).  The limit instances exist in the
+// lane-group family only, so no packed plan and no thread-per-env kernel is consulted and this plan takes the launch: the same
+// plan, marked `limit` and never dense -- the limit instances have the guarded form only)
+LgRolloutPlan plan_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, bool limited = false);
+struct LgStepPlan { int L = 0; bool full = false; bool limit = false; unsigned block = 0, grid = 0; };
+LgStepPlan plan_step_lg(int n_agents, const StepArgs &args, bool limited = false);
+// The names the launchers note for these plans (mapf_last_kernel; at most kKernelNameBytes with the terminator).  A limit plan's
+// name says _limit_guarded (the step: _limit) and LIMIT, and has no DENSE / GUARDED field.
 void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy);
 void lg_step_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms);
-// ... and for the limit instances (mapf_lg_limit.hip): the same fields, and LIMIT
-void lg_rollout_limit_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy);
-void lg_step_limit_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms);
 
 }  // namespace mapf

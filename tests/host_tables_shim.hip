@@ -114,31 +114,43 @@ int shim_plan_rollout_table(uint32_t n_cells, int n_agents, uint64_t n_envs, uin
     return 1;
 }
 
-// plan_rollout_lg over a shape (policy: 0 streamed actions, 1 the in-kernel policy stream, 2 the table policy): out = L, full, mv_lds, dense,
-// block, grid, lds_bytes; name (kKernelNameBytes) = what the launcher notes for that plan; 1 = planned, -1 = bad tune
-int shim_plan_rollout_lg(uint32_t n_cells, int n_agents, uint64_t n_envs, int record, int policy, const char *tune, uint64_t out[7], char *name) {
+// (what the two entries below share; limited: the plan of a launch under an episode step limit)
+static int rollout_lg(uint32_t n_cells, int n_agents, uint64_t n_envs, int record, int policy, const char *tune, bool limited, uint64_t out[7], char *name) {
     std::string err;
     const RolloutTuning t = rollout_tuning_for(256, tune, &err);
     if (!err.empty()) return -1;
     RolloutArgs args{};
     args.c.n_cells = n_cells;
     args.n_envs = n_envs;
-    const LgRolloutPlan plan = plan_rollout_lg(n_agents, args, t);
+    const LgRolloutPlan plan = plan_rollout_lg(n_agents, args, t, limited);
     out[0] = uint64_t(plan.L); out[1] = plan.full ? 1u : 0u; out[2] = plan.mv_lds ? 1u : 0u; out[3] = plan.dense ? 1u : 0u; out[4] = plan.block;
     out[5] = plan.grid; out[6] = plan.lds_bytes;
     lg_rollout_kernel_name(name, plan, record != 0, policy == 0, policy == 2);
     return 1;
 }
+// plan_rollout_lg over a shape (policy: 0 streamed actions, 1 the in-kernel policy stream, 2 the table policy): out = L, full, mv_lds, dense,
+// block, grid, lds_bytes; name (kKernelNameBytes) = what the launcher notes for that plan; 1 = planned, -1 = bad tune
+int shim_plan_rollout_lg(uint32_t n_cells, int n_agents, uint64_t n_envs, int record, int policy, const char *tune, uint64_t out[7], char *name) {
+    return rollout_lg(n_cells, n_agents, n_envs, record, policy, tune, false, out, name);
+}
+// ... under an episode step limit: the plan that names the limit instance
+int shim_plan_limit_rollout_lg(uint32_t n_cells, int n_agents, uint64_t n_envs, int record, int policy, const char *tune, uint64_t out[7], char *name) {
+    return rollout_lg(n_cells, n_agents, n_envs, record, policy, tune, true, out, name);
+}
 
-// plan_step_lg: out = L, full, block, grid; name as above
-int shim_plan_step_lg(int n_agents, uint64_t n_envs, int ext_uniforms, uint64_t out[4], char *name) {
+// (likewise for the single step)
+static int step_lg(int n_agents, uint64_t n_envs, int ext_uniforms, bool limited, uint64_t out[4], char *name) {
     StepArgs args{};
     args.n_envs = n_envs;
-    const LgStepPlan plan = plan_step_lg(n_agents, args);
+    const LgStepPlan plan = plan_step_lg(n_agents, args, limited);
     out[0] = uint64_t(plan.L); out[1] = plan.full ? 1u : 0u; out[2] = plan.block; out[3] = plan.grid;
     lg_step_kernel_name(name, plan, ext_uniforms != 0);
     return 1;
 }
+// plan_step_lg: out = L, full, block, grid; name as above
+int shim_plan_step_lg(int n_agents, uint64_t n_envs, int ext_uniforms, uint64_t out[4], char *name) { return step_lg(n_agents, n_envs, ext_uniforms, false, out, name); }
+// ... under an episode step limit
+int shim_plan_limit_step_lg(int n_agents, uint64_t n_envs, int ext_uniforms, uint64_t out[4], char *name) { return step_lg(n_agents, n_envs, ext_uniforms, true, out, name); }
 
 // does the launcher hold the packed rollout instance (K, Q, form)?  (table: of lq_rollout_kernel_table)
 int shim_rollout_instance_exists(int K, int Q, int form, int table) {

@@ -58,6 +58,9 @@ def load_shim(path):
     if hasattr(lib, 'shim_plan_rollout_lg'):
         lib.shim_plan_rollout_lg.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_char_p]
         lib.shim_plan_step_lg.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p]
+    if hasattr(lib, 'shim_plan_limit_rollout_lg'):
+        lib.shim_plan_limit_rollout_lg.argtypes = lib.shim_plan_rollout_lg.argtypes
+        lib.shim_plan_limit_step_lg.argtypes = lib.shim_plan_step_lg.argtypes
     if hasattr(lib, 'shim_rollout_instance_exists'):
         lib.shim_rollout_instance_exists.argtypes = [ctypes.c_int] * 4
     return lib

@@ -15,7 +15,13 @@ of one shape per distinct name.  The comparison involves no GPU; one GPU test la
 
 writes the fixture from the library MAPF_HIP_LIB names (default: the tree's) and the host shim MAPF_HOST_SHIM names (default:
 built from the tree's sources); `packed` / `lane_group` alone re-records those groups only and keeps the others of OUT.json.
-`lane_group` needs a GPU."""
+`lane_group` needs a GPU.
+
+The limit instances of the lane-group family (mapf_lg_limit.hip) are named by the same two planners, asked for a limit plan.  Their
+plans and full names over LIMIT_* below are compared with tests/golden/plan_decisions_limit.json, recorded on the CPU from the
+commit that still had a planner and name functions of their own for them (tests/golden/generation_info.json says how):
+
+    python tests/test_plan_decisions.py --record-limit [OUT.json]"""
 import ctypes
 import hashlib
 import json
@@ -51,6 +57,12 @@ LG_PACKED = '-'
 LG_ROLLOUT_NAME = re.compile(r'^lg_rollout_kernel(_table)?<L=(\d+),(FULL|RAGGED),(MV_LDS|MV_GLOBAL),(RECORD|TOTALS),(STREAM|POLICY|TABLE),(DENSE|GUARDED)> block=(\d+) ')
 LG_STEP_NAME = re.compile(r'^lg_step_kernel<L=(\d+),(FULL|RAGGED),(EXT_UNIFORMS|PHILOX)> block=(\d+) ')
 LG_ROLLOUT_CODE, LG_STEP_CODE = re.compile(r'^(\d+)([FR])([LG])([DG])(\d+)$'), re.compile(r'^(\d+)([FR])(\d+)$')   # (lg_rollout_code, lg_step_code)
+# the limit instances: every L, full and ragged; one-wave and four-wave blocks, MV_GLOBAL and MV_LDS, ragged and full last blocks; a
+# table of 4 copies per CU, of 2, and one no LDS holds
+FIXTURE_LIMIT = os.path.join(GOLDEN, 'plan_decisions_limit.json')
+LIMIT_AGENTS = (1, 2, 3, 5, 8, 16, 17, 32, 33, 64, 128)
+LIMIT_ENVS = (1, 63, 64, 4096, 65536)
+LIMIT_CELLS = (16, 683, 3300)
 KERNEL_NAME_BYTES = 160                                                # what mapf_last_kernel keeps of a name (the terminator included)
 
 
@@ -170,6 +182,23 @@ def planned_step_lg(shim_lib, A, E, uniforms):
     assert shim_lib.shim_plan_step_lg(A, E, uniforms, out, name) == 1
     L, full, block, grid = out
     return '%d%s%d' % (L, 'F' if full else 'R', block), grid, name.value.decode()
+
+
+def limit_plans(shim_lib):
+    """the limit plans and names of the LIMIT_* sweep: {'rollout': {shape: 'L full mv_lds dense block grid lds_bytes|name'}, 'step':
+    {shape: 'L full block grid|name'}}"""
+    out, name = (ctypes.c_uint64 * 7)(), ctypes.create_string_buffer(2 * KERNEL_NAME_BYTES)
+    rollouts, steps = {}, {}
+    for A in LIMIT_AGENTS:
+        for E in LIMIT_ENVS:
+            for V in LIMIT_CELLS:
+                for record, policy in LG_ROLLOUTS:
+                    assert shim_lib.shim_plan_limit_rollout_lg(V, A, E, record, policy, None, out, name) == 1
+                    rollouts['V=%d A=%d E=%d record=%d policy=%d' % (V, A, E, record, policy)] = '%s|%s' % (' '.join(str(x) for x in out), name.value.decode())
+            for uniforms in LG_STEPS:
+                assert shim_lib.shim_plan_limit_step_lg(A, E, uniforms, out, name) == 1
+                steps['A=%d E=%d uniforms=%d' % (A, E, uniforms)] = '%s|%s' % (' '.join(str(x) for x in out[:4]), name.value.decode())
+    return {'rollout': rollouts, 'step': steps}
 
 
 class LaneGroupLauncher:
@@ -332,6 +361,22 @@ def test_lane_group_plans_are_the_recorded_ones(shim):  # noqa: F811
         assert found == name and len(name) < KERNEL_NAME_BYTES, (where, found, name)
 
 
+def test_limit_plans_and_names_are_the_recorded_ones(shim):  # noqa: F811
+    """plan_rollout_lg and plan_step_lg asked for a limit plan, and the names of those plans, against what the limit family's own
+    planner and name functions gave before the two were folded: every field and every byte of the name; never dense"""
+    with open(FIXTURE_LIMIT) as f:
+        recorded = json.load(f)
+    found = limit_plans(shim)
+    assert len(found['rollout']) == 11 * 5 * 3 * 6 and len(found['step']) == 11 * 5 * 2
+    for kind in ('rollout', 'step'):
+        assert sorted(found[kind]) == sorted(recorded[kind]), kind
+        wrong = [(shape, found[kind][shape], recorded[kind][shape]) for shape in found[kind] if found[kind][shape] != recorded[kind][shape]]
+        assert not wrong, '%d of %d limit %s plans or names differ: %s' % (len(wrong), len(found[kind]), kind, wrong[:6])
+    for line in found['rollout'].values():
+        fields, name = line.split('|')
+        assert fields.split(' ')[3] == '0' and '_limit_guarded<' in name and ',LIMIT> ' in name and len(name) < KERNEL_NAME_BYTES, line
+
+
 def lg_kinds(recorded):
     """{kind: (shape's key, index into LG_ROLLOUTS, recorded name)}: the smallest shape of every combination that exists of full /
     ragged groups, move table in LDS / global memory, dense / guarded and table policy or not; plus the smallest one whose block
@@ -369,6 +414,12 @@ def test_lane_group_launches_print_the_recorded_names():
 
 
 if __name__ == '__main__':
+    if len(sys.argv) >= 2 and sys.argv[1] == '--record-limit':
+        shim_path = os.environ.get('MAPF_HOST_SHIM') or build_shim(tempfile.mkdtemp(prefix='host_tables_'))
+        with open(sys.argv[2] if len(sys.argv) > 2 else FIXTURE_LIMIT, 'w') as f:
+            json.dump(limit_plans(load_shim(shim_path)), f, indent=0, sort_keys=True)
+            f.write('\n')
+        sys.exit(0)
     if len(sys.argv) < 2 or sys.argv[1] != '--record':
         sys.exit(__doc__)
     from gym_mapf_amd import _native

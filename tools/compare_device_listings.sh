@@ -6,8 +6,7 @@
 #   tools/compare_device_listings.sh OLD_TREE NEW_TREE WORK_DIR [JOBS]     (trees: repository roots; exit 0 = all identical)
 #
 # Translation units of NEW_TREE that are not in the list must hold no kernel: their listings are checked for an empty
-# kernel list as well -- except the units of ADDED, which hold kernels OLD_TREE may not have at all (the episode-limit
-# instances of the lane-group family): their kernels are counted and reported, and compared too when OLD_TREE has the unit.
+# kernel list as well.
 set -u
 OLD=$(cd "$1" && pwd); NEW=$(cd "$2" && pwd); WORK=$3; JOBS=${4:-8}
 mkdir -p "$WORK/old" "$WORK/new"
@@ -15,15 +14,13 @@ mkdir -p "$WORK/old" "$WORK/new"
 # name | unit | extra flags
 UNITS="mapf_lg_kernels|mapf_lg_kernels|
 mapf_lg_rollout|mapf_lg_rollout|
+mapf_lg_limit|mapf_lg_limit|
 mapf_transitions|mapf_transitions|
 mapf_lq_step|mapf_lq_step|-mllvm -amdgpu-kernarg-preload-count=14"
 for k in 8 4 2; do for r in 1 0; do UNITS="$UNITS
 mapf_lq_rollout_k${k}_r${r}|mapf_lq_rollout|-DMAPF_LQ_K=$k -DMAPF_LQ_RECORD=$r"; done; done
 for g in 0 1 2 3; do UNITS="$UNITS
 mapf_kernels_g$g|mapf_kernels|-DMAPF_GROUP=$g"; done
-ADDED="mapf_lg_limit"
-for unit in $ADDED; do [ -f "$OLD/gym-mapf_amd/csrc/$unit.hip" ] && UNITS="$UNITS
-$unit|$unit|"; done
 
 listing() {   # tree, side, name, unit, flags
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I"$1/include" -Wall $5 -S --cuda-device-only \
@@ -55,7 +52,6 @@ for f in "$NEW"/gym-mapf_amd/csrc/*.hip; do
     unit=$(basename "$f" .hip)
     echo "$UNITS" | grep -q "|$unit|" && continue
     n=$(grep -c '^  - .agpr_count:' "$WORK/new/$unit.s")
-    if echo " $ADDED " | grep -q " $unit "; then echo "added      $unit.s  $n kernels (not in the old tree)"; continue; fi
     if [ -f "$WORK/new/$unit.s" ] && [ "$n" = 0 ]; then echo "no kernel  $unit.s"; else echo "HAS KERNELS ($n)  $unit.s"; status=1; fi
 done
 exit $status
