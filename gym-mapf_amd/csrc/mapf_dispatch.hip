@@ -45,4 +45,19 @@ bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutT
     return true;
 }
 
+// ... under an episode step limit: the packed table instances' limit forms (mapf_lq_limit.hip), with launch_rollout_lg_limit's pre-checks
+bool try_launch_rollout_lq_limit(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy &table,
+                                 const EpisodeLimit &limit) {
+    LqPlan plan;
+    if (args.n_envs == 0 || args.actions != nullptr || !tune.limit_packed || !plan_rollout_lq_table(n_agents, args, tune, table.table_bytes, &plan, true)) return false;
+    const bool record = args.rec_local != nullptr;
+    const uint32_t A = uint32_t(n_agents);
+    // what the kernels rely on: ages, a limit, and the truncated trajectory exactly when the launch records
+    if (!limit.age || limit.max_steps == 0u || (limit.rec_truncated != nullptr) != record) *err = hipErrorInvalidValue;
+    else if (plan.K == 4) *err = record ? launch_rollout_lq_limit_k4_r1(plan, args, A, stream, table, limit) : launch_rollout_lq_limit_k4_r0(plan, args, A, stream, table, limit);
+    else if (plan.K == 2) *err = record ? launch_rollout_lq_limit_k2_r1(plan, args, A, stream, table, limit) : launch_rollout_lq_limit_k2_r0(plan, args, A, stream, table, limit);
+    else *err = hipErrorInvalidValue;   // (plan_rollout_lq_table plans no other K)
+    return true;
+}
+
 }  // namespace mapf

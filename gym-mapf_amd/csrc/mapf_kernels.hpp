@@ -257,10 +257,13 @@ struct RolloutTuning {
     bool scen_table = true;          // scen_table=0: never build the scenario table (StepArgs::scen) -- tests compare both forms
     int policy_table_lds = -1;       // policy_table_lds=0|1: the packed rollout under the table policy gathers its action bytes from global
                                      //   memory / from a copy staged into LDS behind the table image whenever that fits (default: by shape)
+    bool limit_packed = false;       // limit_packed=1: a table-policy rollout under an episode step limit takes the packed limit instance
+                                     //   (mapf_lq_limit.hip) where the packed table plan applies; default 0: always the lane-group limit instance
 };
 RolloutTuning default_rollout_tuning(int device, std::string *err);   // (asks the device, reads MAPF_TUNE: mapf_dispatch.hip)
 // (limit: the episode limit of a handle that has one, or null -- then the lane-group limit instance takes the launch: no packed
-// form and no thread-per-env kernel is consulted, mapf_lg_limit.hip)
+// form and no thread-per-env kernel is consulted, mapf_lg_limit.hip; the one packed family with limit instances is tried by the
+// caller BEFORE these, try_launch_rollout_lq_limit below)
 hipError_t launch_step_lg(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, const EpisodeLimit *limit = nullptr);
 // packed layout of the single step (mapf_lq_step.hip): true when it took the launch (*err = its status)
 bool try_launch_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err);
@@ -272,6 +275,12 @@ hipError_t launch_rollout_lg_limit(int n_agents, const RolloutArgs &args, const 
                                    const EpisodeLimit &limit);
 hipError_t launch_step_lg_limit(int n_agents, const StepArgs &args, hipStream_t stream, const EpisodeLimit &limit);
 hipError_t launch_reset_ages(uint32_t *age, const uint8_t *mask, uint64_t n_envs, hipStream_t stream);
+// ... under an episode step limit, for a handle whose tuning has limit_packed=1 and a launch that follows the table policy: plans
+// the launch (plan_rollout_lq_table, limited) and routes it to the object of mapf_lq_limit.hip that holds its instance; true when
+// it took the launch (*err = its status, hipErrorInvalidValue when the limit block is incomplete: launch_rollout_lg_limit's
+// pre-checks), false = the lane-group limit instance's
+bool try_launch_rollout_lq_limit(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy &table,
+                                 const EpisodeLimit &limit);
 // packed layout of the fused rollout (2, 4 or 8 agents per lane): plans the launch (mapf_plan.hpp) and routes it to the object that
 // holds its instance (mapf_dispatch.hip); true when it took the launch (*err = its status)
 bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy *table = nullptr);
@@ -284,6 +293,11 @@ hipError_t launch_rollout_lq_k4_r1(const LqPlan &plan, const RolloutArgs &args, 
 hipError_t launch_rollout_lq_k4_r0(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table);
 hipError_t launch_rollout_lq_k2_r1(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table);
 hipError_t launch_rollout_lq_k2_r0(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table);
+// ... and of mapf_lq_limit.hip, compiled once per (four or two agents per lane, recording) pair: the packed table instances under a limit
+hipError_t launch_rollout_lq_limit_k4_r1(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy &table, const EpisodeLimit &limit);
+hipError_t launch_rollout_lq_limit_k4_r0(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy &table, const EpisodeLimit &limit);
+hipError_t launch_rollout_lq_limit_k2_r1(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy &table, const EpisodeLimit &limit);
+hipError_t launch_rollout_lq_limit_k2_r0(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy &table, const EpisodeLimit &limit);
 
 // per-group entry points: group g holds the kernels specialised for A in 4g+1 .. 4g+4
 hipError_t launch_step_g0(int n_agents, const StepArgs &args, hipStream_t stream);

@@ -360,5 +360,16 @@ __device__ __forceinline__ double packed_prob_product(const double (&q)[K]) {
     return run;
 }
 
+// ---- constants of the packed rollout kernels' body (mapf_lq_rollout_kernel.inc), for the units that include it: mapf_lq_rollout.hip, mapf_lq_limit.hip
+// The LDS copy of a table row carries its slip row's byte offset PLUS kRowBias, so that sample_slot_packed's probability
+// address -- that operand minus 8 per threshold not passed -- is never negative and packs into an unsigned field (the
+// systolic probability chain of the rollout files four of them per word); the immediates of the LDS reads absorb the bias.
+constexpr uint32_t kRowBias = kDeltaRowBias;              // (the host-built delta rows carry it too)
+// index (in doubles from kSlipAt) of a +0.0: the all-equal code's list has ONE entry, so thr[1] of its row is the integer 0
+constexpr uint32_t kZeroFactor = (7u * uint32_t(sizeof(SlipRow)) + uint32_t(offsetof(SlipRow, thr)) + 8u) / 8u;
+static_assert(offsetof(SlipRow, thr) % 8 == 0 && kZeroFactor < 128u, "a zero factor the packed probability indices can name");
+// what a bitmap instance's name (mapf_last_kernel) says in its parentheses
+constexpr const char *kBitmapNote = ", collisions through per-env occupancy bitmaps";
+
 }  // namespace
 }  // namespace mapf

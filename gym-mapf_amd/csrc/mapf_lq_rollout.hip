@@ -55,13 +55,7 @@ namespace {
 // RECORD: all five trajectory arrays are written every step; STREAM: actions come from memory, else from the
 // in-kernel policy.  Memory pipeline and store scheme as lg_rollout_kernel<DENSE>.
 // (the LDS image -- kSlipAt, kOutcomeAt, kMoveAt, the column counts and entry sizes of each table form: mapf_layout.hpp)
-// The LDS copy of a table row carries its slip row's byte offset PLUS kRowBias, so that sample_slot_packed's probability
-// address -- that operand minus 8 per threshold not passed -- is never negative and packs into an unsigned field (the
-// systolic probability chain below files four of them per word); the immediates of the LDS reads absorb the bias.
-constexpr uint32_t kRowBias = kDeltaRowBias;              // (the host-built delta rows carry it too)
-// index (in doubles from kSlipAt) of a +0.0: the all-equal code's list has ONE entry, so thr[1] of its row is the integer 0
-constexpr uint32_t kZeroFactor = (7u * uint32_t(sizeof(SlipRow)) + uint32_t(offsetof(SlipRow, thr)) + 8u) / 8u;
-static_assert(offsetof(SlipRow, thr) % 8 == 0 && kZeroFactor < 128u, "a zero factor the packed probability indices can name");
+// (kRowBias, kZeroFactor -- the bias of a table row's slip-row offset, the index of a zero factor: mapf_lq.hpp, shared with mapf_lq_limit.hip)
 
 // TERM = an env may be terminal when a step begins.  With auto-reset on and no env whose START state is itself
 // terminal (the handle knows: mapf_create looks) that cannot happen after the launch's first step -- a done env is back
@@ -86,7 +80,6 @@ static_assert(offsetof(SlipRow, thr) % 8 == 0 && kZeroFactor < 128u, "a zero fac
 
 #undef env_id
 
-constexpr const char *kBitmapNote = ", collisions through per-env occupancy bitmaps";
 // One family of instances, launched as planned: FORM's traits (mapf_layout.hpp) give the kernel's (COMPACT, BITMAP) and what the
 // kernel's name says; the plan (mapf_plan.hpp) gives the block, where the bitmaps begin (lds_bytes) and the launch's dynamic LDS segment (lds_total)
 template <int Q, int K, bool RECORD, bool STREAM, TableForm FORM>

@@ -9,10 +9,20 @@
 //     policy instances fill).
 // Textual inclusion, not a shared function template: the first kernel's token stream is what it was before the table policy
 // existed, so its instances (which sit at the edge of their register budgets) compile to the same code.
+// mapf_lq_limit.hip includes it once more with MAPF_ROLLOUT_TABLE_KERNEL 1 and MAPF_ROLLOUT_LIMIT 1 (the episode step limit,
+// include/mapf_hip.h mapf_set_episode_limit): lq_rollout_kernel_table_limit carries the env's age in a register beside `terminal`,
+// counts truncations in a register beside `counts`, stores the truncated byte with the pending step's other flags and goes back
+// to the start cells on done OR truncated.  Its 512-thread bound leaves the registers for that; the other packed kernels have
+// no limit form.
 #if MAPF_ROLLOUT_TABLE_KERNEL
 template <int Q, int K, bool RECORD, bool SOC, bool COMPACT, bool TERM, int BITMAP, int TABLE>
+#if MAPF_ROLLOUT_LIMIT
+__global__ void __launch_bounds__(512) lq_rollout_kernel_table_limit(const RolloutArgs p, const uint32_t n_agents, const uint32_t bitmap_base, const TablePolicy tp,
+                                                                     const uint32_t table_at, const EpisodeLimit lim) {
+#else
 __global__ void __launch_bounds__(512) lq_rollout_kernel_table(const RolloutArgs p, const uint32_t n_agents, const uint32_t bitmap_base, const TablePolicy tp,
                                                                const uint32_t table_at) {
+#endif
     static_assert(TABLE == 1 || TABLE == 2, "1: action bytes from global memory, 2: from the LDS copy");
     constexpr bool STREAM = false;   // (a table instance runs the launches without streamed actions)
 #else
@@ -51,6 +61,12 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
 #pragma unroll
         for (int i = 0; i < P; ++i) { c[i] = cells.v[i]; g[i] = gl.v[i]; start_c[i] = sc.v[i]; }
     }
+#if MAPF_ROLLOUT_LIMIT
+    // the env's age: read once by every lane of the group (one address per group: each lane decides `back` itself), written
+    // back once by the leader
+    uint32_t age = *at(lim.age, e);
+    const uint32_t max_steps = lim.max_steps;
+#endif
     // (requested HERE, with the state / goal / start rows and ahead of the table copy: a launch's fixed cost -- 8-12 us, a third
     // of a T = 32 launch, profiles/r05_rollout_T_sweep.txt -- is mostly memory round trips in a row, so they travel together)
     const uint8_t *act_lane = STREAM ? p.actions + lane_cell : nullptr;
@@ -228,6 +244,13 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
         rec_lane = (gu16)p.rec_local + lane_cell;
     }
     asm volatile("" : "+v"(wide_lane), "+v"(prob_lane), "+v"(narrow_lane), "+v"(coll_lane), "+v"(rec_lane));
+#if MAPF_ROLLOUT_LIMIT
+    // the truncated byte of a step: EVERY lane of the group stores it through its own pointer (same byte, same address), as the
+    // reward is stored by all lanes but the last -- no exec-masked store in the step loop
+    gu8 trunc_lane = RECORD ? (gu8)lim.rec_truncated + e : nullptr;
+    asm volatile("" : "+v"(trunc_lane));
+    uint32_t p_trunc = 0u, truncs = 0u;   // p_trunc: truncated (0 / 1) of the pending step; truncs: the launch's count
+#endif
 #pragma unroll
     for (uint32_t j = 0; j < kAhead; ++j) asm volatile("" : "+v"(raw[j]));   // consumed here: the loop's waits are counted ones
     asm volatile("" : "+v"(raw_first), "+v"(raw_head[0]), "+v"(raw_head[1]));
@@ -329,6 +352,10 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
                 *prob_lane = prob;
                 *coll_lane = uint8_t(p_status >> 16);
             }
+#if MAPF_ROLLOUT_LIMIT
+            asm volatile("" : "+v"(p_trunc));
+            *trunc_lane = uint8_t(p_trunc);
+#endif
         }
     };
 
@@ -505,6 +532,9 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
                 else wide_lane += step_rows;
                 narrow_lane += step_rows;
                 if (Q == 1) { prob_lane += step_rows; coll_lane += step_rows; }
+#if MAPF_ROLLOUT_LIMIT
+                trunc_lane += step_rows;                       // (not delayed with SYS: only prob trails)
+#endif
             }
         }
         STAMP(1);   // previous step: probability chain, totals, trajectory stores
@@ -684,8 +714,22 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
         // the episode; the returned state is terminal after a vertex collision or on goal (mapf_env.py:210-223), a swap
         // alone is not: bits 0 (vertex), 2 (flipped: on goal) and 3 (was terminal) of code ^ 4
         const uint32_t ended = code16 ^ (4u * 16u);
+#if MAPF_ROLLOUT_LIMIT
+        // The episode step limit, from the group-uniform code (the outcome row is still on its way): a live step ages the episode
+        // (saturating); it is truncated when it did not end the episode -- code 4 is the one code that does not -- and the age has
+        // reached the limit.  A step from a terminal state leaves the age alone and is never truncated.  Done or truncated: start
+        // cells, age 0 (with auto-reset; without it the age is kept and every later live step is truncated again).
+        const uint32_t aged = was_terminal ? age : age + (age != 0xFFFFFFFFu ? 1u : 0u);
+        const uint32_t truncated = (!was_terminal && code16 == 4u * 16u && aged >= max_steps) ? 1u : 0u;
+        truncs += truncated;
+        if (RECORD) p_trunc = truncated;
+        // (as below: one compare of an integer against a wave-uniform constant; the NO_TERMINAL instance runs with auto-reset only)
+        const bool back = MAYBE_TERMINAL ? (ended | truncated) > reset_above : (ended | truncated) != 0u;
+        age = back ? 0u : aged;
+#else
         // (the instance without terminal handling only runs with auto-reset on: one compare against the code itself)
         const bool back = MAYBE_TERMINAL ? ended > reset_above : code16 != 4u * 16u;   // never with auto-reset off
+#endif
 #pragma unroll
         for (int i = 0; i < P; ++i) c[i] = back ? start_c[i] : n[i];
         if (MAYBE_TERMINAL) terminal = back ? start_terminal : min(ended & (13u * 16u), 1u);
@@ -819,6 +863,10 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
         if (ret_p) *ret_p = ret;
         if (epi_p) *epi_p = (p.accumulate ? *epi_p : 0u) + (counts & 0xFFFFu);
         if (col_p) *col_p = (p.accumulate ? *col_p : 0u) + (counts >> 16);
+#if MAPF_ROLLOUT_LIMIT
+        *at(lim.age, e) = age;
+        if (lim.out_truncations) *at(lim.out_truncations, e) = (p.accumulate ? *at(lim.out_truncations, e) : 0u) + truncs;
+#endif
     }
 }
 

@@ -13,7 +13,7 @@ namespace mapf {
 // ONE override: the environment variable MAPF_TUNE, "key=value,key=value,...", read by default_rollout_tuning (mapf_dispatch.hip) at handle creation, so a process
 // can hold handles with different settings (the tests and the A/B tools do).  Keys (include/mapf_hip.h documents them):
 //   quad_lanes, k, quad_min_lanes, oct_min_lanes, mv_lds_max_bytes, scen_table, bitmap_pairs, bitmap_block, bitmap_staycol,
-//   bitmap_delta, step_big, step_block, step_delta, policy_table_lds.
+//   bitmap_delta, step_big, step_block, step_delta, policy_table_lds, limit_packed.
 // An unknown key or a malformed item is an error (*err names it): a typo must not silently measure the default.
 RolloutTuning rollout_tuning_for(int n_cu, const char *text, std::string *err) {
     RolloutTuning t;
@@ -51,6 +51,7 @@ RolloutTuning rollout_tuning_for(int n_cu, const char *text, std::string *err) {
         else if (key == "step_block") t.step_block = unsigned(v);
         else if (key == "step_delta") t.step_delta = int(v);
         else if (key == "policy_table_lds") t.policy_table_lds = v != 0 ? 1 : 0;
+        else if (key == "limit_packed") t.limit_packed = v != 0;
         else { if (err) *err = "MAPF_TUNE: unknown key '" + key + "'"; return t; }
     }
     return t;
@@ -163,7 +164,8 @@ bool plan_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning 
 // ... under the table policy.  Which of the two table forms: the LDS copy whenever image + bitmaps + policy table fit the CU's LDS
 // at the residency the launch would have without it (blocks per CU: what the image alone allows, but no more than the grid
 // gives every CU); MAPF_TUNE policy_table_lds=0 never, =1 whenever one block's segment fits.  DESIGN.md has the measurements.
-bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutTuning &tune_in, const size_t table_bytes, LqPlan *plan) {
+// (limited: the same plan names the limit instance of the same fields, lq_rollout_kernel_table_limit -- one exists for every table instance)
+bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutTuning &tune_in, const size_t table_bytes, LqPlan *plan, const bool limited) {
     RolloutTuning tune = tune_in;
     const int n_cu = tune.n_cu;
     if (args.actions != nullptr || tune.force_k == 8) return false;
@@ -188,6 +190,7 @@ bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutT
         plan->table_at = uint32_t(at16);
         plan->lds_total = with_table;
     }
+    plan->limit = limited;
     return true;
 }
 

@@ -22,11 +22,15 @@ struct LqPlan {
     size_t lds_total = 0;            // the dynamic LDS segment of the launch, <= 160 KB: launch_lds_bytes(form, ...), with the bitmaps (and the policy table)
     bool table_lds = false;          // table policy: the action bytes are staged into LDS behind the image (and the bitmaps) ...
     uint32_t table_at = 0;           // ... at this byte, a multiple of 16 (lds_total then includes them)
+    bool limit = false;              // the family the plan names: lq_rollout_kernel_table_limit (mapf_lq_limit.hip), the table instances under
+                                     // an episode step limit -- the same K, Q, form, block and LDS segment as without it
 };
 bool plan_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, LqPlan *plan);
 // ... under the table policy (args.actions == null): the packed table instances exist for two and four agents per lane over full
 // 16-byte rows and for the 32-agent bitmap form over delta rows, in blocks of at most 512 threads.  false = lane-group kernel.
-bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, size_t table_bytes, LqPlan *plan);
+// (limited: the launch runs under an episode step limit and the handle's tuning has limit_packed=1 -- the plan is the unlimited
+// one, marked `limit`: no LDS is added and the block is unchanged.  Where it declines, the lane-group limit instance takes the launch)
+bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, size_t table_bytes, LqPlan *plan, bool limited = false);
 
 // The forms of the packed single step: the plain step, or a resident grid with the move table in LDS (the values: the kernel's BIG)
 enum class StepForm : int { Plain = 0, FullRows = 1, DeltaRows = 2, DeltaRowsBitmap = 3 };   // (16-byte rows; 4-byte delta rows; ... + per-env occupancy bitmaps)
@@ -58,9 +62,10 @@ struct LgRolloutPlan {
     unsigned block = 0, grid = 0;
     size_t lds_bytes = 0;            // dynamic LDS segment: the move table, or 0 (the launcher raises the limit beyond 32 KB)
 };
-// (limited: the launch runs under an episode step limit (EpisodeLimit, mapf_kernels.hpp).  The limit instances exist in the
-// lane-group family only, so no packed plan and no thread-per-env kernel is consulted and this plan takes the launch: the same
-// plan, marked `limit` and never dense -- the limit instances have the guarded form only)
+// (limited: the launch runs under an episode step limit (EpisodeLimit, mapf_kernels.hpp).  Apart from the packed table instances
+// behind MAPF_TUNE limit_packed=1 (LqPlan::limit) the limit instances exist in the lane-group family only, so no other packed plan
+// and no thread-per-env kernel is consulted and this plan takes the launch: the same plan, marked `limit` and never dense -- the
+// limit instances have the guarded form only)
 LgRolloutPlan plan_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, bool limited = false);
 struct LgStepPlan { int L = 0; bool full = false; bool limit = false; unsigned block = 0, grid = 0; };
 LgStepPlan plan_step_lg(int n_agents, const StepArgs &args, bool limited = false);

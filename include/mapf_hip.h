@@ -112,6 +112,9 @@ typedef struct mapf_desc {
  *   step_block=64|128|256|512   block size of the plain packed single step
  *   policy_table_lds=0|1 the packed rollout under MAPF_POLICY_TABLE: action bytes gathered from global memory / from a copy of the
  *                        policy table staged into LDS behind the table image whenever one block's segment fits (default: by shape)
+ *   limit_packed=0|1     a rollout under MAPF_POLICY_TABLE and an episode step limit (mapf_set_episode_limit): always the lane-group
+ *                        limit kernels (0, the default) / the packed table kernels' limit forms wherever the packed table plan
+ *                        applies (1; not on a handle created with MAPF_FLAG_LANE_GROUP).  Same results either way.
  */
 
 /* Replaces MapfEnv.__init__'s state setup; state = start cells, step index t = 0. */

@@ -14,6 +14,8 @@ and alternate block by block.  --write merges the run into the file under its la
   packed_unlimited     the default dispatch without a limit (a packed kernel): what a limit form of the packed kernels would aim at
   limit_far        (b) N = 2^31: the limit instance runs and the limit is never reached
   limit_64         (c) N = 64
+  limit_far_packed     (b) with MAPF_TUNE=limit_packed=1: the packed table instance's limit form (lq_rollout_kernel_table_limit)
+  limit_64_packed      (c) likewise; both are skipped on a tree whose library does not know the key
   host_loop        (d) the loop the feature replaces, N = 64: T x (torch gather of the table actions, mapf_step with auto-reset, a
                        torch age update, mapf_reset(mask of the envs whose age reached N)), recorded into a hipGraph where that
                        works, else plain launches
@@ -35,7 +37,19 @@ from gym_mapf_amd.envs.vec_env import VecMapfEnv  # noqa: E402
 
 T, N_LIMIT, N_FAR = 256, 64, 1 << 31
 HAS_LIMIT = hasattr(VecMapfEnv, 'set_episode_limit')
-LEGS = {'lg_unlimited': ('quad_lanes=0', None), 'packed_unlimited': (None, None), 'limit_far': (None, N_FAR), 'limit_64': (None, N_LIMIT)}
+LEGS = {'lg_unlimited': ('quad_lanes=0', None), 'packed_unlimited': (None, None), 'limit_far': (None, N_FAR), 'limit_64': (None, N_LIMIT),
+        'limit_far_packed': ('limit_packed=1', N_FAR), 'limit_64_packed': ('limit_packed=1', N_LIMIT)}
+
+
+def has_limit_packed():
+    """does the library know the MAPF_TUNE key limit_packed?  (asked of the planner's debug entry, which parses a tune string without a device)"""
+    import ctypes
+    from gym_mapf_amd import _native as nat
+    lib = nat.load()
+    if not HAS_LIMIT or not hasattr(lib, 'mapf_debug_rollout_plan_limited'):
+        return False
+    out = (ctypes.c_uint64 * 6)()
+    return lib.mapf_debug_rollout_plan_limited(683, 8, 65536, T, 0, 1, 256, b'limit_packed=1', N_LIMIT, out) == 0
 
 
 class RolloutLeg:
@@ -150,8 +164,10 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('bench_episode_limit.py needs a GPU')
-    default = ['lg_unlimited', 'packed_unlimited'] + (['limit_far', 'limit_64'] if HAS_LIMIT else []) + ['host_loop']
-    kinds = [k for k in (args.legs.split(',') if args.legs else default) if k]
+    packed_limit = has_limit_packed()
+    default = ['lg_unlimited', 'packed_unlimited'] + (['limit_far', 'limit_64'] if HAS_LIMIT else []) + \
+              (['limit_far_packed', 'limit_64_packed'] if packed_limit else []) + ['host_loop']
+    kinds = [k for k in (args.legs.split(',') if args.legs else default) if k and (packed_limit or not k.endswith('_packed'))]
     cfg = bench.CONFIGS['c3']
     E = 65536
     grid, _, nbr, start, goal = bench.workload_tables(cfg, E, 0)
@@ -159,7 +175,7 @@ def main():
     rows = lookup[goal.astype(np.int64)].astype(np.uint16)
     A = cfg['agents']
     run = {'tool': 'bench_episode_limit', 'label': args.label, 'device': torch.cuda.get_device_name(0), 'T': T, 'limit': N_LIMIT, 'launches': args.launches,
-           'blocks': args.blocks, 'unit': 'agent-steps/s', 'has_episode_limit': HAS_LIMIT,
+           'blocks': args.blocks, 'unit': 'agent-steps/s', 'has_episode_limit': HAS_LIMIT, 'has_limit_packed': packed_limit,
            'workload': '%s: %s, %d agents, slip %g, %d envs, shortest-path table policy' % (cfg['baseline'], cfg['map'], A, cfg['fail_prob'], E)}
     for record in (False, True):
         legs = [HostLoopLeg(cfg, grid, start, goal, table, rows, record) if k == 'host_loop' else RolloutLeg(k, cfg, grid, start, goal, table, rows, record)

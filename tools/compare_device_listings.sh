@@ -6,7 +6,7 @@
 #   tools/compare_device_listings.sh OLD_TREE NEW_TREE WORK_DIR [JOBS]     (trees: repository roots; exit 0 = all identical)
 #
 # Translation units of NEW_TREE that are not in the list must hold no kernel: their listings are checked for an empty
-# kernel list as well.
+# kernel list as well.  A unit of the list that OLD_TREE does not have yet is compiled from NEW_TREE alone and reported as new.
 set -u
 OLD=$(cd "$1" && pwd); NEW=$(cd "$2" && pwd); WORK=$3; JOBS=${4:-8}
 mkdir -p "$WORK/old" "$WORK/new"
@@ -19,6 +19,8 @@ mapf_transitions|mapf_transitions|
 mapf_lq_step|mapf_lq_step|-mllvm -amdgpu-kernarg-preload-count=14"
 for k in 8 4 2; do for r in 1 0; do UNITS="$UNITS
 mapf_lq_rollout_k${k}_r${r}|mapf_lq_rollout|-DMAPF_LQ_K=$k -DMAPF_LQ_RECORD=$r"; done; done
+for k in 4 2; do for r in 1 0; do UNITS="$UNITS
+mapf_lq_limit_k${k}_r${r}|mapf_lq_limit|-DMAPF_LQ_K=$k -DMAPF_LQ_RECORD=$r"; done; done
 for g in 0 1 2 3; do UNITS="$UNITS
 mapf_kernels_g$g|mapf_kernels|-DMAPF_GROUP=$g"; done
 
@@ -30,7 +32,7 @@ listing() {   # tree, side, name, unit, flags
 export -f listing; export WORK
 {
     echo "$UNITS" | while IFS='|' read -r name unit flags; do
-        [ -s "$WORK/old/$name.s" ] || printf '%s\0%s\0%s\0%s\0%s\0' "$OLD" old "$name" "$unit" "$flags"
+        [ -s "$WORK/old/$name.s" ] || [ ! -f "$OLD/gym-mapf_amd/csrc/$unit.hip" ] || printf '%s\0%s\0%s\0%s\0%s\0' "$OLD" old "$name" "$unit" "$flags"
         printf '%s\0%s\0%s\0%s\0%s\0' "$NEW" new "$name" "$unit" "$flags"
     done
     for f in "$NEW"/gym-mapf_amd/csrc/*.hip; do
@@ -42,7 +44,9 @@ export -f listing; export WORK
 status=0
 echo "device listings, hipcc -S --cuda-device-only, __hip_cuid_* masked: old tree vs new tree"
 while IFS='|' read -r name unit flags; do
-    if cmp -s "$WORK/old/$name.s" "$WORK/new/$name.s" && [ -s "$WORK/new/$name.s" ]; then
+    if [ ! -f "$OLD/gym-mapf_amd/csrc/$unit.hip" ] && [ -s "$WORK/new/$name.s" ]; then
+        echo "new unit   $name.s  $(wc -l < "$WORK/new/$name.s") lines  $(grep -c '^  - .agpr_count:' "$WORK/new/$name.s") kernels"
+    elif cmp -s "$WORK/old/$name.s" "$WORK/new/$name.s" && [ -s "$WORK/new/$name.s" ]; then
         echo "identical  $name.s  $(wc -l < "$WORK/new/$name.s") lines  $(grep -c '^  - .agpr_count:' "$WORK/new/$name.s") kernels"
     else
         echo "DIFFERENT  $name.s"; status=1
