@@ -439,6 +439,7 @@ int mapf_create(const mapf_desc *d, mapf_handle_t *out_handle) {
     std::string error;
     h->tune = mapf::default_rollout_tuning(d->device, &error);
     if (!error.empty()) return fail(MAPF_EINVAL, error);
+    if (d->flags & MAPF_FLAG_LANE_GROUP) h->tune.limit_packed = false;   // (the ONE statement of: such a handle never takes the packed limit instance)
 
     // the host tables (mapf_tables.hip): table image, the move table in its three forms, the scenario table
     mapf::TableImage image;
@@ -691,9 +692,8 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
     a.accumulate = io->accumulate != 0;
     a.start_terminal_any = h->start_terminal_any;
     a.mv_delta8 = h->mv_delta8;
-    // (the episode limit travels beside the argument block too: its kernels are the lane-group family's limit instances -- and,
-    // for a handle with MAPF_TUNE limit_packed=1 that was not created with MAPF_FLAG_LANE_GROUP, the packed table instances'
-    // where their plan applies)
+    // (the episode limit travels beside the argument block too: its kernels are the lane-group family's limit instances -- and the
+    // packed table instances' where the handle's tuning opts into them: launch_rollout_lg picks, as it does without a limit)
     mapf::EpisodeLimit lim{h->age, h->episode_limit, nullptr, nullptr};
     const mapf::EpisodeLimit *limit = h->episode_limit ? &lim : nullptr;
     // (the totals are inputs too when the call accumulates)
@@ -716,14 +716,8 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
         if (int rc = reserve_stand_in(h, h->x_trunc, TE, "rec_truncated")) return rc;
         lim.rec_truncated = static_cast<uint8_t *>(h->x_trunc.ptr);
     }
-    // the packed limit launcher first, where it is opted into; whatever it declines is the lane-group limit instance's, as without the key
-    hipError_t packed_status = hipSuccess;
-    const bool packed_limit = limit && table && h->tune.limit_packed && !(h->flags & MAPF_FLAG_LANE_GROUP) &&
-                              mapf::try_launch_rollout_lq_limit(int(h->A), a, h->tune, h->stream, &packed_status, *table, lim);
-    if (packed_limit) HIP_TRY(packed_status);
-    else
-        HIP_TRY((h->lane_group_rollout || limit) ? mapf::launch_rollout_lg(int(h->A), a, h->tune, h->stream, table, limit)
-                                                 : mapf::launch_rollout(int(h->A), a, h->stream, table));
+    HIP_TRY((h->lane_group_rollout || limit) ? mapf::launch_rollout_lg(int(h->A), a, h->tune, h->stream, table, limit)
+                                             : mapf::launch_rollout(int(h->A), a, h->stream, table));
     after_launch(h, h->last_rollout_kernel, io->n_steps, a.auto_reset);
     if (int rc = fetch_arrays(h, arrays)) return rc;
     if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));

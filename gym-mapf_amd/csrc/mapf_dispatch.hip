@@ -33,30 +33,23 @@ hipError_t launch_rollout(int n_agents, const RolloutArgs &args, hipStream_t str
     MAPF_ROUTE(launch_rollout, n_agents, args, stream, table)
 }
 
-// true when a packed layout took the launch (*err = its status); false = not applicable, use the lane-group kernel
-bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy *table) {
+// true when a packed layout took the launch (*err = its status); false = not applicable, use the lane-group kernel.  Under an
+// episode step limit the packed instances are the table policy's (mapf_lq_limit.hip), opted into by MAPF_TUNE limit_packed=1
+bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy *table,
+                           const EpisodeLimit *limit) {
     LqPlan plan;
-    if (table ? !plan_rollout_lq_table(n_agents, args, tune, table->table_bytes, &plan) : !plan_rollout_lq(n_agents, args, tune, &plan)) return false;
+    if (limit && (args.n_envs == 0 || args.actions != nullptr || !table || !tune.limit_packed)) return false;
+    if (table ? !plan_rollout_lq_table(n_agents, args, tune, table->table_bytes, &plan, limit != nullptr) : !plan_rollout_lq(n_agents, args, tune, &plan)) return false;
     const bool record = args.rec_local != nullptr;
-    const uint32_t A = uint32_t(n_agents);
-    if (plan.K == 8) *err = record ? launch_rollout_lq_k8_r1(plan, args, A, stream, table) : launch_rollout_lq_k8_r0(plan, args, A, stream, table);
-    else if (plan.K == 4) *err = record ? launch_rollout_lq_k4_r1(plan, args, A, stream, table) : launch_rollout_lq_k4_r0(plan, args, A, stream, table);
-    else *err = record ? launch_rollout_lq_k2_r1(plan, args, A, stream, table) : launch_rollout_lq_k2_r0(plan, args, A, stream, table);
-    return true;
-}
-
-// ... under an episode step limit: the packed table instances' limit forms (mapf_lq_limit.hip), with launch_rollout_lg_limit's pre-checks
-bool try_launch_rollout_lq_limit(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy &table,
-                                 const EpisodeLimit &limit) {
-    LqPlan plan;
-    if (args.n_envs == 0 || args.actions != nullptr || !tune.limit_packed || !plan_rollout_lq_table(n_agents, args, tune, table.table_bytes, &plan, true)) return false;
-    const bool record = args.rec_local != nullptr;
-    const uint32_t A = uint32_t(n_agents);
-    // what the kernels rely on: ages, a limit, and the truncated trajectory exactly when the launch records
-    if (!limit.age || limit.max_steps == 0u || (limit.rec_truncated != nullptr) != record) *err = hipErrorInvalidValue;
-    else if (plan.K == 4) *err = record ? launch_rollout_lq_limit_k4_r1(plan, args, A, stream, table, limit) : launch_rollout_lq_limit_k4_r0(plan, args, A, stream, table, limit);
-    else if (plan.K == 2) *err = record ? launch_rollout_lq_limit_k2_r1(plan, args, A, stream, table, limit) : launch_rollout_lq_limit_k2_r0(plan, args, A, stream, table, limit);
-    else *err = hipErrorInvalidValue;   // (plan_rollout_lq_table plans no other K)
+    // the object that holds the plan's instance: [under a limit][8, 4, 2 agents per lane][recording]
+    using Launcher = hipError_t (*)(const LqPlan &, const RolloutArgs &, uint32_t, hipStream_t, const TablePolicy *, const EpisodeLimit *);
+    static constexpr Launcher objects[2][3][2] = {
+        {{launch_rollout_lq_k8_r0, launch_rollout_lq_k8_r1}, {launch_rollout_lq_k4_r0, launch_rollout_lq_k4_r1}, {launch_rollout_lq_k2_r0, launch_rollout_lq_k2_r1}},
+        {{nullptr, nullptr}, {launch_rollout_lq_limit_k4_r0, launch_rollout_lq_limit_k4_r1}, {launch_rollout_lq_limit_k2_r0, launch_rollout_lq_limit_k2_r1}}};
+    const Launcher launch = objects[limit ? 1 : 0][plan.K == 8 ? 0 : (plan.K == 4 ? 1 : 2)][record ? 1 : 0];
+    // what the limit kernels rely on: ages, a limit, and the truncated trajectory exactly when the launch records
+    const bool incomplete = limit && (!limit->age || limit->max_steps == 0u || (limit->rec_truncated != nullptr) != record);
+    *err = (incomplete || !launch) ? hipErrorInvalidValue : launch(plan, args, uint32_t(n_agents), stream, table, limit);   // (no limit object with eight per lane)
     return true;
 }
 

@@ -259,11 +259,12 @@ struct RolloutTuning {
                                      //   memory / from a copy staged into LDS behind the table image whenever that fits (default: by shape)
     bool limit_packed = false;       // limit_packed=1: a table-policy rollout under an episode step limit takes the packed limit instance
                                      //   (mapf_lq_limit.hip) where the packed table plan applies; default 0: always the lane-group limit instance
+                                     //   (mapf_create clears it for a handle created with MAPF_FLAG_LANE_GROUP; read by try_launch_rollout_lq alone)
 };
 RolloutTuning default_rollout_tuning(int device, std::string *err);   // (asks the device, reads MAPF_TUNE: mapf_dispatch.hip)
-// (limit: the episode limit of a handle that has one, or null -- then the lane-group limit instance takes the launch: no packed
-// form and no thread-per-env kernel is consulted, mapf_lg_limit.hip; the one packed family with limit instances is tried by the
-// caller BEFORE these, try_launch_rollout_lq_limit below)
+// (limit: the episode limit of a handle that has one, or null -- then the lane-group limit instance takes the launch, mapf_lg_limit.hip:
+// no thread-per-env kernel is consulted, and of the packed forms only the one family with limit instances, which launch_rollout_lg
+// tries first as it tries the packed forms without a limit)
 hipError_t launch_step_lg(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, const EpisodeLimit *limit = nullptr);
 // packed layout of the single step (mapf_lq_step.hip): true when it took the launch (*err = its status)
 bool try_launch_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err);
@@ -275,29 +276,24 @@ hipError_t launch_rollout_lg_limit(int n_agents, const RolloutArgs &args, const 
                                    const EpisodeLimit &limit);
 hipError_t launch_step_lg_limit(int n_agents, const StepArgs &args, hipStream_t stream, const EpisodeLimit &limit);
 hipError_t launch_reset_ages(uint32_t *age, const uint8_t *mask, uint64_t n_envs, hipStream_t stream);
-// ... under an episode step limit, for a handle whose tuning has limit_packed=1 and a launch that follows the table policy: plans
-// the launch (plan_rollout_lq_table, limited) and routes it to the object of mapf_lq_limit.hip that holds its instance; true when
-// it took the launch (*err = its status, hipErrorInvalidValue when the limit block is incomplete: launch_rollout_lg_limit's
-// pre-checks), false = the lane-group limit instance's
-bool try_launch_rollout_lq_limit(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy &table,
-                                 const EpisodeLimit &limit);
 // packed layout of the fused rollout (2, 4 or 8 agents per lane): plans the launch (mapf_plan.hpp) and routes it to the object that
-// holds its instance (mapf_dispatch.hip); true when it took the launch (*err = its status)
-bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy *table = nullptr);
-// ... the launchers of those objects: mapf_lq_rollout.hip compiled once per (agents per lane, recording) pair; each launches the
-// instance the plan names (table: the table policy, or null)
+// holds its instance (mapf_dispatch.hip); true when it took the launch (*err = its status), false = the lane-group family's.
+// Under an episode step limit the packed instances are the table policy's limit forms (mapf_lq_limit.hip): not applicable unless
+// the handle's tuning has limit_packed=1, the launch follows the table policy and the limited table plan applies; *err =
+// hipErrorInvalidValue when the limit block is incomplete (launch_rollout_lg_limit's pre-checks)
+bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy *table = nullptr,
+                           const EpisodeLimit *limit = nullptr);
+// ... the launchers of those objects: mapf_lq_rollout.hip compiled once per (agents per lane, recording) pair, mapf_lq_limit.hip
+// once per (four or two agents per lane, recording) pair; each launches the instance the plan names through the family's one
+// launcher (mapf_lq_launch.hpp).  ONE signature (table: the table policy, or null; limit: the episode limit, or null): an
+// object without limit instances refuses a limit, the limit objects refuse a launch without a table or without a limit
 struct LqPlan;   // mapf_plan.hpp
-hipError_t launch_rollout_lq_k8_r1(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table);
-hipError_t launch_rollout_lq_k8_r0(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table);
-hipError_t launch_rollout_lq_k4_r1(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table);
-hipError_t launch_rollout_lq_k4_r0(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table);
-hipError_t launch_rollout_lq_k2_r1(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table);
-hipError_t launch_rollout_lq_k2_r0(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table);
-// ... and of mapf_lq_limit.hip, compiled once per (four or two agents per lane, recording) pair: the packed table instances under a limit
-hipError_t launch_rollout_lq_limit_k4_r1(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy &table, const EpisodeLimit &limit);
-hipError_t launch_rollout_lq_limit_k4_r0(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy &table, const EpisodeLimit &limit);
-hipError_t launch_rollout_lq_limit_k2_r1(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy &table, const EpisodeLimit &limit);
-hipError_t launch_rollout_lq_limit_k2_r0(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy &table, const EpisodeLimit &limit);
+#define MAPF_LQ_LAUNCHERS(X) X(rollout_lq_k8_r1) X(rollout_lq_k8_r0) X(rollout_lq_k4_r1) X(rollout_lq_k4_r0) X(rollout_lq_k2_r1) X(rollout_lq_k2_r0) \
+    X(rollout_lq_limit_k4_r1) X(rollout_lq_limit_k4_r0) X(rollout_lq_limit_k2_r1) X(rollout_lq_limit_k2_r0)
+#define X(name) \
+    hipError_t launch_##name(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table, const EpisodeLimit *limit);
+MAPF_LQ_LAUNCHERS(X)
+#undef X
 
 // per-group entry points: group g holds the kernels specialised for A in 4g+1 .. 4g+4
 hipError_t launch_step_g0(int n_agents, const StepArgs &args, hipStream_t stream);

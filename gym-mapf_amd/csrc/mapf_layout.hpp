@@ -46,6 +46,7 @@ constexpr TableFormTraits table_form_traits(TableForm form) {
         default:                         return {false, 0, kMoveCols, uint32_t(sizeof(MoveEntry)), "", ""};   // FullRows
     }
 }
+constexpr const char *kBitmapNote = ", collisions through per-env occupancy bitmaps";   // ... and, in the parentheses, about a form with bitmaps
 // ... and back: the form a kernel instance <COMPACT, BITMAP> reads
 constexpr int find_table_form(bool compact, int bitmap) {
     for (int f = 0; f < kTableForms; ++f)
@@ -68,7 +69,7 @@ constexpr size_t launch_lds_bytes(TableForm form, uint32_t n_cells, unsigned blo
 }
 
 // Which instances of the packed rollout kernels exist: X(K, Q, form) per family (each: streamed actions and the in-kernel policies, every criteria /
-// terminal variant, recording or not).  mapf_lq_rollout.hip generates its dispatch from these lists, in this order; mapf_plan.hip plans nothing else.
+// terminal variant, recording or not).  mapf_lq_launch.hpp generates a family's dispatch from its list, in this order; mapf_plan.hip plans nothing else.
 #define MAPF_LQ_ROLLOUT_INSTANCES(X)                                                                                       \
     X(8, 4, Rows8) X(8, 1, FullRows) X(8, 2, FullRows) X(8, 4, FullRows)                                                   \
     X(4, 8, DeltaRowsBitmap) X(4, 8, FullRowsBitmap) X(4, 8, Rows8x5Bitmap) X(4, 8, Rows8x4Bitmap)                         \

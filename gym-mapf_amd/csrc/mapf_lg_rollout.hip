@@ -36,9 +36,9 @@ struct LgRolloutFamily {
 hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table,
                              const EpisodeLimit *limit) {
     if (args.n_envs == 0) return hipSuccess;
-    if (limit) return launch_rollout_lg_limit(n_agents, args, tune, stream, table, *limit);   // (before any packed plan is consulted)
-    hipError_t packed_status;
-    if (try_launch_rollout_lq(n_agents, args, tune, stream, &packed_status, table)) return packed_status;
+    hipError_t packed_status;   // packed first, else lane-group: under a limit too (the packed table instances' limit forms, where opted into)
+    if (try_launch_rollout_lq(n_agents, args, tune, stream, &packed_status, table, limit)) return packed_status;
+    if (limit) return launch_rollout_lg_limit(n_agents, args, tune, stream, table, *limit);
     const LgRolloutPlan plan = plan_rollout_lg(n_agents, args, tune);
     return table ? launch_lg_rollout<LgRolloutFamily, true>(plan, args, uint32_t(n_agents), stream, *table)
                  : launch_lg_rollout<LgRolloutFamily, false>(plan, args, uint32_t(n_agents), stream);

@@ -368,8 +368,6 @@ constexpr uint32_t kRowBias = kDeltaRowBias;              // (the host-built del
 // index (in doubles from kSlipAt) of a +0.0: the all-equal code's list has ONE entry, so thr[1] of its row is the integer 0
 constexpr uint32_t kZeroFactor = (7u * uint32_t(sizeof(SlipRow)) + uint32_t(offsetof(SlipRow, thr)) + 8u) / 8u;
 static_assert(offsetof(SlipRow, thr) % 8 == 0 && kZeroFactor < 128u, "a zero factor the packed probability indices can name");
-// what a bitmap instance's name (mapf_last_kernel) says in its parentheses
-constexpr const char *kBitmapNote = ", collisions through per-env occupancy bitmaps";
 
 }  // namespace
 }  // namespace mapf

@@ -43,10 +43,7 @@
 // LDS -- the bench configurations and their neighbours.  Everything else (odd agent counts, ragged batches, tables
 // beyond the LDS budget, single steps) stays with mapf_lg_rollout.hip; launch_rollout_lg() picks.  Same stream,
 // same arithmetic, same outputs: the parity tests run all layouts against the oracle.
-#include "mapf_lq.hpp"
-#include "mapf_plan.hpp"
-
-#include <type_traits>
+#include "mapf_lq_launch.hpp"
 
 namespace mapf {
 
@@ -56,6 +53,7 @@ namespace {
 // in-kernel policy.  Memory pipeline and store scheme as lg_rollout_kernel<DENSE>.
 // (the LDS image -- kSlipAt, kOutcomeAt, kMoveAt, the column counts and entry sizes of each table form: mapf_layout.hpp)
 // (kRowBias, kZeroFactor -- the bias of a table row's slip-row offset, the index of a zero factor: mapf_lq.hpp, shared with mapf_lq_limit.hip)
+// (the launcher: mapf_lq_launch.hpp, shared with mapf_lq_limit.hip too)
 
 // TERM = an env may be terminal when a step begins.  With auto-reset on and no env whose START state is itself
 // terminal (the handle knows: mapf_create looks) that cannot happen after the launch's first step -- a done env is back
@@ -80,93 +78,25 @@ namespace {
 
 #undef env_id
 
-// One family of instances, launched as planned: FORM's traits (mapf_layout.hpp) give the kernel's (COMPACT, BITMAP) and what the
-// kernel's name says; the plan (mapf_plan.hpp) gives the block, where the bitmaps begin (lds_bytes) and the launch's dynamic LDS segment (lds_total)
-template <int Q, int K, bool RECORD, bool STREAM, TableForm FORM>
-hipError_t launch_impl(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream) {
-    constexpr TableFormTraits form = table_form_traits(FORM);
-    constexpr bool COMPACT = form.compact; constexpr int BITMAP = form.bitmap;   // the kernel's template arguments
-    // (criteria, may-be-terminal): the instance without terminal handling exists for Makespan only
-    const bool term = !(args.auto_reset && !args.start_terminal_any);
-    auto kern = args.c.criteria != 0u ? lq_rollout_kernel<Q, K, RECORD, STREAM, true, COMPACT, true, BITMAP>
-                : term            ? lq_rollout_kernel<Q, K, RECORD, STREAM, false, COMPACT, true, BITMAP>
-                                  : lq_rollout_kernel<Q, K, RECORD, STREAM, false, COMPACT, false, BITMAP>;
-    if (plan.lds_total > 32 * 1024) {
-        // (this kernel has no static LDS object: its dynamic segment may be the CU's whole 160 KB -- the limit every form's
-        // "does it fit" test in plan_rollout_lq compares against)
-        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(kLdsBytes))) return e;
-    }
-    const unsigned block = plan.block, grid = unsigned(args.n_envs / (block / unsigned(Q)));
-    note_kernel("lq_rollout_kernel<Q=%d,K=%d,%s,%s,%s%s%s%s> block=%u (packed layout: %d agents per lane%s%s)", Q, K, RECORD ? "RECORD" : "TOTALS",
-                STREAM ? "STREAM" : "POLICY", args.c.criteria != 0u ? "SOC" : "MAKESPAN", COMPACT ? ",COMPACT" : "",
-                (args.c.criteria == 0u && !term) ? ",NO_TERMINAL" : "", form.tag, block, K, form.note, BITMAP ? kBitmapNote : "");
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), plan.lds_total, stream, args, A, uint32_t(plan.lds_bytes));   // (the bitmaps follow the table)
-    return hipGetLastError();
-}
-
-// the launcher of the table instances (plan_rollout_lq_table's plan: the bitmaps follow the image, the policy table follows them at table_at)
-template <int Q, int K, bool RECORD, TableForm FORM>
-hipError_t launch_impl_table(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy &tp) {
-    constexpr TableFormTraits form = table_form_traits(FORM);
-    constexpr bool COMPACT = form.compact; constexpr int BITMAP = form.bitmap;
-    const bool term = !(args.auto_reset && !args.start_terminal_any), table_lds = plan.table_lds;
-    auto pick = [&](auto tag) {
-        constexpr int T = decltype(tag)::value;
-        return args.c.criteria != 0u ? lq_rollout_kernel_table<Q, K, RECORD, true, COMPACT, true, BITMAP, T>
-               : term            ? lq_rollout_kernel_table<Q, K, RECORD, false, COMPACT, true, BITMAP, T>
-                                 : lq_rollout_kernel_table<Q, K, RECORD, false, COMPACT, false, BITMAP, T>;
-    };
-    auto kern = table_lds ? pick(std::integral_constant<int, 2>{}) : pick(std::integral_constant<int, 1>{});
-    const unsigned block = plan.block;
-    if (plan.lds_total > kLdsBytes || block > 512u) return hipErrorInvalidValue;   // (the table instances are built for 512 threads)
-    if (plan.lds_total > 32 * 1024) {
-        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(kLdsBytes))) return e;
-    }
-    const unsigned grid = unsigned(args.n_envs / (block / unsigned(Q)));
-    note_kernel("lq_rollout_kernel_table<Q=%d,K=%d,%s,TABLE,%s%s%s%s,%s> block=%u (packed layout: %d agents per lane%s%s; table policy: %u action bytes %s)", Q, K,
-                RECORD ? "RECORD" : "TOTALS", args.c.criteria != 0u ? "SOC" : "MAKESPAN", COMPACT ? ",COMPACT" : "",
-                (args.c.criteria == 0u && !term) ? ",NO_TERMINAL" : "", form.tag, table_lds ? "TABLE_LDS" : "TABLE_GLOBAL", block, K,
-                form.note, BITMAP ? kBitmapNote : "", tp.table_bytes, table_lds ? "staged into LDS behind the image" : "gathered from global memory");
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), plan.lds_total, stream, args, A, uint32_t(plan.lds_bytes), tp, plan.table_at);
-    return hipGetLastError();
-}
-
-// The instances of one object -- K agents per lane, recording or not -- by the lists of mapf_layout.hpp (what lq_rollout_instance_exists
-// answers from): a launch whose (Q, form) is in none of this K's lines is refused.  (A template, so that the lines of the other
-// K's are discarded, not instantiated.)
-template <int K, bool R>
-hipError_t launch_planned(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table) {
-    if (table) {
-#define X(KK, QQ, FF)                                                                                                                        \
-    if constexpr (KK == K) {                                                                                                                 \
-        if (plan.Q == QQ && plan.form == TableForm::FF) return launch_impl_table<QQ, K, R, TableForm::FF>(plan, args, A, stream, *table);    \
-    }
-        MAPF_LQ_ROLLOUT_TABLE_INSTANCES(X)
-#undef X
-        return hipErrorInvalidValue;
-    }
-#define X(KK, QQ, FF)                                                                                                                        \
-    if constexpr (KK == K) {                                                                                                                 \
-        if (plan.Q == QQ && plan.form == TableForm::FF) return args.actions ? launch_impl<QQ, K, R, true, TableForm::FF>(plan, args, A, stream)     \
-                                                                            : launch_impl<QQ, K, R, false, TableForm::FF>(plan, args, A, stream);   \
-    }
-    MAPF_LQ_ROLLOUT_INSTANCES(X)
-#undef X
-    return hipErrorInvalidValue;
-}
+// The instances without an episode limit: lq_rollout_kernel (streamed actions, the in-kernel policies) and lq_rollout_kernel_table
+struct LqFamily {
+    static constexpr bool kTable = false, kLimit = false;
+    template <int Q, int K, bool RECORD, bool STREAM, bool SOC, bool COMPACT, bool TERM, int BITMAP, int TABLE>
+    static auto kernel() { return lq_rollout_kernel<Q, K, RECORD, STREAM, SOC, COMPACT, TERM, BITMAP>; }
+};
+struct LqTableFamily {
+    static constexpr bool kTable = true, kLimit = false;
+    template <int Q, int K, bool RECORD, bool STREAM, bool SOC, bool COMPACT, bool TERM, int BITMAP, int TABLE>
+    static auto kernel() { return lq_rollout_kernel_table<Q, K, RECORD, SOC, COMPACT, TERM, BITMAP, TABLE>; }
+};
 
 }  // namespace
 
-// This file is compiled once per (agents per lane, recording) pair -- -DMAPF_LQ_K=8|4|2 -DMAPF_LQ_RECORD=1|0 -- so that
-// its kernel instances build in parallel; each object exports one launcher (prototypes: mapf_kernels.hpp; the router: mapf_dispatch.hip).
-#if !defined(MAPF_LQ_K) || !defined(MAPF_LQ_RECORD)
-#error "compile with -DMAPF_LQ_K=8|4|2 -DMAPF_LQ_RECORD=1|0"
-#endif
-#define MAPF_LQ_CAT3(a, b, c) a##b##_r##c
-#define MAPF_LQ_NAME(k, r) MAPF_LQ_CAT3(launch_rollout_lq_k, k, r)
-
-hipError_t MAPF_LQ_NAME(MAPF_LQ_K, MAPF_LQ_RECORD)(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table) {
-    return launch_planned<MAPF_LQ_K, MAPF_LQ_RECORD != 0>(plan, args, A, stream, table);
+// (table: the table policy, or null; this object has no limit instances)
+MAPF_LQ_LAUNCHER(launch_rollout_lq_k) {
+    if (limit) return hipErrorInvalidValue;
+    return table ? launch_lq_rollout<LqTableFamily, kLqK, kLqRecord>(plan, args, A, stream, table)
+                 : launch_lq_rollout<LqFamily, kLqK, kLqRecord>(plan, args, A, stream, table);
 }
 
 }  // namespace mapf

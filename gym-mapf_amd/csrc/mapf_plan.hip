@@ -194,6 +194,21 @@ bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutT
     return true;
 }
 
+// (the table family's two parts: behind the form's tag, and at the note's end)
+void lq_rollout_kernel_name(char *name, const LqPlan &plan, bool record, bool streamed, bool table_policy, bool soc, bool may_be_terminal, uint32_t table_bytes) {
+    const TableFormTraits form = table_form_traits(plan.form);
+    char tag[32] = "", note[128] = "";
+    if (table_policy) {
+        snprintf(tag, sizeof(tag), ",%s%s", plan.table_lds ? "TABLE_LDS" : "TABLE_GLOBAL", plan.limit ? ",LIMIT" : "");
+        snprintf(note, sizeof(note), "%s; table policy: %u action bytes %s", plan.limit ? "; episode step limit" : "", table_bytes,
+                 plan.table_lds ? "staged into LDS behind the image" : "gathered from global memory");
+    }
+    snprintf(name, kKernelNameBytes, "lq_rollout_kernel%s%s<Q=%d,K=%d,%s,%s,%s%s%s%s%s> block=%u (packed layout: %d agents per lane%s%s%s)", table_policy ? "_table" : "",
+             plan.limit ? "_limit" : "", plan.Q, plan.K, record ? "RECORD" : "TOTALS", table_policy ? "TABLE" : (streamed ? "STREAM" : "POLICY"), soc ? "SOC" : "MAKESPAN",
+             form.compact ? ",COMPACT" : "", (!soc && !may_be_terminal) ? ",NO_TERMINAL" : "", form.tag, tag, plan.block, plan.K, form.note,
+             form.bitmap ? kBitmapNote : "", note);
+}
+
 // The packed single step (mapf_lq_step.hip): full groups of K = 4 or 2 agents per lane, Q = A / K lanes per env a power of two.
 // The forms are tried in this order, and a form whose divisibility test fails falls through to the next one: eight agents per
 // lane over the LDS table, delta rows (with or without bitmaps), BIG, the plain step.  false = not applicable, use lg_step_kernel.

@@ -13,7 +13,7 @@ RolloutTuning rollout_tuning_for(int n_cu, const char *text, std::string *err);
 
 // What try_launch_rollout_lq decides before it launches, from the launch's shape (args.c.n_cells, n_envs, n_steps, c.top_tie,
 // actions / mv4 / mv_delta8 present or not) and the tuning (its n_cu included): false = no packed form applies.  The whole plan:
-// the launchers of mapf_lq_rollout.hip are handed nothing else.
+// the packed family's one launcher (mapf_lq_launch.hpp) is handed nothing else.
 struct LqPlan {
     int K = 0, Q = 0;                // agents per lane, lanes per env
     TableForm form = TableForm::FullRows;   // how the move table lies in LDS (mapf_layout.hpp; DESIGN.md 4.1 lists the six forms)
@@ -31,6 +31,13 @@ bool plan_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning 
 // (limited: the launch runs under an episode step limit and the handle's tuning has limit_packed=1 -- the plan is the unlimited
 // one, marked `limit`: no LDS is added and the block is unchanged.  Where it declines, the lane-group limit instance takes the launch)
 bool plan_rollout_lq_table(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, size_t table_bytes, LqPlan *plan, bool limited = false);
+// TERM of the packed rollout instances: may an env be terminal when a step of the launch begins?  With auto-reset on and no env whose
+// START state is itself terminal it cannot -- the ONE statement of that rule: the instance pick and the name read this value
+inline bool rollout_may_be_terminal(const RolloutArgs &args) { return !(args.auto_reset && !args.start_terminal_any); }
+// The name the launcher notes for a packed plan (mapf_last_kernel; kKernelNameBytes as the lane-group names below), from the plan
+// and what the launch says: recording or not; streamed actions, the in-kernel policy or the table policy (then table_bytes action
+// bytes); criteria; may-be-terminal.  A limit plan's name says _table_limit, LIMIT and "; episode step limit".
+void lq_rollout_kernel_name(char *name, const LqPlan &plan, bool record, bool streamed, bool table_policy, bool soc, bool may_be_terminal, uint32_t table_bytes);
 
 // The forms of the packed single step: the plain step, or a resident grid with the move table in LDS (the values: the kernel's BIG)
 enum class StepForm : int { Plain = 0, FullRows = 1, DeltaRows = 2, DeltaRowsBitmap = 3 };   // (16-byte rows; 4-byte delta rows; ... + per-env occupancy bitmaps)

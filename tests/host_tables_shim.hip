@@ -93,24 +93,47 @@ int shim_plan_step(uint32_t n_cells, int n_agents, uint64_t n_envs, int has_delt
     return 1;
 }
 
-// plan_rollout_lq_table over a shape (a launch without streamed actions, under a policy table of table_bytes): out = K, Q, form,
-// block, lds_bytes, lds_total, table_lds, table_at; 1 = a packed table instance, 0 = none, -1 = bad tune
-int shim_plan_rollout_table(uint32_t n_cells, int n_agents, uint64_t n_envs, uint32_t n_steps, int has_delta_rows, uint64_t table_bytes, int n_cu,
-                            const char *tune, uint64_t out[8]) {
-    std::string err;
-    const RolloutTuning t = rollout_tuning_for(n_cu, tune, &err);
-    if (!err.empty()) return -1;
+// (only the fields a rollout plan reads: the shape, and which optional arrays are present -- never dereferenced)
+static RolloutArgs rollout_shape(uint32_t n_cells, uint64_t n_envs, uint32_t n_steps, int has_delta_rows, bool streamed) {
     static const uint32_t present = 0;
     RolloutArgs args{};
     args.c.n_cells = n_cells;
     args.n_envs = n_envs;
     args.n_steps = n_steps;
+    args.actions = streamed ? reinterpret_cast<const uint8_t *>(&present) : nullptr;
     args.mv_delta8 = has_delta_rows != 0;
     args.mv4 = has_delta_rows ? &present : nullptr;
+    return args;
+}
+
+// plan_rollout_lq_table over a shape (a launch without streamed actions, under a policy table of table_bytes; limited: under an
+// episode step limit with limit_packed=1): out = K, Q, form, block, lds_bytes, lds_total, table_lds, table_at, limit;
+// 1 = a packed table instance, 0 = none, -1 = bad tune; *limit_packed (may be null) = what the tune string says of the key
+int shim_plan_rollout_table(uint32_t n_cells, int n_agents, uint64_t n_envs, uint32_t n_steps, int has_delta_rows, uint64_t table_bytes, int n_cu,
+                            const char *tune, int limited, uint64_t out[9], int *limit_packed) {
+    std::string err;
+    const RolloutTuning t = rollout_tuning_for(n_cu, tune, &err);
+    if (!err.empty()) return -1;
+    if (limit_packed) *limit_packed = t.limit_packed ? 1 : 0;
     LqPlan plan;
-    if (!plan_rollout_lq_table(n_agents, args, t, size_t(table_bytes), &plan)) return 0;
+    if (!plan_rollout_lq_table(n_agents, rollout_shape(n_cells, n_envs, n_steps, has_delta_rows, false), t, size_t(table_bytes), &plan, limited != 0)) return 0;
     out[0] = uint64_t(plan.K); out[1] = uint64_t(plan.Q); out[2] = uint64_t(int(plan.form)); out[3] = plan.block; out[4] = plan.lds_bytes;
-    out[5] = plan.lds_total; out[6] = plan.table_lds ? 1u : 0u; out[7] = plan.table_at;
+    out[5] = plan.lds_total; out[6] = plan.table_lds ? 1u : 0u; out[7] = plan.table_at; out[8] = plan.limit ? 1u : 0u;
+    return 1;
+}
+
+// The packed plan of a one-step launch as try_launch_rollout_lq makes it (policy: 0 streamed actions, 1 the in-kernel policy, 2 the
+// table policy of table_bytes; limited: ... under an episode step limit) and the name the launcher notes for it (kKernelNameBytes);
+// 1 = planned, 0 = no packed form, -1 = bad tune
+int shim_lq_rollout_name(uint32_t n_cells, int n_agents, uint64_t n_envs, int has_delta_rows, uint64_t table_bytes, int n_cu, const char *tune, int policy,
+                         int limited, int record, int soc, int may_be_terminal, char *name) {
+    std::string err;
+    const RolloutTuning t = rollout_tuning_for(n_cu, tune, &err);
+    if (!err.empty()) return -1;
+    const RolloutArgs args = rollout_shape(n_cells, n_envs, 1, has_delta_rows, policy == 0);
+    LqPlan plan;
+    if (policy == 2 ? !plan_rollout_lq_table(n_agents, args, t, size_t(table_bytes), &plan, limited != 0) : !plan_rollout_lq(n_agents, args, t, &plan)) return 0;
+    lq_rollout_kernel_name(name, plan, record != 0, policy == 0, policy == 2, soc != 0, may_be_terminal != 0, uint32_t(table_bytes));
     return 1;
 }
 
@@ -155,6 +178,14 @@ int shim_plan_limit_step_lg(int n_agents, uint64_t n_envs, int ext_uniforms, uin
 // does the launcher hold the packed rollout instance (K, Q, form)?  (table: of lq_rollout_kernel_table)
 int shim_rollout_instance_exists(int K, int Q, int form, int table) {
     return form >= 0 && form < kTableForms && lq_rollout_instance_exists(K, Q, TableForm(form), table != 0) ? 1 : 0;
+}
+// how many table instances (MAPF_LQ_ROLLOUT_TABLE_INSTANCES) there are with K agents per lane (0: in all)
+int shim_table_instance_count(int K) {
+    int n = 0;
+#define X(KK, QQ, FF) n += (KK == K || K == 0) ? 1 : 0;
+    MAPF_LQ_ROLLOUT_TABLE_INSTANCES(X)
+#undef X
+    return n;
 }
 
 }  // extern "C"

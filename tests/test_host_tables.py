@@ -54,7 +54,10 @@ def load_shim(path):
     lib.shim_greedy_cells.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
     lib.shim_plan_step.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p]
     lib.shim_plan_rollout_table.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int,
-                                            ctypes.c_char_p, ctypes.c_void_p]
+                                            ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    lib.shim_lq_rollout_name.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p] + \
+        [ctypes.c_int] * 5 + [ctypes.c_char_p]
+    lib.shim_table_instance_count.argtypes = [ctypes.c_int]
     if hasattr(lib, 'shim_plan_rollout_lg'):
         lib.shim_plan_rollout_lg.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_char_p]
         lib.shim_plan_step_lg.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p]

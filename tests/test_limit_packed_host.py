@@ -13,32 +13,17 @@ import limit_packed_cases as lp
 from conftest import ROOT
 from gym_mapf_amd import _native as nat
 from test_cabi_and_host import ROLLOUT_PLAN_CELLS
+from test_host_tables import shim  # noqa: F401  (the host shim, built once per run)
 from test_plan_decisions import TABLE_AGENTS, TABLE_BYTES, TABLE_ENVS, TABLE_TUNES
 
 CSRC = os.path.join(ROOT, 'gym-mapf_amd', 'csrc')
 LDS = 160 * 1024
 
 
-@pytest.fixture(scope='module')
-def shim(tmp_path_factory):
-    """tests/limit_packed_shim.hip with the planner, built like tests/test_host_tables.py's build_shim"""
-    out = str(tmp_path_factory.mktemp('limit_packed') / 'liblimit_packed_shim.so')
-    cmd = ['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-shared', '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC,
-           os.path.join(ROOT, 'tests', 'limit_packed_shim.hip'), os.path.join(CSRC, 'mapf_plan.hip'), '-o', out]
-    proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert proc.returncode == 0, proc.stdout.decode('utf-8', 'replace')[-3000:]
-    lib = ctypes.CDLL(out)
-    lib.lp_plan_rollout_table.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p,
-                                          ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-    lib.lp_table_instance_exists.argtypes = [ctypes.c_int] * 3
-    lib.lp_table_instance_count.argtypes = [ctypes.c_int]
-    return lib
-
-
 def _plan(shim, V, A, E, tune, limited, n_steps=64, delta=1, table_bytes=None):
     """(rc, the nine plan fields, what the tune string says of limit_packed)"""
     out, key = (ctypes.c_uint64 * 9)(), ctypes.c_int(-1)
-    rc = shim.lp_plan_rollout_table(V, A, E, n_steps, delta, V * V if table_bytes is None else table_bytes, lp.N_CU, tune, int(limited), out, ctypes.byref(key))
+    rc = shim.shim_plan_rollout_table(V, A, E, n_steps, delta, V * V if table_bytes is None else table_bytes, lp.N_CU, tune, int(limited), out, ctypes.byref(key))
     return rc, tuple(out), key.value
 
 
@@ -71,7 +56,7 @@ def test_every_case_plans_the_instance_it_names(shim, case):
         assert rc == 1, (c.id, table_lds)
         K, Q, form, block, image, total, lds, table_at, mark = limited
         assert (K, Q, form, block, lds, mark) == (c.K, c.Q, c.form, c.block, table_lds, 1), (c.id, limited)
-        assert c.A == K * Q and c.E * Q == 1024 and total <= LDS and shim.lp_table_instance_exists(K, Q, form) == 1
+        assert c.A == K * Q and c.E * Q == 1024 and total <= LDS and shim.shim_rollout_instance_exists(K, Q, form, 1) == 1
         rc, plain, _ = _plan(shim, lp.V, c.A, c.E, tune, False)
         assert rc == 1 and plain == limited[:8] + (0,), (c.id, plain, limited)
         # (without the key in the string the planner answers the same: the key is the dispatch's condition, not the planner's)
@@ -83,9 +68,9 @@ def test_every_case_plans_the_instance_it_names(shim, case):
 
 
 def test_the_case_table_covers_every_table_instance_once(shim):
-    assert shim.lp_table_instance_count(0) == 9 and shim.lp_table_instance_count(4) == 5 and shim.lp_table_instance_count(2) == 4
+    assert shim.shim_table_instance_count(0) == 9 and shim.shim_table_instance_count(4) == 5 and shim.shim_table_instance_count(2) == 4
     assert len({(c.K, c.Q, c.form) for c in lp.CASES}) == len(lp.CASES) == 9
-    assert all(shim.lp_table_instance_exists(c.K, c.Q, c.form) for c in lp.CASES)
+    assert all(shim.shim_rollout_instance_exists(c.K, c.Q, c.form, 1) for c in lp.CASES)
 
 
 def test_whatever_is_planned_limited_is_a_table_instance_within_the_block_and_lds_bounds(shim):
@@ -108,7 +93,7 @@ def test_whatever_is_planned_limited_is_a_table_instance_within_the_block_and_ld
                             K, Q, form, block, image, total, lds, table_at, mark = limited
                             forms.add(form)
                             assert mark == 1 and limited[:8] == plain[1][:8] and plain[1][8] == 0, ctx
-                            assert shim.lp_table_instance_exists(K, Q, form) == 1 and K in (2, 4), ctx
+                            assert shim.shim_rollout_instance_exists(K, Q, form, 1) == 1 and K in (2, 4), ctx
                             assert block <= 512 and E % (block // Q) == 0 and 1024 < image <= total <= LDS, ctx
     assert n_planned > 20000 and forms == {lp.FULL_ROWS, lp.DELTA_ROWS_BITMAP}, (n_planned, forms)
 

@@ -21,7 +21,14 @@ The limit instances of the lane-group family (mapf_lg_limit.hip) are named by th
 plans and full names over LIMIT_* below are compared with tests/golden/plan_decisions_limit.json, recorded on the CPU from the
 commit that still had a planner and name functions of their own for them (tests/golden/generation_info.json says how):
 
-    python tests/test_plan_decisions.py --record-limit [OUT.json]"""
+    python tests/test_plan_decisions.py --record-limit [OUT.json]
+
+The packed rollout launches are named by lq_rollout_kernel_name.  tests/golden/lq_kernel_names.json holds what mapf_last_kernel said
+after a one-step rollout of every launch of lq_launches() below -- every packed instance list entry, every policy, criteria /
+terminal variant, recording or not, both table forms, with and without the limit -- on an MI355X, from the library of the commit
+whose launchers still formatted these names themselves (MAPF_HIP_LIB; generation_info.json says how):
+
+    python tests/test_plan_decisions.py --record-lq-names [OUT.json]"""
 import ctypes
 import hashlib
 import json
@@ -64,6 +71,12 @@ LIMIT_AGENTS = (1, 2, 3, 5, 8, 16, 17, 32, 33, 64, 128)
 LIMIT_ENVS = (1, 63, 64, 4096, 65536)
 LIMIT_CELLS = (16, 683, 3300)
 KERNEL_NAME_BYTES = 160                                                # what mapf_last_kernel keeps of a name (the terminator included)
+# the packed names: every launch on the 20 x 20 map of the limit cases (V = 341, delta rows present), a table of LQ_TABLE_ROWS rows
+FIXTURE_LQ_NAMES = os.path.join(GOLDEN, 'lq_kernel_names.json')
+LQ_TABLE_ROWS = 64
+# (criteria, auto-reset): no env of these launches starts terminal, so a launch may meet a terminal env exactly without auto-reset
+LQ_VARIANTS = {'SOC': ('SoC', True), 'MAKESPAN': ('Makespan', False), 'NO_TERMINAL': ('Makespan', True)}
+LQ_POLICIES = ('STREAM', 'POLICY', 'TABLE')
 
 
 def _name(tune):
@@ -94,7 +107,7 @@ def rollout_digests(lib):
 
 def table_plans(shim_lib):
     """plan_rollout_lq_table over the same cells: yields (group, result or None)"""
-    out = (ctypes.c_uint64 * 8)()
+    out = (ctypes.c_uint64 * 9)()
     for tune in TABLE_TUNES:
         for A in TABLE_AGENTS:
             for mult in TABLE_BYTES:
@@ -102,9 +115,9 @@ def table_plans(shim_lib):
                     group = '%s A=%d table_bytes=%dV delta=%d' % (_name(tune), A, mult, delta)
                     for E in TABLE_ENVS:
                         for V in ROLLOUT_PLAN_CELLS:
-                            rc = shim_lib.shim_plan_rollout_table(V, A, E, 64, delta, mult * V, 256, tune, out)
-                            assert rc in (0, 1), (rc, tune)
-                            yield group, (V, E, tuple(out)) if rc else None
+                            rc = shim_lib.shim_plan_rollout_table(V, A, E, 64, delta, mult * V, 256, tune, 0, out, None)
+                            assert rc in (0, 1) and (not rc or out[8] == 0), (rc, tune)
+                            yield group, (V, E, tuple(out)[:8]) if rc else None   # (the recorded eight fields; the ninth marks a limit plan)
 
 
 def table_digests(shim_lib):
@@ -199,6 +212,77 @@ def limit_plans(shim_lib):
                 assert shim_lib.shim_plan_limit_step_lg(A, E, uniforms, out, name) == 1
                 steps['A=%d E=%d uniforms=%d' % (A, E, uniforms)] = '%s|%s' % (' '.join(str(x) for x in out[:4]), name.value.decode())
     return {'rollout': rollouts, 'step': steps}
+
+
+def lq_launches():
+    """the handles of the packed-name fixture: (key, family, A, E, tune text, policy, limited, the parts the case says the names hold)"""
+    import limit_packed_cases as lp
+    import totals_cases as tc
+    for c in tc.PACKED_CASES:
+        for policy in LQ_POLICIES[:2]:
+            yield '%s %s' % (c.id, policy), 'plain', c.A, c.E, c.tune_text(), policy, False, ('<Q=%d,K=%d,' % (c.Q, c.K),) + tc.FORM_NAME[c.form]
+    for c in lp.CASES:
+        for table_lds in lp.TABLE_LDS:
+            for limited in (False, True):
+                tune = c.tune_bytes(table_lds, limit_packed=limited).decode()
+                parts = c.name_parts(table_lds) if limited else ('lq_rollout_kernel_table<Q=%d,K=%d,' % (c.Q, c.K),) + c.name_parts(table_lds)[1:2] + c.name_parts(table_lds)[3:]
+                yield '%s lds=%d limit=%d' % (c.id, table_lds, limited), 'table', c.A, c.E, tune, 'TABLE', limited, parts
+
+
+def launch_lq(grid, A, E, tune, policy, limited, criteria, runs):
+    """a handle of that shape under `tune`, and the names of its one-step rollouts `runs` = [(auto_reset, record), ...]"""
+    import numpy as np
+    from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
+    V, outer_tune = len(grid.tables()[0]), os.environ.pop('MAPF_TUNE', None)
+    os.environ['MAPF_TUNE'] = tune                              # (read when the handle is created)
+    try:
+        env = VecMapfEnv(grid, A, None, None, 0.2, -1000.0, 100.0, -1.0, OptimizationCriteria[criteria], n_envs=E, start_local=np.arange(A), goal_local=np.arange(A) + 1)
+    finally:
+        os.environ.pop('MAPF_TUNE', None)
+        if outer_tune is not None:
+            os.environ['MAPF_TUNE'] = outer_tune
+    try:
+        if policy == 'TABLE':
+            env.set_policy('table', table=np.zeros((LQ_TABLE_ROWS, V), np.uint8), rows=np.zeros(A, np.uint16))
+        if limited:
+            env.set_episode_limit(4)
+        names = []
+        for auto_reset, record in runs:
+            env.rollout(1, actions=np.zeros((1, E, A), np.uint8) if policy == 'STREAM' else None, auto_reset=auto_reset, record=record)
+            names.append(env.last_kernel('rollout'))
+        return names
+    finally:
+        env.close()
+
+
+def record_lq_names(n_cu):
+    """{'n_cu', 'launches': {key: {'V', 'A', 'E', 'tune', 'delta', 'table_bytes', 'policy', 'limited', 'names': {'<variant> <RECORD|TOTALS>': full
+    name}}}}: what the CPU side needs to plan the same launch, and what the GPU side said"""
+    import episode_limit_cases as ec
+    grid, found = ec.random_map(3), {}
+    V = len(grid.tables()[0])
+    for key, family, A, E, tune, policy, limited, parts in lq_launches():
+        names = {}
+        for criteria in ('SoC', 'Makespan'):                    # (one handle per criteria)
+            runs = [(variant, auto_reset, record) for variant, (c, auto_reset) in LQ_VARIANTS.items() if c == criteria for record in (True, False)]
+            for (variant, _, record), name in zip(runs, launch_lq(grid, A, E, tune, policy, limited, criteria, [run[1:] for run in runs])):
+                says = (',RECORD,' if record else ',TOTALS,', ',%s,' % policy, ',SOC' if criteria == 'SoC' else ',MAKESPAN')
+                assert all(part in name for part in parts + says) and ('NO_TERMINAL' in name) == (variant == 'NO_TERMINAL'), (key, variant, name, parts)
+                names['%s %s' % (variant, 'RECORD' if record else 'TOTALS')] = name
+        print('launched %s' % key, flush=True)
+        found[key] = {'V': V, 'A': A, 'E': E, 'tune': tune, 'delta': 1, 'table_bytes': LQ_TABLE_ROWS * V if policy == 'TABLE' else 0, 'policy': policy,
+                      'limited': int(limited), 'names': names}
+    return {'n_cu': n_cu, 'launches': found}
+
+
+def planned_lq_name(shim_lib, n_cu, launch, variant, record):
+    """the same launch through the planner and lq_rollout_kernel_name (the shim): the name, or None where no packed form applies"""
+    name = ctypes.create_string_buffer(2 * KERNEL_NAME_BYTES)
+    criteria, auto_reset = LQ_VARIANTS[variant]
+    rc = shim_lib.shim_lq_rollout_name(launch['V'], launch['A'], launch['E'], launch['delta'], launch['table_bytes'], n_cu, launch['tune'].encode() or None,
+                                       LQ_POLICIES.index(launch['policy']), launch['limited'], int(record), int(criteria == 'SoC'), int(not auto_reset), name)
+    assert rc in (0, 1), (rc, launch)
+    return name.value.decode() if rc else None
 
 
 class LaneGroupLauncher:
@@ -377,6 +461,49 @@ def test_limit_plans_and_names_are_the_recorded_ones(shim):  # noqa: F811
         assert fields.split(' ')[3] == '0' and '_limit_guarded<' in name and ',LIMIT> ' in name and len(name) < KERNEL_NAME_BYTES, line
 
 
+def _lq_fixture():
+    with open(FIXTURE_LQ_NAMES) as f:
+        return json.load(f)
+
+
+def test_packed_rollout_names_are_the_recorded_ones(shim):  # noqa: F811
+    """the planner and lq_rollout_kernel_name, asked for every launch of the fixture, against what the launchers' own format strings
+    printed on the GPU before the name had one function: byte for byte, and shorter than what mapf_last_kernel keeps"""
+    recorded = _lq_fixture()
+    launches, n = recorded['launches'], 0
+    wanted = list(lq_launches())
+    assert sorted(launches) == sorted(w[0] for w in wanted) and len(wanted) == 20 * 2 + 9 * 2 * 2
+    for key, family, A, E, tune, policy, limited, parts in wanted:
+        launch = launches[key]
+        assert (launch['A'], launch['E'], launch['tune'], launch['policy'], launch['limited']) == (A, E, tune, policy, int(limited)), key
+        assert sorted(launch['names']) == sorted('%s %s' % (v, r) for v in LQ_VARIANTS for r in ('RECORD', 'TOTALS')), key
+        for which, name in launch['names'].items():
+            variant, recording = which.split(' ')
+            found = planned_lq_name(shim, recorded['n_cu'], launch, variant, recording == 'RECORD')
+            assert found == name and len(name) < KERNEL_NAME_BYTES and all(part in name for part in parts), (key, which, found, name)
+            n += 1
+    assert n == 20 * 2 * 6 + 9 * 2 * 2 * 6 and len({name for launch in launches.values() for name in launch['names'].values()}) == n
+
+
+# one launch set per packed family: the smallest full-block batches of the case tables (plain streamed, plain in-kernel policy, the
+# table policy over full rows and over delta rows, both without and under the limit)
+LQ_GPU_LAUNCHES = ('K2-Q16-FullRows STREAM', 'K4-Q8-DeltaRowsBitmap POLICY', 'k2-4x512 lds=0 limit=0', 'mv_lds_max_bytes1024-32x128 lds=1 limit=0',
+                   'k2-4x512 lds=0 limit=1', 'mv_lds_max_bytes1024-32x128 lds=1 limit=1')
+
+
+@pytest.mark.gpu
+def test_packed_launches_print_the_recorded_names():
+    """the launcher that takes a plan notes the name the plan's name function gives: a launch of every packed family, without terminal
+    handling and totals only, then with it and recording, each compared in full with the recorded name"""
+    import episode_limit_cases as ec
+    launches, grid = _lq_fixture()['launches'], ec.random_map(3)
+    for key in LQ_GPU_LAUNCHES:
+        launch = launches[key]
+        assert (launch['A'], launch['E']) in ((32, 1024), (32, 2048), (4, 512), (32, 128)) and launch['V'] == len(grid.tables()[0]), key
+        found = launch_lq(grid, launch['A'], launch['E'], launch['tune'], launch['policy'], launch['limited'], 'Makespan', [(True, False), (False, True)])
+        assert found == [launch['names']['NO_TERMINAL TOTALS'], launch['names']['MAKESPAN RECORD']], (key, found)
+
+
 def lg_kinds(recorded):
     """{kind: (shape's key, index into LG_ROLLOUTS, recorded name)}: the smallest shape of every combination that exists of full /
     ragged groups, move table in LDS / global memory, dense / guarded and table policy or not; plus the smallest one whose block
@@ -419,6 +546,14 @@ if __name__ == '__main__':
         with open(sys.argv[2] if len(sys.argv) > 2 else FIXTURE_LIMIT, 'w') as f:
             json.dump(limit_plans(load_shim(shim_path)), f, indent=0, sort_keys=True)
             f.write('\n')
+        sys.exit(0)
+    if len(sys.argv) >= 2 and sys.argv[1] == '--record-lq-names':   # (needs a GPU: its CU count is what the handles' tuning starts from)
+        import torch
+        from gym_mapf_amd import _native
+        with open(sys.argv[2] if len(sys.argv) > 2 else FIXTURE_LQ_NAMES, 'w') as f:
+            json.dump(record_lq_names(torch.cuda.get_device_properties(0).multi_processor_count), f, indent=0, sort_keys=True)
+            f.write('\n')
+        print('recorded the packed rollout names from %s' % _native.LIB_PATH)
         sys.exit(0)
     if len(sys.argv) < 2 or sys.argv[1] != '--record':
         sys.exit(__doc__)

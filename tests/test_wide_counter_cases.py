@@ -162,13 +162,13 @@ def test_rollout_case_plans_the_form_it_names(case, shim):  # noqa: F811
     grid, nbr, start, goal, policy = wc.tables_of(case)
     V, tune = nbr.shape[0], case.tune_text().encode() or None
     delta = int(_move_tables(shim, nbr, wc.SLIP)[2] is not None)
-    out = (ctypes.c_uint64 * 8)()
+    out = (ctypes.c_uint64 * 9)()
     launches = [(n, 0 if w.mode == 'policy' else 1) for w in wc.rollout_windows(wc.CROSSINGS[0], case.table) for n in w.lengths]
     assert launches == ([(5, 1), (7, 1)] if case.table else [(5, 1), (7, 1), (12, 0)])
     for T, streamed in launches:
         rc = lib.mapf_debug_rollout_plan(V, case.A, case.E, T, streamed, delta, N_CU, tune, out)       # (-1: a key the planner does not know)
         if case.table:
-            assert shim.shim_plan_rollout_table(V, case.A, case.E, T, delta, policy[0].size, N_CU, tune, out) == 1
+            assert shim.shim_plan_rollout_table(V, case.A, case.E, T, delta, policy[0].size, N_CU, tune, 0, out, None) == 1
             assert (out[0], out[1]) == _shape(case) and case.E % (out[3] // out[1]) == 0
         elif case.form is not None:
             assert rc == 1 and (out[0], out[1]) == _shape(case) and out[2] == wc.FORMS.index(case.form), (T, streamed, rc, tuple(out))
