@@ -170,6 +170,11 @@ struct mapf_handle_s : StreamAndEvents {
     uint32_t episode_limit = 0;
     DevicePtr<uint32_t> age;
     DeviceBuf s_trunc, s_rtrunc, s_age, x_trunc;   // staging of out_truncations / rec_truncated / the ages; stand-in for rec_truncated
+    // episode budget (mapf_set_episode_budget): B (0 = none) and the per-env episodes left, which are all zero while B == 0 -- only the
+    // budget kernels, mapf_set_episode_budget and mapf_episodes_left write them
+    uint32_t episode_budget = 0;
+    DevicePtr<uint32_t> left;
+    DeviceBuf s_live;                 // staging of out_live_steps
     // host-pointer mode staging
     DeviceBuf s_actions, s_uniforms, s_local, s_reward, s_prob, s_done, s_coll, s_term, s_mask, s_ret, s_epi, s_ncoll;
     DeviceBuf x_local, x_reward, x_prob, x_done, x_coll;   // stand-ins for trajectory arrays the caller left out
@@ -474,6 +479,8 @@ int mapf_create(const mapf_desc *d, mapf_handle_t *out_handle) {
     HIP_TRY(hipMemset(h->t_dev, 0, sizeof(uint64_t)));
     HIP_TRY(h->age.alloc(E ? E : 1));
     HIP_TRY(hipMemset(h->age, 0, (E ? E : 1) * sizeof(uint32_t)));
+    HIP_TRY(h->left.alloc(E ? E : 1));
+    HIP_TRY(hipMemset(h->left, 0, (E ? E : 1) * sizeof(uint32_t)));
     if (scen.n) {
         h->n_scen = scen.n;
         HIP_TRY(h->scen.upload(scen.scen.data(), scen.scen.size()));
@@ -566,6 +573,7 @@ int step_impl(mapf_handle_t h, const uint8_t *actions, const double *uniforms, u
     if (int rc = check_handle(h)) return rc;
     if (!actions) return fail(MAPF_EINVAL, "actions is null");
     if (out_truncated && !h->episode_limit) return fail(MAPF_EINVAL, "step_limited: out_truncated on a handle without an episode limit (mapf_set_episode_limit)");
+    if (h->episode_budget) return fail(MAPF_EUNSUPPORTED, "step: a handle with an episode budget takes fused rollouts only (mapf_set_episode_budget(h, 0) first)");
     if (step_flags & ~MAPF_STEP_AUTO_RESET) return fail(MAPF_EINVAL, "unknown step flag");
     if (int rc = check_foreign_capture(h, "mapf_step")) return rc;
     if (int rc = check_extent(h, h->E, uniforms != nullptr)) return rc;
@@ -672,13 +680,18 @@ int complete_recording(mapf_handle_t h, mapf::RolloutArgs &a, size_t TE, size_t 
 }  // namespace
 
 namespace {
-// mapf_rollout and mapf_rollout_limited (out_truncations, rec_truncated: null from mapf_rollout)
-int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_truncations, uint8_t *rec_truncated) {
+// mapf_rollout, mapf_rollout_limited and mapf_rollout_budgeted (out_truncations, rec_truncated: null from mapf_rollout; out_live_steps:
+// null from both)
+int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_truncations, uint8_t *rec_truncated, uint32_t *out_live_steps) {
     if (int rc = check_handle(h)) return rc;
     if (!io || io->struct_size != sizeof(mapf_rollout_io)) return fail(MAPF_EINVAL, "bad mapf_rollout_io");
     if (io->step_flags & ~MAPF_STEP_AUTO_RESET) return fail(MAPF_EINVAL, "unknown step flag");
     if ((out_truncations || rec_truncated) && !h->episode_limit)
         return fail(MAPF_EINVAL, "rollout_limited: out_truncations / rec_truncated on a handle without an episode limit (mapf_set_episode_limit)");
+    if (out_live_steps && !h->episode_budget)
+        return fail(MAPF_EINVAL, "rollout_budgeted: out_live_steps on a handle without an episode budget (mapf_set_episode_budget)");
+    if (h->episode_budget && !(io->step_flags & MAPF_STEP_AUTO_RESET))
+        return fail(MAPF_EINVAL, "rollout: step_flags without MAPF_STEP_AUTO_RESET on a handle with an episode budget (mapf_set_episode_budget)");
     if (int rc = check_foreign_capture(h, "mapf_rollout")) return rc;
     if (int rc = check_extent(h, uint64_t(h->E) * io->n_steps, false)) return rc;
     const size_t E = size_t(h->E), T = io->n_steps, TE = T * E, TEA = TE * h->A;
@@ -694,8 +707,12 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
     a.mv_delta8 = h->mv_delta8;
     // (the episode limit travels beside the argument block too: its kernels are the lane-group family's limit instances -- and the
     // packed table instances' where the handle's tuning opts into them: launch_rollout_lg picks, as it does without a limit)
+    // (... and the episode budget beside the limit: its kernels are the lane-group family's budget instances, which take the limit
+    // block too -- with max_steps 0 on a handle without a limit)
     mapf::EpisodeLimit lim{h->age, h->episode_limit, nullptr, nullptr};
-    const mapf::EpisodeLimit *limit = h->episode_limit ? &lim : nullptr;
+    mapf::EpisodeBudget bud{h->left, nullptr};
+    const mapf::EpisodeBudget *budget = h->episode_budget ? &bud : nullptr;
+    const mapf::EpisodeLimit *limit = (h->episode_limit || budget) ? &lim : nullptr;
     // (the totals are inputs too when the call accumulates)
     const CallArray arrays[] = {input(h->s_actions, io->actions, TEA, &a.actions, "actions"),
                                 output(h->s_ret, io->out_returns, E, &a.out_returns, "out_returns", a.accumulate),
@@ -705,7 +722,8 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
                                 output(h->s_prob, io->rec_prob, TE, &a.rec_prob, "rec_prob"), output(h->s_done, io->rec_done, TE, &a.rec_done, "rec_done"),
                                 output(h->s_coll, io->rec_collision, TE, &a.rec_collision, "rec_collision"),
                                 output(h->s_trunc, out_truncations, E, &lim.out_truncations, "out_truncations", a.accumulate),
-                                output(h->s_rtrunc, rec_truncated, TE, &lim.rec_truncated, "rec_truncated")};
+                                output(h->s_rtrunc, rec_truncated, TE, &lim.rec_truncated, "rec_truncated"),
+                                output(h->s_live, out_live_steps, E, &bud.out_live_steps, "out_live_steps", a.accumulate)};
     if (int rc = stage_arrays(h, arrays)) return rc;
     if (limit && lim.rec_truncated && !a.rec_local) {   // the truncated bytes alone make the launch a recording one
         if (int rc = reserve_stand_in(h, h->x_local, TEA * sizeof(uint16_t), "rec_local")) return rc;
@@ -716,7 +734,7 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
         if (int rc = reserve_stand_in(h, h->x_trunc, TE, "rec_truncated")) return rc;
         lim.rec_truncated = static_cast<uint8_t *>(h->x_trunc.ptr);
     }
-    HIP_TRY((h->lane_group_rollout || limit) ? mapf::launch_rollout_lg(int(h->A), a, h->tune, h->stream, table, limit)
+    HIP_TRY((h->lane_group_rollout || limit) ? mapf::launch_rollout_lg(int(h->A), a, h->tune, h->stream, table, limit, budget)
                                              : mapf::launch_rollout(int(h->A), a, h->stream, table));
     after_launch(h, h->last_rollout_kernel, io->n_steps, a.auto_reset);
     if (int rc = fetch_arrays(h, arrays)) return rc;
@@ -726,10 +744,41 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
 
 }  // namespace
 
-int mapf_rollout(mapf_handle_t h, const mapf_rollout_io *io) { return rollout_impl(h, io, nullptr, nullptr); }
+int mapf_rollout(mapf_handle_t h, const mapf_rollout_io *io) { return rollout_impl(h, io, nullptr, nullptr, nullptr); }
 
 int mapf_rollout_limited(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_truncations, uint8_t *rec_truncated) {
-    return rollout_impl(h, io, out_truncations, rec_truncated);
+    return rollout_impl(h, io, out_truncations, rec_truncated, nullptr);
+}
+
+int mapf_rollout_budgeted(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_truncations, uint8_t *rec_truncated, uint32_t *out_live_steps) {
+    return rollout_impl(h, io, out_truncations, rec_truncated, out_live_steps);
+}
+
+int mapf_set_episode_budget(mapf_handle_t h, uint32_t n_episodes) {
+    if (!h) return fail(MAPF_EINVAL, "set_episode_budget: null handle");
+    if (int rc = check_not_recording(h, "mapf_set_episode_budget")) return rc;
+    if (!h->graphs.empty()) return fail(MAPF_EINVAL, "set_episode_budget: recorded graphs hold launches without a budget (destroy them first)");
+    if (int rc = check_handle(h)) return rc;
+    // every call re-arms every env: left[e] = n_episodes (state and ages stay)
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->left.ptr), int(n_episodes), h->E ? size_t(h->E) : 1, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->episode_budget = n_episodes;
+    return MAPF_OK;
+}
+
+int mapf_episodes_left(mapf_handle_t h, uint32_t *out_left, const uint32_t *set_left) {
+    if (!h) return fail(MAPF_EINVAL, "episodes_left: null handle");
+    if (!out_left && !set_left) return fail(MAPF_EINVAL, "episodes_left: out_left and set_left are both null");
+    if (set_left && !h->episode_budget) return fail(MAPF_EINVAL, "episodes_left: set_left on a handle without an episode budget (mapf_set_episode_budget)");
+    if (int rc = check_not_recording(h, "mapf_episodes_left")) return rc;
+    if (h->device_ptrs && (misaligned(out_left) || misaligned(set_left))) return fail(MAPF_EINVAL, "episodes_left: device pointer must be 16-byte aligned");
+    if (int rc = check_handle(h)) return rc;
+    const size_t bytes = size_t(h->E) * sizeof(uint32_t);
+    // (out_left receives the counts as they are before set_left replaces them)
+    if (out_left && bytes) HIP_TRY(hipMemcpyAsync(out_left, h->left, bytes, h->device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    if (set_left && bytes) HIP_TRY(hipMemcpyAsync(h->left, set_left, bytes, h->device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
+    return MAPF_OK;
 }
 
 int mapf_set_episode_limit(mapf_handle_t h, uint32_t max_steps) {
@@ -1001,6 +1050,7 @@ int mapf_graph_begin(mapf_handle_t h) {
     if (!h->device_ptrs) return fail(MAPF_EINVAL, "graph_begin: only handles created with MAPF_FLAG_DEVICE_PTRS can be recorded (host-pointer calls wait for the stream)");
     if (h->capturing) return fail(MAPF_EINVAL, "graph_begin: already recording");
     if (h->episode_limit) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with an episode limit cannot be recorded (mapf_set_episode_limit(h, 0) first)");
+    if (h->episode_budget) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with an episode budget cannot be recorded (mapf_set_episode_budget(h, 0) first)");
     HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed));
     h->capturing = true;
     h->cap_steps = 0;

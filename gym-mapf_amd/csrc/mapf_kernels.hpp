@@ -169,6 +169,14 @@ struct EpisodeLimit {
     uint8_t *rec_truncated;        // rollout: [T*E], non-null exactly when the launch records; single step: [E] or null
 };
 
+// Episode budget (include/mapf_hip.h mapf_set_episode_budget): the handle's per-env counts of episodes left and where a launch
+// reports its live steps.  A block of its own beside EpisodeLimit, which stays as it is; the budget instances (mapf_lg_budget.hip)
+// take both -- the limit block with max_steps == 0 on a handle without a limit: the ages are then left alone and nothing truncates.
+struct EpisodeBudget {
+    uint32_t *left;                // [E] episodes the env may still end (done or truncated); 0 = parked
+    uint32_t *out_live_steps;      // [E] or null (RolloutArgs::accumulate applies): steps neither parked nor terminal on entry
+};
+
 // Every launcher names the kernel instance (and block size) that took the launch; the C ABI keeps the name of a
 // handle's last step / rollout launch (mapf_last_kernel) so a benchmark labels its numbers with what actually ran.
 constexpr size_t kKernelNameBytes = 160;   // what is kept of a name, the terminator included
@@ -268,8 +276,12 @@ RolloutTuning default_rollout_tuning(int device, std::string *err);   // (asks t
 hipError_t launch_step_lg(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, const EpisodeLimit *limit = nullptr);
 // packed layout of the single step (mapf_lq_step.hip): true when it took the launch (*err = its status)
 bool try_launch_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err);
+// (budget: the episode budget of a handle that has one, or null -- then `limit` is non-null too (max_steps 0 without a limit) and the
+// lane-group budget instance takes the launch before any packed plan or thread-per-env kernel is consulted, mapf_lg_budget.hip)
 hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table = nullptr,
-                             const EpisodeLimit *limit = nullptr);
+                             const EpisodeLimit *limit = nullptr, const EpisodeBudget *budget = nullptr);
+hipError_t launch_rollout_lg_budget(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table,
+                                    const EpisodeLimit &limit, const EpisodeBudget &budget);
 // the limit instances (mapf_lg_limit.hip): the lane-group kernels with a per-env age, and the masked zeroing of the ages.  These
 // two and the two above check their launch, plan it and hand the plan to the family's one launcher (mapf_lg_launch.hpp)
 hipError_t launch_rollout_lg_limit(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table,

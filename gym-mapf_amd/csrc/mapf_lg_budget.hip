@@ -1,0 +1,49 @@
+// Lane-group family under an episode budget (include/mapf_hip.h mapf_set_episode_budget; EpisodeBudget in mapf_kernels.hpp): the
+// budget forms of the fused rollout kernels, the family that names them to the shared launcher (mapf_lg_launch.hpp), and the entry
+// launcher.  A translation unit of its own: the kernels that exist without the budget (mapf_lg_rollout.hip, mapf_lg_limit.hip) keep
+// their code.
+//
+// Per env and step of an auto-reset rollout under a budget B (the header has the definition): an env with no episode left is PARKED
+// and the step does nothing -- no state, age, count or total changes, nothing is drawn, a recording launch writes the env's cells
+// and zeros.  Any other step is the limit kernels' step (with max_steps == 0: the step without a limit); it counts as a live step
+// unless the env was terminal on entry, and takes one from the env's episodes left when it reports done or truncated.
+#include "mapf_lg_launch.hpp"
+
+namespace mapf {
+
+// lg_rollout_kernel_budget_guarded (streamed actions, the policy stream, the greedy policy) and
+// lg_rollout_kernel_table_budget_guarded (the table policy): the body of the rollout kernels with its limit and budget sections
+#define MAPF_ROLLOUT_LIMIT 1
+#define MAPF_ROLLOUT_BUDGET 1
+#define MAPF_ROLLOUT_TABLE_KERNEL 0
+#include "mapf_lg_rollout_kernel.inc"
+#undef MAPF_ROLLOUT_TABLE_KERNEL
+#define MAPF_ROLLOUT_TABLE_KERNEL 1
+#include "mapf_lg_rollout_kernel.inc"
+#undef MAPF_ROLLOUT_TABLE_KERNEL
+#undef MAPF_ROLLOUT_BUDGET
+#undef MAPF_ROLLOUT_LIMIT
+
+// the budget instances: guarded only, as the limit instances are.  7 group sizes x FULL x MV_LDS x RECORD x (STREAM | table)
+struct LgRolloutBudgetFamily {
+    template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM, bool TABLE>
+    static auto kernel(bool) {
+        if constexpr (TABLE) return lg_rollout_kernel_table_budget_guarded<L, FULL, MV_LDS, RECORD>;
+        else return lg_rollout_kernel_budget_guarded<L, FULL, MV_LDS, RECORD, STREAM>;
+    }
+};
+
+// the pre-checks of a launch under a budget, then the limit plan, marked `budget`, and the shared launcher (mapf_lg_launch.hpp)
+hipError_t launch_rollout_lg_budget(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table,
+                                    const EpisodeLimit &limit, const EpisodeBudget &budget) {
+    if (args.n_envs == 0) return hipSuccess;
+    // what the kernels rely on: ages and counts, auto-reset, and the truncated trajectory exactly when the launch records (the
+    // limit itself may be 0: a budget without a limit)
+    if (!limit.age || !budget.left || !args.auto_reset || (limit.rec_truncated != nullptr) != (args.rec_local != nullptr)) return hipErrorInvalidValue;
+    LgRolloutPlan plan = plan_rollout_lg(n_agents, args, tune, true);
+    plan.budget = true;
+    return table ? launch_lg_rollout<LgRolloutBudgetFamily, true>(plan, args, uint32_t(n_agents), stream, *table, limit, budget)
+                 : launch_lg_rollout<LgRolloutBudgetFamily, false>(plan, args, uint32_t(n_agents), stream, limit, budget);
+}
+
+}  // namespace mapf

@@ -3,10 +3,11 @@
 // say, through a family type:
 //   rollout -- Family::kernel<L, FULL, MV_LDS, RECORD, STREAM, TABLE>(dense) returns the kernel's address (mapf_lg_rollout.hip:
 //              lg_rollout_kernel / lg_rollout_kernel_table, DENSE for full groups only; mapf_lg_limit.hip: the limit instances,
-//              guarded only);
+//              guarded only; mapf_lg_budget.hip: the budget instances, guarded only);
 //   step    -- Family::kernel<L, FULL, EXT_UNIFORMS>() likewise (mapf_lg_kernels.hip: lg_step_kernel; mapf_lg_limit.hip:
 //              lg_step_kernel_limit).
-// `extra` are the kernel's arguments behind (args, A): nothing, the table policy, the episode limit, or both in that order.
+// `extra` are the kernel's arguments behind (args, A): nothing, the table policy, the episode limit, or both in that order; the
+// budget instances take the episode budget behind the limit.
 #pragma once
 #include "mapf_lg.hpp"
 #include "mapf_plan.hpp"

@@ -34,8 +34,10 @@ struct LgRolloutFamily {
 };
 
 hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table,
-                             const EpisodeLimit *limit) {
+                             const EpisodeLimit *limit, const EpisodeBudget *budget) {
     if (args.n_envs == 0) return hipSuccess;
+    // an episode budget: the budget instances exist in the lane-group family only -- no packed plan, whatever the tuning says
+    if (budget) return limit ? launch_rollout_lg_budget(n_agents, args, tune, stream, table, *limit, *budget) : hipErrorInvalidValue;
     hipError_t packed_status;   // packed first, else lane-group: under a limit too (the packed table instances' limit forms, where opted into)
     if (try_launch_rollout_lq(n_agents, args, tune, stream, &packed_status, table, limit)) return packed_status;
     if (limit) return launch_rollout_lg_limit(n_agents, args, tune, stream, table, *limit);

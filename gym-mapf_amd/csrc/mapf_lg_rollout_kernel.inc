@@ -9,7 +9,21 @@
 // mapf_set_episode_limit): lg_rollout_kernel_limit_guarded and lg_rollout_kernel_table_limit_guarded carry the env's age in a
 // register beside `terminal`, count truncations like episodes, store the truncated byte with the delayed flag bytes and go
 // back to the start cells on done OR truncated.  They have no DENSE form (the name says so): always the guarded one.
-#if MAPF_ROLLOUT_LIMIT && MAPF_ROLLOUT_TABLE_KERNEL
+// mapf_lg_budget.hip includes it twice again with MAPF_ROLLOUT_LIMIT 1 and MAPF_ROLLOUT_BUDGET 1 (the episode budget, include/mapf_hip.h
+// mapf_set_episode_budget): lg_rollout_kernel_budget_guarded and lg_rollout_kernel_table_budget_guarded are the limit kernels with a
+// per-env count of episodes left beside the age.  An env whose count is 0 is PARKED: it folds into the `terminal` the transition is
+// told, so its step draws and moves nothing, and its done bit is cleared before anything counts or records it.
+#if MAPF_ROLLOUT_BUDGET && MAPF_ROLLOUT_TABLE_KERNEL
+template <int L, bool FULL, bool MV_LDS, bool RECORD, bool TABLE = true>
+__global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel_table_budget_guarded(const RolloutArgs p, const uint32_t n_agents, const TablePolicy tp,
+                                                                                                 const EpisodeLimit lim, const EpisodeBudget bud) {
+    constexpr bool STREAM = false, DENSE = false;
+#elif MAPF_ROLLOUT_BUDGET
+template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM>
+__global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel_budget_guarded(const RolloutArgs p, const uint32_t n_agents, const EpisodeLimit lim,
+                                                                                           const EpisodeBudget bud) {
+    constexpr bool DENSE = false;
+#elif MAPF_ROLLOUT_LIMIT && MAPF_ROLLOUT_TABLE_KERNEL
 template <int L, bool FULL, bool MV_LDS, bool RECORD, bool TABLE = true>
 __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel_table_limit_guarded(const RolloutArgs p, const uint32_t n_agents, const TablePolicy tp,
                                                                                                 const EpisodeLimit lim) {
@@ -93,6 +107,15 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
     uint32_t age = *age_p;
     uint32_t truncations = (p.accumulate && trn_p && leader) ? *trn_p : 0u;
     const uint32_t max_steps = lim.max_steps;
+#endif
+#if MAPF_ROLLOUT_BUDGET
+    // the env's episodes left: read and written back like the age (lanes past the last env are parked: they write nothing anyway)
+    gu32 left_p = (gu32)at(bud.left, e);
+    gu32 liv_p = (gu32)(bud.out_live_steps ? at(bud.out_live_steps, e) : nullptr);
+    asm volatile("" : "+v"(left_p), "+v"(liv_p));
+    uint32_t left = live ? *left_p : 0u;
+    uint32_t live_steps = (p.accumulate && liv_p && leader) ? *liv_p : 0u;
+    uint32_t idle = 0u;                    // steps that were parked or terminal on entry: live steps = n_steps - idle
 #endif
     const uint64_t env_id = p.env_id_offset + e;
     const uint32_t n_envs = uint32_t(p.n_envs);
@@ -182,6 +205,10 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
     const uint64_t t_first = first_step_index(p);
     for (uint32_t s = 0; s < p.n_steps; ++s) {
         const uint64_t t = t_first + s;
+#if MAPF_ROLLOUT_BUDGET
+        const bool parked = left == 0u;
+        const bool no_op = parked || terminal != 0u;       // a parked step is the terminal no-op: nothing drawn, nothing moved ...
+#endif
         uint32_t act0, act1;
         if (STREAM) {
             act0 = raw & 0xFFu; act1 = (raw >> 8) & 0xFFu;   // only the low half-word of `raw` is defined
@@ -220,25 +247,47 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
         // my pair's words of a four-step block (one slip-stream call per lane, traded with the neighbour lane): refresh when
         // t is a multiple of 4 (and at the first step)
         if (p.c.need_rng && ((t & 3u) == 0u || s == 0u)) rng = pair_block_words<(L > 1)>(p.c, env_id, t, x.g);
+#if MAPF_ROLLOUT_BUDGET
+        lg_transition<L, FULL, false, true, MV_LDS, true>(p.c, mv, slip, outcome, x, n_agents, cur0, cur1, goal0, goal1, act0, act1, 0.0, 0.0,
+                                            env_id, t, step_word(rng, t), no_op, next0, next1, o STAMP_ARG);
+        // ... but it reports no done: a no-op's status is kTerminalStatus, whose byte 0 goes and whose byte 2 stays (the carried `terminal`
+        // is 1 from here on).  Its reward is +0.0, and ret + 0.0 would turn an accumulated -0.0 into +0.0: what is added is -0.0
+        o.status -= parked ? 1u : 0u;
+        ret = __dadd_rn(ret, __hiloint2double(parked ? int(0x80000000u) : __double2hiint(o.reward), __double2loint(o.reward)));
+#else
         lg_transition<L, FULL, false, true, MV_LDS, true>(p.c, mv, slip, outcome, x, n_agents, cur0, cur1, goal0, goal1, act0, act1, 0.0, 0.0,
                                             env_id, t, step_word(rng, t), terminal != 0u, next0, next1, o STAMP_ARG);
         STAMP(6);   // reward / selects
         ret = __dadd_rn(ret, o.reward);
+#endif
         episodes += o.status & 0xFFu;
         collisions += (o.status >> 8) & 0xFFu;
         if (RECORD) {
             d_next0 = next0; d_next1 = next1; d_reward = o.reward; d_prob = o.prob;
             d_flags = o.status;                            // byte 0 done, byte 1 collision
         }
-#if MAPF_ROLLOUT_LIMIT
+#if MAPF_ROLLOUT_BUDGET
+        // the limit's rules below, switched off as a whole by max_steps == 0 (a budget without a limit: the ages stay zero); a step
+        // that was neither parked nor terminal on entry is a live step, and one that reports done or truncated takes an episode
+        // from the env's count (a parked step reports neither, so the count stops at 0)
+        const bool ageing = !no_op && max_steps != 0u;
+        const uint32_t aged = ageing ? (age + (age != 0xFFFFFFFFu ? 1u : 0u)) : age;
+        const uint32_t truncated = (ageing && (o.status & 0xFFu) == 0u && aged >= max_steps) ? 1u : 0u;
+        idle += no_op ? 1u : 0u;
+#elif MAPF_ROLLOUT_LIMIT
         // a live step ages the episode (saturating); it is truncated when it did not end the episode and the age has reached
         // the limit.  A step from a terminal state (a no-op) leaves the age alone and is never truncated.
         const uint32_t aged = terminal != 0u ? age : (age + (age != 0xFFFFFFFFu ? 1u : 0u));
         const uint32_t truncated = (terminal == 0u && (o.status & 0xFFu) == 0u && aged >= max_steps) ? 1u : 0u;
+#endif
+#if MAPF_ROLLOUT_LIMIT
         truncations += truncated;
         if (RECORD) d_flags |= truncated << 24;
         const bool back = p.auto_reset && ((o.status & 0xFFu) != 0u || truncated != 0u);   // done or truncated: start cells, age 0
         age = back ? 0u : aged;
+#if MAPF_ROLLOUT_BUDGET
+        left -= back ? 1u : 0u;                // (the budget instances run auto-reset launches only: back == done || truncated)
+#endif
 #else
         const bool back = p.auto_reset && (o.status & 0xFFu) != 0u;   // MapfEnv.reset(): start cells, no reseed
 #endif
@@ -263,6 +312,10 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
 #if MAPF_ROLLOUT_LIMIT
         *age_p = age;
         if (trn_p) *trn_p = truncations;
+#endif
+#if MAPF_ROLLOUT_BUDGET
+        *left_p = left;
+        if (liv_p) *liv_p = live_steps + (p.n_steps - idle);
 #endif
     }
 }

@@ -340,12 +340,15 @@ LgStepPlan plan_step_lg(int n_agents, const StepArgs &args, bool limited) {
     return plan;
 }
 
-// (a limit plan: _limit_guarded and LIMIT where the others say DENSE or GUARDED, and the note)
+// (a limit plan: _limit_guarded and LIMIT where the others say DENSE or GUARDED, and the note; a budget plan: _budget_guarded, BUDGET)
 void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy) {
+    const char *family = plan.budget ? "_budget_guarded" : (plan.limit ? "_limit_guarded" : "");
+    const char *form = plan.budget ? "BUDGET" : (plan.limit ? "LIMIT" : (plan.dense ? "DENSE" : "GUARDED"));
+    const char *note = plan.budget ? "; episode budget" : (plan.limit ? "; episode step limit" : "");
     snprintf(name, kKernelNameBytes, "lg_rollout_kernel%s%s<L=%d,%s,%s,%s,%s,%s> block=%u (pair layout: 2 agents per lane%s%s)", table_policy ? "_table" : "",
-             plan.limit ? "_limit_guarded" : "", plan.L, plan.full ? "FULL" : "RAGGED", plan.mv_lds ? "MV_LDS" : "MV_GLOBAL", record ? "RECORD" : "TOTALS",
-             table_policy ? "TABLE" : (streamed ? "STREAM" : "POLICY"), plan.limit ? "LIMIT" : (plan.dense ? "DENSE" : "GUARDED"), plan.block,
-             plan.limit ? "; episode step limit" : "", table_policy ? "; table policy: action bytes gathered from global memory" : "");
+             family, plan.L, plan.full ? "FULL" : "RAGGED", plan.mv_lds ? "MV_LDS" : "MV_GLOBAL", record ? "RECORD" : "TOTALS",
+             table_policy ? "TABLE" : (streamed ? "STREAM" : "POLICY"), form, plan.block, note,
+             table_policy ? "; table policy: action bytes gathered from global memory" : "");
 }
 
 void lg_step_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms) {

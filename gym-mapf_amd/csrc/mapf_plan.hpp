@@ -66,6 +66,7 @@ struct LgRolloutPlan {
     bool mv_lds = false;             // the whole move table is staged into LDS once per block
     bool dense = false;              // full groups and the env count fills every block: no per-lane predicates
     bool limit = false;              // the family the plan names: the instances under an episode step limit, or those without
+    bool budget = false;             // ... or, of a limit plan, the instances under an episode budget (mapf_lg_budget.hip): their launcher sets it
     unsigned block = 0, grid = 0;
     size_t lds_bytes = 0;            // dynamic LDS segment: the move table, or 0 (the launcher raises the limit beyond 32 KB)
 };
@@ -77,7 +78,7 @@ LgRolloutPlan plan_rollout_lg(int n_agents, const RolloutArgs &args, const Rollo
 struct LgStepPlan { int L = 0; bool full = false; bool limit = false; unsigned block = 0, grid = 0; };
 LgStepPlan plan_step_lg(int n_agents, const StepArgs &args, bool limited = false);
 // The names the launchers note for these plans (mapf_last_kernel; at most kKernelNameBytes with the terminator).  A limit plan's
-// name says _limit_guarded (the step: _limit) and LIMIT, and has no DENSE / GUARDED field.
+// name says _limit_guarded (the step: _limit) and LIMIT, and has no DENSE / GUARDED field; a budget plan's says _budget_guarded and BUDGET.
 void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy);
 void lg_step_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms);
 

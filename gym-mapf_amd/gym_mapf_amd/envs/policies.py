@@ -82,3 +82,33 @@ def row_from_policy(local_env, policy):
             raise ValueError('policy(%d) = %d is not an action code 0..%d' % (c, a, len(ACTIONS) - 1))
         row[c] = a
     return row
+
+
+def evaluate(env, n_episodes, max_steps, chunk=256):
+    """Monte-Carlo evaluation of whatever drives ``env``'s ``rollout(actions=None)`` -- a table policy, the greedy policy or the
+    random stream: EXACTLY ``n_episodes`` episodes of at most ``max_steps`` steps in every env of a ``VecMapfEnv``, inside
+    totals-only fused rollouts.  Sets the episode limit and the episode budget (``set_episode_limit``, ``set_episode_budget``; both
+    stay set), resets, then issues ``ceil(n_episodes * max_steps / chunk)`` launches of ``chunk`` steps that accumulate into one set
+    of totals.  Every episode ends within ``max_steps`` steps, so after that many steps every env is parked by construction: nothing
+    is polled, and ``episodes_left().max() == 0`` is asserted at the end.  Returns a dict of host arrays, one value per env:
+    ``returns`` f64 (the rewards of the ``n_episodes`` episodes, no cut-off episode among them), ``goal_ends`` (= episodes -
+    collisions: episodes that ended on the goals, a terminal start state included), ``collisions``, ``truncations`` and
+    ``live_steps`` (the steps those episodes took), uint32 -- ``goal_ends + collisions + truncations == n_episodes`` everywhere.
+    Not covered: the multi-map and union-map wrappers and the scalar ``MapfEnv``."""
+    n_episodes, max_steps, chunk = int(n_episodes), int(max_steps), int(chunk)
+    if n_episodes < 1 or max_steps < 1 or chunk < 1:
+        raise ValueError('evaluate needs n_episodes >= 1, max_steps >= 1 and chunk >= 1')
+    env.set_episode_limit(max_steps)
+    env.set_episode_budget(n_episodes)
+    env.reset()
+    totals = None
+    for _ in range(-(-n_episodes * max_steps // chunk)):
+        totals = env.rollout(chunk, auto_reset=True, accumulate_into=totals)
+    env.sync()
+    host = lambda a: a.cpu().numpy() if hasattr(a, 'cpu') else np.asarray(a)
+    left = host(env.episodes_left())
+    env.sync()
+    assert int(left.max(initial=0)) == 0, 'after n_episodes * max_steps steps every env is parked'
+    out = {k: host(totals[k]) for k in ('returns', 'collisions', 'truncations', 'live_steps')}
+    out['goal_ends'] = host(totals['episodes']) - out['collisions']
+    return out

@@ -39,6 +39,8 @@ ROLLOUT_TOTALS = (('returns', np.float64), ('episodes', np.uint32), ('collisions
 # rollout's rec_truncated, the rollout's out_truncations
 STEP_TRUNCATED = ('truncated', np.uint8, False)
 ROLLOUT_TRUNCATIONS = ('truncations', np.uint32)
+# ... and an env with an episode budget (set_episode_budget): the rollout's out_live_steps
+ROLLOUT_LIVE_STEPS = ('live_steps', np.uint32)
 _TORCH_DTYPE = {np.uint8: 'uint8', np.uint16: 'uint16', np.uint32: 'uint32', np.uint64: 'uint64', np.float64: 'float64'}
 # rollout(out=...): the argument block of the last such call, with what it was made from
 _RolloutIO = collections.namedtuple('_RolloutIO', 'out call arrays actions io call_args')
@@ -177,6 +179,7 @@ class VecMapfEnv:
         self.policy = 'random'         # on-device policy of rollout(actions=None): see set_policy
         self._rollout_io = None        # rollout(out=...): the _RolloutIO of the last such call
         self.episode_limit = 0         # set_episode_limit: steps per episode, 0 = no limit
+        self.episode_budget = 0        # set_episode_budget: episodes per env, 0 = no budget
 
     # ------------------------------------------------------------------ construction
     def _as_local(self, locations, local_ids, what):
@@ -332,7 +335,8 @@ class VecMapfEnv:
         eight new ones per call (totals overwritten, unlike ``accumulate_into``); a training loop that calls
         ``rollout(T=16..64)`` thousands of times wants this (profiles/r05_rollout_T_sweep.txt).
         With an episode limit (``set_episode_limit``) the dict also has ``truncations`` u32 [E] and, when ``record``,
-        ``truncated`` u8 [T, E]; ``out`` and ``accumulate_into`` cover them."""
+        ``truncated`` u8 [T, E]; ``out`` and ``accumulate_into`` cover them.  With an episode budget (``set_episode_budget``) it
+        has ``live_steps`` u32 [E] as well (covered likewise), and ``auto_reset=False`` raises ``ValueError``."""
         E, A, T = self.n_envs, self.n_agents, int(n_steps)
         if out is not None and accumulate_into is None:
             # the repeat call of a training loop: the same dict of arrays, the same shape.  The argument block of the earlier call
@@ -357,11 +361,14 @@ class VecMapfEnv:
         if out is not None and accumulate_into is not None:
             raise ValueError('pass either out= (overwrite) or accumulate_into= (add), not both')
         res = accumulate_into if accumulate_into is not None else (out if out is not None else {})
-        limited = bool(self.episode_limit)
+        limited, budgeted = bool(self.episode_limit), bool(self.episode_budget)
+        if budgeted and not auto_reset:
+            raise ValueError('an env with an episode budget rolls out with auto_reset=True only (set_episode_budget(None) switches it off)')
         trajectory = (STEP_OUTPUTS[:5] + ((STEP_TRUNCATED,) if limited else ())) if record else ()
-        total_spec = ROLLOUT_TOTALS + ((ROLLOUT_TRUNCATIONS,) if limited else ())
-        if limited and accumulate_into is not None and 'truncations' not in res:   # (totals of a call without the limit: count from 0)
-            res['truncations'] = self._torch.zeros((E,), dtype=self._torch.uint32, device=self._tdev) if self.device_arrays else np.zeros((E,), np.uint32)
+        total_spec = ROLLOUT_TOTALS + ((ROLLOUT_TRUNCATIONS,) if limited else ()) + ((ROLLOUT_LIVE_STEPS,) if budgeted else ())
+        for name, on in (('truncations', limited), ('live_steps', budgeted)):
+            if on and accumulate_into is not None and name not in res:   # (totals of a call without the limit / budget: count from 0)
+                res[name] = self._torch.zeros((E,), dtype=self._torch.uint32, device=self._tdev) if self.device_arrays else np.zeros((E,), np.uint32)
         res, totals = self._outputs([(name, dt, (E,)) for name, dt in total_spec], res, fill=True)
         for name, dt, per_agent in trajectory:
             shape = (T, E, A) if per_agent else (T, E)
@@ -380,10 +387,14 @@ class VecMapfEnv:
             for name, dt, per_agent in trajectory:
                 fields['rec_' + name] = self._ptr(res[name][sl], dt, (n, E, A) if per_agent else (n, E), name)
             # (the truncation outputs are mapf_rollout_limited's two arguments behind the block, which stays mapf_rollout's)
-            beside = (fields.pop('out_truncations'), fields.pop('rec_truncated', None)) if limited else ()
+            # (... and the live steps mapf_rollout_budgeted's third; without a limit its truncation arguments are NULL)
+            beside = (fields.pop('out_truncations', None), fields.pop('rec_truncated', None)) if (limited or budgeted) else ()
+            entry = self._lib.mapf_rollout_limited if limited else self._lib.mapf_rollout
+            if budgeted:
+                beside, entry = beside + (fields.pop('out_live_steps'),), self._lib.mapf_rollout_budgeted
             io = nat.MapfRolloutIO(struct_size=ctypes.sizeof(nat.MapfRolloutIO), n_steps=n, step_flags=nat.MAPF_STEP_AUTO_RESET if auto_reset else 0,
                                    accumulate=1 if accumulate else 0, **fields)
-            call_args = (self._lib.mapf_rollout_limited if limited else self._lib.mapf_rollout, self._h, ctypes.byref(io)) + beside
+            call_args = (entry, self._h, ctypes.byref(io)) + beside
             nat.check(call_args[0](*call_args[1:]))
             first += n
             if first >= T:
@@ -509,6 +520,33 @@ class VecMapfEnv:
         nat.check(self._lib.mapf_set_episode_limit(self._h, int(n)))
         self._rollout_io = None            # (a cached argument block names the arrays of the other mode)
         self.episode_limit = int(n)
+
+    def set_episode_budget(self, n):
+        """Episode budget: every env stops after ``n`` episodes.  An episode ends with ``done`` or ``truncated`` (``set_episode_limit``);
+        an env that has ended ``n`` of them is PARKED on its start cells and later steps of a ``rollout`` do nothing for it -- no
+        move, no random number, no total; a recording rollout writes the env's cells and zeros (``done == 0`` and ``prob == 0``).  So
+        totals-only rollouts give unbiased per-env episode statistics: exactly ``n`` episodes each and no cut-off episode in
+        ``returns`` once every env is parked (``episodes_left().max() == 0``).  ``None`` or 0 switches the budget off (the default);
+        every call re-arms every env and touches neither state nor ages.  With a budget ``rollout`` also returns ``live_steps``, needs
+        ``auto_reset=True``, and runs the lane-group kernels' budget instances (``last_kernel`` says BUDGET); ``step`` and
+        ``graph_begin`` are refused.  Not covered: the multi-map and union-map wrappers and the scalar ``MapfEnv``."""
+        n = 0 if n is None else n
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= 0xFFFFFFFF:
+            raise ValueError('the episode budget must be None or an integer 0 .. 2**32 - 1, got %r' % (n,))
+        nat.check(self._lib.mapf_set_episode_budget(self._h, int(n)))
+        self._rollout_io = None            # (a cached argument block names the arrays of the other mode)
+        self.episode_budget = int(n)
+
+    def episodes_left(self, out=None, set=None):
+        """The episodes every env may still end, uint32 [E] (all zero without a budget; 0 = parked); ``set`` uint32 [E] replaces them
+        afterwards -- per-env budgets, or re-arming single envs (needs a budget).  Host arrays, or CUDA tensors in device mode (then
+        only enqueued).  Not covered: the multi-map and union-map wrappers and the scalar ``MapfEnv``."""
+        shape = (self.n_envs,)
+        set = self._coerce(set, np.uint32, shape, 'set')
+        if out is None:
+            out = self._empty(shape, np.uint32)
+        nat.check(self._lib.mapf_episodes_left(self._h, self._ptr(out, np.uint32, shape, 'out'), self._ptr(set, np.uint32, shape, 'set')))
+        return out
 
     def episode_steps(self, out=None, set=None):
         """The steps every env's current episode has taken since it began, uint32 [E] (all zero without a limit); ``set`` uint32 [E]

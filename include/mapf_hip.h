@@ -114,7 +114,8 @@ typedef struct mapf_desc {
  *                        policy table staged into LDS behind the table image whenever one block's segment fits (default: by shape)
  *   limit_packed=0|1     a rollout under MAPF_POLICY_TABLE and an episode step limit (mapf_set_episode_limit): always the lane-group
  *                        limit kernels (0, the default) / the packed table kernels' limit forms wherever the packed table plan
- *                        applies (1; not on a handle created with MAPF_FLAG_LANE_GROUP).  Same results either way.
+ *                        applies (1; not on a handle created with MAPF_FLAG_LANE_GROUP).  Same results either way.  A handle with an
+ *                        episode budget (mapf_set_episode_budget) takes the lane-group budget kernels whatever this key says.
  */
 
 /* Replaces MapfEnv.__init__'s state setup; state = start cells, step index t = 0. */
@@ -214,6 +215,45 @@ int mapf_step_limited(mapf_handle_t h, const uint8_t *actions, const double *uni
                       uint16_t *out_local, double *out_reward, uint8_t *out_done,
                       uint8_t *out_collision, double *out_prob, uint8_t *out_was_terminal,
                       uint8_t *out_truncated, uint32_t step_flags);
+
+/*
+ * Episode budget (ABI 6, new symbols only): fused rollouts that stop each env after n episodes -- the other half of "n episodes of
+ * at most max_steps steps".  A rollout with auto-reset runs every env for exactly T steps, so envs whose episodes end quickly run
+ * more of them (pooled returns / episodes over-weight short episodes) and returns[e] ends with the rewards of an episode the launch
+ * cut off.  THE DEFINITION.  A handle has an episode budget B (u32; 0 = none, the default) and a per-env count left (u32[E], device
+ * memory, all zero at mapf_create).  An env is PARKED when B > 0 and left[e] == 0.  The budget applies to mapf_rollout* launches that
+ * carry MAPF_STEP_AUTO_RESET.  For every env and step of such a launch:
+ *   0. parked on entry: nothing happens.  State, age and left are unchanged, nothing is drawn from either stream, no total changes
+ *      (returns stays bit for bit what it was, an accumulated -0.0 included); a recording launch writes the env's current cells,
+ *      reward +0.0, prob +0.0, done 0, collision 0, truncated 0.  A parked row is recognisable by done == 0 && prob == 0;
+ *   1. otherwise the four rules of the episode limit apply unchanged (with N == 0 truncated is always 0 and the ages stay zero);
+ *      rule 1, the terminal-on-entry no-op, is part of this;
+ *   2. live_steps[e] counts the steps that were neither parked nor terminal on entry;
+ *   3. a step that reports done or truncated takes one from left[e] -- the terminal no-op too, which episodes counts as well.  The
+ *      env goes back to its start cells and age 0 as under auto-reset, also when left reaches 0: a parked env stands on its start
+ *      cells with age 0, and re-arming it begins a fresh batch of episodes.
+ * Since arming, B - left[e] == episodes[e] + truncations[e], which is B once the env is parked.  Truncation and parking change no
+ * Philox counter; the step index advances by T as always.
+ *
+ * mapf_set_episode_budget: sets B and left[e] = n_episodes for every env (every call re-arms all envs); touches neither state nor
+ *   ages; refused (MAPF_EINVAL) while recording and while recorded graphs live, as mapf_set_episode_limit is.
+ * mapf_episodes_left: out_left u32[E] receives the counts, then set_left u32[E] replaces them (per-env budgets, re-arming single
+ *   envs; needs a budget); the pointer rules of mapf_episode_steps.
+ * mapf_rollout_budgeted is mapf_rollout_limited plus out_live_steps u32[E] (io->accumulate applies to it; NULL allowed, non-NULL on a
+ *   handle without a budget: MAPF_EINVAL).  The truncation pointers need a limit, as there.  mapf_rollout and mapf_rollout_limited
+ *   on a handle with a budget apply the budget and report no live steps.
+ * On a handle with a budget a rollout without MAPF_STEP_AUTO_RESET returns MAPF_EINVAL; mapf_step, mapf_step_limited and
+ *   mapf_graph_begin return MAPF_EUNSUPPORTED.  mapf_reset(mask), mapf_set_state and mapf_set_episode_limit leave left alone.
+ * Everything is validated on the host before any device work.  Budget launches run the lane-group kernels' budget instances
+ * whatever the handle's family flag or limit_packed, and mapf_last_kernel says BUDGET; with B == 0 every launch, kernel instance
+ * and name is what it is without this feature.
+ * Out of scope: budget forms of the packed (lq_*) and thread-per-env kernels (a handle with a budget takes the lane-group speed),
+ * the single step and recorded graphs, the multi-map / union-map wrappers and the scalar MapfEnv, a per-episode log, discounting.
+ * No policy is computed on the device.
+ */
+int mapf_set_episode_budget(mapf_handle_t h, uint32_t n_episodes);
+int mapf_episodes_left(mapf_handle_t h, uint32_t *out_left, const uint32_t *set_left);
+int mapf_rollout_budgeted(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_truncations, uint8_t *rec_truncated, uint32_t *out_live_steps);
 
 /* Synthetic policy used by bench/rollout: fills actions u8[n_steps*E*A] for step indices
  * t0 .. t0+n_steps-1 from the policy stream (oracle/philox.py random_actions_np; ABI 5: key seed + 1, ONE Philox

@@ -15,6 +15,7 @@ mkdir -p "$WORK/old" "$WORK/new"
 UNITS="mapf_lg_kernels|mapf_lg_kernels|
 mapf_lg_rollout|mapf_lg_rollout|
 mapf_lg_limit|mapf_lg_limit|
+mapf_lg_budget|mapf_lg_budget|
 mapf_transitions|mapf_transitions|
 mapf_lq_step|mapf_lq_step|-mllvm -amdgpu-kernarg-preload-count=14"
 for k in 8 4 2; do for r in 1 0; do UNITS="$UNITS
