@@ -274,7 +274,8 @@ RolloutTuning default_rollout_tuning(int device, std::string *err);   // (asks t
 // no thread-per-env kernel is consulted, and of the packed forms only the one family with limit instances, which launch_rollout_lg
 // tries first as it tries the packed forms without a limit)
 hipError_t launch_step_lg(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, const EpisodeLimit *limit = nullptr);
-// packed layout of the single step (mapf_lq_step.hip): true when it took the launch (*err = its status)
+// packed layout of the single step (mapf_lq_step.hip): true when it took the launch (*err = its status) -- the instance plan_step_lq
+// names (mapf_plan.hpp), one of MAPF_LQ_STEP_INSTANCES (mapf_layout.hpp), noted under lq_step_kernel_name's name
 bool try_launch_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err);
 // (budget: the episode budget of a handle that has one, or null -- then `limit` is non-null too (max_steps 0 without a limit) and the
 // lane-group budget instance takes the launch before any packed plan or thread-per-env kernel is consulted, mapf_lg_budget.hip)

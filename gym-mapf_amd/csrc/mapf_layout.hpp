@@ -1,5 +1,7 @@
 // LDS layout of the kernels that keep the move table in LDS: ONE definition for the kernels (mapf_lg_rollout.hip,
 // mapf_lq_rollout.hip, mapf_lq_step.hip) and for the launch planner (mapf_plan.hip), which decides whether an image fits.
+// Also the forms of the packed kernels and the lists of their instances (MAPF_LQ_ROLLOUT_INSTANCES, ..._TABLE_INSTANCES,
+// MAPF_LQ_STEP_INSTANCES): the planner asks them, the launchers are generated from them.
 #pragma once
 #include "mapf_kernels.hpp"
 
@@ -83,6 +85,38 @@ constexpr size_t launch_lds_bytes(TableForm form, uint32_t n_cells, unsigned blo
 constexpr bool lq_rollout_instance_exists(int K, int Q, TableForm form, bool table_policy) {
 #define X(KK, QQ, FF) if (K == KK && Q == QQ && form == TableForm::FF) return true;
     if (table_policy) { MAPF_LQ_ROLLOUT_TABLE_INSTANCES(X) } else { MAPF_LQ_ROLLOUT_INSTANCES(X) }
+#undef X
+    return false;
+}
+
+// The forms of the packed single step (mapf_lq_step.hip): the plain step, or a resident grid with the move table in LDS.  The values
+// are the kernel's BIG template argument and the `form` number of a step plan (mapf_plan.hpp).
+enum class StepForm : int { Plain = 0, FullRows = 1, DeltaRows = 2, DeltaRowsBitmap = 3 };   // (16-byte rows; 4-byte delta rows; ... + per-env occupancy bitmaps)
+struct StepFormTraits {
+    bool resident, bitmap;           // a resident grid walks the batch in chunks; per-env occupancy bitmaps follow the table (kBitmapNote)
+    const char *tag, *note;          // what the kernel's name says about the form, as TableFormTraits
+};
+constexpr StepFormTraits step_form_traits(StepForm form) {
+    switch (form) {
+        case StepForm::FullRows:        return {true, false, ",BIG", ", move table in LDS"};
+        case StepForm::DeltaRows:       return {true, false, ",DELTA", ", 4-byte delta rows of the move table in LDS"};
+        case StepForm::DeltaRowsBitmap: return {true, true, ",DELTA,BITMAP", ", 4-byte delta rows of the move table in LDS"};
+        default:                        return {false, false, "", ""};   // Plain
+    }
+}
+// Which instances of lq_step_kernel exist: X(Q, K, form), each with and without the scenario table and terminal handling, in the order
+// plan_step_lq tries their forms.  mapf_lq_step.hip generates its dispatch from the list, in this order (which is what keeps the
+// kernels' places in the object); mapf_plan.hip plans nothing else.
+#define MAPF_LQ_STEP_INSTANCES(X)                                                                                          \
+    X(1, 8, FullRows) X(2, 8, FullRows) X(4, 8, FullRows)                                                                  \
+    X(8, 4, DeltaRowsBitmap)                                                                                               \
+    X(1, 4, DeltaRows) X(2, 4, DeltaRows) X(4, 4, DeltaRows) X(8, 4, DeltaRows)                                            \
+    X(1, 4, FullRows) X(2, 4, FullRows) X(4, 4, FullRows) X(8, 4, FullRows)                                                \
+    X(1, 4, Plain) X(2, 4, Plain) X(4, 4, Plain) X(8, 4, Plain) X(16, 4, Plain)                                            \
+    X(2, 2, Plain) X(4, 2, Plain) X(8, 2, Plain) X(16, 2, Plain)
+constexpr bool lq_step_instance_exists(int K, int Q, StepForm form) {
+#define X(QQ, KK, FF) if (Q == QQ && K == KK && form == StepForm::FF) return true;
+    MAPF_LQ_STEP_INSTANCES(X)
 #undef X
     return false;
 }

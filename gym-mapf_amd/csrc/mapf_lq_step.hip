@@ -1,8 +1,9 @@
-// Packed-layout single step: one MapfEnv.step() of every env per launch (mapf_step with device-drawn uniforms), K = 2 or
-// 4 agents per lane, Q = A/K lanes per env -- the lane layout of mapf_lq_rollout.hip applied to the one-launch-per-step
+// Packed-layout single step: one MapfEnv.step() of every env per launch (mapf_step with device-drawn uniforms), K = 2, 4
+// or 8 agents per lane, Q = A/K lanes per env -- the lane layout of mapf_lq_rollout.hip applied to the one-launch-per-step
 // path, for full groups and batches that fill their blocks; everything else (caller-supplied uniforms, odd agent
 // counts, ragged batches) stays with lg_step_kernel (mapf_lg_kernels.hip), whose semantics this kernel reproduces
-// line by line.
+// line by line.  Which instances exist is MAPF_LQ_STEP_INSTANCES' say (mapf_layout.hpp); which one a launch takes and what
+// it is called, mapf_plan.hip's (plan_step_lq, lq_step_kernel_name): the launcher at this file's end walks the list.
 //
 // A single step is launch- and latency-bound (argument block -> state / actions -> table rows -> stores, with ~225 vector
 // instructions in between and ~1 us of dispatch overhead around it): what the kernel is built around is described at its
@@ -109,7 +110,7 @@ __global__ void __launch_bounds__(BIG ? 1024 : 512) lq_step_kernel(uint16_t *con
                                                       const uint32_t agents_block, const uint32_t t_lo, const uint32_t seed_lo,
                                                       const uint32_t seed_hi, const StepArgs p_block, const uint32_t n_chunks) {
     constexpr int P = K / 2;
-    // BIG is a StepForm's number (mapf_plan.hpp): resident grid with the move table in LDS; ... as 4-byte delta rows; ... with per-env bitmaps behind them
+    // BIG is a StepForm's number (mapf_layout.hpp): resident grid with the move table in LDS; ... as 4-byte delta rows; ... with per-env bitmaps behind them
     constexpr bool kResident = BIG != 0, kDeltaRows = BIG >= 2, kBitmaps = BIG == 3;
 #ifdef MAPF_STEP_STAMPS
     unsigned long long stamp_[8] = {}, real0_, cyc0_;
@@ -532,35 +533,22 @@ static hipError_t launch_step_instance(const StepPlan &plan, const StepArgs &arg
     return hipGetLastError();
 }
 
-// true when the packed layout took the launch (*err = its status); false = not applicable, use lg_step_kernel
+// true when the packed layout took the launch (*err = its status); false = not applicable, use lg_step_kernel.  The plan
+// (plan_step_lq) names the instance and lq_step_kernel_name its name; the launcher decides nothing itself.
 bool try_launch_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err) {
 #ifndef MAPF_STEP_STAMPS   // (the diagnostic build receives its stamp buffer through `uniforms`)
     if (args.uniforms != nullptr) return false;
 #endif
     StepPlan plan;
     if (!plan_step_lq(n_agents, args, tune, &plan)) return false;
-    const bool scen = args.scen != nullptr, term = !args.state_not_terminal;
-    const char *const scen_tag = scen ? ",SCEN" : "", *const term_tag = term ? "" : ",NO_TERMINAL",
-               *const scen_note = scen ? ", start / goal rows from the scenario table" : "";
-    const int Q = plan.Q, K = plan.K;
-    const bool bitmaps = plan.big == StepForm::DeltaRowsBitmap;
-    if (plan.big == StepForm::FullRows)
-        note_kernel("lq_step_kernel<Q=%d,K=%d%s%s,BIG> block=1024 resident grid (packed layout: %d agents per lane, move table in LDS%s)", Q, K, scen_tag, term_tag, K, scen_note);
-    else if (plan.big != StepForm::Plain)
-        note_kernel("lq_step_kernel<Q=%d,K=%d%s%s,DELTA%s> block=%u resident grid (packed layout: 4 agents per lane, 4-byte delta rows of the move table in LDS%s%s)", Q, K,
-                    scen_tag, term_tag, bitmaps ? ",BITMAP" : "", plan.block, bitmaps ? ", collisions through per-env occupancy bitmaps" : "", scen_note);
-    else
-        note_kernel("lq_step_kernel<Q=%d,K=%d%s%s> block=%u (packed layout: %d agents per lane%s)", Q, K, scen_tag, term_tag, plan.block, K, scen_note);
-    // the instances that exist, in the order plan_step_lq tries their forms
-#define X(QQ, KK, FF) if (Q == QQ && K == KK && plan.big == StepForm::FF) { *err = launch_step_instance<QQ, KK, int(StepForm::FF)>(plan, args, uint32_t(n_agents), stream); return true; }
-    X(1, 8, FullRows) X(2, 8, FullRows) X(4, 8, FullRows)
-    X(8, 4, DeltaRowsBitmap)
-    X(1, 4, DeltaRows) X(2, 4, DeltaRows) X(4, 4, DeltaRows) X(8, 4, DeltaRows)
-    X(1, 4, FullRows) X(2, 4, FullRows) X(4, 4, FullRows) X(8, 4, FullRows)
-    X(1, 4, Plain) X(2, 4, Plain) X(4, 4, Plain) X(8, 4, Plain) X(16, 4, Plain)
-    X(2, 2, Plain) X(4, 2, Plain) X(8, 2, Plain) X(16, 2, Plain)
+    char name[kKernelNameBytes];
+    lq_step_kernel_name(name, plan, args.scen != nullptr, !args.state_not_terminal);
+    note_kernel("%s", name);
+    // the planned instance, by the list in mapf_layout.hpp (what lq_step_instance_exists answers from), in the list's order
+#define X(QQ, KK, FF) if (plan.Q == QQ && plan.K == KK && plan.big == StepForm::FF) { *err = launch_step_instance<QQ, KK, int(StepForm::FF)>(plan, args, uint32_t(n_agents), stream); return true; }
+    MAPF_LQ_STEP_INSTANCES(X)
 #undef X
-    *err = hipErrorInvalidValue;   // (plan_step_lq plans no other instance)
+    *err = hipErrorInvalidValue;   // (not reached: plan_step_lq asks lq_step_instance_exists before it plans)
     return true;
 }
 

@@ -209,9 +209,13 @@ void lq_rollout_kernel_name(char *name, const LqPlan &plan, bool record, bool st
              form.bitmap ? kBitmapNote : "", note);
 }
 
-// The packed single step (mapf_lq_step.hip): full groups of K = 4 or 2 agents per lane, Q = A / K lanes per env a power of two.
-// The forms are tried in this order, and a form whose divisibility test fails falls through to the next one: eight agents per
-// lane over the LDS table, delta rows (with or without bitmaps), BIG, the plain step.  false = not applicable, use lg_step_kernel.
+// what a step plan names must be an instance the launcher holds (MAPF_LQ_STEP_INSTANCES), as first_candidate asks for the rollouts
+static bool step_instance_planned(const StepPlan &plan) { return lq_step_instance_exists(plan.K, plan.Q, plan.big); }
+
+// The packed single step (mapf_lq_step.hip): full groups of K = 4 or 2 agents per lane (8 over the LDS table), Q = A / K lanes per
+// env a power of two.  The forms are tried in this order, and a form whose divisibility test fails falls through to the next one:
+// eight agents per lane over the LDS table, delta rows (with or without bitmaps), BIG, the plain step.  A form that applies but has
+// no instance declines.  false = not applicable, use lg_step_kernel (*plan is then unspecified).
 bool plan_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, StepPlan *plan) {
     // top_tie: a three-entry list whose last cumulative sum rounds below 1.0 needs a third compare per agent; the packed
     // sampling does two (as in the packed rollout), so such a table stays with the lane-group kernel
@@ -242,7 +246,7 @@ bool plan_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune,
         const int Q8 = Q / 2;
         const unsigned block = 1024u, n_chunks = unsigned(args.n_envs * uint64_t(Q8) / block), grid = n_chunks < unsigned(n_cu) ? n_chunks : unsigned(n_cu);
         *plan = StepPlan{8, Q8, StepForm::FullRows, block, grid, n_chunks, big_lds, int(kLdsBytes - kLdsReserve)};
-        return true;
+        return step_instance_planned(*plan);
     }
     // The delta-row forms (StepForm::DeltaRows, DeltaRowsBitmap): where the 16-byte rows do not fit (64x64 maps) but the 4-byte ones do, from a batch of one
     // full residency on (65536 envs of 32 agents) -- below that the table copy per block (79 KB through the XCD's L2 for each of
@@ -268,13 +272,13 @@ bool plan_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune,
             if (per_cu > 2048u / block) per_cu = 2048u / block;
             const unsigned n_chunks = unsigned(lanes / block), grid = n_chunks < per_cu * unsigned(n_cu) ? n_chunks : per_cu * unsigned(n_cu);
             *plan = StepPlan{K, Q, bitmaps ? StepForm::DeltaRowsBitmap : StepForm::DeltaRows, block, grid, n_chunks, form_lds, int(kLdsBytes)};
-            return true;
+            return step_instance_planned(*plan);
         }
     }
     if (big) {
         const unsigned block = 1024u, n_chunks = unsigned(lanes / block), grid = n_chunks < 2u * unsigned(n_cu) ? n_chunks : 2u * unsigned(n_cu);
         *plan = StepPlan{K, Q, StepForm::FullRows, block, grid, n_chunks, big_lds, int(kLdsBytes - kLdsReserve)};
-        return true;
+        return step_instance_planned(*plan);
     }
     unsigned block = 256u;
     while (block > 64u && lanes < 256u * uint64_t(block)) block /= 2u;   // small batches: spread over the CUs
@@ -286,7 +290,15 @@ bool plan_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune,
     if (args.n_envs == 0 || args.n_envs % per_block != 0) return false;
     const unsigned grid = unsigned(args.n_envs / per_block);
     *plan = StepPlan{K, Q, StepForm::Plain, block, grid, grid, 0, 0};
-    return true;
+    return step_instance_planned(*plan);
+}
+
+// (the tags in the kernel's argument order, the form's notes in front of the scenario table's)
+void lq_step_kernel_name(char *name, const StepPlan &plan, bool scen, bool may_be_terminal) {
+    const StepFormTraits form = step_form_traits(plan.big);
+    snprintf(name, kKernelNameBytes, "lq_step_kernel<Q=%d,K=%d%s%s%s> block=%u%s (packed layout: %d agents per lane%s%s%s)", plan.Q, plan.K, scen ? ",SCEN" : "",
+             may_be_terminal ? "" : ",NO_TERMINAL", form.tag, plan.block, form.resident ? " resident grid" : "", plan.K, form.note,
+             form.bitmap ? kBitmapNote : "", scen ? ", start / goal rows from the scenario table" : "");
 }
 
 // ------------------------------------------------------------------- the lane-group family

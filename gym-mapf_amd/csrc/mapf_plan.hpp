@@ -2,7 +2,8 @@
 // takes.  Pure integer arithmetic over the launch's shape, the tuning and the LDS layout (mapf_layout.hpp) -- no kernel, no
 // runtime call -- so it can be swept without a device (mapf_debug_rollout_plan, tests/test_plan_decisions.py).  A launcher
 // takes ONE plan and launches the instance it names; it decides nothing itself (the lane-group plans name their family too: with
-// or without the episode step limit).
+// or without the episode step limit).  The name a launch notes is formatted here as well, one function per planned family -- the
+// packed rollout, the packed step, the lane-group rollout and step -- so a shape's name can be asked for without a launch.
 #pragma once
 #include "mapf_layout.hpp"
 
@@ -39,18 +40,21 @@ inline bool rollout_may_be_terminal(const RolloutArgs &args) { return !(args.aut
 // bytes); criteria; may-be-terminal.  A limit plan's name says _table_limit, LIMIT and "; episode step limit".
 void lq_rollout_kernel_name(char *name, const LqPlan &plan, bool record, bool streamed, bool table_policy, bool soc, bool may_be_terminal, uint32_t table_bytes);
 
-// The forms of the packed single step: the plain step, or a resident grid with the move table in LDS (the values: the kernel's BIG)
-enum class StepForm : int { Plain = 0, FullRows = 1, DeltaRows = 2, DeltaRowsBitmap = 3 };   // (16-byte rows; 4-byte delta rows; ... + per-env occupancy bitmaps)
-// What try_launch_step_lq (mapf_lq_step.hip) launches: the instance lq_step_kernel<Q, K, ., ., form> and its geometry.
+// What try_launch_step_lq (mapf_lq_step.hip) launches: the instance lq_step_kernel<Q, K, ., ., form> (StepForm and the list of the
+// instances: mapf_layout.hpp -- a plan names one of MAPF_LQ_STEP_INSTANCES or there is none) and its geometry.
 struct StepPlan {
     int K = 0, Q = 0;                // agents per lane (2, 4; 8 in the large-batch form), lanes per env
-    StepForm big = StepForm::Plain;   // the form (the name of the kernel's template argument)
+    StepForm big = StepForm::Plain;   // the form, under the name of the kernel's template argument (BIG): any of the four, not one BIG form.
+                                     // The name is what tests/host_tables_shim.hip reads the field by, this commit's and earlier ones'
     unsigned block = 0, grid = 0;
     unsigned n_chunks = 0;           // the kernel's last argument: chunks of `block` lanes the resident grid walks (plain step: the grid)
     size_t lds_bytes = 0;            // dynamic LDS segment (0 for the plain step: its 1 KB image is static)
     int lds_limit = 0;               // what the launcher raises the instance's dynamic-LDS limit to when lds_bytes > 32 KB
 };
 bool plan_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, StepPlan *plan);
+// The name the launcher notes for a step plan (mapf_last_kernel; kKernelNameBytes as the other names), from the plan and what the
+// launch says: start / goal rows from the scenario table or not, and whether an env may be terminal when the step begins.
+void lq_step_kernel_name(char *name, const StepPlan &plan, bool scen, bool may_be_terminal);
 
 // The lane-group family (mapf_lg.hpp) takes every launch the packed kernels decline: odd teams, ragged batches, large maps,
 // caller-supplied uniforms.  L lanes per env: the power of two >= ceil(A / 2) (two agents per lane).

@@ -76,8 +76,8 @@ int shim_greedy_cells(const uint16_t *nbr, uint32_t V, const uint32_t *cell_rc, 
     return 1;
 }
 
-// plan_step_lq over a shape: out = K, Q, form (StepForm's number), block, grid, n_chunks, lds_bytes, lds_limit; 1 = a packed form, 0 = none, -1 = bad tune
-int shim_plan_step(uint32_t n_cells, int n_agents, uint64_t n_envs, int has_delta_rows, int n_cu, const char *tune, uint64_t out[8]) {
+// (what the two entries below share: 1 = a packed form, 0 = none, -1 = bad tune)
+static int step_lq(uint32_t n_cells, int n_agents, uint64_t n_envs, int has_delta_rows, int n_cu, const char *tune, StepPlan *plan) {
     std::string err;
     const RolloutTuning t = rollout_tuning_for(n_cu, tune, &err);
     if (!err.empty()) return -1;
@@ -86,12 +86,26 @@ int shim_plan_step(uint32_t n_cells, int n_agents, uint64_t n_envs, int has_delt
     args.c.n_cells = n_cells;
     args.n_envs = n_envs;
     args.mv4 = has_delta_rows ? &present : nullptr;
+    return plan_step_lq(n_agents, args, t, plan) ? 1 : 0;
+}
+// plan_step_lq over a shape: out = K, Q, form (StepForm's number), block, grid, n_chunks, lds_bytes, lds_limit
+int shim_plan_step(uint32_t n_cells, int n_agents, uint64_t n_envs, int has_delta_rows, int n_cu, const char *tune, uint64_t out[8]) {
     StepPlan plan;
-    if (!plan_step_lq(n_agents, args, t, &plan)) return 0;
+    const int rc = step_lq(n_cells, n_agents, n_envs, has_delta_rows, n_cu, tune, &plan);
+    if (rc != 1) return rc;
     out[0] = uint64_t(plan.K); out[1] = uint64_t(plan.Q); out[2] = uint64_t(int(plan.big)); out[3] = plan.block; out[4] = plan.grid;
     out[5] = plan.n_chunks; out[6] = plan.lds_bytes; out[7] = uint64_t(plan.lds_limit);
     return 1;
 }
+// ... and the name the launcher notes for that plan (kKernelNameBytes)
+int shim_lq_step_name(uint32_t n_cells, int n_agents, uint64_t n_envs, int has_delta_rows, int n_cu, const char *tune, int scen, int may_be_terminal, char *name) {
+    StepPlan plan;
+    const int rc = step_lq(n_cells, n_agents, n_envs, has_delta_rows, n_cu, tune, &plan);
+    if (rc == 1) lq_step_kernel_name(name, plan, scen != 0, may_be_terminal != 0);
+    return rc;
+}
+// does the launcher hold the packed step instance (K, Q, form)?
+int shim_step_instance_exists(int K, int Q, int form) { return form >= 0 && form <= 3 && lq_step_instance_exists(K, Q, StepForm(form)) ? 1 : 0; }
 
 // (only the fields a rollout plan reads: the shape, and which optional arrays are present -- never dereferenced)
 static RolloutArgs rollout_shape(uint32_t n_cells, uint64_t n_envs, uint32_t n_steps, int has_delta_rows, bool streamed) {

@@ -66,6 +66,10 @@ def load_shim(path):
         lib.shim_plan_limit_step_lg.argtypes = lib.shim_plan_step_lg.argtypes
     if hasattr(lib, 'shim_rollout_instance_exists'):
         lib.shim_rollout_instance_exists.argtypes = [ctypes.c_int] * 4
+    if hasattr(lib, 'shim_step_instance_exists'):
+        lib.shim_step_instance_exists.argtypes = [ctypes.c_int] * 3
+        lib.shim_lq_step_name.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_char_p]
     return lib
 
 
@@ -296,6 +300,11 @@ STEP_PLAN_AGENTS = (2, 3, 4, 6, 8, 16, 32, 64, 128)
 STEP_PLAN_ENVS = (0, 1, 64, 1000, 1024, 4096, 16384, 65536, 131072, 262144, 1 << 20, 1 << 22)
 
 
+def step_instances(lib):
+    """the (Q, K, form) of MAPF_LQ_STEP_INSTANCES (csrc/mapf_layout.hpp): the list the planner asks and the launcher walks"""
+    return {(Q, K, form) for K in (2, 4, 8) for Q in range(1, 17) for form in range(4) if lib.shim_step_instance_exists(K, Q, form) == 1}
+
+
 def test_packed_step_plan_stays_within_the_lds_and_its_residency(shim):
     """plan_step_lq swept like the rollout plan (tests/test_cabi_and_host.py): whatever instance is planned exists, fills whole
     blocks, keeps its LDS image within the CU's 160 KB (and within the limit the launcher raises the kernel to), and its
@@ -303,8 +312,8 @@ def test_packed_step_plan_stays_within_the_lds_and_its_residency(shim):
     out = np.zeros(8, np.uint64)
     stride = lambda V: (((V + 31) // 32) * 4 + 15) & ~15                                   # noqa: E731  (bytes of one env's bitmap)
     cells, tunes = STEP_PLAN_CELLS, STEP_PLAN_TUNES
-    instances = {(Q, 8, 1) for Q in (1, 2, 4)} | {(8, 4, 3)} | {(Q, 4, b) for Q in (1, 2, 4, 8) for b in (1, 2)} | \
-                {(Q, 4, 0) for Q in (1, 2, 4, 8, 16)} | {(Q, 2, 0) for Q in (2, 4, 8, 16)}          # mapf_lq_step.hip's instance switch
+    instances = step_instances(shim)
+    assert len(instances) == 21, sorted(instances)
     seen, n_planned = set(), 0
     for tune in tunes:
         for n_cu in STEP_PLAN_CUS:

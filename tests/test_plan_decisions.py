@@ -28,7 +28,14 @@ after a one-step rollout of every launch of lq_launches() below -- every packed 
 terminal variant, recording or not, both table forms, with and without the limit -- on an MI355X, from the library of the commit
 whose launchers still formatted these names themselves (MAPF_HIP_LIB; generation_info.json says how):
 
-    python tests/test_plan_decisions.py --record-lq-names [OUT.json]"""
+    python tests/test_plan_decisions.py --record-lq-names [OUT.json]
+
+The packed single step is named by lq_step_kernel_name.  tests/golden/lq_step_kernel_names.json holds what mapf_last_kernel said after
+a step of every launch of LQ_STEP_LAUNCHES below -- every entry of the step's instance list, with and without the scenario table, a step
+that may meet a terminal env and one that cannot -- on an MI355X, from the library of the commit whose launcher still formatted these
+names itself:
+
+    python tests/test_plan_decisions.py --record-lq-step-names [OUT.json]"""
 import ctypes
 import hashlib
 import json
@@ -77,6 +84,19 @@ LQ_TABLE_ROWS = 64
 # (criteria, auto-reset): no env of these launches starts terminal, so a launch may meet a terminal env exactly without auto-reset
 LQ_VARIANTS = {'SOC': ('SoC', True), 'MAKESPAN': ('Makespan', False), 'NO_TERMINAL': ('Makespan', True)}
 LQ_POLICIES = ('STREAM', 'POLICY', 'TABLE')
+# the packed step's names: every instance on the same map at the smallest batch of full blocks its form accepts -- the plain step in
+# one-wave blocks (two agents per lane: k=2), the LDS-table form in its 1024-thread blocks (eight agents per lane unless k=4), the
+# delta-row forms in 512-thread blocks
+FIXTURE_LQ_STEP_NAMES = os.path.join(GOLDEN, 'lq_step_kernel_names.json')
+STEP_FORMS = ('Plain', 'FullRows', 'DeltaRows', 'DeltaRowsBitmap')   # StepForm's numbers; what a name says of each: its tag, its block
+STEP_FORM_TAG, STEP_FORM_BLOCK = ('', ',BIG', ',DELTA', ',DELTA,BITMAP'), (64, 1024, 512, 512)
+LQ_STEP_LAUNCHES = {'%s-K%d-Q%d' % (STEP_FORMS[form], K, Q): (form, K, Q, E, tune) for form, K, Q, E, tune in
+                    [(0, 4, Q, max(64, 512 // Q), '') for Q in (1, 2, 4, 8, 16)] + [(0, 2, Q, max(64, 512 // Q), 'k=2') for Q in (2, 4, 8, 16)] +
+                    [(1, 4, Q, 1024 // Q, 'step_big=2,k=4') for Q in (1, 2, 4, 8)] + [(1, 8, Q, 1024 // Q, 'step_big=2') for Q in (1, 2, 4)] +
+                    [(2, 4, Q, 512 // Q, 'step_delta=2,bitmap_pairs=0') for Q in (1, 2, 4, 8)] + [(3, 4, 8, 64, 'step_delta=2')]}
+# (scenario table, may be terminal): the handles' rows come from five scenarios, so MAPF_TUNE scen_table=0 is what leaves the table out;
+# no env starts terminal, so a step may meet a terminal env exactly when the step before it ran without auto-reset
+LQ_STEP_VARIANTS = {'%s %s' % ('SCEN' if scen else 'ROWS', 'TERMINAL' if term else 'NO_TERMINAL'): (scen, term) for scen in (True, False) for term in (True, False)}
 
 
 def _name(tune):
@@ -229,18 +249,24 @@ def lq_launches():
                 yield '%s lds=%d limit=%d' % (c.id, table_lds, limited), 'table', c.A, c.E, tune, 'TABLE', limited, parts
 
 
-def launch_lq(grid, A, E, tune, policy, limited, criteria, runs):
-    """a handle of that shape under `tune`, and the names of its one-step rollouts `runs` = [(auto_reset, record), ...]"""
-    import numpy as np
+def tuned_env(grid, A, E, tune, criteria, start, goal):
+    """a handle created under MAPF_TUNE = `tune` (read when the handle is created)"""
     from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
-    V, outer_tune = len(grid.tables()[0]), os.environ.pop('MAPF_TUNE', None)
-    os.environ['MAPF_TUNE'] = tune                              # (read when the handle is created)
+    outer_tune = os.environ.pop('MAPF_TUNE', None)
+    os.environ['MAPF_TUNE'] = tune
     try:
-        env = VecMapfEnv(grid, A, None, None, 0.2, -1000.0, 100.0, -1.0, OptimizationCriteria[criteria], n_envs=E, start_local=np.arange(A), goal_local=np.arange(A) + 1)
+        return VecMapfEnv(grid, A, None, None, 0.2, -1000.0, 100.0, -1.0, OptimizationCriteria[criteria], n_envs=E, start_local=start, goal_local=goal)
     finally:
         os.environ.pop('MAPF_TUNE', None)
         if outer_tune is not None:
             os.environ['MAPF_TUNE'] = outer_tune
+
+
+def launch_lq(grid, A, E, tune, policy, limited, criteria, runs):
+    """a handle of that shape under `tune`, and the names of its one-step rollouts `runs` = [(auto_reset, record), ...]"""
+    import numpy as np
+    V = len(grid.tables()[0])
+    env = tuned_env(grid, A, E, tune, criteria, np.arange(A), np.arange(A) + 1)
     try:
         if policy == 'TABLE':
             env.set_policy('table', table=np.zeros((LQ_TABLE_ROWS, V), np.uint8), rows=np.zeros(A, np.uint16))
@@ -283,6 +309,54 @@ def planned_lq_name(shim_lib, n_cu, launch, variant, record):
                                        LQ_POLICIES.index(launch['policy']), launch['limited'], int(record), int(criteria == 'SoC'), int(not auto_reset), name)
     assert rc in (0, 1), (rc, launch)
     return name.value.decode() if rc else None
+
+
+def launch_lq_step(grid, A, E, tune, scen):
+    """a handle of that shape under `tune` whose rows come from five scenarios (scen: through the scenario table; else scen_table=0),
+    and the names of two of its steps: one that may meet a terminal env (the step before it ran without auto-reset) and, right after
+    that auto-reset step, one that cannot"""
+    import numpy as np
+    rows = (np.arange(E) % 5)[:, None] + np.arange(A)[None, :]
+    env = tuned_env(grid, A, E, ','.join(filter(None, (tune, '' if scen else 'scen_table=0'))), 'Makespan', rows, rows + 1)
+    try:
+        names, actions = [], np.zeros((E, A), np.uint8)
+        for auto_reset in (False, True, True):
+            env.step(actions, auto_reset=auto_reset)
+            names.append(env.last_kernel('step'))
+        return names[1:]
+    finally:
+        env.close()
+
+
+def lq_step_head(form, K, Q, scen, term):
+    """what the name of that instance begins with"""
+    return 'lq_step_kernel<Q=%d,K=%d%s%s%s> block=%d ' % (Q, K, ',SCEN' if scen else '', '' if term else ',NO_TERMINAL', STEP_FORM_TAG[form], STEP_FORM_BLOCK[form])
+
+
+def record_lq_step_names(n_cu):
+    """{'n_cu', 'launches': {key: {'V', 'A', 'E', 'tune', 'delta', 'names': {'<SCEN|ROWS> <TERMINAL|NO_TERMINAL>': full name}}}}"""
+    import episode_limit_cases as ec
+    grid, found = ec.random_map(3), {}
+    V = len(grid.tables()[0])
+    for key, (form, K, Q, E, tune) in LQ_STEP_LAUNCHES.items():
+        names = {}
+        for scen in (True, False):
+            for term, name in zip((True, False), launch_lq_step(grid, K * Q, E, tune, scen)):
+                assert name.startswith(lq_step_head(form, K, Q, scen, term)), (key, scen, term, name)
+                names['%s %s' % ('SCEN' if scen else 'ROWS', 'TERMINAL' if term else 'NO_TERMINAL')] = name
+        print('launched %s' % key, flush=True)
+        found[key] = {'V': V, 'A': K * Q, 'E': E, 'tune': tune, 'delta': 1, 'names': names}
+    return {'n_cu': n_cu, 'launches': found}
+
+
+def planned_lq_step(shim_lib, n_cu, launch, scen, term):
+    """the same step through the planner and lq_step_kernel_name (the shim): ((Q, K, form), name), or None where no packed form applies"""
+    out, name = (ctypes.c_uint64 * 8)(), ctypes.create_string_buffer(2 * KERNEL_NAME_BYTES)
+    tune = ','.join(filter(None, (launch['tune'], '' if scen else 'scen_table=0'))).encode() or None
+    shape = (launch['V'], launch['A'], launch['E'], launch['delta'], n_cu, tune)
+    rc = shim_lib.shim_lq_step_name(*shape, int(scen), int(term), name)
+    assert rc in (0, 1) and shim_lib.shim_plan_step(*shape, out) == rc, (rc, launch)
+    return ((out[1], out[0], out[2]), name.value.decode()) if rc else None
 
 
 class LaneGroupLauncher:
@@ -504,6 +578,49 @@ def test_packed_launches_print_the_recorded_names():
         assert found == [launch['names']['NO_TERMINAL TOTALS'], launch['names']['MAKESPAN RECORD']], (key, found)
 
 
+def _lq_step_fixture():
+    with open(FIXTURE_LQ_STEP_NAMES) as f:
+        return json.load(f)
+
+
+def test_packed_step_names_are_the_recorded_ones(shim):  # noqa: F811
+    """plan_step_lq and lq_step_kernel_name, asked for every step of the fixture, against what the launcher's own format strings printed
+    on the GPU before the name had a function: byte for byte, shorter than what mapf_last_kernel keeps, every instance of the list"""
+    from test_host_tables import step_instances
+    recorded = _lq_step_fixture()
+    launches, names, seen = recorded['launches'], set(), set()
+    assert sorted(launches) == sorted(LQ_STEP_LAUNCHES) and len(launches) == 21
+    for key, (form, K, Q, E, tune) in LQ_STEP_LAUNCHES.items():
+        launch = launches[key]
+        assert (launch['A'], launch['E'], launch['tune']) == (K * Q, E, tune) and sorted(launch['names']) == sorted(LQ_STEP_VARIANTS), key
+        for which, (scen, term) in LQ_STEP_VARIANTS.items():
+            name = launch['names'][which]
+            instance, found = planned_lq_step(shim, recorded['n_cu'], launch, scen, term)
+            assert instance == (Q, K, form) and found == name and len(name) < KERNEL_NAME_BYTES and name.startswith(lq_step_head(form, K, Q, scen, term)), \
+                (key, which, instance, found, name)
+            names.add(name)
+            seen.add(instance)
+    assert len(names) == 84 and seen == step_instances(shim), (len(names), sorted(seen))
+
+
+# one step launch per form: the shapes of wide_counter_cases.STEP_CASES' rows A8-Q2K4-SCEN, A8-Q4K2, A16-Q2K8-BIG, A32-DELTA and
+# A32-DELTA-BITMAP at the fixture's batches (scenario table or not, as those rows have it)
+LQ_STEP_GPU_LAUNCHES = (('Plain-K4-Q2', True), ('Plain-K2-Q4', False), ('FullRows-K8-Q2', False), ('DeltaRows-K4-Q8', False), ('DeltaRowsBitmap-K4-Q8', False))
+
+
+@pytest.mark.gpu
+def test_packed_step_launches_print_the_recorded_names():
+    """the step's launcher notes the name the plan's name function gives: a launch of every form, a step that may be terminal and then
+    one after an auto-reset step, each compared in full with the recorded name"""
+    import episode_limit_cases as ec
+    launches, grid = _lq_step_fixture()['launches'], ec.random_map(3)
+    for key, scen in LQ_STEP_GPU_LAUNCHES:
+        launch, rows = launches[key], 'SCEN' if scen else 'ROWS'
+        assert launch['E'] <= 1024 and launch['V'] == len(grid.tables()[0]), key
+        found = launch_lq_step(grid, launch['A'], launch['E'], launch['tune'], scen)
+        assert found == [launch['names'][rows + ' TERMINAL'], launch['names'][rows + ' NO_TERMINAL']], (key, found)
+
+
 def lg_kinds(recorded):
     """{kind: (shape's key, index into LG_ROLLOUTS, recorded name)}: the smallest shape of every combination that exists of full /
     ragged groups, move table in LDS / global memory, dense / guarded and table policy or not; plus the smallest one whose block
@@ -547,13 +664,14 @@ if __name__ == '__main__':
             json.dump(limit_plans(load_shim(shim_path)), f, indent=0, sort_keys=True)
             f.write('\n')
         sys.exit(0)
-    if len(sys.argv) >= 2 and sys.argv[1] == '--record-lq-names':   # (needs a GPU: its CU count is what the handles' tuning starts from)
+    if len(sys.argv) >= 2 and sys.argv[1] in ('--record-lq-names', '--record-lq-step-names'):   # (need a GPU: its CU count is what the handles' tuning starts from)
         import torch
         from gym_mapf_amd import _native
-        with open(sys.argv[2] if len(sys.argv) > 2 else FIXTURE_LQ_NAMES, 'w') as f:
-            json.dump(record_lq_names(torch.cuda.get_device_properties(0).multi_processor_count), f, indent=0, sort_keys=True)
+        record, default = (record_lq_names, FIXTURE_LQ_NAMES) if sys.argv[1] == '--record-lq-names' else (record_lq_step_names, FIXTURE_LQ_STEP_NAMES)
+        with open(sys.argv[2] if len(sys.argv) > 2 else default, 'w') as f:
+            json.dump(record(torch.cuda.get_device_properties(0).multi_processor_count), f, indent=0, sort_keys=True)
             f.write('\n')
-        print('recorded the packed rollout names from %s' % _native.LIB_PATH)
+        print('recorded the packed %s names from %s' % ('rollout' if record is record_lq_names else 'step', _native.LIB_PATH))
         sys.exit(0)
     if len(sys.argv) < 2 or sys.argv[1] != '--record':
         sys.exit(__doc__)

@@ -205,6 +205,11 @@ def test_step_case_plans_the_form_it_names(case, shim):  # noqa: F811
         n = shim.shim_scen_table(start.ctypes.data, 0, goal.ctypes.data, 0, case.E, case.A, scen.ctypes.data, rows.ctypes.data)
         assert n == (0 if case.scen is None else 5), n
         assert (',SCEN' in case.layout) == (case.scen is True) and (case.scen is not False or case.tune.get('scen_table') == '0')
+        # ... and step_name's prefixes are prefixes of the name the launcher notes for that plan (the graph cases name the first call only)
+        name = ctypes.create_string_buffer(2 * KERNEL_NAME_BYTES)
+        for call in (0, 1) if case in wc.STEP_CASES else (0,):
+            assert shim.shim_lq_step_name(V, case.A, case.E, delta, N_CU, tune, int(case.scen is True), int(call == 0), name) == 1
+            assert name.value.decode().startswith(wc.step_name(case, call)), (call, name.value, wc.step_name(case, call))
     else:
         assert rc == 0, (rc, tuple(out))
         plan, name = (ctypes.c_uint64 * 4)(), ctypes.create_string_buffer(2 * KERNEL_NAME_BYTES)
