@@ -140,10 +140,7 @@ struct mapf_handle_s : StreamAndEvents {
     mapf::EnvConsts c{};
     bool start_broadcast = false, goal_broadcast = false, device_ptrs = false;
     bool stream_exposed = false;   // mapf_get_stream was called: somebody else may capture the stream (check_foreign_capture)
-    bool lane_group = false;   // kernel family
-    // The thread-per-env rollout specialisations for A >= 8 need SGPR spills (the pointer-heavy argument block
-    // plus A-wide unrolling); only spill-free kernels are dispatched, so those sizes use the lane-group rollout.
-    bool lane_group_rollout = false;
+    mapf::FamilyPreference prefer = mapf::FamilyPreference::Auto;   // the kernel family the create flags ask for (what a launch takes: mapf_plan.hpp's route)
     bool start_terminal_any = true;   // is_terminal(start) for some env (looked up once at create)
     bool mv_delta8 = false;           // every neighbour id lies within +-127 of its cell's id (the 4-byte delta rows of the bitmap rollout)
     // Can some env be terminal right now?  Not after a call that auto-reset every finished episode (unless a START state
@@ -324,14 +321,15 @@ void after_launch(mapf_handle_t h, std::string &last_kernel, uint64_t n_steps, b
     if (n_steps) h->terminal_possible() = auto_reset ? h->start_terminal_any : true;
 }
 
-// (limit: the handle's episode limit, or null -- the limit instances exist in the lane-group family only, which then takes the launch)
+// (limit: the handle's episode limit, or null)
 int launch_step_and_advance(mapf_handle_t h, const mapf::StepArgs &a, const mapf::EpisodeLimit *limit) {
-    HIP_TRY((h->lane_group || limit) ? mapf::launch_step_lg(int(h->A), a, h->tune, h->stream, limit) : mapf::launch_step(int(h->A), a, h->stream));
+    HIP_TRY(mapf::launch_step(int(h->A), a, h->tune, h->prefer, h->stream, limit));
     after_launch(h, h->last_step_kernel, 1, a.auto_reset);
     return MAPF_OK;
 }
 // The two mapf_debug_rollout_plan* entries (`who`: the one the shape message names): the null / shape checks, the tuning parse, and
-// the plan a launch of that shape takes -- under an episode limit (max_steps != 0) the lane-group limit plan, else the packed one
+// the plan the route gives a launch of that shape on a handle that prefers the lane-group family, without a table policy -- under an
+// episode limit (max_steps != 0) the lane-group limit plan, else the packed one (zeros and 0 where no packed form applies)
 int debug_rollout_plan(const char *who, uint32_t n_cells, int n_agents, uint64_t n_envs, uint32_t n_steps, int streamed, int delta_rows, int n_cu,
                        const char *tune, uint32_t max_steps, uint64_t out[6]) {
     if (!out) return fail(MAPF_EINVAL, "out is null");
@@ -348,17 +346,15 @@ int debug_rollout_plan(const char *who, uint32_t n_cells, int n_agents, uint64_t
     args.actions = streamed ? &present : nullptr;
     args.mv_delta8 = delta_rows != 0;
     args.mv4 = delta_rows ? reinterpret_cast<const uint32_t *>(&present) : nullptr;
-    if (max_steps != 0u) {   // (the lane-group plan reads the shape only)
-        const mapf::LgRolloutPlan plan = mapf::plan_rollout_lg(n_agents, args, t, true);
-        out[0] = 2; out[1] = uint64_t(plan.L); out[2] = plan.mv_lds ? 1 : 0;
-        out[3] = plan.block; out[4] = plan.lds_bytes; out[5] = plan.grid;
+    const mapf::RolloutRoute r = mapf::route_rollout(n_agents, args, t, mapf::FamilyPreference::LaneGroup, false, 0u, max_steps != 0u, false);
+    if (max_steps != 0u) {
+        out[0] = 2; out[1] = uint64_t(r.lg.L); out[2] = r.lg.mv_lds ? 1 : 0;
+        out[3] = r.lg.block; out[4] = r.lg.lds_bytes; out[5] = r.lg.grid;
         return 0;
     }
-    mapf::LqPlan plan;
-    const bool packed = mapf::plan_rollout_lq(n_agents, args, t, &plan);
-    out[0] = uint64_t(plan.K); out[1] = uint64_t(plan.Q); out[2] = uint64_t(int(plan.form));
-    out[3] = plan.block; out[4] = plan.lds_bytes; out[5] = plan.lds_total;
-    return packed ? 1 : 0;
+    out[0] = uint64_t(r.lq.K); out[1] = uint64_t(r.lq.Q); out[2] = uint64_t(int(r.lq.form));
+    out[3] = r.lq.block; out[4] = r.lq.lds_bytes; out[5] = r.lq.lds_total;
+    return r.family == mapf::KernelFamily::Packed ? 1 : 0;
 }
 }  // namespace
 
@@ -436,15 +432,11 @@ int mapf_create(const mapf_desc *d, mapf_handle_t *out_handle) {
     h->env_id_offset = d->env_id_offset; h->t = 0;
     h->start_broadcast = sb; h->goal_broadcast = gb;
     h->device_ptrs = d->flags & MAPF_FLAG_DEVICE_PTRS;
-    // kernel family: forced by flag, else lane groups whenever an env has more than one agent pair
-    if (d->flags & MAPF_FLAG_THREAD_PER_ENV) h->lane_group = false;
-    else if (d->flags & MAPF_FLAG_LANE_GROUP) h->lane_group = true;
-    else h->lane_group = A > 2;
-    h->lane_group_rollout = h->lane_group || A > uint32_t(mapf::kTpeRolloutMaxAgents);
+    if (d->flags & MAPF_FLAG_THREAD_PER_ENV) h->prefer = mapf::FamilyPreference::ThreadPerEnv;
+    else if (d->flags & MAPF_FLAG_LANE_GROUP) h->prefer = mapf::FamilyPreference::LaneGroup;
     std::string error;
     h->tune = mapf::default_rollout_tuning(d->device, &error);
     if (!error.empty()) return fail(MAPF_EINVAL, error);
-    if (d->flags & MAPF_FLAG_LANE_GROUP) h->tune.limit_packed = false;   // (the ONE statement of: such a handle never takes the packed limit instance)
 
     // the host tables (mapf_tables.hip): table image, the move table in its three forms, the scenario table
     mapf::TableImage image;
@@ -606,7 +598,7 @@ int step_impl(mapf_handle_t h, const uint8_t *actions, const double *uniforms, u
                 void *dev = io[i].user ? dp + at[i] : nullptr;
                 std::memcpy(io[i].slot, &dev, sizeof(dev));
             }
-            const uint64_t launch_threads = (h->lane_group || limit) ? E * uint64_t(mapf::lg_group_size(int(h->A))) : E;
+            const uint64_t launch_threads = mapf::step_is_thread_per_env(int(h->A), a, h->tune, h->prefer, limit) ? E : E * uint64_t(mapf::lg_group_size(int(h->A)));
             const bool flagged = launch_threads <= 64;             // one wave: see below
             const uint32_t seq = uint32_t(h->t) + 1u;
             if (flagged) {
@@ -706,7 +698,7 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
     a.start_terminal_any = h->start_terminal_any;
     a.mv_delta8 = h->mv_delta8;
     // (the episode limit travels beside the argument block too: its kernels are the lane-group family's limit instances -- and the
-    // packed table instances' where the handle's tuning opts into them: launch_rollout_lg picks, as it does without a limit)
+    // packed table instances' where the handle's tuning opts into them: the route picks, as it does without a limit)
     // (... and the episode budget beside the limit: its kernels are the lane-group family's budget instances, which take the limit
     // block too -- with max_steps 0 on a handle without a limit)
     mapf::EpisodeLimit lim{h->age, h->episode_limit, nullptr, nullptr};
@@ -734,8 +726,7 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
         if (int rc = reserve_stand_in(h, h->x_trunc, TE, "rec_truncated")) return rc;
         lim.rec_truncated = static_cast<uint8_t *>(h->x_trunc.ptr);
     }
-    HIP_TRY((h->lane_group_rollout || limit) ? mapf::launch_rollout_lg(int(h->A), a, h->tune, h->stream, table, limit, budget)
-                                             : mapf::launch_rollout(int(h->A), a, h->stream, table));
+    HIP_TRY(mapf::launch_rollout(int(h->A), a, h->tune, h->prefer, h->stream, table, limit, budget));
     after_launch(h, h->last_rollout_kernel, io->n_steps, a.auto_reset);
     if (int rc = fetch_arrays(h, arrays)) return rc;
     if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));

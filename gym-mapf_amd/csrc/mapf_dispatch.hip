@@ -1,5 +1,6 @@
-// Routes a launch to the translation unit that holds the kernels specialised for its shape: the thread-per-env family by agent
-// count, the packed rollout by its plan (mapf_plan.hpp).  Holds no kernel itself.
+// The dispatcher: launch_rollout and launch_step, the only launch entries the C ABI calls.  Each asks the route (route_rollout /
+// route_step, mapf_plan.hpp: which family takes the launch, and that family's plan) ONCE, checks the limit / budget block once, and
+// hands the plan to the family's launcher -- the one place where a launch meets its translation unit.  Holds no kernel itself.
 #include "mapf_kernels.hpp"
 #include "mapf_plan.hpp"
 
@@ -14,43 +15,75 @@ RolloutTuning default_rollout_tuning(int device, std::string *err) {
     return rollout_tuning_for(n_cu, getenv("MAPF_TUNE"), err);
 }
 
-#define MAPF_ROUTE(fn, A, ...)                          \
+// What the limit and budget kernels rely on: ages and a limit; of a rollout, the truncated trajectory exactly when the launch
+// records; under a budget the counts and auto-reset as well, and the limit itself may then be 0 (a budget without a limit).
+static bool limit_block_complete(const EpisodeLimit *limit, const EpisodeBudget *budget, bool rollout, bool record, bool auto_reset) {
+    if (!limit) return budget == nullptr;
+    if (!limit->age || (rollout && (limit->rec_truncated != nullptr) != record)) return false;
+    return budget ? (budget->left && auto_reset) : limit->max_steps != 0u;
+}
+
+// the thread-per-env object that holds the kernels of the launch's agent count
+#define MAPF_TPE_GROUP(fn, A, ...)                      \
     switch (((A) - 1) / 4) {                            \
-        case 0: return fn##_g0(A, __VA_ARGS__);         \
-        case 1: return fn##_g1(A, __VA_ARGS__);         \
-        case 2: return fn##_g2(A, __VA_ARGS__);         \
-        case 3: return fn##_g3(A, __VA_ARGS__);         \
+        case 0: return fn##_g0(__VA_ARGS__);            \
+        case 1: return fn##_g1(__VA_ARGS__);            \
+        case 2: return fn##_g2(__VA_ARGS__);            \
+        case 3: return fn##_g3(__VA_ARGS__);            \
         default: return hipErrorInvalidValue;           \
     }
 
-hipError_t launch_step(int n_agents, const StepArgs &args, hipStream_t stream) {
-    if (n_agents < 1) return hipErrorInvalidValue;
-    MAPF_ROUTE(launch_step, n_agents, args, stream)
-}
-
-hipError_t launch_rollout(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table) {
-    if (n_agents < 1) return hipErrorInvalidValue;
-    MAPF_ROUTE(launch_rollout, n_agents, args, stream, table)
-}
-
-// true when a packed layout took the launch (*err = its status); false = not applicable, use the lane-group kernel.  Under an
-// episode step limit the packed instances are the table policy's (mapf_lq_limit.hip), opted into by MAPF_TUNE limit_packed=1
-bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy *table,
-                           const EpisodeLimit *limit) {
-    LqPlan plan;
-    if (limit && (args.n_envs == 0 || args.actions != nullptr || !table || !tune.limit_packed)) return false;
-    if (table ? !plan_rollout_lq_table(n_agents, args, tune, table->table_bytes, &plan, limit != nullptr) : !plan_rollout_lq(n_agents, args, tune, &plan)) return false;
-    const bool record = args.rec_local != nullptr;
-    // the object that holds the plan's instance: [under a limit][8, 4, 2 agents per lane][recording]
+// the packed rollout object that holds the plan's instance: [under a limit][8, 4, 2 agents per lane][recording]
+static hipError_t launch_rollout_lq(const LqPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table, const EpisodeLimit *limit) {
     using Launcher = hipError_t (*)(const LqPlan &, const RolloutArgs &, uint32_t, hipStream_t, const TablePolicy *, const EpisodeLimit *);
     static constexpr Launcher objects[2][3][2] = {
         {{launch_rollout_lq_k8_r0, launch_rollout_lq_k8_r1}, {launch_rollout_lq_k4_r0, launch_rollout_lq_k4_r1}, {launch_rollout_lq_k2_r0, launch_rollout_lq_k2_r1}},
         {{nullptr, nullptr}, {launch_rollout_lq_limit_k4_r0, launch_rollout_lq_limit_k4_r1}, {launch_rollout_lq_limit_k2_r0, launch_rollout_lq_limit_k2_r1}}};
-    const Launcher launch = objects[limit ? 1 : 0][plan.K == 8 ? 0 : (plan.K == 4 ? 1 : 2)][record ? 1 : 0];
-    // what the limit kernels rely on: ages, a limit, and the truncated trajectory exactly when the launch records
-    const bool incomplete = limit && (!limit->age || limit->max_steps == 0u || (limit->rec_truncated != nullptr) != record);
-    *err = (incomplete || !launch) ? hipErrorInvalidValue : launch(plan, args, uint32_t(n_agents), stream, table, limit);   // (no limit object with eight per lane)
-    return true;
+    const Launcher launch = objects[plan.limit ? 1 : 0][plan.K == 8 ? 0 : (plan.K == 4 ? 1 : 2)][args.rec_local ? 1 : 0];
+    return launch ? launch(plan, args, uint32_t(n_agents), stream, table, limit) : hipErrorInvalidValue;   // (no limit object with eight per lane)
+}
+
+hipError_t launch_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, hipStream_t stream, const TablePolicy *table,
+                          const EpisodeLimit *limit, const EpisodeBudget *budget) {
+    if (n_agents < 1) return hipErrorInvalidValue;
+    if (args.n_envs == 0) return hipSuccess;
+    const RolloutRoute r = route_rollout(n_agents, args, tune, prefer, table != nullptr, table ? table->table_bytes : 0u, limit != nullptr, budget != nullptr);
+    if (!limit_block_complete(limit, budget, true, args.rec_local != nullptr, args.auto_reset)) return hipErrorInvalidValue;
+    switch (r.family) {
+        case KernelFamily::ThreadPerEnv: MAPF_TPE_GROUP(launch_rollout, n_agents, r.tpe, n_agents, args, stream, table)
+        case KernelFamily::Packed: return launch_rollout_lq(r.lq, n_agents, args, stream, table, limit);
+        case KernelFamily::LaneGroup: break;
+    }
+    if (budget) return launch_rollout_lg_budget(r.lg, n_agents, args, stream, table, *limit, *budget);
+    return limit ? launch_rollout_lg_limit(r.lg, n_agents, args, stream, table, *limit) : launch_rollout_lg(r.lg, n_agents, args, stream, table);
+}
+
+// the route of a step launch (the caller supplies uniforms: a pointer is there -- but the diagnostic build of the packed step,
+// `make step_stamps`, receives its stamp buffer through `uniforms`)
+static StepRoute route_of(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, const EpisodeLimit *limit) {
+#ifdef MAPF_STEP_STAMPS
+    const bool ext_uniforms = false;
+#else
+    const bool ext_uniforms = args.uniforms != nullptr;
+#endif
+    return route_step(n_agents, args, tune, prefer, limit != nullptr, ext_uniforms);
+}
+
+bool step_is_thread_per_env(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, const EpisodeLimit *limit) {
+    return route_of(n_agents, args, tune, prefer, limit).family == KernelFamily::ThreadPerEnv;
+}
+
+hipError_t launch_step(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, hipStream_t stream, const EpisodeLimit *limit) {
+    if (n_agents < 1) return hipErrorInvalidValue;
+    if (args.n_envs == 0) return hipSuccess;
+    const StepRoute r = route_of(n_agents, args, tune, prefer, limit);
+    if (!limit_block_complete(limit, nullptr, false, false, args.auto_reset)) return hipErrorInvalidValue;
+    switch (r.family) {
+        case KernelFamily::ThreadPerEnv: MAPF_TPE_GROUP(launch_step, n_agents, r.tpe, n_agents, args, stream)
+        case KernelFamily::Packed: return launch_step_lq(r.lq, n_agents, args, stream);
+        case KernelFamily::LaneGroup: break;
+    }
+    return limit ? launch_step_lg_limit(r.lg, n_agents, args, stream, *limit) : launch_step_lg(r.lg, n_agents, args, stream);
 }
 
 }  // namespace mapf

@@ -12,6 +12,7 @@
 // reads/writes its whole row with the widest aligned access (dwordx4 at A = 8).
 #include "mapf_kernels.hpp"
 #include "mapf_device.hpp"
+#include "mapf_plan.hpp"
 
 namespace mapf {
 
@@ -158,11 +159,9 @@ __global__ void __launch_bounds__(256) rollout_kernel_table(const RolloutArgs p,
 }
 
 // ------------------------------------------------------------------- launchers
-static inline unsigned pick_block(uint64_t n) { return n <= (1u << 18) ? 64u : 256u; }
-static inline unsigned grid_for(uint64_t n, unsigned block) { return unsigned((n + block - 1) / block); }
-
+// Each takes the family's plan (plan_tpe, mapf_plan.hpp: block and grid) and notes the name the plan's name function gives.
 // This file is compiled once per agent-count group g (-DMAPF_GROUP=g, A in 4g+1 .. 4g+4) so the
-// 32 specialisations build in parallel; mapf_dispatch.hip routes a launch to its group.
+// 32 specialisations build in parallel; mapf_dispatch.hip hands a launch to its group.
 #ifndef MAPF_GROUP
 #error "compile with -DMAPF_GROUP=0..3"
 #endif
@@ -172,10 +171,11 @@ static inline unsigned grid_for(uint64_t n, unsigned block) { return unsigned((n
 #define MAPF_CAT(a, b) MAPF_CAT2(a, b)
 #define MAPF_G(name) MAPF_CAT(name, MAPF_GROUP)
 
-hipError_t MAPF_G(launch_step_g)(int n_agents, const StepArgs &args, hipStream_t stream) {
-    if (args.n_envs == 0) return hipSuccess;
-    const unsigned block = pick_block(args.n_envs), grid = grid_for(args.n_envs, block);
-    note_kernel("step_kernel<A=%d,%s> block=%u (thread per env)", n_agents, args.uniforms ? "EXT_UNIFORMS" : "PHILOX", block);
+hipError_t MAPF_G(launch_step_g)(const TpePlan &plan, int n_agents, const StepArgs &args, hipStream_t stream) {
+    const unsigned block = plan.block, grid = plan.grid;
+    char name[kKernelNameBytes];
+    tpe_step_kernel_name(name, n_agents, plan, args.uniforms != nullptr);
+    note_kernel("%s", name);
     switch (n_agents) {
 #define X(N)                                                                                       \
     case N:                                                                                        \
@@ -202,13 +202,12 @@ static hipError_t launch_tpe_rollout(const RolloutArgs &args, unsigned grid, uns
     }
 }
 
-hipError_t MAPF_G(launch_rollout_g)(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table) {
-    if (args.n_envs == 0) return hipSuccess;
-    const unsigned block = pick_block(args.n_envs), grid = grid_for(args.n_envs, block);
-    if (table) note_kernel("rollout_kernel_table<A=%d,TABLE> block=%u (thread per env, table policy: action bytes gathered from global memory)", n_agents, block);
-    else note_kernel("rollout_kernel<A=%d> block=%u (thread per env)", n_agents, block);
+hipError_t MAPF_G(launch_rollout_g)(const TpePlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table) {
+    char name[kKernelNameBytes];
+    tpe_rollout_kernel_name(name, n_agents, plan, table != nullptr);
+    note_kernel("%s", name);
     switch (n_agents) {
-#define X(N) case N: return launch_tpe_rollout<N>(args, grid, block, stream, table);
+#define X(N) case N: return launch_tpe_rollout<N>(args, plan.grid, plan.block, stream, table);
         MAPF_FOR_EACH_A(X)
 #undef X
         default: return hipErrorInvalidValue;

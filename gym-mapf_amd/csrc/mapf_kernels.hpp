@@ -1,6 +1,6 @@
-// Argument blocks and launcher prototypes shared by the kernel files, the router (mapf_dispatch.hip) and the C ABI
+// Argument blocks and launcher prototypes shared by the kernel files, the dispatcher (mapf_dispatch.hip) and the C ABI
 // (mapf_capi.hip).  The tables these blocks point to are built on the host by mapf_tables.hip; which packed form a launch
-// takes is planned by mapf_plan.hip (mapf_plan.hpp) over the LDS layout of mapf_layout.hpp.
+// takes, and which family takes it, is planned by mapf_plan.hip (mapf_plan.hpp) over the LDS layout of mapf_layout.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -182,7 +182,6 @@ struct EpisodeBudget {
 constexpr size_t kKernelNameBytes = 160;   // what is kept of a name, the terminator included
 void note_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 
-// routed by agent count (mapf_dispatch.hip)
 struct TransitionsArgs {
     EnvConsts c;
     const MoveEntry *mv;
@@ -217,12 +216,6 @@ uint64_t transitions_scan_blocks(uint64_t n_queries);
 // args.out_reward / out_done / out_collision [N] (max_branches, out_count, out_next, out_prob unused)
 hipError_t launch_transition_rewards(const TransitionsArgs &args, const uint16_t *next, hipStream_t stream);
 
-hipError_t launch_step(int n_agents, const StepArgs &args, hipStream_t stream);
-// (table: the table policy of an actions == null launch, or null: streamed actions take precedence over it as over the other
-// policies, and the C ABI, which applies that rule, never passes both -- a launcher whose family has no table instance for the
-// launch's shape returns hipErrorInvalidValue: a missing kernel is an error, never another policy.  A recording launch names
-// all five rec_* arrays: the C ABI substitutes scratch for absent ones)
-hipError_t launch_rollout(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table = nullptr);
 hipError_t launch_reset(int n_agents, uint16_t *state, const uint16_t *start, bool start_broadcast,
                         const uint8_t *mask, uint64_t n_envs, hipStream_t stream);
 hipError_t launch_fill_actions(int n_agents, uint8_t *actions, const EnvConsts &c, uint64_t env_id_offset,
@@ -236,7 +229,6 @@ hipError_t launch_set_step_index(uint64_t *t_dev, uint64_t value, hipStream_t st
 hipError_t launch_query_terminal(int n_agents, const uint16_t *state, const uint16_t *goal, bool goal_broadcast,
                                  uint8_t *out, uint64_t n_envs, hipStream_t stream);
 
-// lane-group family (mapf_lg_kernels.hip): any A up to 128, run-time A
 constexpr int kTpeMaxAgents = 16;         // thread-per-env step kernels are specialised for A = 1..16
 #ifndef MAPF_TPE_ROLLOUT_MAX              // (tools/exp/tpe_spill_repro.sh builds a library that dispatches the spilling ones)
 #define MAPF_TPE_ROLLOUT_MAX 6
@@ -267,55 +259,56 @@ struct RolloutTuning {
                                      //   memory / from a copy staged into LDS behind the table image whenever that fits (default: by shape)
     bool limit_packed = false;       // limit_packed=1: a table-policy rollout under an episode step limit takes the packed limit instance
                                      //   (mapf_lq_limit.hip) where the packed table plan applies; default 0: always the lane-group limit instance
-                                     //   (mapf_create clears it for a handle created with MAPF_FLAG_LANE_GROUP; read by try_launch_rollout_lq alone)
+                                     //   (never on a handle created with MAPF_FLAG_LANE_GROUP; read by route_rollout alone, mapf_plan.hpp)
 };
 RolloutTuning default_rollout_tuning(int device, std::string *err);   // (asks the device, reads MAPF_TUNE: mapf_dispatch.hip)
-// (limit: the episode limit of a handle that has one, or null -- then the lane-group limit instance takes the launch, mapf_lg_limit.hip:
-// no thread-per-env kernel is consulted, and of the packed forms only the one family with limit instances, which launch_rollout_lg
-// tries first as it tries the packed forms without a limit)
-hipError_t launch_step_lg(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, const EpisodeLimit *limit = nullptr);
-// packed layout of the single step (mapf_lq_step.hip): true when it took the launch (*err = its status) -- the instance plan_step_lq
-// names (mapf_plan.hpp), one of MAPF_LQ_STEP_INSTANCES (mapf_layout.hpp), noted under lq_step_kernel_name's name
-bool try_launch_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err);
-// (budget: the episode budget of a handle that has one, or null -- then `limit` is non-null too (max_steps 0 without a limit) and the
-// lane-group budget instance takes the launch before any packed plan or thread-per-env kernel is consulted, mapf_lg_budget.hip)
-hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table = nullptr,
-                             const EpisodeLimit *limit = nullptr, const EpisodeBudget *budget = nullptr);
-hipError_t launch_rollout_lg_budget(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table,
+// The kernel family a handle prefers, from its create flags: MAPF_FLAG_THREAD_PER_ENV, MAPF_FLAG_LANE_GROUP, or neither (Auto).
+// What a launch then takes is route_rollout's / route_step's say (mapf_plan.hpp).
+enum class FamilyPreference { Auto, ThreadPerEnv, LaneGroup };
+
+// The dispatcher (mapf_dispatch.hip): the only launch entries the C ABI calls.  Each returns hipSuccess for an empty batch before
+// anything is noted; else it asks the route (mapf_plan.hpp) once, checks the limit / budget block once (hipErrorInvalidValue when
+// it is incomplete) and hands the plan to the family's launcher below.
+// (table: the table policy of an actions == null launch, or null: streamed actions take precedence over it as over the other
+// policies, and the C ABI, which applies that rule, never passes both.  A recording launch names all five rec_* arrays: the C ABI
+// substitutes scratch for absent ones.  limit / budget: those of a handle that has them, or null; with a budget `limit` is
+// non-null too, max_steps 0 on a handle without a limit)
+hipError_t launch_step(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, hipStream_t stream, const EpisodeLimit *limit = nullptr);
+hipError_t launch_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, hipStream_t stream,
+                          const TablePolicy *table = nullptr, const EpisodeLimit *limit = nullptr, const EpisodeBudget *budget = nullptr);
+// is the step launch_step would launch a thread-per-env one (one thread per env), else lg_group_size(A) threads per env?
+bool step_is_thread_per_env(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, const EpisodeLimit *limit);
+
+// The family launchers: each takes the plan the route made (mapf_plan.hpp), launches the instance it names under the plan's name
+// and decides nothing -- it calls no planner and no other family's launcher.  A family without an instance for what it is handed
+// returns hipErrorInvalidValue: a missing kernel is an error, never another policy.
+struct TpePlan; struct LqPlan; struct StepPlan; struct LgRolloutPlan; struct LgStepPlan;
+// lane-group (any A up to 128, run-time A): mapf_lg_rollout.hip, mapf_lg_kernels.hip; its limit instances and the masked zeroing
+// of the ages: mapf_lg_limit.hip; its budget instances: mapf_lg_budget.hip
+hipError_t launch_rollout_lg(const LgRolloutPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table);
+hipError_t launch_rollout_lg_limit(const LgRolloutPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table, const EpisodeLimit &limit);
+hipError_t launch_rollout_lg_budget(const LgRolloutPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table,
                                     const EpisodeLimit &limit, const EpisodeBudget &budget);
-// the limit instances (mapf_lg_limit.hip): the lane-group kernels with a per-env age, and the masked zeroing of the ages.  These
-// two and the two above check their launch, plan it and hand the plan to the family's one launcher (mapf_lg_launch.hpp)
-hipError_t launch_rollout_lg_limit(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table,
-                                   const EpisodeLimit &limit);
-hipError_t launch_step_lg_limit(int n_agents, const StepArgs &args, hipStream_t stream, const EpisodeLimit &limit);
+hipError_t launch_step_lg(const LgStepPlan &plan, int n_agents, const StepArgs &args, hipStream_t stream);
+hipError_t launch_step_lg_limit(const LgStepPlan &plan, int n_agents, const StepArgs &args, hipStream_t stream, const EpisodeLimit &limit);
 hipError_t launch_reset_ages(uint32_t *age, const uint8_t *mask, uint64_t n_envs, hipStream_t stream);
-// packed layout of the fused rollout (2, 4 or 8 agents per lane): plans the launch (mapf_plan.hpp) and routes it to the object that
-// holds its instance (mapf_dispatch.hip); true when it took the launch (*err = its status), false = the lane-group family's.
-// Under an episode step limit the packed instances are the table policy's limit forms (mapf_lq_limit.hip): not applicable unless
-// the handle's tuning has limit_packed=1, the launch follows the table policy and the limited table plan applies; *err =
-// hipErrorInvalidValue when the limit block is incomplete (launch_rollout_lg_limit's pre-checks)
-bool try_launch_rollout_lq(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err, const TablePolicy *table = nullptr,
-                           const EpisodeLimit *limit = nullptr);
-// ... the launchers of those objects: mapf_lq_rollout.hip compiled once per (agents per lane, recording) pair, mapf_lq_limit.hip
-// once per (four or two agents per lane, recording) pair; each launches the instance the plan names through the family's one
-// launcher (mapf_lq_launch.hpp).  ONE signature (table: the table policy, or null; limit: the episode limit, or null): an
+// packed single step (mapf_lq_step.hip): one of MAPF_LQ_STEP_INSTANCES (mapf_layout.hpp)
+hipError_t launch_step_lq(const StepPlan &plan, int n_agents, const StepArgs &args, hipStream_t stream);
+// packed rollout (2, 4 or 8 agents per lane): mapf_lq_rollout.hip compiled once per (agents per lane, recording) pair, mapf_lq_limit.hip
+// (the table policy's instances under an episode step limit) once per (four or two agents per lane, recording) pair; the dispatcher
+// keeps the table of these objects.  ONE signature (table: the table policy, or null; limit: the episode limit, or null): an
 // object without limit instances refuses a limit, the limit objects refuse a launch without a table or without a limit
-struct LqPlan;   // mapf_plan.hpp
 #define MAPF_LQ_LAUNCHERS(X) X(rollout_lq_k8_r1) X(rollout_lq_k8_r0) X(rollout_lq_k4_r1) X(rollout_lq_k4_r0) X(rollout_lq_k2_r1) X(rollout_lq_k2_r0) \
     X(rollout_lq_limit_k4_r1) X(rollout_lq_limit_k4_r0) X(rollout_lq_limit_k2_r1) X(rollout_lq_limit_k2_r0)
 #define X(name) \
     hipError_t launch_##name(const LqPlan &plan, const RolloutArgs &args, uint32_t A, hipStream_t stream, const TablePolicy *table, const EpisodeLimit *limit);
 MAPF_LQ_LAUNCHERS(X)
 #undef X
-
-// per-group entry points: group g holds the kernels specialised for A in 4g+1 .. 4g+4
-hipError_t launch_step_g0(int n_agents, const StepArgs &args, hipStream_t stream);
-hipError_t launch_rollout_g0(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table);
-hipError_t launch_step_g1(int n_agents, const StepArgs &args, hipStream_t stream);
-hipError_t launch_rollout_g1(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table);
-hipError_t launch_step_g2(int n_agents, const StepArgs &args, hipStream_t stream);
-hipError_t launch_rollout_g2(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table);
-hipError_t launch_step_g3(int n_agents, const StepArgs &args, hipStream_t stream);
-hipError_t launch_rollout_g3(int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table);
+// thread-per-env (mapf_kernels.hip): group g holds the kernels specialised for A in 4g+1 .. 4g+4
+#define X(g)                                                                                                        \
+    hipError_t launch_step_g##g(const TpePlan &plan, int n_agents, const StepArgs &args, hipStream_t stream);      \
+    hipError_t launch_rollout_g##g(const TpePlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table);
+X(0) X(1) X(2) X(3)
+#undef X
 
 }  // namespace mapf

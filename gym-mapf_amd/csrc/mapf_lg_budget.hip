@@ -1,6 +1,6 @@
 // Lane-group family under an episode budget (include/mapf_hip.h mapf_set_episode_budget; EpisodeBudget in mapf_kernels.hpp): the
-// budget forms of the fused rollout kernels, the family that names them to the shared launcher (mapf_lg_launch.hpp), and the entry
-// launcher.  A translation unit of its own: the kernels that exist without the budget (mapf_lg_rollout.hip, mapf_lg_limit.hip) keep
+// budget forms of the fused rollout kernels, the family that names them to the shared launcher (mapf_lg_launch.hpp), and the
+// launcher that takes the route's budget plan.  A translation unit of its own: the kernels that exist without the budget (mapf_lg_rollout.hip, mapf_lg_limit.hip) keep
 // their code.
 //
 // Per env and step of an auto-reset rollout under a budget B (the header has the definition): an env with no episode left is PARKED
@@ -33,15 +33,9 @@ struct LgRolloutBudgetFamily {
     }
 };
 
-// the pre-checks of a launch under a budget, then the limit plan, marked `budget`, and the shared launcher (mapf_lg_launch.hpp)
-hipError_t launch_rollout_lg_budget(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table,
+// the route's limit plan, marked `budget` (the dispatcher has checked the limit and budget blocks), to the shared launcher (mapf_lg_launch.hpp)
+hipError_t launch_rollout_lg_budget(const LgRolloutPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table,
                                     const EpisodeLimit &limit, const EpisodeBudget &budget) {
-    if (args.n_envs == 0) return hipSuccess;
-    // what the kernels rely on: ages and counts, auto-reset, and the truncated trajectory exactly when the launch records (the
-    // limit itself may be 0: a budget without a limit)
-    if (!limit.age || !budget.left || !args.auto_reset || (limit.rec_truncated != nullptr) != (args.rec_local != nullptr)) return hipErrorInvalidValue;
-    LgRolloutPlan plan = plan_rollout_lg(n_agents, args, tune, true);
-    plan.budget = true;
     return table ? launch_lg_rollout<LgRolloutBudgetFamily, true>(plan, args, uint32_t(n_agents), stream, *table, limit, budget)
                  : launch_lg_rollout<LgRolloutBudgetFamily, false>(plan, args, uint32_t(n_agents), stream, limit, budget);
 }

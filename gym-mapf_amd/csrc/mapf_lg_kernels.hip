@@ -1,5 +1,5 @@
 // Lane-group family: single-step kernel, run-time-A helper kernels and their launchers (device code: mapf_lg.hpp; the step's
-// launcher proper: mapf_lg_launch.hpp).
+// plan: the route's, mapf_plan.hip; its launcher proper: mapf_lg_launch.hpp).
 #include "mapf_lg_launch.hpp"
 
 namespace mapf {
@@ -125,13 +125,8 @@ hipError_t launch_fill_actions(int n_agents, uint8_t *actions, const EnvConsts &
 }
 
 // ------------------------------------------------------------------- launchers
-// launches the instance plan_step_lg names (mapf_plan.hip), unless the packed single step takes the launch
-hipError_t launch_step_lg(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, const EpisodeLimit *limit) {
-    if (args.n_envs == 0) return hipSuccess;
-    if (limit) return launch_step_lg_limit(n_agents, args, stream, *limit);   // (before the packed single step is consulted)
-    hipError_t packed_status;
-    if (try_launch_step_lq(n_agents, args, tune, stream, &packed_status)) return packed_status;
-    return launch_lg_step<LgStepFamily>(plan_step_lg(n_agents, args), args, uint32_t(n_agents), stream);
+hipError_t launch_step_lg(const LgStepPlan &plan, int n_agents, const StepArgs &args, hipStream_t stream) {
+    return launch_lg_step<LgStepFamily>(plan, args, uint32_t(n_agents), stream);
 }
 
 }  // namespace mapf

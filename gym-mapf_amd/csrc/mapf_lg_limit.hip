@@ -1,6 +1,6 @@
 // Lane-group family under an episode step limit (include/mapf_hip.h mapf_set_episode_limit; EpisodeLimit in mapf_kernels.hpp):
 // the limit forms of the fused rollout kernels and of the single step, the families that name them to the shared launchers
-// (mapf_lg_launch.hpp), and the entry launchers.  A translation unit of its own: the kernels that exist without the limit
+// (mapf_lg_launch.hpp), and the launchers that take the route's limit plans.  A translation unit of its own: the kernels that exist without the limit
 // (mapf_lg_rollout.hip, mapf_lg_kernels.hip) keep their code.
 //
 // Per env and step taken under a limit N (the header has the definition): a step from a terminal state is the usual no-op and
@@ -59,21 +59,15 @@ hipError_t launch_reset_ages(uint32_t *age, const uint8_t *mask, uint64_t n_envs
 }
 
 // ------------------------------------------------------------------- launchers
-// the pre-checks of a launch under a limit, then the limit plan and the shared launcher (mapf_lg_launch.hpp)
-hipError_t launch_rollout_lg_limit(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table,
+// the limit plan the route made (the dispatcher has checked the limit block) to the shared launcher (mapf_lg_launch.hpp)
+hipError_t launch_rollout_lg_limit(const LgRolloutPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table,
                                    const EpisodeLimit &limit) {
-    if (args.n_envs == 0) return hipSuccess;
-    // what the kernels rely on: ages, a limit, and the truncated trajectory exactly when the launch records
-    if (!limit.age || limit.max_steps == 0u || (limit.rec_truncated != nullptr) != (args.rec_local != nullptr)) return hipErrorInvalidValue;
-    const LgRolloutPlan plan = plan_rollout_lg(n_agents, args, tune, true);
     return table ? launch_lg_rollout<LgRolloutLimitFamily, true>(plan, args, uint32_t(n_agents), stream, *table, limit)
                  : launch_lg_rollout<LgRolloutLimitFamily, false>(plan, args, uint32_t(n_agents), stream, limit);
 }
 
-hipError_t launch_step_lg_limit(int n_agents, const StepArgs &args, hipStream_t stream, const EpisodeLimit &limit) {
-    if (args.n_envs == 0) return hipSuccess;
-    if (!limit.age || limit.max_steps == 0u) return hipErrorInvalidValue;
-    return launch_lg_step<LgStepLimitFamily>(plan_step_lg(n_agents, args, true), args, uint32_t(n_agents), stream, limit);
+hipError_t launch_step_lg_limit(const LgStepPlan &plan, int n_agents, const StepArgs &args, hipStream_t stream, const EpisodeLimit &limit) {
+    return launch_lg_step<LgStepLimitFamily>(plan, args, uint32_t(n_agents), stream, limit);
 }
 
 }  // namespace mapf

@@ -1,5 +1,5 @@
-// Lane-group family: fused T-step rollout kernel and its launcher (device code: mapf_lg.hpp; the launch's plan: mapf_plan.hip; the
-// launcher proper: mapf_lg_launch.hpp).
+// Lane-group family: fused T-step rollout kernel and the launcher of its instances without an episode limit (device code:
+// mapf_lg.hpp; the launch's plan: the route's, mapf_plan.hip; the launcher proper: mapf_lg_launch.hpp).
 #include "mapf_lg_launch.hpp"
 
 namespace mapf {
@@ -33,15 +33,7 @@ struct LgRolloutFamily {
     }
 };
 
-hipError_t launch_rollout_lg(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, hipStream_t stream, const TablePolicy *table,
-                             const EpisodeLimit *limit, const EpisodeBudget *budget) {
-    if (args.n_envs == 0) return hipSuccess;
-    // an episode budget: the budget instances exist in the lane-group family only -- no packed plan, whatever the tuning says
-    if (budget) return limit ? launch_rollout_lg_budget(n_agents, args, tune, stream, table, *limit, *budget) : hipErrorInvalidValue;
-    hipError_t packed_status;   // packed first, else lane-group: under a limit too (the packed table instances' limit forms, where opted into)
-    if (try_launch_rollout_lq(n_agents, args, tune, stream, &packed_status, table, limit)) return packed_status;
-    if (limit) return launch_rollout_lg_limit(n_agents, args, tune, stream, table, *limit);
-    const LgRolloutPlan plan = plan_rollout_lg(n_agents, args, tune);
+hipError_t launch_rollout_lg(const LgRolloutPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table) {
     return table ? launch_lg_rollout<LgRolloutFamily, true>(plan, args, uint32_t(n_agents), stream, *table)
                  : launch_lg_rollout<LgRolloutFamily, false>(plan, args, uint32_t(n_agents), stream);
 }

@@ -1,7 +1,7 @@
 // Packed table-policy rollout under an episode step limit (include/mapf_hip.h mapf_set_episode_limit; EpisodeLimit in
 // mapf_kernels.hpp): lq_rollout_kernel_table_limit, the limit form of lq_rollout_kernel_table (mapf_lq_rollout.hip), and the family
 // that names it to the shared launcher (mapf_lq_launch.hpp).  A translation unit of its own: the packed kernels that exist without
-// the limit keep their code.  Reached only with MAPF_TUNE limit_packed=1 (try_launch_rollout_lq, mapf_dispatch.hip); every launch
+// the limit keep their code.  Reached only with MAPF_TUNE limit_packed=1 (route_rollout, mapf_plan.hip); every launch
 // this family declines -- and every launch under a limit without the key -- is the lane-group limit instance's (mapf_lg_limit.hip).
 //
 // The four rules of the limit are mapf_lg_limit.hip's.  In the packed body they hang on the group-uniform code of the step

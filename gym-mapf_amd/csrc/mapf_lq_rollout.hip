@@ -41,7 +41,7 @@
 //
 // Scope: the fused rollout of FULL groups only (A = K * Q, Q a power of two <= 16), every block full, move table in
 // LDS -- the bench configurations and their neighbours.  Everything else (odd agent counts, ragged batches, tables
-// beyond the LDS budget, single steps) stays with mapf_lg_rollout.hip; launch_rollout_lg() picks.  Same stream,
+// beyond the LDS budget, single steps) stays with mapf_lg_rollout.hip; route_rollout (mapf_plan.hip) picks.  Same stream,
 // same arithmetic, same outputs: the parity tests run all layouts against the oracle.
 #include "mapf_lq_launch.hpp"
 

@@ -1,8 +1,8 @@
 // Packed-layout single step: one MapfEnv.step() of every env per launch (mapf_step with device-drawn uniforms), K = 2, 4
 // or 8 agents per lane, Q = A/K lanes per env -- the lane layout of mapf_lq_rollout.hip applied to the one-launch-per-step
 // path, for full groups and batches that fill their blocks; everything else (caller-supplied uniforms, odd agent
-// counts, ragged batches) stays with lg_step_kernel (mapf_lg_kernels.hip), whose semantics this kernel reproduces
-// line by line.  Which instances exist is MAPF_LQ_STEP_INSTANCES' say (mapf_layout.hpp); which one a launch takes and what
+// counts, ragged batches) stays with lg_step_kernel (mapf_lg_kernels.hip: route_step's say, mapf_plan.hpp), whose semantics
+// this kernel reproduces line by line.  Which instances exist is MAPF_LQ_STEP_INSTANCES' say (mapf_layout.hpp); which one a launch takes and what
 // it is called, mapf_plan.hip's (plan_step_lq, lq_step_kernel_name): the launcher at this file's end walks the list.
 //
 // A single step is launch- and latency-bound (argument block -> state / actions -> table rows -> stores, with ~225 vector
@@ -533,23 +533,16 @@ static hipError_t launch_step_instance(const StepPlan &plan, const StepArgs &arg
     return hipGetLastError();
 }
 
-// true when the packed layout took the launch (*err = its status); false = not applicable, use lg_step_kernel.  The plan
-// (plan_step_lq) names the instance and lq_step_kernel_name its name; the launcher decides nothing itself.
-bool try_launch_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune, hipStream_t stream, hipError_t *err) {
-#ifndef MAPF_STEP_STAMPS   // (the diagnostic build receives its stamp buffer through `uniforms`)
-    if (args.uniforms != nullptr) return false;
-#endif
-    StepPlan plan;
-    if (!plan_step_lq(n_agents, args, tune, &plan)) return false;
+// The plan (the route's: plan_step_lq) names the instance and lq_step_kernel_name its name; the launcher decides nothing itself.
+hipError_t launch_step_lq(const StepPlan &plan, int n_agents, const StepArgs &args, hipStream_t stream) {
     char name[kKernelNameBytes];
     lq_step_kernel_name(name, plan, args.scen != nullptr, !args.state_not_terminal);
     note_kernel("%s", name);
     // the planned instance, by the list in mapf_layout.hpp (what lq_step_instance_exists answers from), in the list's order
-#define X(QQ, KK, FF) if (plan.Q == QQ && plan.K == KK && plan.big == StepForm::FF) { *err = launch_step_instance<QQ, KK, int(StepForm::FF)>(plan, args, uint32_t(n_agents), stream); return true; }
+#define X(QQ, KK, FF) if (plan.Q == QQ && plan.K == KK && plan.big == StepForm::FF) return launch_step_instance<QQ, KK, int(StepForm::FF)>(plan, args, uint32_t(n_agents), stream);
     MAPF_LQ_STEP_INSTANCES(X)
 #undef X
-    *err = hipErrorInvalidValue;   // (not reached: plan_step_lq asks lq_step_instance_exists before it plans)
-    return true;
+    return hipErrorInvalidValue;   // (not reached: plan_step_lq asks lq_step_instance_exists before it plans)
 }
 
 }  // namespace mapf

@@ -1,4 +1,4 @@
-// Launch planning of the packed and the lane-group kernels (mapf_plan.hpp): host-only integer arithmetic, no kernel and no runtime call.
+// Launch planning (mapf_plan.hpp) -- the family that takes a launch, and its plan within each family: host-only integer arithmetic, no kernel and no runtime call.
 #include "mapf_plan.hpp"
 
 #include <algorithm>
@@ -367,6 +367,74 @@ void lg_step_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms) 
     snprintf(name, kKernelNameBytes, "lg_step_kernel%s<L=%d,%s,%s%s> block=%u (pair layout: 2 agents per lane%s)", plan.limit ? "_limit" : "", plan.L,
              plan.full ? "FULL" : "RAGGED", ext_uniforms ? "EXT_UNIFORMS" : "PHILOX", plan.limit ? ",LIMIT" : "", plan.block,
              plan.limit ? "; episode step limit" : "");
+}
+
+// ------------------------------------------------------------------- the thread-per-env family
+TpePlan plan_tpe(uint64_t n_envs) {
+    TpePlan plan;
+    plan.block = n_envs <= (1u << 18) ? 64u : 256u;
+    plan.grid = unsigned((n_envs + plan.block - 1) / plan.block);
+    return plan;
+}
+
+void tpe_step_kernel_name(char *name, int n_agents, const TpePlan &plan, bool ext_uniforms) {
+    snprintf(name, kKernelNameBytes, "step_kernel<A=%d,%s> block=%u (thread per env)", n_agents, ext_uniforms ? "EXT_UNIFORMS" : "PHILOX", plan.block);
+}
+
+void tpe_rollout_kernel_name(char *name, int n_agents, const TpePlan &plan, bool table_policy) {
+    if (table_policy) snprintf(name, kKernelNameBytes, "rollout_kernel_table<A=%d,TABLE> block=%u (thread per env, table policy: action bytes gathered from global memory)", n_agents, plan.block);
+    else snprintf(name, kKernelNameBytes, "rollout_kernel<A=%d> block=%u (thread per env)", n_agents, plan.block);
+}
+
+// ------------------------------------------------------------------- the route (mapf_plan.hpp lists the rules)
+// thread-per-env is what the handle prefers: by flag, or an env of at most one agent pair (lane groups from two pairs on)
+static bool prefers_tpe(FamilyPreference prefer, int n_agents) {
+    return prefer == FamilyPreference::ThreadPerEnv || (prefer == FamilyPreference::Auto && n_agents <= 2);
+}
+
+RolloutRoute route_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool table_policy, size_t table_bytes,
+                           bool limited, bool budgeted) {
+    RolloutRoute r;
+    if (budgeted) {   // the budget instances exist in the lane-group family only -- no packed plan, whatever the tuning says
+        r.lg = plan_rollout_lg(n_agents, args, tune, true);
+        r.lg.budget = true;
+        return r;
+    }
+    // (the thread-per-env rollout specialisations beyond kTpeRolloutMaxAgents need SGPR spills and are not dispatched)
+    if (!limited && prefers_tpe(prefer, n_agents) && n_agents <= kTpeRolloutMaxAgents) {
+        r.family = KernelFamily::ThreadPerEnv;
+        r.tpe = plan_tpe(args.n_envs);
+        return r;
+    }
+    // under a limit the packed instances are the table policy's (mapf_lq_limit.hip), opted into by MAPF_TUNE limit_packed=1
+    const bool packed_allowed = !limited || (table_policy && args.actions == nullptr && tune.limit_packed && prefer != FamilyPreference::LaneGroup);
+    if (packed_allowed && (table_policy ? plan_rollout_lq_table(n_agents, args, tune, table_bytes, &r.lq, limited) : plan_rollout_lq(n_agents, args, tune, &r.lq))) {
+        r.family = KernelFamily::Packed;
+        return r;
+    }
+    r.lq = LqPlan{};
+    r.lg = plan_rollout_lg(n_agents, args, tune, limited);
+    return r;
+}
+
+StepRoute route_step(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool limited, bool ext_uniforms) {
+    StepRoute r;
+    if (limited) {   // the step's limit instances exist in the lane-group family only
+        r.lg = plan_step_lg(n_agents, args, true);
+        return r;
+    }
+    if (prefers_tpe(prefer, n_agents) && n_agents <= kTpeMaxAgents) {
+        r.family = KernelFamily::ThreadPerEnv;
+        r.tpe = plan_tpe(args.n_envs);
+        return r;
+    }
+    if (!ext_uniforms && plan_step_lq(n_agents, args, tune, &r.lq)) {
+        r.family = KernelFamily::Packed;
+        return r;
+    }
+    r.lq = StepPlan{};
+    r.lg = plan_step_lg(n_agents, args);
+    return r;
 }
 
 }  // namespace mapf

@@ -1,9 +1,10 @@
-// Launch planning of the packed and the lane-group kernels: which form, block, grid and LDS image a launch of a given shape
-// takes.  Pure integer arithmetic over the launch's shape, the tuning and the LDS layout (mapf_layout.hpp) -- no kernel, no
-// runtime call -- so it can be swept without a device (mapf_debug_rollout_plan, tests/test_plan_decisions.py).  A launcher
-// takes ONE plan and launches the instance it names; it decides nothing itself (the lane-group plans name their family too: with
-// or without the episode step limit).  The name a launch notes is formatted here as well, one function per planned family -- the
-// packed rollout, the packed step, the lane-group rollout and step -- so a shape's name can be asked for without a launch.
+// Launch planning: which kernel family takes a launch (route_rollout, route_step -- the ONE statement of the routing order), and
+// which form, block, grid and LDS image a launch of a given shape takes within its family.  Pure integer arithmetic over the
+// launch's shape, the tuning and the LDS layout (mapf_layout.hpp) -- no kernel, no runtime call -- so it can be swept without a
+// device (mapf_debug_rollout_plan, tests/test_plan_decisions.py).  The dispatcher (mapf_dispatch.hip) asks the route once per launch
+// and hands its plan to the family's launcher; a launcher takes ONE plan and launches the instance it names: it decides neither the
+// instance nor the family.  The name a launch notes is formatted here as well, one function per planned family -- thread-per-env,
+// the packed rollout, the packed step, the lane-group rollout and step -- so a shape's name can be asked for without a launch.
 #pragma once
 #include "mapf_layout.hpp"
 
@@ -12,7 +13,7 @@ namespace mapf {
 // the defaults of a device with n_cu compute units, overridden by `text` (MAPF_TUNE: "key=value,...", may be null)
 RolloutTuning rollout_tuning_for(int n_cu, const char *text, std::string *err);
 
-// What try_launch_rollout_lq decides before it launches, from the launch's shape (args.c.n_cells, n_envs, n_steps, c.top_tie,
+// The packed rollout's plan, from the launch's shape (args.c.n_cells, n_envs, n_steps, c.top_tie,
 // actions / mv4 / mv_delta8 present or not) and the tuning (its n_cu included): false = no packed form applies.  The whole plan:
 // the packed family's one launcher (mapf_lq_launch.hpp) is handed nothing else.
 struct LqPlan {
@@ -40,7 +41,7 @@ inline bool rollout_may_be_terminal(const RolloutArgs &args) { return !(args.aut
 // bytes); criteria; may-be-terminal.  A limit plan's name says _table_limit, LIMIT and "; episode step limit".
 void lq_rollout_kernel_name(char *name, const LqPlan &plan, bool record, bool streamed, bool table_policy, bool soc, bool may_be_terminal, uint32_t table_bytes);
 
-// What try_launch_step_lq (mapf_lq_step.hip) launches: the instance lq_step_kernel<Q, K, ., ., form> (StepForm and the list of the
+// What launch_step_lq (mapf_lq_step.hip) launches: the instance lq_step_kernel<Q, K, ., ., form> (StepForm and the list of the
 // instances: mapf_layout.hpp -- a plan names one of MAPF_LQ_STEP_INSTANCES or there is none) and its geometry.
 struct StepPlan {
     int K = 0, Q = 0;                // agents per lane (2, 4; 8 in the large-batch form), lanes per env
@@ -85,5 +86,31 @@ LgStepPlan plan_step_lg(int n_agents, const StepArgs &args, bool limited = false
 // name says _limit_guarded (the step: _limit) and LIMIT, and has no DENSE / GUARDED field; a budget plan's says _budget_guarded and BUDGET.
 void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy);
 void lg_step_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms);
+
+// The thread-per-env family (mapf_kernels.hip): one thread per env, kernels specialised by agent count
+struct TpePlan { unsigned block = 0, grid = 0; };
+TpePlan plan_tpe(uint64_t n_envs);
+void tpe_step_kernel_name(char *name, int n_agents, const TpePlan &plan, bool ext_uniforms);
+void tpe_rollout_kernel_name(char *name, int n_agents, const TpePlan &plan, bool table_policy);
+
+// ------------------------------------------------------------------- the route
+// Which family takes a launch, with that family's plan (the other plans stay as constructed).  The rules, each written once, in
+// route_rollout / route_step, in this order:
+//   a budget takes the lane-group budget plan (a limit plan marked `budget`) before anything else;
+//   a limit never goes to thread-per-env, and the step under a limit has the lane-group limit instance only;
+//   thread-per-env takes what the handle prefers it for (FamilyPreference; Auto: A <= 2) where its kernels exist: steps up to
+//     kTpeMaxAgents, rollouts up to kTpeRolloutMaxAgents;
+//   packed comes before lane-group.  Under a limit it applies only to a table-policy launch without streamed actions, with
+//     limit_packed=1, on a handle not created with MAPF_FLAG_LANE_GROUP; the packed step declines caller-supplied uniforms;
+//   lane-group takes everything else.
+enum class KernelFamily { ThreadPerEnv, Packed, LaneGroup };
+struct RolloutRoute { KernelFamily family = KernelFamily::LaneGroup; TpePlan tpe; LqPlan lq; LgRolloutPlan lg; };
+struct StepRoute { KernelFamily family = KernelFamily::LaneGroup; TpePlan tpe; StepPlan lq; LgStepPlan lg; };
+// (table_policy: the launch follows the table policy, of table_bytes action bytes; limited / budgeted: it runs under an episode
+// step limit / an episode budget.  args is never dereferenced)
+RolloutRoute route_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool table_policy, size_t table_bytes,
+                           bool limited, bool budgeted);
+// (ext_uniforms: the caller supplies the uniforms)
+StepRoute route_step(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool limited, bool ext_uniforms);
 
 }  // namespace mapf

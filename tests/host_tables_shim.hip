@@ -136,7 +136,7 @@ int shim_plan_rollout_table(uint32_t n_cells, int n_agents, uint64_t n_envs, uin
     return 1;
 }
 
-// The packed plan of a one-step launch as try_launch_rollout_lq makes it (policy: 0 streamed actions, 1 the in-kernel policy, 2 the
+// The packed plan of a one-step launch as route_rollout makes it (policy: 0 streamed actions, 1 the in-kernel policy, 2 the
 // table policy of table_bytes; limited: ... under an episode step limit) and the name the launcher notes for it (kKernelNameBytes);
 // 1 = planned, 0 = no packed form, -1 = bad tune
 int shim_lq_rollout_name(uint32_t n_cells, int n_agents, uint64_t n_envs, int has_delta_rows, uint64_t table_bytes, int n_cu, const char *tune, int policy,
@@ -188,6 +188,61 @@ static int step_lg(int n_agents, uint64_t n_envs, int ext_uniforms, bool limited
 int shim_plan_step_lg(int n_agents, uint64_t n_envs, int ext_uniforms, uint64_t out[4], char *name) { return step_lg(n_agents, n_envs, ext_uniforms, false, out, name); }
 // ... under an episode step limit
 int shim_plan_limit_step_lg(int n_agents, uint64_t n_envs, int ext_uniforms, uint64_t out[4], char *name) { return step_lg(n_agents, n_envs, ext_uniforms, true, out, name); }
+
+// route_rollout over a one-step launch (prefer: FamilyPreference's number -- 0 auto, 1 thread-per-env, 2 lane-group; policy: 0 streamed
+// actions, 1 the in-kernel policy, 2 the table policy of table_bytes; limited / budgeted: under an episode step limit / budget):
+// returns the family (KernelFamily's number: 0 thread-per-env, 1 packed, 2 lane-group; -1 = bad tune), its plan in the layout of the
+// entries above -- thread-per-env: block, grid; packed: shim_plan_rollout_table's nine; lane-group: shim_plan_rollout_lg's seven, then
+// limit, budget -- and the name its launcher notes (kKernelNameBytes)
+int shim_route_rollout(uint32_t n_cells, int n_agents, uint64_t n_envs, int has_delta_rows, uint64_t table_bytes, int n_cu, const char *tune, int prefer, int policy,
+                       int limited, int budgeted, int record, int soc, int may_be_terminal, uint64_t out[9], char *name) {
+    std::string err;
+    const RolloutTuning t = rollout_tuning_for(n_cu, tune, &err);
+    if (!err.empty()) return -1;
+    const RolloutRoute r = route_rollout(n_agents, rollout_shape(n_cells, n_envs, 1, has_delta_rows, policy == 0), t, FamilyPreference(prefer), policy == 2,
+                                         size_t(table_bytes), limited != 0, budgeted != 0);
+    std::memset(out, 0, 9 * sizeof(uint64_t));
+    if (r.family == KernelFamily::ThreadPerEnv) {
+        out[0] = r.tpe.block; out[1] = r.tpe.grid;
+        tpe_rollout_kernel_name(name, n_agents, r.tpe, policy == 2);
+    } else if (r.family == KernelFamily::Packed) {
+        out[0] = uint64_t(r.lq.K); out[1] = uint64_t(r.lq.Q); out[2] = uint64_t(int(r.lq.form)); out[3] = r.lq.block; out[4] = r.lq.lds_bytes;
+        out[5] = r.lq.lds_total; out[6] = r.lq.table_lds ? 1u : 0u; out[7] = r.lq.table_at; out[8] = r.lq.limit ? 1u : 0u;
+        lq_rollout_kernel_name(name, r.lq, record != 0, policy == 0, policy == 2, soc != 0, may_be_terminal != 0, uint32_t(table_bytes));
+    } else {
+        out[0] = uint64_t(r.lg.L); out[1] = r.lg.full ? 1u : 0u; out[2] = r.lg.mv_lds ? 1u : 0u; out[3] = r.lg.dense ? 1u : 0u; out[4] = r.lg.block;
+        out[5] = r.lg.grid; out[6] = r.lg.lds_bytes; out[7] = r.lg.limit ? 1u : 0u; out[8] = r.lg.budget ? 1u : 0u;
+        lg_rollout_kernel_name(name, r.lg, record != 0, policy == 0, policy == 2);
+    }
+    return int(r.family);
+}
+// route_step likewise (uniforms: the caller supplies them; scen: rows from the scenario table): thread-per-env: block, grid; packed:
+// shim_plan_step's eight; lane-group: shim_plan_step_lg's four, then limit
+int shim_route_step(uint32_t n_cells, int n_agents, uint64_t n_envs, int has_delta_rows, int n_cu, const char *tune, int prefer, int limited, int uniforms, int scen,
+                    int may_be_terminal, uint64_t out[8], char *name) {
+    std::string err;
+    const RolloutTuning t = rollout_tuning_for(n_cu, tune, &err);
+    if (!err.empty()) return -1;
+    static const uint32_t present = 0;
+    StepArgs args{};
+    args.c.n_cells = n_cells;
+    args.n_envs = n_envs;
+    args.mv4 = has_delta_rows ? &present : nullptr;
+    const StepRoute r = route_step(n_agents, args, t, FamilyPreference(prefer), limited != 0, uniforms != 0);
+    std::memset(out, 0, 8 * sizeof(uint64_t));
+    if (r.family == KernelFamily::ThreadPerEnv) {
+        out[0] = r.tpe.block; out[1] = r.tpe.grid;
+        tpe_step_kernel_name(name, n_agents, r.tpe, uniforms != 0);
+    } else if (r.family == KernelFamily::Packed) {
+        out[0] = uint64_t(r.lq.K); out[1] = uint64_t(r.lq.Q); out[2] = uint64_t(int(r.lq.big)); out[3] = r.lq.block; out[4] = r.lq.grid;
+        out[5] = r.lq.n_chunks; out[6] = r.lq.lds_bytes; out[7] = uint64_t(r.lq.lds_limit);
+        lq_step_kernel_name(name, r.lq, scen != 0, may_be_terminal != 0);
+    } else {
+        out[0] = uint64_t(r.lg.L); out[1] = r.lg.full ? 1u : 0u; out[2] = r.lg.block; out[3] = r.lg.grid; out[4] = r.lg.limit ? 1u : 0u;
+        lg_step_kernel_name(name, r.lg, uniforms != 0);
+    }
+    return int(r.family);
+}
 
 // does the launcher hold the packed rollout instance (K, Q, form)?  (table: of lq_rollout_kernel_table)
 int shim_rollout_instance_exists(int K, int Q, int form, int table) {

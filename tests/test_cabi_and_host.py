@@ -212,7 +212,7 @@ ROLLOUT_PLAN_ENVS = (64, 1000, 1024, 4096, 16384, 16448, 65536, 131072, 262144)
 
 
 def test_packed_rollout_dispatch_never_plans_past_the_lds_or_launch_bounds(shim):
-    """mapf_debug_rollout_plan is the arithmetic try_launch_rollout_lq runs before every packed rollout launch (no device
+    """mapf_debug_rollout_plan is the arithmetic the route (route_rollout) runs before every packed rollout launch (no device
     involved).  Swept over map sizes across every form's LDS boundary, agent counts, batch sizes, streamed / in-kernel policy,
     delta rows or not, and the MAPF_TUNE overrides the tests use: whatever form is planned fits the CU's 160 KB of LDS (the limit
     the launcher raises the kernel's dynamic segment to), fills whole blocks, and stays within its instance's launch bounds;

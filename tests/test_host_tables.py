@@ -70,6 +70,11 @@ def load_shim(path):
         lib.shim_step_instance_exists.argtypes = [ctypes.c_int] * 3
         lib.shim_lq_step_name.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_char_p]
+    if hasattr(lib, 'shim_route_rollout'):
+        lib.shim_route_rollout.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p] + \
+            [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_char_p]
+        lib.shim_route_step.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p] + [ctypes.c_int] * 5 + \
+            [ctypes.c_void_p, ctypes.c_char_p]
     return lib
 
 

@@ -217,6 +217,28 @@ def planned_step_lg(shim_lib, A, E, uniforms):
     return '%d%s%d' % (L, 'F' if full else 'R', block), grid, name.value.decode()
 
 
+# the route (route_rollout, route_step: tests/test_route.py has their tests)
+AUTO, PREFER_TPE, PREFER_LG = 0, 1, 2                                  # FamilyPreference's numbers (csrc/mapf_kernels.hpp)
+TPE, PACKED, LG = 0, 1, 2                                              # KernelFamily's numbers (csrc/mapf_plan.hpp)
+N_CU = 256                                                             # the MI355X the fixtures were recorded on
+
+
+def routed_rollout(shim_lib, V, A, E, prefer, policy, tune=None, *, delta=1, table_bytes=None, n_cu=N_CU, limited=0, budgeted=0, record=0, soc=0, term=0):
+    """route_rollout over a one-step launch, through the shim: (family, the plan's nine fields, the name its launcher notes)"""
+    out, name = (ctypes.c_uint64 * 9)(), ctypes.create_string_buffer(2 * KERNEL_NAME_BYTES)
+    table_bytes = (V if policy == 2 else 0) if table_bytes is None else table_bytes
+    family = shim_lib.shim_route_rollout(V, A, E, delta, table_bytes, n_cu, tune, prefer, policy, limited, budgeted, record, soc, term, out, name)
+    assert family in (TPE, PACKED, LG), (family, tune)
+    return family, tuple(out), name.value.decode()
+
+
+def routed_step(shim_lib, V, A, E, prefer, uniforms, tune=None, *, delta=1, n_cu=N_CU, limited=0, scen=0, term=0):
+    out, name = (ctypes.c_uint64 * 8)(), ctypes.create_string_buffer(2 * KERNEL_NAME_BYTES)
+    family = shim_lib.shim_route_step(V, A, E, delta, n_cu, tune, prefer, limited, uniforms, scen, term, out, name)
+    assert family in (TPE, PACKED, LG), (family, tune)
+    return family, tuple(out), name.value.decode()
+
+
 def limit_plans(shim_lib):
     """the limit plans and names of the LIMIT_* sweep: {'rollout': {shape: 'L full mv_lds dense block grid lds_bytes|name'}, 'step':
     {shape: 'L full block grid|name'}}"""
@@ -474,8 +496,9 @@ def _fixture():
 
 def test_lane_group_plans_are_the_recorded_ones(shim):  # noqa: F811
     """plan_rollout_lg and plan_step_lg decide what the inline launchers decided on the GPU, shape by shape; the grid follows from
-    block, L and E, the dynamic LDS segment is the move table or nothing; the kept names are formatted byte for byte.  Shapes a
-    packed kernel took are skipped: none with the packed layout off, and no more than half of the sweep in all."""
+    block, L and E, the dynamic LDS segment is the move table or nothing; the kept names are formatted byte for byte.  Where a
+    packed kernel took the launch there is no lane-group plan to compare: the route must say packed there (tests/test_route.py
+    compares the route with every entry) -- none with the packed layout off, and no more than half of the sweep in all."""
     recorded = _fixture()
     rollouts, steps, names = recorded['plan_rollout_lg'], recorded['plan_step_lg'], recorded['lg_kernel_names']
     keys = [lg_key(tune, rows * cols, A, E) for tune, rows, cols, A, E in lg_shapes()]
@@ -494,6 +517,8 @@ def test_lane_group_plans_are_the_recorded_ones(shim):  # noqa: F811
             if want == LG_PACKED:
                 skipped += 1
                 skipped_unpacked += unpacked
+                if routed_rollout(shim, V, A, E, PREFER_LG, policy, tune, record=record)[0] != PACKED:
+                    wrong.append((key, record, policy, want))
                 continue
             code, grid, lds_bytes, _ = planned_rollout_lg(shim, tune, V, A, E, record, policy)
             L, _, mv, _, block = LG_ROLLOUT_CODE.match(want).groups()
@@ -504,6 +529,8 @@ def test_lane_group_plans_are_the_recorded_ones(shim):  # noqa: F811
             if want == LG_PACKED:
                 skipped += 1
                 skipped_unpacked += unpacked
+                if routed_step(shim, V, A, E, PREFER_LG, uniforms, tune)[0] != PACKED:
+                    wrong.append((key, 'step', uniforms, want))
                 continue
             code, grid, _ = planned_step_lg(shim, A, E, uniforms)
             L, _, block = LG_STEP_CODE.match(want).groups()
