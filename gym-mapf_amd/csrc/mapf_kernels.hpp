@@ -254,6 +254,8 @@ struct RolloutTuning {
     unsigned step_block = 0;         // step_block=64|128|256|512: block size of the plain packed single step (experiments; 0 = by batch)
     int step_delta = 1;              // step_delta: the single step's LDS table of 4-byte delta rows -- 0 never, 1 where the 16-byte rows
                                      //   do not fit and the batch gives every CU a block (default), 2 whenever it fits (tests, experiments)
+    unsigned step_grid = 0;          // step_grid=n: at most n blocks in the grid of the single step's resident forms, so that a block walks many
+                                     //   chunks of a small batch (tests; 0 = by the device's CU count; the plain step ignores it)
     bool scen_table = true;          // scen_table=0: never build the scenario table (StepArgs::scen) -- tests compare both forms
     int policy_table_lds = -1;       // policy_table_lds=0|1: the packed rollout under the table policy gathers its action bytes from global
                                      //   memory / from a copy staged into LDS behind the table image whenever that fits (default: by shape)

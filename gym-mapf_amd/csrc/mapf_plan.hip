@@ -13,7 +13,7 @@ namespace mapf {
 // ONE override: the environment variable MAPF_TUNE, "key=value,key=value,...", read by default_rollout_tuning (mapf_dispatch.hip) at handle creation, so a process
 // can hold handles with different settings (the tests and the A/B tools do).  Keys (include/mapf_hip.h documents them):
 //   quad_lanes, k, quad_min_lanes, oct_min_lanes, mv_lds_max_bytes, scen_table, bitmap_pairs, bitmap_block, bitmap_staycol,
-//   bitmap_delta, step_big, step_block, step_delta, policy_table_lds, limit_packed.
+//   bitmap_delta, step_big, step_block, step_delta, step_grid, policy_table_lds, limit_packed.
 // An unknown key or a malformed item is an error (*err names it): a typo must not silently measure the default.
 RolloutTuning rollout_tuning_for(int n_cu, const char *text, std::string *err) {
     RolloutTuning t;
@@ -50,6 +50,7 @@ RolloutTuning rollout_tuning_for(int n_cu, const char *text, std::string *err) {
         else if (key == "step_big") t.step_big = int(v);
         else if (key == "step_block") t.step_block = unsigned(v);
         else if (key == "step_delta") t.step_delta = int(v);
+        else if (key == "step_grid") t.step_grid = unsigned(v);
         else if (key == "policy_table_lds") t.policy_table_lds = v != 0 ? 1 : 0;
         else if (key == "limit_packed") t.limit_packed = v != 0;
         else { if (err) *err = "MAPF_TUNE: unknown key '" + key + "'"; return t; }
@@ -232,6 +233,9 @@ bool plan_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune,
     // MAPF_TUNE step_big=0 never, =2 whenever it fits.
     const size_t big_lds = kStepMoveAt + size_t(args.c.n_cells) * kBigCols * sizeof(MoveEntry);
     const int n_cu = tune.n_cu;
+    // MAPF_TUNE step_grid=n: at most n blocks in a resident form's grid (the kernel strides by its grid: a block then walks more
+    // chunks than any batch a test can afford gives it on a whole device); 0 = the grid below
+    auto capped = [&tune](unsigned grid) { return tune.step_grid != 0u && tune.step_grid < grid ? tune.step_grid : grid; };
     const uint64_t resident_lanes = uint64_t(n_cu) * 2048u;
     const bool big_fits = K == 4 && Q <= 8 && tune.step_big != 0 && args.n_envs > 0 && args.n_envs % (1024u / unsigned(Q)) == 0 &&
                           2u * big_lds <= kLdsBytes;
@@ -244,7 +248,7 @@ bool plan_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune,
     if (big_fits && (tune.step_big == 2 || lanes >= 2u * resident_lanes) && Q >= 2 && args.n_envs % (1024u / unsigned(Q / 2)) == 0 &&
         tune.force_k != 4) {
         const int Q8 = Q / 2;
-        const unsigned block = 1024u, n_chunks = unsigned(args.n_envs * uint64_t(Q8) / block), grid = n_chunks < unsigned(n_cu) ? n_chunks : unsigned(n_cu);
+        const unsigned block = 1024u, n_chunks = unsigned(args.n_envs * uint64_t(Q8) / block), grid = capped(n_chunks < unsigned(n_cu) ? n_chunks : unsigned(n_cu));
         *plan = StepPlan{8, Q8, StepForm::FullRows, block, grid, n_chunks, big_lds, int(kLdsBytes - kLdsReserve)};
         return step_instance_planned(*plan);
     }
@@ -270,13 +274,13 @@ bool plan_step_lq(int n_agents, const StepArgs &args, const RolloutTuning &tune,
         if (args.n_envs % (block / unsigned(Q)) == 0) {
             unsigned per_cu = unsigned(kLdsBytes / form_lds);
             if (per_cu > 2048u / block) per_cu = 2048u / block;
-            const unsigned n_chunks = unsigned(lanes / block), grid = n_chunks < per_cu * unsigned(n_cu) ? n_chunks : per_cu * unsigned(n_cu);
+            const unsigned n_chunks = unsigned(lanes / block), grid = capped(n_chunks < per_cu * unsigned(n_cu) ? n_chunks : per_cu * unsigned(n_cu));
             *plan = StepPlan{K, Q, bitmaps ? StepForm::DeltaRowsBitmap : StepForm::DeltaRows, block, grid, n_chunks, form_lds, int(kLdsBytes)};
             return step_instance_planned(*plan);
         }
     }
     if (big) {
-        const unsigned block = 1024u, n_chunks = unsigned(lanes / block), grid = n_chunks < 2u * unsigned(n_cu) ? n_chunks : 2u * unsigned(n_cu);
+        const unsigned block = 1024u, n_chunks = unsigned(lanes / block), grid = capped(n_chunks < 2u * unsigned(n_cu) ? n_chunks : 2u * unsigned(n_cu));
         *plan = StepPlan{K, Q, StepForm::FullRows, block, grid, n_chunks, big_lds, int(kLdsBytes - kLdsReserve)};
         return step_instance_planned(*plan);
     }

@@ -110,6 +110,8 @@ typedef struct mapf_desc {
  *   step_big=0|1|2       the single step's resident grid with the move table in LDS: never / by batch (default) / whenever it fits
  *   step_delta=0|1|2     ... with 4-byte delta rows (64x64 maps): never / from one full residency on (default) / whenever it fits
  *   step_block=64|128|256|512   block size of the plain packed single step
+ *   step_grid=n          at most n blocks in the grid of the single step's resident forms (step_big, step_delta): each block then walks
+ *                        more chunks of the batch (tests; 0, the default: by the device's CU count; the plain step ignores it)
  *   policy_table_lds=0|1 the packed rollout under MAPF_POLICY_TABLE: action bytes gathered from global memory / from a copy of the
  *                        policy table staged into LDS behind the table image whenever one block's segment fits (default: by shape)
  *   limit_packed=0|1     a rollout under MAPF_POLICY_TABLE and an episode step limit (mapf_set_episode_limit): always the lane-group

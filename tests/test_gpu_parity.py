@@ -1519,7 +1519,7 @@ def test_mapf_tune_is_the_one_override_and_rejects_what_it_does_not_know(monkeyp
     grid = MapfGrid(['....', '....', '....', '....'])
     make = lambda: VecMapfEnv(grid, 4, ((0, 0), (1, 1), (2, 2), (3, 3)), ((3, 0), (2, 1), (1, 2), (0, 3)), 0.2, -1000.0, 100.0, -1.0,
                               OptimizationCriteria.Makespan, n_envs=4096)
-    for bad, what in (('k=4,no_such_key=1', 'unknown key'), ('k', 'malformed'), ('k=four', 'malformed')):
+    for bad, what in (('k=4,no_such_key=1', 'unknown key'), ('k', 'malformed'), ('k=four', 'malformed'), ('step_grid=x', 'malformed')):
         monkeypatch.setenv('MAPF_TUNE', bad)
         with pytest.raises(nat.MapfNativeError) as err:
             make()

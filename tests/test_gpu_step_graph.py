@@ -178,9 +178,11 @@ def test_scenario_table_step_equals_plain_rows(monkeypatch, n_agents, n_envs):
 @pytest.mark.parametrize('big', ['2', '2k4', '0'])
 def test_single_step_at_a_batch_larger_than_the_device_holds(monkeypatch, big, rewards=R):
     """393216 envs x 8 agents: more than an MI355X holds at once.  MAPF_TUNE step_big=2 forces the form the library uses from
-    1 M envs on -- a resident grid of 512 blocks of 1024 threads with the move table in LDS, walking 768 chunks (half
-    of the blocks take two) -- step_big=0 the one-block-per-256-lanes form.  Six steps against the C oracle, the
-    first one with the is_terminal test (a state set by the caller), then without."""
+    1 M envs on -- a resident grid of 1024-thread blocks with the move table in LDS: eight agents per lane ('2') on 256
+    blocks that walk 384 chunks, four per lane ('2k4') on 512 blocks that walk 768 (half of the blocks take two either
+    way) -- step_big=0 the one-block-per-256-lanes form.  Neither resident variant walks a third chunk, the first one
+    computed from registers refilled inside the loop: tests/test_gpu_step_forms.py does, under MAPF_TUNE step_grid.
+    Six steps against the C oracle, the first one with the is_terminal test (a state set by the caller), then without."""
     set_tune(monkeypatch, step_big=big[0])
     if big == '2k4':
         set_tune(monkeypatch, k='4')                      # (the BIG form prefers eight agents per lane: pin four)
