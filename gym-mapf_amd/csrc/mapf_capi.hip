@@ -8,7 +8,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -111,12 +110,7 @@ constexpr size_t kZeroCopyMaxBytes = 16 * 1024;   // beyond this the DMA copies 
 }  // namespace
 
 namespace mapf {
-void note_kernel(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_noted_kernel, sizeof(g_noted_kernel), fmt, ap);
-    va_end(ap);
-}
+void note_kernel(const char *name) { snprintf(g_noted_kernel, sizeof(g_noted_kernel), "%s", name); }
 }  // namespace mapf
 
 struct mapf_graph_s {

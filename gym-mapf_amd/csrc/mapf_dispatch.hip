@@ -1,6 +1,7 @@
-// The dispatcher: launch_rollout and launch_step, the only launch entries the C ABI calls.  Each asks the route (route_rollout /
-// route_step, mapf_plan.hpp: which family takes the launch, and that family's plan) ONCE, checks the limit / budget block once, and
-// hands the plan to the family's launcher -- the one place where a launch meets its translation unit.  Holds no kernel itself.
+// The dispatcher: launch_rollout, launch_step and launch_transitions, the planned launch entries the C ABI calls.  Each asks the
+// planner (route_rollout / route_step, mapf_plan.hpp: which family takes the launch, and that family's plan; plan_transitions) ONCE,
+// the first two check the limit / budget block once, and hands the plan to the family's launcher -- the one place where a launch
+// meets its translation unit.  Holds no kernel itself.
 #include "mapf_kernels.hpp"
 #include "mapf_plan.hpp"
 
@@ -84,6 +85,18 @@ hipError_t launch_step(int n_agents, const StepArgs &args, const RolloutTuning &
         case KernelFamily::LaneGroup: break;
     }
     return limit ? launch_step_lg_limit(r.lg, n_agents, args, stream, *limit) : launch_step_lg(r.lg, n_agents, args, stream);
+}
+
+// env.P[s][a]: no route -- the agent count names the family -- but one plan, made here from the call's five shape facts
+hipError_t launch_transitions(const TransitionsArgs &args, hipStream_t stream) {
+    if (args.n_queries == 0 || args.max_branches == 0) return hipSuccess;
+    const bool all_out = args.out_next && args.out_prob && args.out_reward && args.out_done && args.out_collision;
+    TransitionsPlan plan;
+    if (!plan_transitions(args.n_agents, args.n_queries, args.max_branches, args.compact, all_out, &plan)) return hipErrorInvalidValue;
+    if (plan.scan_passes != 0) {
+        if (hipError_t e = launch_transitions_scan(plan, args, stream)) return e;
+    }
+    return plan.wide ? launch_transitions_wide(plan, args, stream) : launch_transitions_rows(plan, args, stream);
 }
 
 }  // namespace mapf

@@ -175,7 +175,7 @@ hipError_t MAPF_G(launch_step_g)(const TpePlan &plan, int n_agents, const StepAr
     const unsigned block = plan.block, grid = plan.grid;
     char name[kKernelNameBytes];
     tpe_step_kernel_name(name, n_agents, plan, args.uniforms != nullptr);
-    note_kernel("%s", name);
+    note_kernel(name);
     switch (n_agents) {
 #define X(N)                                                                                       \
     case N:                                                                                        \
@@ -205,7 +205,7 @@ static hipError_t launch_tpe_rollout(const RolloutArgs &args, unsigned grid, uns
 hipError_t MAPF_G(launch_rollout_g)(const TpePlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table) {
     char name[kKernelNameBytes];
     tpe_rollout_kernel_name(name, n_agents, plan, table != nullptr);
-    note_kernel("%s", name);
+    note_kernel(name);
     switch (n_agents) {
 #define X(N) case N: return launch_tpe_rollout<N>(args, plan.grid, plan.block, stream, table);
         MAPF_FOR_EACH_A(X)

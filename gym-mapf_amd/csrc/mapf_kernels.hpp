@@ -180,7 +180,7 @@ struct EpisodeBudget {
 // Every launcher names the kernel instance (and block size) that took the launch; the C ABI keeps the name of a
 // handle's last step / rollout launch (mapf_last_kernel) so a benchmark labels its numbers with what actually ran.
 constexpr size_t kKernelNameBytes = 160;   // what is kept of a name, the terminator included
-void note_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+void note_kernel(const char *name);
 
 struct TransitionsArgs {
     EnvConsts c;
@@ -204,14 +204,20 @@ struct TransitionsArgs {
     // out_offset[q] receives q's first row, out_offset[N] the total) -- else reserved rows (row j of query q's window at
     // q * max_branches + j).  Rows at or beyond `capacity` are not written.
     uint32_t *rel;                 // scratch u32[N]
-    uint64_t *block_base;          // scratch u64[transitions_scan_blocks(N) + 1]
+    uint64_t *block_base;          // scratch u64[transitions_scan_blocks(N) + 1] (mapf_plan.hpp)
     uint64_t *out_offset;
     uint64_t capacity;
     bool compact;
 };
 constexpr int kTransitionsMaxAgents = 16;   // 3^16 = 43 M branches per query, returned in windows
+// The dispatcher's entry (mapf_dispatch.hip): hipSuccess for an empty call before anything is noted; else plan_transitions
+// (mapf_plan.hpp) once, hipErrorInvalidValue where it declines, then the launchers of mapf_transitions.hip, which take that plan and
+// decide nothing: the scan passes it names, then its family's instance under its name
 hipError_t launch_transitions(const TransitionsArgs &args, hipStream_t stream);
-uint64_t transitions_scan_blocks(uint64_t n_queries);
+struct TransitionsPlan;
+hipError_t launch_transitions_scan(const TransitionsPlan &plan, const TransitionsArgs &args, hipStream_t stream);
+hipError_t launch_transitions_rows(const TransitionsPlan &plan, const TransitionsArgs &args, hipStream_t stream);
+hipError_t launch_transitions_wide(const TransitionsPlan &plan, const TransitionsArgs &args, hipStream_t stream);
 // calc_transition_reward_from_local_states for N (prev = args.local, args.actions, next) triples; fills
 // args.out_reward / out_done / out_collision [N] (max_branches, out_count, out_next, out_prob unused)
 hipError_t launch_transition_rewards(const TransitionsArgs &args, const uint16_t *next, hipStream_t stream);

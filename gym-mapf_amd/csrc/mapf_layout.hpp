@@ -1,7 +1,8 @@
 // LDS layout of the kernels that keep the move table in LDS: ONE definition for the kernels (mapf_lg_rollout.hip,
 // mapf_lq_rollout.hip, mapf_lq_step.hip) and for the launch planner (mapf_plan.hip), which decides whether an image fits.
 // Also the forms of the packed kernels and the lists of their instances (MAPF_LQ_ROLLOUT_INSTANCES, ..._TABLE_INSTANCES,
-// MAPF_LQ_STEP_INSTANCES): the planner asks them, the launchers are generated from them.
+// MAPF_LQ_STEP_INSTANCES): the planner asks them, the launchers are generated from them.  At the end, a wave's LDS in the env.P
+// rows kernel (mapf_transitions.hip), for that kernel and for plan_transitions.
 #pragma once
 #include "mapf_kernels.hpp"
 
@@ -120,5 +121,16 @@ constexpr bool lq_step_instance_exists(int K, int Q, StepForm form) {
 #undef X
     return false;
 }
+
+// env.P[s][a] for teams of up to eight agents (transitions_rows_kernel<MAXA>, mapf_transitions.hip): a wave's dynamic LDS holds,
+// for its 2^qw_log2 queries, the prefix slots (4 bytes a query), then the queries -- a 48-byte header (QueryHeader) and one 16-byte
+// record per (agent, list entry) each -- then the scratch of the cooperative set-up, which the 6- and 8-agent instances have:
+// 16 bytes per (query, agent)
+constexpr uint32_t kQueryHeader = 48, kRecord = 16;
+constexpr bool transitions_cooperative(int max_a) { return max_a >= 6; }
+constexpr uint32_t transitions_records_bytes(int max_a) { return kQueryHeader + uint32_t(max_a) * 3u * kRecord; }   // header + records
+constexpr uint32_t transitions_scratch_bytes(int max_a) { return transitions_cooperative(max_a) ? uint32_t(max_a) * 16u : 0u; }
+constexpr uint32_t transitions_query_lds_bytes(int max_a) { return transitions_records_bytes(max_a) + 4u + transitions_scratch_bytes(max_a); }
+constexpr size_t transitions_wave_lds_bytes(int max_a, uint32_t qw_log2) { return size_t(transitions_query_lds_bytes(max_a)) << qw_log2; }
 
 }  // namespace mapf

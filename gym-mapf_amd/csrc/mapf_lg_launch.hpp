@@ -25,7 +25,7 @@ hipError_t launch_lg_rollout_instance(const LgRolloutPlan &plan, const RolloutAr
     }
     char name[kKernelNameBytes];
     lg_rollout_kernel_name(name, plan, RECORD, STREAM, TABLE);
-    note_kernel("%s", name);
+    note_kernel(name);
     hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(plan.block), plan.lds_bytes, stream, args, A, extra...);
     return hipGetLastError();
 }
@@ -66,7 +66,7 @@ hipError_t launch_lg_step(const LgStepPlan &plan, const StepArgs &args, uint32_t
     }
     char name[kKernelNameBytes];
     lg_step_kernel_name(name, plan, ext);
-    note_kernel("%s", name);
+    note_kernel(name);
     hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(plan.block), 0, stream, args, A, extra...);
     return hipGetLastError();
 }

@@ -41,7 +41,7 @@ hipError_t launch_lq_rollout_instance(const LqPlan &plan, const RolloutArgs &arg
     }
     char name[kKernelNameBytes];
     lq_rollout_kernel_name(name, plan, RECORD, STREAM, Family::kTable, soc, term, table ? table->table_bytes : 0u);
-    note_kernel("%s", name);
+    note_kernel(name);
     const dim3 grid(unsigned(args.n_envs / (plan.block / unsigned(Q)))), block(plan.block);
     if constexpr (Family::kTable) {   // (the bitmaps follow the table image, the policy table's LDS copy follows them at table_at)
         hipLaunchKernelGGL(kern, grid, block, plan.lds_total, stream, args, A, uint32_t(plan.lds_bytes), *table, plan.table_at, extra...);

@@ -537,7 +537,7 @@ static hipError_t launch_step_instance(const StepPlan &plan, const StepArgs &arg
 hipError_t launch_step_lq(const StepPlan &plan, int n_agents, const StepArgs &args, hipStream_t stream) {
     char name[kKernelNameBytes];
     lq_step_kernel_name(name, plan, args.scen != nullptr, !args.state_not_terminal);
-    note_kernel("%s", name);
+    note_kernel(name);
     // the planned instance, by the list in mapf_layout.hpp (what lq_step_instance_exists answers from), in the list's order
 #define X(QQ, KK, FF) if (plan.Q == QQ && plan.K == KK && plan.big == StepForm::FF) return launch_step_instance<QQ, KK, int(StepForm::FF)>(plan, args, uint32_t(n_agents), stream);
     MAPF_LQ_STEP_INSTANCES(X)

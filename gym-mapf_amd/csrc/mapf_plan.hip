@@ -390,6 +390,97 @@ void tpe_rollout_kernel_name(char *name, int n_agents, const TpePlan &plan, bool
     else snprintf(name, kKernelNameBytes, "rollout_kernel<A=%d> block=%u (thread per env)", n_agents, plan.block);
 }
 
+// ------------------------------------------------------------------- env.P[s][a]
+// the rows family (transitions_rows_kernel<max_a>): queries per wave, pieces, the scan it needs, waves per block
+static bool plan_transitions_rows(uint32_t n_agents, uint64_t n_queries, uint32_t max_branches, bool compact, TransitionsPlan *plan) {
+    const int max_a = plan->max_a;
+    const bool coop = transitions_cooperative(max_a);
+    // queries per wave: as many as keep a block's LDS near 32 KB (five or more blocks per CU), fewer while that leaves the
+    // device short of waves (16 per SIMD queued) -- set-up uses one lane per query, so small teams want many per wave
+    uint32_t qw_log2 = 6;
+    while (qw_log2 > 2 && 4u * (transitions_records_bytes(max_a) + 4u) * (1u << qw_log2) > 36u * 1024u) --qw_log2;
+    while (qw_log2 > (max_a >= 8 ? 2u : 3u) && (n_queries >> qw_log2) < 16384u) --qw_log2;
+    if (coop && qw_log2 > 3u) qw_log2 = 3u;                          // (cooperative set-up: a query's group has a lane per agent)
+    // rows per wave: a batch's windows can hold QW x min(3^A, max_branches) rows; beyond two pieces' worth they are cut into
+    // pieces -- which needs the scan, as compacted rows do.  Pieces of 1024 rows (16 sweeps) while the call is small, so that it
+    // still makes ~24 K waves' worth of work (a room map fills about a fifth of the rows a query can have), up to 4096 for large
+    // calls, where fewer set-ups per row count (profiles/r05_transitions_launch_shapes.txt: 20000 queries of 8 agents 0.43 of the
+    // roofline with 1024-row pieces, 0.37 with 4096; 200000 queries 0.54 against 0.60-0.68)
+    uint64_t most = 1;
+    for (uint32_t i = 0; i < n_agents && most < max_branches; ++i) most *= 3u;
+    if (most > max_branches) most = max_branches;
+    const uint64_t est_rows = n_queries * most / 5u;
+    uint32_t rows_per_wave = 1024u;
+    while (rows_per_wave < 4096u && est_rows / (2u * rows_per_wave) >= 24576u) rows_per_wave *= 2u;
+    most <<= qw_log2;
+    // (the small teams' batches -- at most 64 x 81 rows, set up by one lane per query -- stay whole: their waves all do the same work)
+    const uint32_t pieces_max = (coop && most > 2u * rows_per_wave) ? uint32_t((most + rows_per_wave - 1) / rows_per_wave) : 1u;
+    // the scan: pass 2 is left to the rows kernel's waves (unscanned_blocks != 0) in a call of at most kFusedScanBlocks scan blocks
+    const uint64_t scan_blocks = transitions_scan_blocks(n_queries);
+    const uint32_t unscanned_blocks = scan_blocks <= kFusedScanBlocks ? uint32_t(scan_blocks) : 0u;
+    if (compact || pieces_max > 1u) {
+        if (scan_blocks > 0x7FFFFFFFull) return false;
+        plan->scan_passes = unscanned_blocks == 0u ? 2 : 1;
+        plan->scan_blocks = unsigned(scan_blocks);
+    }
+    const uint64_t waves = ((n_queries + (1u << qw_log2) - 1) >> qw_log2) * pieces_max;
+    // waves per block: ONE for the large teams -- their waves live for very different times (a piece that does not exist leaves
+    // at once, a full one sweeps 64 times) and a block keeps its place until its last wave is done: four waves per block
+    // measured 0.407 ms against 0.277 ms at 8 agents x 20000 queries (profiles/r05_transitions_launch_shapes.txt); the small
+    // teams' waves all do the same work and share a block's slip table
+    const unsigned wpb = coop ? 1u : 4u;
+    const uint64_t grid64 = (waves + wpb - 1) / wpb;
+    if (grid64 > 0x7FFFFFFFull) return false;
+    plan->qw_log2 = qw_log2; plan->pieces_max = pieces_max; plan->rows_per_wave = rows_per_wave; plan->unscanned_blocks = unscanned_blocks;
+    plan->block = 64u * wpb;
+    plan->grid = unsigned(grid64);
+    plan->lds_bytes = wpb * transitions_wave_lds_bytes(max_a, qw_log2);
+    return true;
+}
+
+bool plan_transitions(uint32_t n_agents, uint64_t n_queries, uint32_t max_branches, bool compact, bool all_out, TransitionsPlan *plan) {
+    *plan = TransitionsPlan{};
+    if (n_agents <= 8u) {
+        plan->max_a = n_agents <= 2u ? 2 : (n_agents <= 4u ? 4 : (n_agents <= 6u ? 6 : 8));
+        plan->all_out = all_out;
+        return plan_transitions_rows(n_agents, n_queries, max_branches, compact, plan);
+    }
+    if (n_agents > uint32_t(kTransitionsMaxAgents)) return false;
+    plan->wide = true;
+    plan->max_a = int(n_agents);
+    if (compact) {   // (the wide kernels read the scanned totals: both passes)
+        const uint64_t scan_blocks = transitions_scan_blocks(n_queries);
+        if (scan_blocks > 0x7FFFFFFFull) return false;
+        plan->scan_passes = 2;
+        plan->scan_blocks = unsigned(scan_blocks);
+    }
+    // lanes per group: a wave; a group walks up to 16 x lanes rows, a long window is cut into that many-row chunks (so
+    // that a single query of a large team still fills the device)
+    while (plan->lanes_log2 < 6 && (1u << plan->lanes_log2) < max_branches) ++plan->lanes_log2;
+    const uint32_t lanes = 1u << plan->lanes_log2;
+    plan->walks = std::min<uint32_t>(16u, (max_branches + lanes - 1) / lanes);
+    plan->chunk = lanes * plan->walks;
+    plan->chunks_per_query = (max_branches + plan->chunk - 1) / plan->chunk;
+    const uint64_t threads = n_queries * uint64_t(plan->chunks_per_query) * lanes;
+    const uint64_t grid64 = (threads + 255) / 256;
+    if (grid64 > 0x7FFFFFFFull) return false;
+    plan->block = 256u;
+    plan->grid = unsigned(grid64);
+    return true;
+}
+
+void transitions_kernel_name(char *name, const TransitionsPlan &plan, uint32_t n_agents, bool compact) {
+    const char *rows = compact ? "compacted" : "reserved";
+    char pieces[40] = "";
+    if (plan.wide) {
+        snprintf(name, kKernelNameBytes, "transitions_kernel<%d,EXACT> %u agents, %u lanes x %u rows per group, %u groups per query, %s rows", plan.max_a, n_agents,
+                 1u << plan.lanes_log2, plan.walks, plan.chunks_per_query, rows);
+        return;
+    }
+    if (plan.pieces_max > 1u) snprintf(pieces, sizeof(pieces), " in pieces of %u rows", plan.rows_per_wave);
+    snprintf(name, kKernelNameBytes, "transitions_rows_kernel<%d> %u agents, %u queries per wave%s, %s rows", plan.max_a, n_agents, 1u << plan.qw_log2, pieces, rows);
+}
+
 // ------------------------------------------------------------------- the route (mapf_plan.hpp lists the rules)
 // thread-per-env is what the handle prefers: by flag, or an env of at most one agent pair (lane groups from two pairs on)
 static bool prefers_tpe(FamilyPreference prefer, int n_agents) {

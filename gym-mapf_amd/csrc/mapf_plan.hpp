@@ -4,7 +4,8 @@
 // device (mapf_debug_rollout_plan, tests/test_plan_decisions.py).  The dispatcher (mapf_dispatch.hip) asks the route once per launch
 // and hands its plan to the family's launcher; a launcher takes ONE plan and launches the instance it names: it decides neither the
 // instance nor the family.  The name a launch notes is formatted here as well, one function per planned family -- thread-per-env,
-// the packed rollout, the packed step, the lane-group rollout and step -- so a shape's name can be asked for without a launch.
+// the packed rollout, the packed step, the lane-group rollout and step, env.P[s][a] (which no route precedes: its instance follows
+// from the agent count) -- so a shape's name can be asked for without a launch.
 #pragma once
 #include "mapf_layout.hpp"
 
@@ -92,6 +93,28 @@ struct TpePlan { unsigned block = 0, grid = 0; };
 TpePlan plan_tpe(uint64_t n_envs);
 void tpe_step_kernel_name(char *name, int n_agents, const TpePlan &plan, bool ext_uniforms);
 void tpe_rollout_kernel_name(char *name, int n_agents, const TpePlan &plan, bool table_policy);
+
+// env.P[s][a] (mapf_transitions.hip).  The scan of the windows' lengths works in blocks of kScanBlock queries (the C ABI sizes
+// TransitionsArgs::block_base from it); a call of at most kFusedScanBlocks of them leaves the scan's second pass to the rows
+// kernel's waves.
+constexpr uint32_t kScanBlock = 256, kFusedScanBlocks = 256;
+constexpr uint64_t transitions_scan_blocks(uint64_t n_queries) { return (n_queries + kScanBlock - 1) / kScanBlock; }
+// What launch_transitions (mapf_dispatch.hip) launches: the scan passes, then transitions_rows_kernel<max_a, all_out> (teams of up
+// to eight) or transitions_kernel<max_a, EXACT> (`wide`: 9 to 16 agents), with every argument the kernel takes beside the call's arrays.
+struct TransitionsPlan {
+    bool wide = false;               // the family
+    int max_a = 0;                   // the instance: 2, 4, 6 or 8 agent slots -- wide: the exact agent count, 9..16
+    bool all_out = false;            // rows: all five output arrays are given, ALL_OUT (the wide kernels test each pointer)
+    uint32_t qw_log2 = 0, pieces_max = 0, rows_per_wave = 0, unscanned_blocks = 0;   // rows: the kernel's arguments
+    uint32_t lanes_log2 = 0, walks = 0, chunk = 0, chunks_per_query = 0;             // wide: the kernel's arguments (chunk = walks << lanes_log2)
+    int scan_passes = 0;             // 0: no scan; 1: the count pass (transitions_count_kernel); 2: ... and the block-totals pass
+    unsigned scan_blocks = 0;        // the count pass's grid (0 without a scan)
+    unsigned block = 0, grid = 0;
+    size_t lds_bytes = 0;            // rows: waves per block x transitions_wave_lds_bytes (mapf_layout.hpp)
+};
+// (all_out: as above; false = the launch does not fit a grid: more than 2^31 - 1 blocks or scan blocks, or more than 16 agents)
+bool plan_transitions(uint32_t n_agents, uint64_t n_queries, uint32_t max_branches, bool compact, bool all_out, TransitionsPlan *plan);
+void transitions_kernel_name(char *name, const TransitionsPlan &plan, uint32_t n_agents, bool compact);
 
 // ------------------------------------------------------------------- the route
 // Which family takes a launch, with that family's plan (the other plans stay as constructed).  The rules, each written once, in

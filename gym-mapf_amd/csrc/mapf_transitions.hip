@@ -26,9 +26,10 @@
 //     row -- measured 330 vector instructions per 64 rows at 8 agents and one wave per ~35 rows at 4 agents.)
 //   * transitions_kernel<A, EXACT> for 9..16 agents (48-bit choice sets do not fit the records): a group of 64 lanes owns a
 //     chunk of one query's window, query set-up per lane, all agent pairs per row.
-#include <algorithm>
+// Which instance a call takes, in what shape and behind which scan passes, is plan_transitions' say (mapf_plan.hpp); the
+// launchers at the end of this file launch what a plan names, launch_transitions (mapf_dispatch.hip) calls them.
 #include <type_traits>
-#include "mapf_kernels.hpp"
+#include "mapf_plan.hpp"
 #include "mapf_device.hpp"
 
 namespace mapf {
@@ -75,8 +76,7 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, uint32_t lan
 }  // namespace
 
 // ---- compacted output, pass 1: every query's window length; exclusive scan inside blocks of 256 queries (rel[q]) and the
-// blocks' totals.  Pass 2 (one block) scans the totals into block_base[] and writes the grand total.
-constexpr uint32_t kScanBlock = 256;
+// blocks' totals.  Pass 2 (one block) scans the totals into block_base[] and writes the grand total.  (kScanBlock: mapf_plan.hpp)
 __global__ void __launch_bounds__(kScanBlock) transitions_count_kernel(const TransitionsArgs p, uint32_t *rel, uint64_t *block_total) {
     __shared__ SlipRow slip[8];
     __shared__ uint32_t wave_total[kScanBlock / 64];
@@ -140,8 +140,7 @@ __global__ void __launch_bounds__(1024) scan_block_totals_kernel(uint64_t *block
 // ---------------------------------------------------------------------------------------------------- A <= 8
 namespace {
 
-constexpr uint32_t kQueryHeader = 48, kRecord = 16;
-struct QueryHeader {
+struct QueryHeader {                                              // (kQueryHeader, kRecord and the wave's LDS layout: mapf_layout.hpp)
     uint32_t radix;        // 2 bits per agent: its list length (1 for absent agents and for every agent of a terminal state)
     uint32_t first;        // first branch of the window (<= count)
     uint32_t terminal;     // 1: the single branch ((1.0, False), s, 0, True) of a terminal state
@@ -188,15 +187,15 @@ __global__ void __launch_bounds__(256) transitions_rows_kernel(const Transitions
     __shared__ SlipRow slip[8];
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[];
     stage_slip_table(p.slip, slip);                                // ends with __syncthreads(): the only block-wide one
-    constexpr uint32_t kQueryBytes = kQueryHeader + uint32_t(MAXA) * 3u * kRecord;
+    constexpr uint32_t kQueryBytes = transitions_records_bytes(MAXA);
     const uint32_t QW = 1u << qw_log2;                             // queries per wave (>= 4: the prefix array stays 16-byte aligned)
     const uint32_t lane = threadIdx.x & 63u;
     // COOP (the 6- and 8-agent instances): a query's set-up is spread over the G = 64 / QW >= 8 lanes of its group, one lane per
     // AGENT -- done by one lane per query, four lanes of a wave working, it was 27 % of the kernel's vector instructions
     // (profiles/r05_transitions_a8_q20000_compact.txt: ~2600 per piece against ~180 per 64 rows)
-    constexpr bool COOP = MAXA >= 6;
-    constexpr uint32_t kScratch = COOP ? uint32_t(MAXA) * 16u : 0u;    // per query: {prev, the three list cells} of every agent
-    unsigned char *const wave_lds = lds_dyn + (threadIdx.x >> 6) * (QW * (kQueryBytes + 4u + kScratch));
+    constexpr bool COOP = transitions_cooperative(MAXA);
+    constexpr uint32_t kScratch = transitions_scratch_bytes(MAXA);    // per query: {prev, the three list cells} of every agent
+    unsigned char *const wave_lds = lds_dyn + (threadIdx.x >> 6) * (QW * transitions_query_lds_bytes(MAXA));
     uint32_t *const prefix = reinterpret_cast<uint32_t *>(wave_lds);                     // [QW] exclusive prefix of the windows' lengths
     unsigned char *const queries = wave_lds + QW * 4u;                                     // [QW] header + records
     unsigned char *const scratch = queries + QW * kQueryBytes;                             // [QW][MAXA] uint4 (COOP)
@@ -702,92 +701,41 @@ hipError_t launch_transition_rewards(const TransitionsArgs &args, const uint16_t
     return hipGetLastError();
 }
 
-uint64_t transitions_scan_blocks(uint64_t n_queries) { return (n_queries + kScanBlock - 1) / kScanBlock; }
-
-// passes 1 and 2: args.rel / args.block_base (see TransitionsArgs), the total to args.out_offset[N] when compacting; also fills
-// args.out_count
-constexpr uint32_t kFusedScanBlocks = 256;   // calls of up to this many scan blocks leave pass 2 to the rows kernel's waves
-static hipError_t launch_transitions_offsets(const TransitionsArgs &args, hipStream_t stream, bool scan = true) {
-    const uint64_t blocks = transitions_scan_blocks(args.n_queries);
-    if (blocks == 0 || blocks > 0x7FFFFFFFull) return blocks == 0 ? hipSuccess : hipErrorInvalidValue;
-    hipLaunchKernelGGL(transitions_count_kernel, dim3(unsigned(blocks)), dim3(kScanBlock), 0, stream, args, args.rel, args.block_base);
-    if (scan)
-        hipLaunchKernelGGL(scan_block_totals_kernel, dim3(1), dim3(1024), 0, stream, args.block_base, uint32_t(blocks),
+// passes 1 and 2 as the plan names them: args.rel / args.block_base (see TransitionsArgs), the total to args.out_offset[N] when
+// compacting; also fills args.out_count
+hipError_t launch_transitions_scan(const TransitionsPlan &plan, const TransitionsArgs &args, hipStream_t stream) {
+    hipLaunchKernelGGL(transitions_count_kernel, dim3(plan.scan_blocks), dim3(kScanBlock), 0, stream, args, args.rel, args.block_base);
+    if (plan.scan_passes > 1)
+        hipLaunchKernelGGL(scan_block_totals_kernel, dim3(1), dim3(1024), 0, stream, args.block_base, uint32_t(plan.scan_blocks),
                            (args.compact && args.out_offset) ? args.out_offset + args.n_queries : nullptr);
     return hipGetLastError();
 }
 
-template <int MAXA>
-static hipError_t launch_rows(const TransitionsArgs &args, hipStream_t stream) {
-    constexpr uint32_t kQueryBytes = kQueryHeader + uint32_t(MAXA) * 3u * kRecord;
-    // queries per wave: as many as keep a block's LDS near 32 KB (five or more blocks per CU), fewer while that leaves the
-    // device short of waves (16 per SIMD queued) -- set-up uses one lane per query, so small teams want many per wave
-    uint32_t qw_log2 = 6;
-    while (qw_log2 > 2 && 4u * (kQueryBytes + 4u) * (1u << qw_log2) > 36u * 1024u) --qw_log2;
-    while (qw_log2 > (MAXA >= 8 ? 2u : 3u) && (args.n_queries >> qw_log2) < 16384u) --qw_log2;
-    if (MAXA >= 6 && qw_log2 > 3u) qw_log2 = 3u;                     // (cooperative set-up: a query's group has a lane per agent)
-    // rows per wave: a batch's windows can hold QW x min(3^A, max_branches) rows; beyond two pieces' worth they are cut into
-    // pieces -- which needs the scan, as compacted rows do.  Pieces of 1024 rows (16 sweeps) while the call is small, so that it
-    // still makes ~24 K waves' worth of work (a room map fills about a fifth of the rows a query can have), up to 4096 for large
-    // calls, where fewer set-ups per row count (profiles/r05_transitions_launch_shapes.txt: 20000 queries of 8 agents 0.43 of the
-    // roofline with 1024-row pieces, 0.37 with 4096; 200000 queries 0.54 against 0.60-0.68)
-    uint64_t most = 1;
-    for (uint32_t i = 0; i < args.n_agents && most < args.max_branches; ++i) most *= 3u;
-    if (most > args.max_branches) most = args.max_branches;
-    const uint64_t est_rows = args.n_queries * most / 5u;
-    uint32_t rows_per_wave = 1024u;
-    while (rows_per_wave < 4096u && est_rows / (2u * rows_per_wave) >= 24576u) rows_per_wave *= 2u;
-    most <<= qw_log2;
-    // (the small teams' batches -- at most 64 x 81 rows, set up by one lane per query -- stay whole: their waves all do the same work)
-    const uint32_t pieces_max = (MAXA >= 6 && most > 2u * rows_per_wave) ? uint32_t((most + rows_per_wave - 1) / rows_per_wave) : 1u;
-    const uint64_t scan_blocks = transitions_scan_blocks(args.n_queries);
-    const uint32_t unscanned_blocks = scan_blocks <= kFusedScanBlocks ? uint32_t(scan_blocks) : 0u;
-    if (args.compact || pieces_max > 1u) {
-        if (hipError_t e = launch_transitions_offsets(args, stream, unscanned_blocks == 0u)) return e;
+// the planned instance of the rows family under the planned name: transitions_rows_kernel<plan.max_a, plan.all_out>
+hipError_t launch_transitions_rows(const TransitionsPlan &plan, const TransitionsArgs &args, hipStream_t stream) {
+    char name[kKernelNameBytes];
+    transitions_kernel_name(name, plan, args.n_agents, args.compact);
+    note_kernel(name);
+    switch (plan.max_a * 2 + (plan.all_out ? 1 : 0)) {
+#define X(N, ALL)                                                                                                                   \
+    case N * 2 + (ALL ? 1 : 0):                                                                                                     \
+        hipLaunchKernelGGL((transitions_rows_kernel<N, ALL>), dim3(plan.grid), dim3(plan.block), plan.lds_bytes, stream, args,     \
+                           plan.qw_log2, plan.pieces_max, plan.rows_per_wave, plan.unscanned_blocks);                               \
+        break;
+        X(2, true) X(2, false) X(4, true) X(4, false) X(6, true) X(6, false) X(8, true) X(8, false)
+#undef X
+        default: return hipErrorInvalidValue;
     }
-    const uint64_t waves = ((args.n_queries + (1u << qw_log2) - 1) >> qw_log2) * pieces_max;
-    // waves per block: ONE for the large teams -- their waves live for very different times (a piece that does not exist leaves
-    // at once, a full one sweeps 64 times) and a block keeps its place until its last wave is done: four waves per block
-    // measured 0.407 ms against 0.277 ms at 8 agents x 20000 queries (profiles/r05_transitions_launch_shapes.txt); the small
-    // teams' waves all do the same work and share a block's slip table
-    const unsigned wpb = MAXA >= 6 ? 1u : 4u;
-    const uint64_t grid64 = (waves + wpb - 1) / wpb;
-    if (grid64 > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const size_t lds = wpb * size_t(kQueryBytes + 4u + (MAXA >= 6 ? MAXA * 16u : 0u)) * (size_t(1) << qw_log2);
-    const bool all_out = args.out_next && args.out_prob && args.out_reward && args.out_done && args.out_collision;
-    note_kernel("transitions_rows_kernel<%d> %u agents, %u queries per wave%s, %s rows", MAXA, args.n_agents, 1u << qw_log2,
-                pieces_max > 1u ? (rows_per_wave == 4096u ? " in pieces of 4096 rows" : (rows_per_wave == 2048u ? " in pieces of 2048 rows" : " in pieces of 1024 rows")) : "",
-                args.compact ? "compacted" : "reserved");
-    if (all_out) hipLaunchKernelGGL((transitions_rows_kernel<MAXA, true>), dim3(unsigned(grid64)), dim3(64 * wpb), lds, stream, args, qw_log2, pieces_max, rows_per_wave, unscanned_blocks);
-    else hipLaunchKernelGGL((transitions_rows_kernel<MAXA, false>), dim3(unsigned(grid64)), dim3(64 * wpb), lds, stream, args, qw_log2, pieces_max, rows_per_wave, unscanned_blocks);
     return hipGetLastError();
 }
 
-hipError_t launch_transitions(const TransitionsArgs &args, hipStream_t stream) {
-    if (args.n_queries == 0 || args.max_branches == 0) return hipSuccess;
-    if (args.n_agents <= 2) return launch_rows<2>(args, stream);
-    if (args.n_agents <= 4) return launch_rows<4>(args, stream);
-    if (args.n_agents <= 6) return launch_rows<6>(args, stream);
-    if (args.n_agents <= 8) return launch_rows<8>(args, stream);
-    if (args.compact) {
-        if (hipError_t e = launch_transitions_offsets(args, stream)) return e;
-    }
-    // lanes per group: a wave; a group walks up to 16 x lanes rows, a long window is cut into that many-row chunks (so
-    // that a single query of a large team still fills the device)
-    uint32_t lanes_log2 = 0;
-    while (lanes_log2 < 6 && (1u << lanes_log2) < args.max_branches) ++lanes_log2;
-    const uint32_t lanes = 1u << lanes_log2;
-    const uint32_t walks = std::min<uint32_t>(16u, (args.max_branches + lanes - 1) / lanes);
-    const uint32_t chunk = lanes * walks;
-    const uint32_t chunks_per_query = (args.max_branches + chunk - 1) / chunk;
-    const uint64_t threads = args.n_queries * uint64_t(chunks_per_query) * lanes;
-    const uint64_t grid64 = (threads + 255) / 256;
-    if (grid64 > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const dim3 grid{unsigned(grid64)}, block{256};
-    note_kernel("transitions_kernel<%d,EXACT> %u agents, %u lanes x %u rows per group, %u groups per query, %s rows", int(args.n_agents),
-                args.n_agents, lanes, walks, chunks_per_query, args.compact ? "compacted" : "reserved");
-    switch (args.n_agents) {
-#define X(N) case N: hipLaunchKernelGGL((transitions_kernel<N, true>), grid, block, 0, stream, args, lanes_log2, chunk, chunks_per_query); break;
+// ... of the wide family: transitions_kernel<plan.max_a, EXACT>
+hipError_t launch_transitions_wide(const TransitionsPlan &plan, const TransitionsArgs &args, hipStream_t stream) {
+    char name[kKernelNameBytes];
+    transitions_kernel_name(name, plan, args.n_agents, args.compact);
+    note_kernel(name);
+    switch (plan.max_a) {
+#define X(N) case N: hipLaunchKernelGGL((transitions_kernel<N, true>), dim3(plan.grid), dim3(plan.block), 0, stream, args, plan.lanes_log2, plan.chunk, plan.chunks_per_query); break;
         X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
 #undef X
         default: return hipErrorInvalidValue;

@@ -244,6 +244,27 @@ int shim_route_step(uint32_t n_cells, int n_agents, uint64_t n_envs, int has_del
     return int(r.family);
 }
 
+// plan_transitions over a call's five shape facts: out = wide, max_a, all_out, qw_log2, pieces_max, rows_per_wave, unscanned_blocks,
+// lanes_log2, walks, chunk, chunks_per_query, scan_passes, scan_blocks, block, grid, lds_bytes; 1 = planned, 0 = the call fits no grid
+int shim_plan_transitions(uint32_t n_agents, uint64_t n_queries, uint32_t max_branches, int compact, int all_out, uint64_t out[16]) {
+    TransitionsPlan p;
+    if (!plan_transitions(n_agents, n_queries, max_branches, compact != 0, all_out != 0, &p)) return 0;
+    const uint64_t fields[16] = {p.wide ? 1u : 0u, uint64_t(p.max_a), p.all_out ? 1u : 0u, p.qw_log2, p.pieces_max, p.rows_per_wave, p.unscanned_blocks, p.lanes_log2,
+                                 p.walks, p.chunk, p.chunks_per_query, uint64_t(p.scan_passes), p.scan_blocks, p.block, p.grid, p.lds_bytes};
+    std::memcpy(out, fields, sizeof(fields));
+    return 1;
+}
+// ... and the name the launcher notes for that plan (kKernelNameBytes)
+int shim_transitions_kernel_name(uint32_t n_agents, uint64_t n_queries, uint32_t max_branches, int compact, int all_out, char *name) {
+    TransitionsPlan p;
+    if (!plan_transitions(n_agents, n_queries, max_branches, compact != 0, all_out != 0, &p)) return 0;
+    transitions_kernel_name(name, p, n_agents, compact != 0);
+    return 1;
+}
+// the layout's say on a wave's dynamic LDS in transitions_rows_kernel<max_a>, and the scan's block count
+uint64_t shim_transitions_wave_lds_bytes(int max_a, uint32_t qw_log2) { return transitions_wave_lds_bytes(max_a, qw_log2); }
+uint64_t shim_transitions_scan_blocks(uint64_t n_queries) { return transitions_scan_blocks(n_queries); }
+
 // does the launcher hold the packed rollout instance (K, Q, form)?  (table: of lq_rollout_kernel_table)
 int shim_rollout_instance_exists(int K, int Q, int form, int table) {
     return form >= 0 && form < kTableForms && lq_rollout_instance_exists(K, Q, TableForm(form), table != 0) ? 1 : 0;

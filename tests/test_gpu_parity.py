@@ -12,6 +12,8 @@ from gym_mapf_amd import _native as nat
 from gym_mapf_amd.envs.grid import MapfGrid
 from gym_mapf_amd.envs.vec_env import STEP_OUTPUTS, OptimizationCriteria, VecMapfEnv
 from totals_cases import _assert_a_wrong_rounding_would_show, _goal_scenario_tables   # (shared with the totals-only sweep)
+from test_host_tables import shim  # noqa: F401  (the host shim: the planner's names)
+from test_transitions_plan import declare, planned
 
 pytestmark = pytest.mark.gpu
 KERNELS = ('thread_per_env', 'lane_group')
@@ -1099,7 +1101,7 @@ def _check_compact_against_reserved(env, local, acts, env_index, res, first=0, w
 
 
 @pytest.mark.parametrize('n_agents', [2, 4, 8])
-def test_compacted_transitions_across_the_scan_block_boundaries(n_agents):
+def test_compacted_transitions_across_the_scan_block_boundaries(shim, n_agents):  # noqa: F811
     """The compacted rows' offsets come from a two-level scan: 256 queries per scan block, the blocks' totals added up by the
     emission's waves themselves for calls of up to 256 blocks (65536 queries) and by a second pass beyond.  Query counts on
     both sides of every boundary -- one query, a block +- 1, many blocks, 256 blocks +- 1 (small teams) -- each against the
@@ -1118,6 +1120,7 @@ def test_compacted_transitions_across_the_scan_block_boundaries(n_agents):
         acts = rs.randint(0, 5, size=(N, A)).astype(np.uint8)
         res = env.transitions(local, acts, max_branches=M)
         cmp = env.transitions_compact(local, acts, max_branches=M)
+        assert env.last_kernel('transitions') == planned(declare(shim), (A, N, M, 1, 1))[1]   # (the kernel the planner names: both scan forms)
         rows = np.minimum(res['count'].astype(np.int64), M)
         offset = np.concatenate([[0], np.cumsum(rows)])
         assert np.array_equal(cmp['count'], res['count']) and np.array_equal(cmp['offset'].astype(np.int64), offset), (A, N)
@@ -1185,7 +1188,7 @@ def test_transitions_in_windows_with_inexact_constants():
 @pytest.mark.parametrize('n_agents', list(range(7, 17)))
 def test_every_transitions_kernel_instance_against_oracle(n_agents, slip=0.2, rewards=EXACT):
     """mapf_transitions dispatches transitions_rows_kernel<2|4|6|8> up to 8 agents (the 1..6-agent instances: the test
-    above) and an exact-size transitions_kernel instance for each of 9..16 (mapf_transitions.hip launch_transitions), each
+    above) and an exact-size transitions_kernel instance for each of 9..16 (mapf_plan.hip plan_transitions), each
     with reserved and with compacted rows: every one of them against the pinned Python oracle's enumeration
     (reference mapf_env.py:448-478), both criteria, per-query goals, several window sizes and offsets.  At most seven
     agents of a query move (the others STAY: one-entry lists), which keeps the oracle's list at <= 3^7 branches while

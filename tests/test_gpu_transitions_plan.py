@@ -1,0 +1,190 @@
+"""Every branch of the env.P[s][a] plan (plan_transitions, csrc/mapf_plan.hip) launched on the device: the kernel the library says
+it ran (mapf_last_kernel) is the one the planner names for the call's shape, and what it wrote equals the pinned Python oracle's
+enumeration (reference mapf_env.py:448-478) bit for bit.  The planner is asked through the host shim, as tests/test_route.py asks it.
+
+Rows family: the four instances whole, in pieces of 1024, 2048 and 4096 rows, without a scan, with the count pass alone (the totals
+added up by the rows kernel's waves) and with both passes; an output array left out (ALL_OUT = false).  Wide family: one group per
+query and several, compacted and reserved.  The second scan pass for small teams: test_compacted_transitions_across_the_scan_block_boundaries
+(tests/test_gpu_parity.py)."""
+import functools
+
+import numpy as np
+import pytest
+
+import mapf_oracle as mo
+from gym_mapf_amd import _native as nat
+from gym_mapf_amd.envs.grid import MapfGrid
+from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
+from test_gpu_parity import EXACT, _bits, _check_compact_against_reserved
+from test_host_tables import shim  # noqa: F401  (the host shim, built once per run)
+from test_transitions_plan import declare, planned
+
+pytestmark = pytest.mark.gpu
+LINES = ['......'] * 6                                                    # a small open map
+SLIP = 0.2
+
+
+def _setup(A, seed):
+    """env and oracle of A agents with distinct random goals; N-query generator of non-terminal states (distinct cells, off goal)"""
+    rs = np.random.RandomState(seed)
+    grid = MapfGrid(LINES)
+    valid = grid.tables()[0]
+    V = len(valid)
+    goal = rs.choice(V, A, replace=False).astype(np.uint16)
+    start = np.roll(goal, 1)
+    env = VecMapfEnv(grid, A, None, None, SLIP, *EXACT, OptimizationCriteria.SoC, seed=1, start_local=start[None], goal_local=goal[None])
+    orc = mo.OracleEnv(LINES, A, [valid[c] for c in start], [valid[c] for c in goal], SLIP, *EXACT, mo.SOC)
+    return rs, V, goal, env, orc
+
+
+def _queries(rs, V, A, N, movers=None):
+    local = np.stack([rs.choice(V, A, replace=False) for _ in range(N)]).astype(np.uint16)
+    acts = rs.randint(1, 5, size=(N, A)).astype(np.uint8)
+    if movers is not None:                                                # at most `movers` agents move: the oracle's list stays short
+        for q in range(N):
+            acts[q, rs.choice(A, A - movers, replace=False)] = 0
+    return local, acts
+
+
+def _expected(orc, local, acts):
+    return [orc.transitions(tuple(int(c) for c in local[q]), acts[q].tolist()) for q in range(local.shape[0])]
+
+
+def _check_rows(rows, exp, first, tag):
+    """rows: (next, prob, reward, done, collision) of a query's window; exp: the oracle's branches from `first` on"""
+    nxt, prob, reward, done, coll = rows
+    n = len(exp)
+    assert np.array_equal(nxt[:n], np.array([e[1] for e in exp], np.uint16).reshape(n, -1)), tag
+    assert np.array_equal(_bits(prob[:n]), _bits([e[0][0] for e in exp])) and np.array_equal(_bits(reward[:n]), _bits([e[2] for e in exp])), tag
+    assert np.array_equal(done[:n].astype(bool), np.array([e[3] for e in exp], bool)) and np.array_equal(coll[:n].astype(bool), np.array([e[0][1] for e in exp], bool)), tag
+
+
+def _check_reserved(res, exp, window, first=0):
+    for q, branches in enumerate(exp):
+        assert int(res['count'][q]) == len(branches), q
+        part = branches[first:first + window]
+        _check_rows(tuple(res[k][q] for k in ('next', 'prob', 'reward', 'done', 'collision')), part, first, q)
+
+
+def _check_compacted(cmp, exp, window):
+    rows = np.array([min(len(b), window) for b in exp], np.int64)
+    assert np.array_equal(cmp['count'], np.array([len(b) for b in exp], np.uint32))
+    assert np.array_equal(cmp['offset'].astype(np.int64), np.concatenate([[0], np.cumsum(rows)]))
+    for q, branches in enumerate(exp):
+        o = int(cmp['offset'][q])
+        _check_rows(tuple(cmp[k][o:o + int(rows[q])] for k in ('next', 'prob', 'reward', 'done', 'collision')), branches[:window], 0, q)
+
+
+# (agents, queries, compacted) and what the plan of that shape must say for the case to be the branch it is here for
+ROWS_CASES = [
+    pytest.param(2, 1, False, dict(max_a=2, pieces_max=1, scan_passes=0), id='rows2-whole-no-scan'),
+    pytest.param(4, 257, True, dict(max_a=4, pieces_max=1, scan_passes=1, unscanned_blocks=2), id='rows4-count-pass-totals-fused'),
+    pytest.param(5, 1, False, dict(max_a=6, pieces_max=1, scan_passes=0), id='rows6-whole'),
+    pytest.param(6, 1, False, dict(max_a=6, pieces_max=6, rows_per_wave=1024, scan_passes=1), id='rows6-six-pieces'),
+    pytest.param(8, 1, True, dict(max_a=8, pieces_max=26, rows_per_wave=1024, scan_passes=1), id='rows8-pieces-compacted'),
+]
+
+
+@pytest.mark.parametrize('A,N,compact,facts', ROWS_CASES)
+def test_rows_instances_launch_the_planned_kernel(shim, A, N, compact, facts):  # noqa: F811
+    lib = declare(shim)
+    rs, V, goal, env, orc = _setup(A, 500 + A)
+    M = 3 ** A
+    plan, name = planned(lib, (A, N, M, int(compact), 1))
+    assert not plan['wide'] and plan['all_out'] == 1 and {k: plan[k] for k in facts} == facts, plan
+    local, acts = _queries(rs, V, A, N)
+    if N > 2:
+        local[1] = goal                                                   # a terminal state: a window of one row
+    exp = _expected(orc, local, acts)
+    assert max(len(b) for b in exp) > 3 ** A // 4
+    if compact:
+        _check_compacted(env.transitions_compact(local, acts), exp, M)
+    else:
+        _check_reserved(env.transitions(local, acts), exp, M)
+    assert env.last_kernel('transitions') == name
+    env.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _five_live_queries():
+    """8 agents: five non-terminal queries and the oracle's enumeration of each, computed once for both batch sizes"""
+    rs, V, goal, env, orc = _setup(8, 508)
+    env.close()
+    local, acts = _queries(rs, V, 8, 5)
+    exp = _expected(orc, local, acts)
+    assert all(len(b) > 1000 for b in exp)
+    return goal, local, acts, exp
+
+
+@pytest.mark.parametrize('N,rows_per_wave,scan_passes', [(38400, 2048, 1), (76800, 4096, 2)])
+def test_larger_pieces_launch_the_planned_kernel(shim, N, rows_per_wave, scan_passes):  # noqa: F811
+    """The piece size follows from the query count and the window alone, so all but five queries are terminal (every agent on its goal: one
+    row each); the live ones sit at index 0, on both sides of a scan-block boundary, in the middle and at the end."""
+    lib, A, M = declare(shim), 8, 3 ** 8
+    plan, name = planned(lib, (A, N, M, 1, 1))
+    assert (plan['rows_per_wave'], plan['scan_passes'], plan['max_a']) == (rows_per_wave, scan_passes, 8) and plan['pieces_max'] > 1, plan
+    assert ' in pieces of %d rows' % rows_per_wave in name
+    goal, live_local, live_acts, exp = _five_live_queries()
+    rs, V, goal2, env, orc = _setup(8, 508)
+    assert np.array_equal(goal, goal2)
+    at = [0, 255, 256, N // 2 + 3, N - 1]
+    local = np.tile(goal, (N, 1))
+    acts = rs.randint(0, 5, size=(N, A)).astype(np.uint8)
+    local[at], acts[at] = live_local, live_acts
+    cmp = env.transitions_compact(local, acts, capacity=120000)
+    assert env.last_kernel('transitions') == name
+    count = np.ones(N, np.int64)
+    count[at] = [len(b) for b in exp]
+    offset = np.concatenate([[0], np.cumsum(np.minimum(count, M))])
+    assert offset[N] <= 120000
+    assert np.array_equal(cmp['count'].astype(np.int64), count) and np.array_equal(cmp['offset'].astype(np.int64), offset)
+    for q, branches in zip(at, exp):
+        o = int(offset[q])
+        _check_rows(tuple(cmp[k][o:o + len(branches)] for k in ('next', 'prob', 'reward', 'done', 'collision')), branches, 0, q)
+    terminal = np.ones(N, bool)
+    terminal[at] = False
+    rows = offset[:N][terminal]                                           # every terminal query's single row: ((1.0, False), s, 0, True)
+    assert np.array_equal(cmp['next'][rows], local[terminal])
+    assert np.array_equal(_bits(cmp['prob'][rows]), _bits(np.ones(len(rows)))) and np.array_equal(_bits(cmp['reward'][rows]), _bits(np.zeros(len(rows))))
+    assert np.all(cmp['done'][rows] == 1) and np.all(cmp['collision'][rows] == 0)
+    env.close()
+
+
+@pytest.mark.parametrize('window,walks,groups', [(100, 2, 1), (3000, 16, 3)])
+def test_wide_family_launches_the_planned_kernel(shim, window, walks, groups):  # noqa: F811
+    lib, A = declare(shim), 9
+    rs, V, goal, env, orc = _setup(A, 509)
+    local, acts = _queries(rs, V, A, 1, movers=7)
+    exp = _expected(orc, local, acts)
+    assert 100 < len(exp[0]) <= 3 ** 7
+    for compact in (1, 0):
+        plan, name = planned(lib, (A, 1, window, compact, 1))
+        assert plan['wide'] and (plan['max_a'], plan['walks'], plan['chunks_per_query'], plan['scan_passes']) == (9, walks, groups, 2 * compact), plan
+        res = env.transitions_compact(local, acts, max_branches=window) if compact else env.transitions(local, acts, max_branches=window)
+        assert env.last_kernel('transitions') == name
+        if compact:
+            _check_compacted(res, exp, window)
+        else:
+            _check_reserved(res, exp, window)
+            _check_compact_against_reserved(env, local, acts, None, res, window=window)
+    env.close()
+
+
+def test_an_output_left_out_takes_the_some_out_instance(shim):  # noqa: F811
+    """mapf_transitions_window through ctypes with out_done = NULL: transitions_rows_kernel<4, false>, named as the all-out instance is,
+    the four other outputs as the oracle has them and as the all-out call wrote them"""
+    lib, A, N, M = declare(shim), 4, 9, 81
+    rs, V, goal, env, orc = _setup(A, 504)
+    local, acts = _queries(rs, V, A, N)
+    exp = _expected(orc, local, acts)
+    plan, name = planned(lib, (A, N, M, 0, 0))
+    assert (plan['max_a'], plan['all_out']) == (4, 0) and name == planned(lib, (A, N, M, 0, 1))[1]
+    full = env.transitions(local, acts)
+    out = dict(count=np.zeros(N, np.uint32), next=np.zeros((N, M, A), np.uint16), prob=np.zeros((N, M)), reward=np.zeros((N, M)), collision=np.full((N, M), 7, np.uint8))
+    nat.check(env._lib.mapf_transitions_window(env._h, N, local.ctypes.data, acts.ctypes.data, None, 0, M, out['count'].ctypes.data, out['next'].ctypes.data,
+                                               out['prob'].ctypes.data, out['reward'].ctypes.data, None, out['collision'].ctypes.data))
+    assert env.last_kernel('transitions') == name
+    out['done'] = full['done']                                            # (checked by the all-out call below; this call had nowhere to write it)
+    _check_reserved(full, exp, M)
+    _check_reserved(out, exp, M)
+    env.close()
