@@ -6,6 +6,7 @@ import functools
 import os
 import re
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -15,6 +16,13 @@ from gym_mapf_amd import _native as nat
 from gym_mapf_amd.envs.grid import MapfGrid
 from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
 from test_host_tables import shim  # noqa: F401  (the host shim, built once per run)
+
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+try:
+    import device_listings as device_listings_of
+    import kernel_meta
+finally:
+    sys.path.pop(0)
 
 HEADER = os.path.join(ROOT, 'include', 'mapf_hip.h')
 CSRC = os.path.join(ROOT, 'gym-mapf_amd', 'csrc')
@@ -92,68 +100,58 @@ def test_product_never_imports_the_oracle():
                 assert 'mapf_oracle' not in text and 'c_oracle' not in text and 'import philox' not in text, f
 
 
-def _kernel_resources(asm_text):
-    """{kernel symbol: (sgpr spills, vgpr spills, scratch bytes)} from the .amdgpu_metadata of a -S listing."""
-    out = {}
-    for block in asm_text.split('  - .agpr_count:')[1:]:
-        name = re.search(r'\.name:\s+(\S+)', block).group(1)
-        out[name] = (int(re.search(r'\.sgpr_spill_count:\s+(\d+)', block).group(1)),
-                     int(re.search(r'\.vgpr_spill_count:\s+(\d+)', block).group(1)),
-                     int(re.search(r'\.private_segment_fixed_size:\s+(\d+)', block).group(1)))
-    return out
+# kernels per device listing (gym-mapf_amd/csrc/Makefile's table names the listings): a unit or an instance that drops out of the
+# library, or one that enters it, has to change this table
+KERNELS_PER_LISTING = {
+    'mapf_lg_kernels': 32, 'mapf_lg_rollout': 252, 'mapf_lg_limit': 197, 'mapf_lg_budget': 168, 'mapf_transitions': 19, 'mapf_lq_step': 84,
+    'mapf_lq_rollout_k8_r1': 24, 'mapf_lq_rollout_k8_r0': 24, 'mapf_lq_rollout_k4_r1': 102, 'mapf_lq_rollout_k4_r0': 102,
+    'mapf_lq_rollout_k2_r1': 48, 'mapf_lq_rollout_k2_r0': 48,
+    'mapf_lq_limit_k4_r1': 30, 'mapf_lq_limit_k4_r0': 30, 'mapf_lq_limit_k2_r1': 24, 'mapf_lq_limit_k2_r0': 24,
+    'mapf_kernels_g0': 16, 'mapf_kernels_g1': 12, 'mapf_kernels_g2': 8, 'mapf_kernels_g3': 8,
+}
 
 
 @pytest.fixture(scope='module')
-def device_listings(tmp_path_factory):
-    """hipcc -S listings (gfx950 device code + .amdgpu_metadata) of every translation unit that holds dispatchable kernels,
-    compiled with the Makefile's flags: {listing name: text}."""
-    tmp_path = tmp_path_factory.mktemp('listings')
-    jobs = []
-    flags = ['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-I' + os.path.join(ROOT, 'include'),
-             '-S', '--cuda-device-only']
-    for unit in ('mapf_lg_kernels', 'mapf_lg_rollout', 'mapf_transitions'):
-        jobs.append((unit, [], tmp_path / (unit + '.s')))
-    jobs.append(('mapf_lq_step', ['-mllvm', '-amdgpu-kernarg-preload-count=14'], tmp_path / 'mapf_lq_step.s'))   # (as the Makefile)
-    for k in (8, 4, 2):                                           # packed-layout rollout: one object per (K, RECORD)
-        for r in (1, 0):
-            jobs.append(('mapf_lq_rollout', ['-DMAPF_LQ_K=%d' % k, '-DMAPF_LQ_RECORD=%d' % r], tmp_path / ('mapf_lq_k%d_r%d.s' % (k, r))))
-    for g in range(4):
-        jobs.append(('mapf_kernels', ['-DMAPF_GROUP=%d' % g], tmp_path / ('mapf_kernels_g%d.s' % g)))
-    procs = [(out, subprocess.Popen(flags + extra + [os.path.join(CSRC, unit + '.hip'), '-o', str(out)],
-                                    stderr=subprocess.DEVNULL)) for unit, extra, out in jobs]
-    listings = {}
-    for out, proc in procs:
-        assert proc.wait() == 0, out
-        listings[out.name] = out.read_text()
-    return listings
+def device_listings():
+    """the gfx950 device listing (code + .amdgpu_metadata) of every kernel-holding compilation of the library, as the Makefile
+    compiles it: {name: text}"""
+    return device_listings_of.listings()
+
+
+def test_the_listed_compilations_are_the_makefiles_and_hold_every_kernel(device_listings):
+    """The tests' and tools' names are the Makefile's table (`make print-kernel-units`), and a translation unit outside that table
+    holds no kernel: a unit cannot enter the library without entering the gates below."""
+    table = subprocess.check_output(['make', '--no-print-directory', '-C', CSRC, 'print-kernel-units'], universal_newlines=True)
+    table = [line.split() for line in table.splitlines()]
+    assert [name for name, _ in table] == list(device_listings) == list(device_listings_of.units()) and len(table) == 20
+    assert sorted(device_listings) == sorted(KERNELS_PER_LISTING)
+    sources = {unit for _, unit in table}
+    others = sorted(f[:-4] for f in os.listdir(CSRC) if f.endswith('.hip') and f[:-4] not in sources)
+    assert others == ['mapf_capi', 'mapf_dispatch', 'mapf_plan', 'mapf_tables']
+    for unit, text in device_listings_of.listings(*others).items():
+        assert kernel_meta.kernels(text) == [] and '.amdhsa_kernel' not in text, unit
 
 
 def test_every_dispatchable_kernel_is_free_of_register_spills(device_listings):
     """No code object the launchers can reach may spill registers: a spilling thread-per-env rollout kernel is the
     one place a wrong result was ever observed on the GPU (compiler notes), and spills cost time.  Covers
-    the lane-group and packed-layout families, the transition kernels AND the thread-per-env family (mapf_kernels.hip,
-    compiled once per agent-count group like the Makefile does); of the latter's rollout kernels only those
-    launch_rollout_g* dispatches (A <= kTpeRolloutMaxAgents) are held to it -- the others are never launched."""
-    resources = {}
-    for text in device_listings.values():
-        resources.update(_kernel_resources(text))
-    assert len(resources) >= 200
+    every listing of the Makefile's table: the lane-group and packed-layout families with their limit and budget units, the
+    transition kernels AND the thread-per-env family (mapf_kernels.hip, one listing per agent-count group); of the latter's
+    rollout kernels only those launch_rollout_g* dispatches (A <= kTpeRolloutMaxAgents) are held to it -- the others are
+    never launched."""
     max_tpe_rollout = int(re.search(r'#define MAPF_TPE_ROLLOUT_MAX\s+(\d+)', open(os.path.join(CSRC, 'mapf_kernels.hpp')).read()).group(1))
-    checked = tpe_step = tpe_rollout = 0
-    for name, (sgpr, vgpr, scratch) in resources.items():
-        m = re.match(r'_ZN4mapf14rollout_kernelILi(\d+)E', name)
-        if m and int(m.group(1)) > max_tpe_rollout:
-            continue                                              # compiled, never dispatched
-        tpe_rollout += bool(m)
-        tpe_step += name.startswith('_ZN4mapf11step_kernelILi')
-        assert (sgpr, vgpr, scratch) == (0, 0, 0), (name, sgpr, vgpr, scratch)
-        checked += 1
-    assert tpe_step == 32 and tpe_rollout == max_tpe_rollout and checked >= 130
-
-
-def _kernel_metadata_blocks(asm_text):
-    """{kernel symbol: its block of the .amdgpu_metadata kernel list}"""
-    return {re.search(r'\.name:\s+(\S+)', block).group(1): block for block in asm_text.split('  - .agpr_count:')[1:]}
+    tpe_step = tpe_rollout = 0
+    for listing, text in device_listings.items():
+        kernels = kernel_meta.kernels(text)
+        assert len(kernels) == len({k['name'] for k in kernels}) == KERNELS_PER_LISTING[listing], (listing, len(kernels))
+        for k in kernels:
+            m = re.match(r'_ZN4mapf14rollout_kernelILi(\d+)E', k['name'])
+            if m and int(m.group(1)) > max_tpe_rollout:
+                continue                                          # compiled, never dispatched
+            tpe_rollout += bool(m)
+            tpe_step += k['name'].startswith('_ZN4mapf11step_kernelILi')
+            assert (k['sgpr_spill'], k['vgpr_spill'], k['scratch']) == (0, 0, 0), (listing, k['name'], k['sgpr_spill'], k['vgpr_spill'], k['scratch'])
+    assert tpe_step == 32 and tpe_rollout == max_tpe_rollout
 
 
 def test_packed_kernels_layout_assumptions_hold_in_the_compiled_objects(device_listings):
@@ -167,9 +165,8 @@ def test_packed_kernels_layout_assumptions_hold_in_the_compiled_objects(device_l
     src = open(os.path.join(CSRC, 'mapf_lq_step.hip')).read()
     m = re.search(r'constexpr uint32_t kStepArgsOffset = ([0-9 *+]+);', src)
     args_offset = eval(m.group(1))                                # "5 * 8 + 4 * 4": plain integer arithmetic
-    text = device_listings['mapf_lq_step.s']
-    blocks = _kernel_metadata_blocks(text)
-    step = {n: b for n, b in blocks.items() if 'lq_step_kernel' in n}
+    text = device_listings['mapf_lq_step']
+    step = {k['name']: k['block'] for k in kernel_meta.kernels(text) if 'lq_step_kernel' in k['name']}
     assert len(step) >= 60                                        # 9 plain (Q, K) x 4 + BIG forms
     n_big = 0
     for name, block in step.items():
@@ -190,11 +187,11 @@ def test_packed_kernels_layout_assumptions_hold_in_the_compiled_objects(device_l
     assert n_big >= 40                                            # 3 x 4 (eight agents per lane) + 4 x 4 (four) + 4 x 4 (delta rows) + 4 (delta rows + bitmaps)
     n_rollout = 0
     for listing, text in device_listings.items():
-        if not listing.startswith('mapf_lq_k'):
+        if not listing.startswith('mapf_lq_rollout_k'):
             continue
-        for name, block in _kernel_metadata_blocks(text).items():
-            if 'lq_rollout_kernel' in name:
-                assert int(re.search(r'\.group_segment_fixed_size:\s+(\d+)', block).group(1)) == 0, name
+        for k in kernel_meta.kernels(text):
+            if 'lq_rollout_kernel' in k['name']:
+                assert k['lds'] == 0, k['name']
                 n_rollout += 1
     assert n_rollout >= 100
     # ... and no trap instruction stands in for these checks in the shipped kernels any more

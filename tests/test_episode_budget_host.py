@@ -6,7 +6,6 @@ auto-reset, step and graph_begin under a budget -- is refused on the GPU in test
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -14,6 +13,13 @@ import pytest
 
 from conftest import ROOT
 from gym_mapf_amd import _native as nat
+
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+try:
+    import device_listings
+    import kernel_meta
+finally:
+    sys.path.pop(0)
 
 HEADER = os.path.join(ROOT, 'include', 'mapf_hip.h')
 CSRC = os.path.join(ROOT, 'gym-mapf_amd', 'csrc')
@@ -62,20 +68,12 @@ def test_the_limit_plans_are_what_they_were():
 
 
 @pytest.fixture(scope='module')
-def budget_listing(tmp_path_factory):
-    """the gfx950 device listing of the budget unit, with the Makefile's flags"""
-    out = tmp_path_factory.mktemp('listings') / 'mapf_lg_budget.s'
-    subprocess.check_call(['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-I' + os.path.join(ROOT, 'include'), '-S',
-                           '--cuda-device-only', os.path.join(CSRC, 'mapf_lg_budget.hip'), '-o', str(out)], stderr=subprocess.DEVNULL)
-    return out.read_text()
+def budget_listing():
+    """the gfx950 device listing of the budget unit, as the Makefile compiles it"""
+    return device_listings.listings('mapf_lg_budget')['mapf_lg_budget']
 
 
 def test_the_budget_unit_holds_its_declared_instances_free_of_spills_and_scratch(budget_listing):
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    try:
-        import kernel_meta
-    finally:
-        sys.path.pop(0)
     kernels = kernel_meta.kernels(budget_listing)
     rollout = [k for k in kernels if 'lg_rollout_kernel_budget_guarded' in k['name']]
     table = [k for k in kernels if 'lg_rollout_kernel_table_budget_guarded' in k['name']]

@@ -4,7 +4,6 @@ plan, and the limit instances of the lane-group kernels compile without register
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -14,8 +13,14 @@ from conftest import ROOT
 from gym_mapf_amd import _native as nat
 from test_cabi_and_host import ROLLOUT_PLAN_AGENTS, ROLLOUT_PLAN_CELLS, ROLLOUT_PLAN_ENVS, ROLLOUT_PLAN_TUNES
 
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+try:
+    import device_listings
+    import kernel_meta
+finally:
+    sys.path.pop(0)
+
 HEADER = os.path.join(ROOT, 'include', 'mapf_hip.h')
-CSRC = os.path.join(ROOT, 'gym-mapf_amd', 'csrc')
 NEW_SYMBOLS = ('mapf_set_episode_limit', 'mapf_episode_steps', 'mapf_step_limited', 'mapf_rollout_limited', 'mapf_debug_rollout_plan_limited')
 
 
@@ -82,20 +87,12 @@ def test_no_packed_plan_is_chosen_under_a_limit():
 
 
 @pytest.fixture(scope='module')
-def limit_listing(tmp_path_factory):
-    """the gfx950 device listing of the limit unit, with the Makefile's flags"""
-    out = tmp_path_factory.mktemp('listings') / 'mapf_lg_limit.s'
-    subprocess.check_call(['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-I' + os.path.join(ROOT, 'include'), '-S',
-                           '--cuda-device-only', os.path.join(CSRC, 'mapf_lg_limit.hip'), '-o', str(out)], stderr=subprocess.DEVNULL)
-    return out.read_text()
+def limit_listing():
+    """the gfx950 device listing of the limit unit, as the Makefile compiles it"""
+    return device_listings.listings('mapf_lg_limit')['mapf_lg_limit']
 
 
 def test_the_limit_instances_are_free_of_register_spills(limit_listing):
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    try:
-        import kernel_meta
-    finally:
-        sys.path.pop(0)
     kernels = kernel_meta.kernels(limit_listing)
     rollout = [k for k in kernels if 'lg_rollout_kernel_limit_guarded' in k['name']]
     table = [k for k in kernels if 'lg_rollout_kernel_table_limit_guarded' in k['name']]

@@ -3,7 +3,6 @@ the tuning key, the limited form of plan_rollout_lq_table over the case table of
 of the limit unit, and the outcomes the reference shows for every case.  No compute is launched here."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import pytest
@@ -16,7 +15,13 @@ from test_cabi_and_host import ROLLOUT_PLAN_CELLS
 from test_host_tables import shim  # noqa: F401  (the host shim, built once per run)
 from test_plan_decisions import TABLE_AGENTS, TABLE_BYTES, TABLE_ENVS, TABLE_TUNES
 
-CSRC = os.path.join(ROOT, 'gym-mapf_amd', 'csrc')
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+try:
+    import device_listings
+    import kernel_meta
+finally:
+    sys.path.pop(0)
+
 LDS = 160 * 1024
 
 
@@ -99,27 +104,14 @@ def test_whatever_is_planned_limited_is_a_table_instance_within_the_block_and_ld
 
 
 @pytest.fixture(scope='module')
-def limit_listings(tmp_path_factory):
-    """the four gfx950 device listings of mapf_lq_limit.hip, with the Makefile's flags (compiled side by side)"""
-    out_dir = tmp_path_factory.mktemp('listings')
-    jobs = {}
-    for K in (4, 2):
-        for record in (1, 0):
-            out = out_dir / ('mapf_lq_limit_k%d_r%d.s' % (K, record))
-            jobs[(K, record)] = (out, subprocess.Popen(
-                ['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-I' + os.path.join(ROOT, 'include'), '-DMAPF_LQ_K=%d' % K,
-                 '-DMAPF_LQ_RECORD=%d' % record, '-S', '--cuda-device-only', os.path.join(CSRC, 'mapf_lq_limit.hip'), '-o', str(out)], stderr=subprocess.DEVNULL))
-    for out, proc in jobs.values():
-        assert proc.wait() == 0, out
-    return {key: out.read_text() for key, (out, _) in jobs.items()}
+def limit_listings():
+    """the four gfx950 device listings of mapf_lq_limit.hip, as the Makefile compiles them (side by side): {(K, RECORD): text}"""
+    names = {(K, record): 'mapf_lq_limit_k%d_r%d' % (K, record) for K in (4, 2) for record in (1, 0)}
+    texts = device_listings.listings(*names.values())
+    return {key: texts[name] for key, name in names.items()}
 
 
 def test_the_limit_listings_hold_108_kernels_free_of_register_spills(limit_listings):
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    try:
-        import kernel_meta
-    finally:
-        sys.path.pop(0)
     total = 0
     for (K, record), text in limit_listings.items():
         kernels = kernel_meta.kernels(text)

@@ -1,14 +1,9 @@
 #!/usr/bin/env python3
 """Instruction histogram of one kernel group: python isa_stats.py <group> [substring ...]"""
-import subprocess, sys, collections, os
+import collections, re, sys
+import device_listings
 g = sys.argv[1]
-here = os.path.dirname(os.path.abspath(__file__))
-out = '/tmp/mapf_g%s.s' % g
-subprocess.check_call(['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off',
-                       '-I' + os.path.join(here, '..', '..', 'include'), '-DMAPF_GROUP=' + g, '-S', '--cuda-device-only',
-                       os.path.join(here, 'mapf_kernels.hip'), '-o', out], stderr=subprocess.DEVNULL)
-s = open(out).read()
-import re
+s = device_listings.listings('mapf_kernels_g' + g)['mapf_kernels_g' + g]
 for m in re.finditer(r'^(_ZN4mapf\w+):', s, re.M):
     name = m.group(1)
     if len(sys.argv) > 2 and not any(x in name for x in sys.argv[2:]):

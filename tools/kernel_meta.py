@@ -8,7 +8,8 @@ def kernels(text):
         name = re.search(r'\.name:\s+(\S+)', blk)
         f = lambda k: int(re.search(r'\.%s:\s+(\d+)' % k, blk).group(1))
         out.append(dict(name=name.group(1), sgpr=f('sgpr_count'), vgpr=f('vgpr_count'), sgpr_spill=f('sgpr_spill_count'),
-                        vgpr_spill=f('vgpr_spill_count'), scratch=f('private_segment_fixed_size'), lds=f('group_segment_fixed_size')))
+                        vgpr_spill=f('vgpr_spill_count'), scratch=f('private_segment_fixed_size'), lds=f('group_segment_fixed_size'),
+                        block=blk))                               # the kernel's whole metadata entry (its argument list, for one)
     return out
 
 if __name__ == '__main__':

@@ -14,13 +14,12 @@ launch's counted vector instructions with it.
 import json
 import os
 import re
-import subprocess
 import sys
-import tempfile
+
+import device_listings
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-CSRC = os.path.join(ROOT, 'gym-mapf_amd', 'csrc')
 # measured fast (profiles/r04_valu_issue_cost_forms.txt): bitwise logic, add / sub, right shifts and moves -- in the 32-bit or
 # the VOP3 encoding, with vector registers, inline constants or a literal -- and v_bitop3 on vector registers.  Measured
 # ordinary (1.5-1.65 x): LEFT shifts, v_min / v_max, compares, selects, multiplies, v_perm, v_alignbit, v_lshl_add / _or,
@@ -43,19 +42,8 @@ def classify(line):
     return 'ordinary'
 
 
-_LISTINGS = {}
-
-
-def mix_of(unit_flags, instance_re):
-    key = tuple(unit_flags)
-    if key not in _LISTINGS:                                     # one hipcc -S per translation unit, not per instance
-        with tempfile.TemporaryDirectory() as tmp:
-            out = os.path.join(tmp, 'k.s')
-            subprocess.check_call(['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off',
-                                   '-I' + os.path.join(ROOT, 'include'), '-S', '--cuda-device-only'] + unit_flags +
-                                  [os.path.join(CSRC, 'mapf_lq_rollout.hip'), '-o', out], stderr=subprocess.DEVNULL)
-            _LISTINGS[key] = open(out).read()
-    text = _LISTINGS[key]
+def mix_of(listing, instance_re):
+    text = device_listings.listings(listing)[listing]            # one compilation per translation unit, not per instance
     m = re.search(r'^(_ZN4mapf\S*lq_rollout_kernel' + instance_re + r'\S*):', text, re.M)
     body = text[m.end():text.index('.Lfunc_end', m.end())].split('\n')
     counts = {'fast': 0, 'ordinary': 0, 'wide': 0}
@@ -68,19 +56,19 @@ def mix_of(unit_flags, instance_re):
 
 def main():
     import bench
-    # (rocprofv3's spelling of the instance, -D flags of its translation unit, mangled template arguments)
+    # (rocprofv3's spelling of the instance, the listing of its compilation, mangled template arguments)
     instances = [
-        ('lq_rollout_kernel<2, 4, true, true, false, false, false, 0>', ['-DMAPF_LQ_K=4', '-DMAPF_LQ_RECORD=1'], 'ILi2ELi4ELb1ELb1ELb0ELb0ELb0ELi0E'),
-        ('lq_rollout_kernel<2, 4, true, false, false, false, false, 0>', ['-DMAPF_LQ_K=4', '-DMAPF_LQ_RECORD=1'], 'ILi2ELi4ELb1ELb0ELb0ELb0ELb0ELi0E'),   # ... with the in-kernel policy
-        ('lq_rollout_kernel<8, 4, true, true, false, true, false, 2>', ['-DMAPF_LQ_K=4', '-DMAPF_LQ_RECORD=1'], 'ILi8ELi4ELb1ELb1ELb0ELb1ELb0ELi2E'),
-        ('lq_rollout_kernel<8, 4, true, true, false, true, false, 1>', ['-DMAPF_LQ_K=4', '-DMAPF_LQ_RECORD=1'], 'ILi8ELi4ELb1ELb1ELb0ELb1ELb0ELi1E'),
-        ('lq_rollout_kernel<8, 4, true, true, false, true, false, 3>', ['-DMAPF_LQ_K=4', '-DMAPF_LQ_RECORD=1'], 'ILi8ELi4ELb1ELb1ELb0ELb1ELb0ELi3E'),
-        ('lq_rollout_kernel<4, 8, true, true, false, true, false, 0>', ['-DMAPF_LQ_K=8', '-DMAPF_LQ_RECORD=1'], 'ILi4ELi8ELb1ELb1ELb0ELb1ELb0ELi0E'),
-        ('lq_rollout_kernel<1, 8, true, true, false, false, false, 0>', ['-DMAPF_LQ_K=8', '-DMAPF_LQ_RECORD=1'], 'ILi1ELi8ELb1ELb1ELb0ELb0ELb0ELi0E'),
+        ('lq_rollout_kernel<2, 4, true, true, false, false, false, 0>', 'mapf_lq_rollout_k4_r1', 'ILi2ELi4ELb1ELb1ELb0ELb0ELb0ELi0E'),
+        ('lq_rollout_kernel<2, 4, true, false, false, false, false, 0>', 'mapf_lq_rollout_k4_r1', 'ILi2ELi4ELb1ELb0ELb0ELb0ELb0ELi0E'),   # ... with the in-kernel policy
+        ('lq_rollout_kernel<8, 4, true, true, false, true, false, 2>', 'mapf_lq_rollout_k4_r1', 'ILi8ELi4ELb1ELb1ELb0ELb1ELb0ELi2E'),
+        ('lq_rollout_kernel<8, 4, true, true, false, true, false, 1>', 'mapf_lq_rollout_k4_r1', 'ILi8ELi4ELb1ELb1ELb0ELb1ELb0ELi1E'),
+        ('lq_rollout_kernel<8, 4, true, true, false, true, false, 3>', 'mapf_lq_rollout_k4_r1', 'ILi8ELi4ELb1ELb1ELb0ELb1ELb0ELi3E'),
+        ('lq_rollout_kernel<4, 8, true, true, false, true, false, 0>', 'mapf_lq_rollout_k8_r1', 'ILi4ELi8ELb1ELb1ELb0ELb1ELb0ELi0E'),
+        ('lq_rollout_kernel<1, 8, true, true, false, false, false, 0>', 'mapf_lq_rollout_k8_r1', 'ILi1ELi8ELb1ELb1ELb0ELb0ELb0ELi0E'),
     ]
     doc = {'_how': ' '.join(__doc__.split('\n\n')[0].split()), 'csrc_hash': bench.csrc_hash(), 'instances': {}}
-    for name, flags, mangled in instances:
-        c = mix_of(flags, mangled)
+    for name, listing, mangled in instances:
+        c = mix_of(listing, mangled)
         n32 = c['fast'] + c['ordinary']
         doc['instances'][name] = dict(c, fast_share_of_32bit=c['fast'] / n32)
         print('%-70s fast %5d ordinary %5d wide %5d -> fast share of the 32-bit ones %.3f' % (name, c['fast'], c['ordinary'], c['wide'], c['fast'] / n32))
