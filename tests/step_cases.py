@@ -18,14 +18,12 @@ occur at least MIN_TIES times among the non-terminal envs of every pass.  No sma
 is the first of SEEDS_SEARCHED that does (`python tests/step_cases.py --search` prints the table below; a case whose shape no seed
 serves doubles its batch, keeping the form's divisibility rule).  Nothing is searched at test time."""
 import functools
-import os
 import sys
 from fractions import Fraction
 
 import numpy as np
 
 if __name__ == '__main__':
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import conftest  # noqa: F401  (the paths of the oracle and the package)
 
 import c_oracle
@@ -103,7 +101,7 @@ class Case:
         return [(scen, p) for scen in (True, False) for p in PASSES]
 
 
-# (form, K, Q, E, tune, (makespan seed, soc seed)): LQ_STEP_LAUNCHES of tests/test_plan_decisions.py, entry by entry (held against
+# (form, K, Q, E, tune, (makespan seed, soc seed)): LQ_STEP_LAUNCHES of tests/plan_sweeps.py, entry by entry (held against
 # it by tests/test_step_cases.py; no case had to double its batch).  Seeds: the search's output.
 INSTANCE_CASES = [Case(*row) for row in (
     (0, 4, 1, 512, '', (76, 52)), (0, 4, 2, 256, '', (39, 43)), (0, 4, 4, 128, '', (14, 26)), (0, 4, 8, 64, '', (14, 31)), (0, 4, 16, 64, '', (7, 3)),
@@ -319,12 +317,12 @@ def tie_outcomes(run, thresholds53):
 def _search():
     """prints, per distinct (shape, pass), the first seed of SEEDS_SEARCHED with MIN_TIES ties (the tables above hold the output)"""
     import tempfile
-    from test_host_tables import _slip_rows, build_shim, load_shim
+    from host_shim import build_shim, load_shim, slip_rows
     with tempfile.TemporaryDirectory() as tmp:
         shim = load_shim(build_shim(tmp))
         th16 = {}
         for p in PASSES:
-            rows = _slip_rows(shim, p.fail_prob)[0]
+            rows = slip_rows(shim, p.fail_prob)[0]
             th16[p.name] = sorted({int(row['th'][k]) for row in rows for k in range(int(row['n']) - 1)})
     seen = set()
     for case in CASES:

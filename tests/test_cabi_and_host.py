@@ -6,7 +6,6 @@ import functools
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,17 +14,12 @@ from conftest import ROOT
 from gym_mapf_amd import _native as nat
 from gym_mapf_amd.envs.grid import MapfGrid
 from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
-from test_host_tables import shim  # noqa: F401  (the host shim, built once per run)
-
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-try:
-    import device_listings as device_listings_of
-    import kernel_meta
-finally:
-    sys.path.pop(0)
+from host_shim import device_listings as device_listings_of
+from host_shim import CSRC, kernel_meta
+from host_shim import shim  # noqa: F401  (the host shim, built once per run)
+from plan_sweeps import ROLLOUT_PLAN_AGENTS, ROLLOUT_PLAN_CELLS, ROLLOUT_PLAN_ENVS, ROLLOUT_PLAN_TUNES
 
 HEADER = os.path.join(ROOT, 'include', 'mapf_hip.h')
-CSRC = os.path.join(ROOT, 'gym-mapf_amd', 'csrc')
 
 
 def _declared_functions():
@@ -197,15 +191,6 @@ def test_packed_kernels_layout_assumptions_hold_in_the_compiled_objects(device_l
     # ... and no trap instruction stands in for these checks in the shipped kernels any more
     for unit in ('mapf_lq_step.hip', 'mapf_lq_rollout.hip'):
         assert '__builtin_trap' not in open(os.path.join(CSRC, unit)).read(), unit
-
-
-# the sweep of plan_rollout_lq (tests/test_plan_decisions.py digests the same one, and more)
-ROLLOUT_PLAN_CELLS = sorted(set(list(range(2, 200, 7)) + list(range(600, 760, 3)) + list(range(800, 1800, 11)) + list(range(1650, 1720)) +
-                                list(range(3000, 3400, 5)) + list(range(4000, 20500, 61)) + list(range(19700, 20300, 3)) + [683, 3278, 4097, 65535]))
-ROLLOUT_PLAN_TUNES = [None, b'k=8', b'k=4', b'k=2', b'bitmap_block=1024', b'bitmap_block=512', b'bitmap_pairs=0', b'bitmap_delta=0',
-                      b'bitmap_staycol=0', b'mv_lds_max_bytes=163840', b'mv_lds_max_bytes=0', b'quad_min_lanes=0,oct_min_lanes=0']
-ROLLOUT_PLAN_AGENTS = (2, 4, 8, 16, 32, 64, 128)
-ROLLOUT_PLAN_ENVS = (64, 1000, 1024, 4096, 16384, 16448, 65536, 131072, 262144)
 
 
 def test_packed_rollout_dispatch_never_plans_past_the_lds_or_launch_bounds(shim):

@@ -6,23 +6,15 @@ auto-reset, step and graph_begin under a budget -- is refused on the GPU in test
 import ctypes
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
 from gym_mapf_amd import _native as nat
-
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-try:
-    import device_listings
-    import kernel_meta
-finally:
-    sys.path.pop(0)
+from host_shim import CSRC, device_listings, kernel_meta
 
 HEADER = os.path.join(ROOT, 'include', 'mapf_hip.h')
-CSRC = os.path.join(ROOT, 'gym-mapf_amd', 'csrc')
 NEW_SYMBOLS = ('mapf_set_episode_budget', 'mapf_episodes_left', 'mapf_rollout_budgeted')
 
 

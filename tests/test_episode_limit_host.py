@@ -4,21 +4,14 @@ plan, and the limit instances of the lane-group kernels compile without register
 import ctypes
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
 from gym_mapf_amd import _native as nat
-from test_cabi_and_host import ROLLOUT_PLAN_AGENTS, ROLLOUT_PLAN_CELLS, ROLLOUT_PLAN_ENVS, ROLLOUT_PLAN_TUNES
-
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-try:
-    import device_listings
-    import kernel_meta
-finally:
-    sys.path.pop(0)
+from host_shim import device_listings, kernel_meta
+from plan_sweeps import ROLLOUT_PLAN_AGENTS, ROLLOUT_PLAN_CELLS, ROLLOUT_PLAN_ENVS, ROLLOUT_PLAN_TUNES
 
 HEADER = os.path.join(ROOT, 'include', 'mapf_hip.h')
 NEW_SYMBOLS = ('mapf_set_episode_limit', 'mapf_episode_steps', 'mapf_step_limited', 'mapf_rollout_limited', 'mapf_debug_rollout_plan_limited')

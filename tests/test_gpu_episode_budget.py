@@ -12,14 +12,14 @@ import episode_limit_cases as ec
 from conftest import set_tune
 from gym_mapf_amd import _native as nat
 from gym_mapf_amd.envs import policies
-from test_gpu_episode_limit import SOURCE_TAG, _bits, _make, _np
+from parity_checks import SOURCE_TAG, make, raw_bytes, to_np
 
 pytestmark = pytest.mark.gpu
 
 
 def _budgeted(w, N, slip, B, criteria='Makespan', source='table', **kw):
     """a handle under the limit N (0: none) and the budget B, and its reference"""
-    env, lim = _make(w, N, slip, criteria, source, **kw)
+    env, lim = make(w, N, slip, criteria, source, **kw)
     env.set_episode_budget(B)
     assert env.episode_budget == B
     return env, bc.BudgetOracle(lim, B)
@@ -49,12 +49,12 @@ def _check(env, ref, res, refs, want, N, record, tag):
     assert sorted(res) == sorted(totals + recorded), (tag, sorted(res))
     for key in recorded:
         for t, r in enumerate(refs):
-            assert np.array_equal(_bits(res[key][t]), _bits(r[key])), (tag, key, t)
+            assert np.array_equal(raw_bytes(res[key][t]), raw_bytes(r[key])), (tag, key, t)
     for key in totals:
-        assert np.array_equal(_bits(res[key]), _bits(want[key])), (tag, key)
+        assert np.array_equal(raw_bytes(res[key]), raw_bytes(want[key])), (tag, key)
     local, ages, left = env.get_state()[0], env.episode_steps(), env.episodes_left()
     env.sync()
-    assert np.array_equal(_np(local), ref.co.state) and np.array_equal(_np(ages), ref.age) and np.array_equal(_np(left), ref.left), tag
+    assert np.array_equal(to_np(local), ref.co.state) and np.array_equal(to_np(ages), ref.age) and np.array_equal(to_np(left), ref.left), tag
     assert env.t == ref.co.t, tag
 
 
@@ -173,7 +173,7 @@ def test_kernel_names_with_and_without_a_budget(monkeypatch):
         _check(env, ref, res, refs, bc.totals_of(refs), 4, False, (tune, kw))
         env.set_episode_budget(None)
         assert env.episode_budget == 0
-        plain, lim = _make(w, 4, 0.2, 'Makespan', 'table', **kw)
+        plain, lim = make(w, 4, 0.2, 'Makespan', 'table', **kw)
         env.reset()
         env.set_state(t=0)
         a, b = env.rollout(6, record=True), plain.rollout(6, record=True)
@@ -181,14 +181,14 @@ def test_kernel_names_with_and_without_a_budget(monkeypatch):
         assert ('lq_rollout_kernel_table_limit' in env.last_kernel('rollout')) == bool(tune)
         assert sorted(a) == sorted(b) and 'live_steps' not in a
         for key in b:
-            assert np.array_equal(_bits(a[key]), _bits(b[key])), key
+            assert np.array_equal(raw_bytes(a[key]), raw_bytes(b[key])), key
         env.close()
         plain.close()
 
 
 def test_refusals_under_a_budget():
     w = ec.Workload(3, 37, 4)
-    env, _ = _make(w, 4, 0.2, 'Makespan', 'policy')
+    env, _ = make(w, 4, 0.2, 'Makespan', 'policy')
     lib, E = env._lib, w.E
     buf = np.zeros(E, np.uint32)
     io = nat.MapfRolloutIO(struct_size=ctypes.sizeof(nat.MapfRolloutIO), n_steps=1, step_flags=nat.MAPF_STEP_AUTO_RESET)
@@ -216,7 +216,7 @@ def test_refusals_under_a_budget():
         with pytest.raises(ValueError):
             env.set_episode_budget(bad)
     env.close()
-    dev, _ = _make(w, 4, 0.2, 'Makespan', 'policy', device_arrays=True)
+    dev, _ = make(w, 4, 0.2, 'Makespan', 'policy', device_arrays=True)
     dev.set_episode_budget(2)
     with pytest.raises(nat.MapfNativeError) as err:
         dev.graph_begin()
@@ -238,7 +238,7 @@ def test_refusals_under_a_budget():
 @pytest.mark.parametrize('device_arrays', [False, True])
 def test_policies_evaluate_against_the_oracle_run_to_all_parked(device_arrays):
     w = ec.Workload(8, 64, 4)
-    env, _ = _make(w, None, 0.2, 'Makespan', 'table', device_arrays=device_arrays)
+    env, _ = make(w, None, 0.2, 'Makespan', 'table', device_arrays=device_arrays)
     got = policies.evaluate(env, 3, 4, chunk=5)                             # ceil(12 / 5) = 3 launches of 5
     assert env.t == 15 and 'BUDGET' in env.last_kernel('rollout') and (env.episode_limit, env.episode_budget) == (4, 3)
     ref = bc.oracle(w, 4, 0.2, 3)
@@ -246,7 +246,7 @@ def test_policies_evaluate_against_the_oracle_run_to_all_parked(device_arrays):
     assert not ref.left.any()
     assert sorted(got) == ['collisions', 'goal_ends', 'live_steps', 'returns', 'truncations']
     for key in ('returns', 'collisions', 'truncations', 'live_steps'):
-        assert np.array_equal(_bits(got[key]), _bits(want[key])), key
+        assert np.array_equal(raw_bytes(got[key]), raw_bytes(want[key])), key
     assert np.array_equal(got['goal_ends'], want['episodes'] - want['collisions'])
     assert (got['goal_ends'] + got['collisions'] + got['truncations'] == 3).all()
     env.close()

@@ -8,41 +8,9 @@ import pytest
 import episode_limit_cases as ec
 from conftest import set_tune
 from gym_mapf_amd import _native as nat
-from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
+from parity_checks import RECORDED, SOURCE_TAG, TOTALS, check_handle, check_record, check_totals, make, raw_bytes
 
 pytestmark = pytest.mark.gpu
-CRIT = {'Makespan': OptimizationCriteria.Makespan, 'SoC': OptimizationCriteria.SoC}
-SOURCE_TAG = {'stream': 'STREAM', 'policy': 'POLICY', 'greedy': 'POLICY', 'table': 'TABLE'}
-RECORDED = ('local', 'reward', 'prob', 'done', 'collision', 'truncated')
-TOTALS = ('returns', 'episodes', 'collisions', 'truncations')
-
-
-def _bits(x):
-    return np.ascontiguousarray(_np(x)).view(np.uint8)
-
-
-def _np(x):
-    return x.cpu().numpy() if hasattr(x, 'cpu') else np.asarray(x)
-
-
-def _make(w, N, slip, criteria='Makespan', source='table', **kw):
-    """a handle and its reference over the workload, under the action source and the limit N (0 / None: no limit)"""
-    env = VecMapfEnv(w.grid, w.A, None, None, slip, *ec.INEXACT, CRIT[criteria], seed=ec.ORACLE_SEED, start_local=w.start, goal_local=w.goal, **kw)
-    if source == 'greedy':
-        env.set_policy('greedy')
-    elif source == 'table':
-        env.set_policy('table', table=w.table, rows=w.rows)
-    if N:
-        env.set_episode_limit(N)
-        assert env.episode_limit == N
-    return env, w.oracle(N or 0, slip, criteria, offset=kw.get('env_id_offset', 0))
-
-
-def _state(env):
-    local = env.get_state()[0]
-    ages = env.episode_steps()
-    env.sync()
-    return _np(local), _np(ages)
 
 
 def _rollout(env, ref, w, source, n, **kw):
@@ -59,27 +27,11 @@ def _rollout(env, ref, w, source, n, **kw):
     return res, (refs if refs is not None else ref.run(w, source, n))
 
 
-def _check_record(res, refs, tag):
-    for key in RECORDED:
-        for t, r in enumerate(refs):
-            assert np.array_equal(_bits(res[key][t]), _bits(r[key])), (tag, key, t)
-
-
-def _check_totals(res, want, tag):
-    for key in TOTALS:
-        assert np.array_equal(_bits(res[key]), _bits(want[key])), (tag, key)
-
-
-def _check_handle(env, ref, tag):
-    local, ages = _state(env)
-    assert np.array_equal(local, ref.co.state) and np.array_equal(ages, ref.age) and env.t == ref.co.t, tag
-
-
 def _run_pass(w, N, slip, criteria, source, expect=(), **kw):
     """The 36 steps as launches of 5 (recording), 1 (totals only), 18 (accumulated into the 1's totals) and 12 (recording), then the
     12 twice more into the same arrays (out=: in device mode the second reuses the cached argument block); returns the outcome
     counts of the 36."""
-    env, ref = _make(w, N, slip, criteria, source, **kw)
+    env, ref = make(w, N, slip, criteria, source, **kw)
     tag = (w.A, w.E, N, slip, criteria, source)
 
     def name(kind):
@@ -89,30 +41,30 @@ def _run_pass(w, N, slip, criteria, source, expect=(), **kw):
     res, refs5 = _rollout(env, ref, w, source, 5, record=True)
     name('RECORD')
     assert sorted(res) == sorted(RECORDED + TOTALS)
-    _check_record(res, refs5, tag)
-    _check_totals(res, ec.totals_of(refs5), tag)
-    _check_handle(env, ref, tag)
+    check_record(res, refs5, tag)
+    check_totals(res, ec.totals_of(refs5), tag)
+    check_handle(env, ref, tag)
     res, refs1 = _rollout(env, ref, w, source, 1)
     name('TOTALS')
     assert sorted(res) == sorted(TOTALS)
     base = ec.totals_of(refs1)
-    _check_totals(res, base, tag)
+    check_totals(res, base, tag)
     res, refs18 = _rollout(env, ref, w, source, 18, accumulate_into=res)
-    _check_totals(res, ec.totals_of(refs18, base), tag)
-    _check_handle(env, ref, tag)
+    check_totals(res, ec.totals_of(refs18, base), tag)
+    check_handle(env, ref, tag)
     out, refs12 = _rollout(env, ref, w, source, 12, record=True)
-    _check_record(out, refs12, tag)
-    _check_totals(out, ec.totals_of(refs12), tag)
-    _check_handle(env, ref, tag)
+    check_record(out, refs12, tag)
+    check_totals(out, ec.totals_of(refs12), tag)
+    check_handle(env, ref, tag)
     for again in range(2):
         got, more = _rollout(env, ref, w, source, 12, record=True, out=out)
         assert got is out
         name('RECORD')
-        _check_record(out, more, (tag, 'out=', again))
-        _check_totals(out, ec.totals_of(more), (tag, 'out=', again))
+        check_record(out, more, (tag, 'out=', again))
+        check_totals(out, ec.totals_of(more), (tag, 'out=', again))
         if env.device_arrays and source != 'stream':
             assert env._rollout_io is not None
-    _check_handle(env, ref, tag)
+    check_handle(env, ref, tag)
     env.close()
     return ec.outcome_counts(refs5 + refs1 + refs18 + refs12)
 
@@ -156,7 +108,7 @@ def test_single_steps_with_device_philox_and_caller_uniforms(A, E):
     rs = np.random.RandomState(A * 1000 + E)
     for ext in (False, True):
         for auto_reset in (True, False):
-            env, ref = _make(w, 4, 0.2, source='stream')
+            env, ref = make(w, 4, 0.2, source='stream')
             truncs = 0
             for t in range(12):
                 actions = w.actions('stream', ref)
@@ -167,8 +119,8 @@ def test_single_steps_with_device_philox_and_caller_uniforms(A, E):
                 assert 'LIMIT' in name and ('EXT_UNIFORMS' if ext else 'PHILOX') in name, name
                 assert sorted(got) == sorted(RECORDED + ('was_terminal',))
                 for key in RECORDED + ('was_terminal',):
-                    assert np.array_equal(_bits(got[key]), _bits(want[key])), (A, E, ext, auto_reset, t, key)
-                _check_handle(env, ref, (A, E, ext, auto_reset, t))
+                    assert np.array_equal(raw_bytes(got[key]), raw_bytes(want[key])), (A, E, ext, auto_reset, t, key)
+                check_handle(env, ref, (A, E, ext, auto_reset, t))
                 truncs += int(want['truncated'].sum())
             assert truncs > 0
             env.close()
@@ -177,7 +129,7 @@ def test_single_steps_with_device_philox_and_caller_uniforms(A, E):
 @pytest.mark.parametrize('A,E', [(2, 37), (3, 64), (8, 37), (32, 64)])
 def test_without_auto_reset_truncated_repeats_until_a_reset_and_reset_zeroes_the_masked_ages(A, E):
     w = ec.Workload(A, E, 3)
-    env, ref = _make(w, 3, 0.2, source='stream')
+    env, ref = make(w, 3, 0.2, source='stream')
     seen, repeats = np.zeros(E, bool), 0
     for t in range(8):
         actions = w.actions('stream', ref)
@@ -193,16 +145,16 @@ def test_without_auto_reset_truncated_repeats_until_a_reset_and_reset_zeroes_the
     refs = ref.run(w, 'stream', 4, auto_reset=False)
     res = env.rollout(4, actions=np.stack([r['actions'] for r in refs]).astype(np.uint8), auto_reset=False, record=True)
     assert 'LIMIT' in env.last_kernel('rollout')
-    _check_record(res, refs, 'no auto-reset')
-    _check_totals(res, ec.totals_of(refs), 'no auto-reset')
-    _check_handle(env, ref, 'no auto-reset')
+    check_record(res, refs, 'no auto-reset')
+    check_totals(res, ec.totals_of(refs), 'no auto-reset')
+    check_handle(env, ref, 'no auto-reset')
     ages = env.episode_steps()
     mask = (np.arange(E) % 3 == 0).astype(np.uint8)
     env.reset(mask)
     after = env.episode_steps()
     assert not after[mask != 0].any() and np.array_equal(after[mask == 0], ages[mask == 0]) and ages[mask != 0].any()
     ref.reset(mask)
-    _check_handle(env, ref, 'reset(mask)')
+    check_handle(env, ref, 'reset(mask)')
     env.reset()
     assert not env.episode_steps().any()
     env.close()
@@ -213,8 +165,8 @@ def test_a_limit_never_reached_changes_nothing(A, E):
     """N = 2^31 against a handle without a limit under default dispatch (which may be a packed or a thread-per-env kernel)"""
     w = ec.Workload(A, E, 4)
     for source in ec.SOURCES:
-        limited, _ = _make(w, 1 << 31, 0.2, source=source)
-        plain, ref = _make(w, None, 0.2, source=source)
+        limited, _ = make(w, 1 << 31, 0.2, source=source)
+        plain, ref = make(w, None, 0.2, source=source)
         actions = None
         if source == 'stream':
             actions = np.stack([r['actions'] for r in ref.run(w, source, ec.T_TOTAL)]).astype(np.uint8)
@@ -223,7 +175,7 @@ def test_a_limit_never_reached_changes_nothing(A, E):
         assert 'LIMIT' in limited.last_kernel('rollout') and 'LIMIT' not in plain.last_kernel('rollout')
         assert sorted(b) == sorted(k for k in RECORDED + TOTALS if not k.startswith('trunc'))      # exactly today's keys
         for key in b:
-            assert np.array_equal(_bits(a[key]), _bits(b[key])), (A, E, source, key)
+            assert np.array_equal(raw_bytes(a[key]), raw_bytes(b[key])), (A, E, source, key)
         assert not a['truncations'].any() and not a['truncated'].any()
         assert np.array_equal(limited.get_state()[0], plain.get_state()[0]) and limited.t == plain.t
         assert not plain.episode_steps().any()
@@ -234,41 +186,41 @@ def test_a_limit_never_reached_changes_nothing(A, E):
 def test_mixed_calls_against_the_reference():
     """rollout, step, set_state(t=...), set_episode_limit (zeroes the ages), rollout, set_state(cells) (zeroes them too), rollout"""
     w = ec.Workload(8, 64, 4)
-    env, ref = _make(w, 4, 0.2, source='table')
+    env, ref = make(w, 4, 0.2, source='table')
     res, refs = _rollout(env, ref, w, 'table', 7, record=True)
-    _check_record(res, refs, 'first')
+    check_record(res, refs, 'first')
     for t in range(3):
         actions = w.actions('table', ref)
         got = _step_outputs(*env.step(actions, auto_reset=True))
         want = ref.step(actions, auto_reset=True)
         for key in RECORDED:
-            assert np.array_equal(_bits(got[key]), _bits(want[key])), (t, key)
+            assert np.array_equal(raw_bytes(got[key]), raw_bytes(want[key])), (t, key)
     assert ref.age.any()
-    _check_handle(env, ref, 'steps')
+    check_handle(env, ref, 'steps')
     env.set_state(t=1000)                                         # only t: the ages stay
     ref.co.t = 1000
-    _check_handle(env, ref, 'set_state(t)')
+    check_handle(env, ref, 'set_state(t)')
     res, refs = _rollout(env, ref, w, 'table', 3, record=True)
-    _check_record(res, refs, 'after set_state(t)')
+    check_record(res, refs, 'after set_state(t)')
     env.set_episode_limit(2)
     ref.set_limit(2)
-    _check_handle(env, ref, 'set_episode_limit')
+    check_handle(env, ref, 'set_episode_limit')
     res, refs = _rollout(env, ref, w, 'table', 9, record=True)
-    _check_record(res, refs, 'second limit')
-    _check_totals(res, ec.totals_of(refs), 'second limit')
+    check_record(res, refs, 'second limit')
+    check_totals(res, ec.totals_of(refs), 'second limit')
     cells = np.ascontiguousarray(ref.co.state[::-1])
     env.set_state(cells)                                          # cells: new episodes
     ref.co.state[:] = cells
     ref.age[:] = 0
-    _check_handle(env, ref, 'set_state(cells)')
+    check_handle(env, ref, 'set_state(cells)')
     res, refs = _rollout(env, ref, w, 'table', 6, record=True)
-    _check_record(res, refs, 'after set_state(cells)')
+    check_record(res, refs, 'after set_state(cells)')
     ages = np.arange(64, dtype=np.uint32) % 3
     assert np.array_equal(env.episode_steps(set=ages), ref.age)  # (returns the ages before the set)
     ref.age = ages.copy()
     res, refs = _rollout(env, ref, w, 'table', 5, record=True)
-    _check_record(res, refs, 'after episode_steps(set=)')
-    _check_handle(env, ref, 'end')
+    check_record(res, refs, 'after episode_steps(set=)')
+    check_handle(env, ref, 'end')
     env.set_episode_limit(None)                                   # off: today's keys, today's kernels
     out = env.rollout(4, record=True)
     assert 'LIMIT' not in env.last_kernel('rollout') and 'truncations' not in out and 'truncated' not in out
@@ -282,7 +234,7 @@ def test_device_arrays_with_env_ids_beyond_32_bits():
         counts = _run_pass(w, 4, 0.2, 'Makespan', source, device_arrays=True, env_id_offset=(1 << 32) + 5)
         assert counts[2] > 0
     # a handle with a limit is not recorded into a graph, and the limit is not changed under live graphs
-    env, _ = _make(w, 4, 0.2, source='table', device_arrays=True)
+    env, _ = make(w, 4, 0.2, source='table', device_arrays=True)
     with pytest.raises(nat.MapfNativeError) as err:
         env.graph_begin()
     assert err.value.code == nat.MAPF_EUNSUPPORTED
@@ -302,7 +254,7 @@ def test_device_arrays_with_env_ids_beyond_32_bits():
 def test_the_c_abi_refuses_truncation_outputs_without_a_limit():
     import ctypes
     w = ec.Workload(3, 37, 4)
-    env, _ = _make(w, None, 0.2, source='policy')
+    env, _ = make(w, None, 0.2, source='policy')
     lib, E = env._lib, w.E
     buf = np.zeros(E, np.uint32)
     io = nat.MapfRolloutIO(struct_size=ctypes.sizeof(nat.MapfRolloutIO), n_steps=1)

@@ -9,7 +9,7 @@ import pytest
 import episode_limit_cases as ec
 import limit_packed_cases as lp
 from conftest import set_tune
-from test_gpu_episode_limit import RECORDED, TOTALS, _bits, _check_handle, _check_record, _check_totals, _make
+from parity_checks import RECORDED, TOTALS, check_handle, check_record, check_totals, make, raw_bytes
 
 pytestmark = pytest.mark.gpu
 LG_LIMIT = ('lg_rollout_kernel', '_limit_guarded<', ',LIMIT>')      # what a lane-group limit instance's name holds
@@ -35,7 +35,7 @@ def _run_pass(w, N, slip, criteria, expect, source='table', auto_reset=True, age
     """The launch pattern of tests/test_gpu_episode_limit.py's _run_pass: the 36 steps as launches of 5 (recording), 1 (totals only), 18
     (accumulated into the 1's totals) and 12 (recording), then the 12 twice more into the same arrays (out=); everything compared
     after every launch, every kernel name holding all of `expect` and none of `absent`.  Returns the reference steps of the first 36."""
-    env, ref = _make(w, N, slip, criteria, source, **kw)
+    env, ref = make(w, N, slip, criteria, source, **kw)
     if ages is not None:
         env.episode_steps(set=ages)
         ref.age = ages.copy()
@@ -47,31 +47,31 @@ def _run_pass(w, N, slip, criteria, expect, source='table', auto_reset=True, age
     res, refs5, got = _launch(env, ref, w, 5, source, auto_reset, record=True)
     named(got, 'RECORD')
     assert sorted(res) == sorted(RECORDED + TOTALS)
-    _check_record(res, refs5, tag)
-    _check_totals(res, ec.totals_of(refs5), tag)
-    _check_handle(env, ref, tag)
+    check_record(res, refs5, tag)
+    check_totals(res, ec.totals_of(refs5), tag)
+    check_handle(env, ref, tag)
     res, refs1, got = _launch(env, ref, w, 1, source, auto_reset)
     named(got, 'TOTALS')
     assert sorted(res) == sorted(TOTALS)
     base = ec.totals_of(refs1)
-    _check_totals(res, base, tag)
-    _check_handle(env, ref, tag)
+    check_totals(res, base, tag)
+    check_handle(env, ref, tag)
     res, refs18, got = _launch(env, ref, w, 18, source, auto_reset, accumulate_into=res)
     named(got, 'TOTALS')
-    _check_totals(res, ec.totals_of(refs18, base), tag)
-    _check_handle(env, ref, tag)
+    check_totals(res, ec.totals_of(refs18, base), tag)
+    check_handle(env, ref, tag)
     out, refs12, got = _launch(env, ref, w, 12, source, auto_reset, record=True)
     named(got, 'RECORD')
-    _check_record(out, refs12, tag)
-    _check_totals(out, ec.totals_of(refs12), tag)
-    _check_handle(env, ref, tag)
+    check_record(out, refs12, tag)
+    check_totals(out, ec.totals_of(refs12), tag)
+    check_handle(env, ref, tag)
     for again in range(2):
         res, more, got = _launch(env, ref, w, 12, source, auto_reset, record=True, out=out)
         assert res is out
         named(got, 'RECORD')
-        _check_record(out, more, (tag, 'out=', again))
-        _check_totals(out, ec.totals_of(more), (tag, 'out=', again))
-        _check_handle(env, ref, (tag, 'out=', again))
+        check_record(out, more, (tag, 'out=', again))
+        check_totals(out, ec.totals_of(more), (tag, 'out=', again))
+        check_handle(env, ref, (tag, 'out=', again))
     env.close()
     return refs5 + refs1 + refs18 + refs12
 
@@ -125,8 +125,8 @@ def test_a_limit_never_reached_changes_nothing(monkeypatch, case):
     _tune(monkeypatch, case)
     w = lp.workload(case.A, case.E, 4)
     for criteria in ('Makespan', 'SoC'):
-        limited, _ = _make(w, 1 << 31, 0.2, criteria)
-        plain, _ = _make(w, None, 0.2, criteria)
+        limited, _ = make(w, 1 << 31, 0.2, criteria)
+        plain, _ = make(w, None, 0.2, criteria)
         for record in (True, False):
             a = limited.rollout(ec.T_TOTAL, record=record)
             b = plain.rollout(ec.T_TOTAL, record=record)
@@ -138,7 +138,7 @@ def test_a_limit_never_reached_changes_nothing(monkeypatch, case):
             assert ('; episode step limit' in note or len(name) == 159) and base.split(' (', 1)[1].startswith(note.split('; episode step limit')[0][:40]), (name, base)
             assert name != base and sorted(b) == sorted(k for k in (RECORDED if record else ()) + TOTALS if not k.startswith('trunc'))
             for key in b:
-                assert np.array_equal(_bits(a[key]), _bits(b[key])), (case.id, criteria, record, key)
+                assert np.array_equal(raw_bytes(a[key]), raw_bytes(b[key])), (case.id, criteria, record, key)
             assert not a['truncations'].any() and not (record and a['truncated'].any())
             assert np.array_equal(limited.get_state()[0], plain.get_state()[0]) and limited.t == plain.t
         assert not plain.episode_steps().any()
@@ -195,7 +195,7 @@ def test_without_a_limit_the_key_changes_no_launch(monkeypatch):
     names = []
     for value in (0, 1):
         set_tune(monkeypatch, k=2, limit_packed=value)
-        env, _ = _make(w, None, 0.2)
+        env, _ = make(w, None, 0.2)
         env.rollout(4)
         names.append(env.last_kernel('rollout'))
         env.close()

@@ -11,29 +11,20 @@ from conftest import set_tune, load_json
 from gym_mapf_amd import _native as nat
 from gym_mapf_amd.envs.grid import MapfGrid
 from gym_mapf_amd.envs.vec_env import STEP_OUTPUTS, OptimizationCriteria, VecMapfEnv
+from host_shim import shim  # noqa: F401  (the host shim: the planner's names)
+from parity_checks import CRIT, EXACT, INEXACT, bits, check_compact_against_reserved
+from plan_sweeps import declare, planned
 from totals_cases import _assert_a_wrong_rounding_would_show, _goal_scenario_tables   # (shared with the totals-only sweep)
-from test_host_tables import shim  # noqa: F401  (the host shim: the planner's names)
-from test_transitions_plan import declare, planned
+from wide_counter_cases import GOAL_ROWS
 
 pytestmark = pytest.mark.gpu
 KERNELS = ('thread_per_env', 'lane_group')
-# reward constants (clash, goal, living): EXACT -- every product n * living and every sum of rewards is exact in float64, in
-# any order; INEXACT -- they round: fl(fl(n * living) + goal) differs from the correctly rounded n * living + goal at
-# n = 3, 5, 6, 7, 9, 10, 12, 15, 20, 23..26, 28, 30, 31 (the same with clash), n-fold addition of living differs from n * living
-# from n = 6 on, ten left-to-right additions of -0.1 give -0.9999999999999999: a fused multiply-add, a repeated add, a
-# reordered or re-associated sum each change bits (tests/golden/inexact_* were recorded from the reference with such constants)
-EXACT, INEXACT = (-1000.0, 100.0, -1.0), (-0.3, 0.7, -0.1)
 
 
 def _families(n_agents):
     """Kernel families that exist for this agent count (thread-per-env is specialised for A <= 16)."""
     return [k for k in KERNELS if k == 'lane_group' or n_agents <= 16]
-CRIT = {'Makespan': OptimizationCriteria.Makespan, 'SoC': OptimizationCriteria.SoC}
 OCRIT = {'Makespan': mo.MAKESPAN, 'SoC': mo.SOC}
-
-
-def _bits(x):
-    return np.asarray(x, np.float64).view(np.uint64)
 
 
 def _vec(meta, g, sel, env_id_offset=0, **kw):
@@ -44,8 +35,8 @@ def _vec(meta, g, sel, env_id_offset=0, **kw):
 
 def _check_step(local, reward, done, info, g, t, sel, tag):
     assert np.array_equal(local, g['next_local'][t][sel]), tag
-    assert np.array_equal(_bits(reward), _bits(g['reward'][t][sel])), tag
-    assert np.array_equal(_bits(info['prob']), _bits(g['prob'][t][sel])), tag
+    assert np.array_equal(bits(reward), bits(g['reward'][t][sel])), tag
+    assert np.array_equal(bits(info['prob']), bits(g['prob'][t][sel])), tag
     assert np.array_equal(done, g['done'][t][sel]), tag
     assert np.array_equal(info['collision'], g['collision'][t][sel]), tag
     assert np.array_equal(info['was_terminal'], g['was_terminal'][t][sel]), tag
@@ -102,14 +93,14 @@ def test_fused_rollout_matches_reference(trajectory_set):
             env = _vec(meta, g, sel, env_id_offset=int(g['env_ids'][lo]), kernel=kernel)
             res = env.rollout(T, actions=actions, auto_reset=meta['auto_reset'], record=True)
             assert np.array_equal(res['local'], g['next_local'][:, sel])
-            assert np.array_equal(_bits(res['reward']), _bits(g['reward'][:, sel]))
-            assert np.array_equal(_bits(res['prob']), _bits(g['prob'][:, sel]))
+            assert np.array_equal(bits(res['reward']), bits(g['reward'][:, sel]))
+            assert np.array_equal(bits(res['prob']), bits(g['prob'][:, sel]))
             assert np.array_equal(res['done'], g['done'][:, sel])
             assert np.array_equal(res['collision'], g['collision'][:, sel])
             ret = np.zeros(hi - lo)
             for t in range(T):
                 ret = ret + g['reward'][t, sel]          # same left-to-right float64 sum
-            assert np.array_equal(_bits(res['returns']), _bits(ret))
+            assert np.array_equal(bits(res['returns']), bits(ret))
             assert np.array_equal(res['episodes'], g['done'][:, sel].sum(0))
             assert np.array_equal(res['collisions'], g['collision'][:, sel].sum(0))
             # state after the rollout == state a step-by-step run leaves behind
@@ -133,7 +124,7 @@ def test_rollout_split_equals_single_and_accumulates(trajectory_set):
     part = two.rollout(T - T // 3, auto_reset=True, accumulate_into=part)
     st_two, t_two = two.get_state()
     assert t_two == T and np.array_equal(st_full, st_two)
-    assert np.array_equal(_bits(full['returns']), _bits(part['returns']))
+    assert np.array_equal(bits(full['returns']), bits(part['returns']))
     assert np.array_equal(full['episodes'], part['episodes']) and np.array_equal(full['collisions'], part['collisions'])
     one.close(), two.close()
 
@@ -155,8 +146,8 @@ def test_rollout_out_reuses_an_earlier_calls_arrays(trajectory_set):
     b.rollout(T, auto_reset=auto, record=True)
     fresh = b.rollout(T, auto_reset=auto, record=True)
     for k in fresh:
-        assert np.array_equal(_bits(again[k]) if again[k].dtype == np.float64 else again[k],
-                              _bits(fresh[k]) if fresh[k].dtype == np.float64 else fresh[k]), k
+        assert np.array_equal(bits(again[k]) if again[k].dtype == np.float64 else again[k],
+                              bits(fresh[k]) if fresh[k].dtype == np.float64 else fresh[k]), k
     assert any(not np.array_equal(keep[k], again[k]) for k in ('local', 'returns'))
     with pytest.raises(ValueError):
         a.rollout(T, auto_reset=auto, out=first, accumulate_into=first)
@@ -237,7 +228,7 @@ def test_scripted_edge_cases_match_reference():
                                                  uniforms=np.asarray([st['uniforms']]))
             tag = '%s step %d' % (case['name'], k)
             assert local[0].tolist() == st['next_local'], tag
-            assert _bits(reward[0]) == _bits(st['reward']) and _bits(info['prob'][0]) == _bits(st['prob']), tag
+            assert bits(reward[0]) == bits(st['reward']) and bits(info['prob'][0]) == bits(st['prob']), tag
             assert bool(done[0]) == st['done'], tag
             was_term = bool(info['was_terminal'][0])
             assert (None if was_term else bool(info['collision'][0])) == st['collision'], tag
@@ -299,12 +290,12 @@ def test_every_agent_count_against_c_oracle(n_agents, kernel):
             local, reward, done, info = env.step(acts, auto_reset=auto)
             ref = co.step(acts, auto_reset=auto)
             assert np.array_equal(local, ref['local']), (A, t)
-            assert np.array_equal(_bits(reward), _bits(ref['reward'])) and np.array_equal(_bits(info['prob']), _bits(ref['prob']))
+            assert np.array_equal(bits(reward), bits(ref['reward'])) and np.array_equal(bits(info['prob']), bits(ref['prob']))
             assert np.array_equal(done, ref['done']) and np.array_equal(info['collision'], ref['collision'])
             assert np.array_equal(info['was_terminal'], ref['was_terminal'])
         res = env.rollout(25, auto_reset=auto)
         ref = co.rollout(25, auto_reset=auto)
-        assert np.array_equal(_bits(res['returns']), _bits(ref['returns']))
+        assert np.array_equal(bits(res['returns']), bits(ref['returns']))
         assert np.array_equal(res['episodes'], ref['episodes']) and np.array_equal(res['collisions'], ref['collisions'])
         assert np.array_equal(env.get_state()[0], co.state)
         env.close()
@@ -341,12 +332,12 @@ def test_results_do_not_depend_on_how_envs_are_sharded():
         for k, p in enumerate(parts):
             sl = slice(200 * k, 200 * k + 200)
             lp, rp, dp, ip = p.step(acts[t][sl], auto_reset=True)
-            assert np.array_equal(lp, l[sl]) and np.array_equal(_bits(rp), _bits(r[sl])) and np.array_equal(dp, d[sl])
-            assert np.array_equal(_bits(ip['prob']), _bits(info['prob'][sl]))
+            assert np.array_equal(lp, l[sl]) and np.array_equal(bits(rp), bits(r[sl])) and np.array_equal(dp, d[sl])
+            assert np.array_equal(bits(ip['prob']), bits(info['prob'][sl]))
     full = whole.rollout(40)
     for k, p in enumerate(parts):
         sl = slice(200 * k, 200 * k + 200)
-        assert np.array_equal(_bits(p.rollout(40)['returns']), _bits(full['returns'][sl]))
+        assert np.array_equal(bits(p.rollout(40)['returns']), bits(full['returns'][sl]))
     whole.close()
     [p.close() for p in parts]
 
@@ -393,11 +384,11 @@ def test_recorded_rollout_of_full_groups_against_c_oracle(n_agents, n_envs):
         for t in range(T):
             ref = co.step(acts[t], auto_reset=auto)
             assert np.array_equal(res['local'][t], ref['local']), (A, t)
-            assert np.array_equal(_bits(res['reward'][t]), _bits(ref['reward'])), (A, t)
-            assert np.array_equal(_bits(res['prob'][t]), _bits(ref['prob'])), (A, t)
+            assert np.array_equal(bits(res['reward'][t]), bits(ref['reward'])), (A, t)
+            assert np.array_equal(bits(res['prob'][t]), bits(ref['prob'])), (A, t)
             assert np.array_equal(res['done'][t], ref['done']) and np.array_equal(res['collision'][t], ref['collision'])
             ret = ret + ref['reward']
-        assert np.array_equal(_bits(res['returns']), _bits(ret))
+        assert np.array_equal(bits(res['returns']), bits(ret))
         assert np.array_equal(env.get_state()[0], co.state)
         env.close()
 
@@ -441,14 +432,14 @@ def test_dense_rollout_split_launches_accumulate_and_single_steps(n_agents, n_en
     acc = parts.rollout(1, auto_reset=True)
     acc = parts.rollout(4, auto_reset=True, accumulate_into=acc)
     acc = parts.rollout(7, auto_reset=True, accumulate_into=acc)
-    assert np.array_equal(_bits(full['returns']), _bits(acc['returns']))
+    assert np.array_equal(bits(full['returns']), bits(acc['returns']))
     assert np.array_equal(full['episodes'], acc['episodes']) and np.array_equal(full['collisions'], acc['collisions'])
     (s1, t1), (s2, t2) = one.get_state(), parts.get_state()
     assert t1 == t2 == 15 and np.array_equal(s1, s2)
     co = c_oracle.COracle(nbr, A, start, goal, 0.25, *rewards, mo.MAKESPAN, seed=3)
     co.t = 3
     ref = co.rollout(12, auto_reset=True)
-    assert np.array_equal(_bits(full['returns']), _bits(ref['returns'])) and np.array_equal(s1, co.state)
+    assert np.array_equal(bits(full['returns']), bits(ref['returns'])) and np.array_equal(s1, co.state)
     one.close(), parts.close()
 
 
@@ -497,7 +488,7 @@ def test_recorded_launches_of_every_length_and_phase(n_agents, n_envs, k, stream
         for j in range(n):
             ref = co.step(acts[j], auto_reset=True)
             assert np.array_equal(res['local'][j], ref['local']), (n, t, j)
-            assert np.array_equal(_bits(res['reward'][j]), _bits(ref['reward'])) and np.array_equal(_bits(res['prob'][j]), _bits(ref['prob'])), (n, t, j)
+            assert np.array_equal(bits(res['reward'][j]), bits(ref['reward'])) and np.array_equal(bits(res['prob'][j]), bits(ref['prob'])), (n, t, j)
             assert np.array_equal(res['done'][j], ref['done']) and np.array_equal(res['collision'][j], ref['collision']), (n, t, j)
         t += n
     assert np.array_equal(env.get_state()[0], co.state) and env.get_state()[1] == t
@@ -527,7 +518,7 @@ def test_greedy_policy_rollout_against_c_oracle(n_agents, n_envs, kernel):
     for t in range(T):
         ref = co.step(co.greedy_actions(rc), auto_reset=True)
         assert np.array_equal(res['local'][t], ref['local']), (A, t)
-        assert np.array_equal(_bits(res['reward'][t]), _bits(ref['reward'])) and np.array_equal(_bits(res['prob'][t]), _bits(ref['prob']))
+        assert np.array_equal(bits(res['reward'][t]), bits(ref['reward'])) and np.array_equal(bits(res['prob'][t]), bits(ref['prob']))
         assert np.array_equal(res['done'][t], ref['done']) and np.array_equal(res['collision'][t], ref['collision'])
         goals_reached += int((ref['done'] & ~ref['collision']).sum())
     assert np.array_equal(env.get_state()[0], co.state)
@@ -535,7 +526,7 @@ def test_greedy_policy_rollout_against_c_oracle(n_agents, n_envs, kernel):
     env.set_policy('random')
     ref = co.rollout(6, auto_reset=True)
     out = env.rollout(6, auto_reset=True)
-    assert np.array_equal(_bits(out['returns']), _bits(ref['returns'])) and np.array_equal(env.get_state()[0], co.state)
+    assert np.array_equal(bits(out['returns']), bits(ref['returns'])) and np.array_equal(env.get_state()[0], co.state)
     env.close()
 
 
@@ -584,7 +575,7 @@ def _goal_reaching_episodes(n_agents, n_envs, layout, env_vars, monkeypatch, rew
             ret = np.zeros(E)
             for t in range(T):
                 ret = ret + refs[t]['reward']                      # the reference's order: left to right, from zero
-            assert np.array_equal(_bits(res['returns']), _bits(ret)), (A, E, mode, fail_prob)
+            assert np.array_equal(bits(res['returns']), bits(ret)), (A, E, mode, fail_prob)
             assert np.array_equal(res['episodes'], np.sum([ref['done'] for ref in refs], axis=0)), (A, E, mode, fail_prob)
             assert np.array_equal(res['collisions'], np.sum([ref['collision'] for ref in refs], axis=0)), (A, E, mode, fail_prob)
         goals = clash_on_goal = 0
@@ -592,7 +583,7 @@ def _goal_reaching_episodes(n_agents, n_envs, layout, env_vars, monkeypatch, rew
             ref, (local, reward, prob, done, coll) = refs[t], got[t]
             tag = (A, E, mode, fail_prob, t)
             assert np.array_equal(local, ref['local']), tag
-            assert np.array_equal(_bits(reward), _bits(ref['reward'])) and np.array_equal(_bits(prob), _bits(ref['prob'])), tag
+            assert np.array_equal(bits(reward), bits(ref['reward'])) and np.array_equal(bits(prob), bits(ref['prob'])), tag
             assert np.array_equal(done, ref['done']) and np.array_equal(coll, ref['collision']), tag
             fresh = ref['was_terminal'] == 0
             on_goal = (ref['local'] == goal).all(axis=1)
@@ -605,36 +596,7 @@ def _goal_reaching_episodes(n_agents, n_envs, layout, env_vars, monkeypatch, rew
         env.close()
 
 
-@pytest.mark.parametrize('n_agents,n_envs,layout,env_vars', [
-    (4, 16384, 'lq_rollout_kernel<Q=1,K=4', {'k': '4'}), (4, 16512, 'lq_rollout_kernel<Q=2,K=2', {'k': '2'}),
-    (8, 8192, 'lq_rollout_kernel<Q=2,K=4', {'k': '4'}), (8, 16448, 'lq_rollout_kernel<Q=4,K=2', {'k': '2'}),
-    (8, 16448, 'lg_rollout_kernel<L=4,FULL,MV_LDS', {'quad_lanes': '0'}),
-    (16, 4096, 'lq_rollout_kernel<Q=4,K=4', {'k': '4'}), (16, 4128, 'lq_rollout_kernel<Q=8,K=2', {'k': '2'}),
-    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,NO_TERMINAL> block=', {'k': '4', 'bitmap_pairs': '0'}),
-    # (32 agents, full table rows in LDS: occupancy bitmaps behind them -- what MAPF_TUNE k=4 or a batch of one wave per SIMD gets)
-    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,NO_TERMINAL,BITMAP> block=', {'k': '4'}),
-    (32, 1024, 'lq_rollout_kernel<Q=16,K=2', {'k': '2'}),
-    (32, 1024, 'lg_rollout_kernel<L=16,FULL,MV_GLOBAL', {'mv_lds_max_bytes': '0'}),
-    # eight agents per lane (the default only for batches of two waves per SIMD and more)
-    (8, 8192, 'lq_rollout_kernel<Q=1,K=8', {'k': '8'}), (16, 4096, 'lq_rollout_kernel<Q=2,K=8', {'k': '8'}),
-    (32, 2048, 'lq_rollout_kernel<Q=4,K=8', {'k': '8'}),
-    (32, 2048, 'lq_rollout_kernel<Q=4,K=8,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL> block=512', {'mv_lds_max_bytes': '2048', 'k': '8'}),
-    # (a full table "too large" for the LDS budget: the 8-byte-row form of the packed kernel, 512- and 1024-thread blocks)
-    (16, 4096, 'lq_rollout_kernel<Q=4,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL> block=512', {'mv_lds_max_bytes': '2048'}),
-    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL> block=512', {'mv_lds_max_bytes': '2048', 'bitmap_pairs': '0'}),
-    # (32 agents, 8-byte rows: collisions through per-env LDS occupancy bitmaps instead of the 496 agent pairs -- the default)
-    # (five-column table where it leaves room for the bitmaps -- here it does -- else four columns and a made-up STAY row)
-    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL,BITMAP5> block=512', {'mv_lds_max_bytes': '2048', 'bitmap_delta': '0'}),
-    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL,BITMAP> block=512', {'mv_lds_max_bytes': '2048', 'bitmap_staycol': '0', 'bitmap_delta': '0'}),
-    # (... in 1024-thread blocks, 128 bitmaps behind the table: what a batch that fills every CU with such a block gets)
-    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL,BITMAP> block=1024', {'mv_lds_max_bytes': '2048', 'bitmap_block': '1024', 'bitmap_staycol': '0', 'bitmap_delta': '0'}),
-    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL,BITMAP5> block=1024', {'mv_lds_max_bytes': '2048', 'bitmap_block': '1024', 'bitmap_delta': '0'}),
-    # (... behind 4-byte delta rows -- the default wherever a map's neighbour ids lie within +-127 of their cell's)
-    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL,BITMAPD> block=512', {'mv_lds_max_bytes': '2048'}),
-    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL,BITMAPD> block=1024', {'mv_lds_max_bytes': '2048', 'bitmap_block': '1024'}),
-    (64, 16384, 'lq_rollout_kernel<Q=16,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL> block=1024', {'mv_lds_max_bytes': '2048'}),
-    (8, 300, 'lg_rollout_kernel<L=4,FULL,MV_GLOBAL', {}), (5, 600, 'lg_rollout_kernel<L=4,RAGGED', {}),
-    (8, 16417, 'lg_rollout_kernel<L=4,FULL,MV_LDS', {}), (6, 512, 'rollout_kernel<A=6>', {})])
+@pytest.mark.parametrize('n_agents,n_envs,layout,env_vars', GOAL_ROWS)
 def test_goal_reaching_episodes_against_c_oracle(n_agents, n_envs, layout, env_vars, monkeypatch):
     """The goal-reached branch (reward_of_goal + living, done, no collision, then terminal / auto-reset) and "vertex
     collision while every agent sits on its goal" (collision wins) at 4..32 agents, in every rollout kernel -- the
@@ -701,11 +663,11 @@ def test_systolic_probability_chain_over_short_and_split_launches(env_vars, want
             ret = np.zeros(E)
             for t in range(T):
                 ref = co.step(acts[t], auto_reset=True)
-                assert np.array_equal(_bits(res['prob'][t]), _bits(ref['prob'])), (fail_prob, T, t)
-                assert np.array_equal(res['local'][t], ref['local']) and np.array_equal(_bits(res['reward'][t]), _bits(ref['reward']))
+                assert np.array_equal(bits(res['prob'][t]), bits(ref['prob'])), (fail_prob, T, t)
+                assert np.array_equal(res['local'][t], ref['local']) and np.array_equal(bits(res['reward'][t]), bits(ref['reward']))
                 assert np.array_equal(res['done'][t], ref['done']) and np.array_equal(res['collision'][t], ref['collision'])
                 ret = ret + ref['reward']
-            assert np.array_equal(_bits(res['returns']), _bits(ret)), (fail_prob, T)     # this launch's rewards, left to right
+            assert np.array_equal(bits(res['returns']), bits(ret)), (fail_prob, T)     # this launch's rewards, left to right
         assert np.array_equal(env.get_state()[0], co.state)
         env.close()
 
@@ -737,7 +699,7 @@ def _full_size_check(grid, nbr, A, start, goal, fail_prob, crit, ocrit, n_step, 
         local, reward, done, info = env.step(acts, auto_reset=True)
         ref = co.step(acts, auto_reset=True)
         assert np.array_equal(local, ref['local']), t
-        assert np.array_equal(_bits(reward), _bits(ref['reward'])) and np.array_equal(_bits(info['prob']), _bits(ref['prob']))
+        assert np.array_equal(bits(reward), bits(ref['reward'])) and np.array_equal(bits(info['prob']), bits(ref['prob']))
         assert np.array_equal(done, ref['done']) and np.array_equal(info['collision'], ref['collision'])
     if want_step is not None:
         assert want_step in env.last_kernel('step'), env.last_kernel('step')
@@ -750,7 +712,7 @@ def _full_size_check(grid, nbr, A, start, goal, fail_prob, crit, ocrit, n_step, 
         for k in range(n_streamed):
             ref = co.step(acts[k], auto_reset=True)
             assert np.array_equal(res['local'][k], ref['local']), k
-            assert np.array_equal(_bits(res['reward'][k]), _bits(ref['reward'])) and np.array_equal(_bits(res['prob'][k]), _bits(ref['prob'])), k
+            assert np.array_equal(bits(res['reward'][k]), bits(ref['reward'])) and np.array_equal(bits(res['prob'][k]), bits(ref['prob'])), k
             assert np.array_equal(res['done'][k], ref['done']) and np.array_equal(res['collision'][k], ref['collision']), k
         assert np.array_equal(env.get_state()[0], co.state)
     t_pol = env.t
@@ -760,12 +722,12 @@ def _full_size_check(grid, nbr, A, start, goal, fail_prob, crit, ocrit, n_step, 
         acts = philox.random_actions_np(42, ids, t_pol + k, A)        # (what the kernel must have drawn: key seed + 1)
         ref = co.step(acts, auto_reset=True)
         assert np.array_equal(res['local'][k], ref['local']), k
-        assert np.array_equal(_bits(res['reward'][k]), _bits(ref['reward'])) and np.array_equal(_bits(res['prob'][k]), _bits(ref['prob'])), k
+        assert np.array_equal(bits(res['reward'][k]), bits(ref['reward'])) and np.array_equal(bits(res['prob'][k]), bits(ref['prob'])), k
         assert np.array_equal(res['done'][k], ref['done']) and np.array_equal(res['collision'][k], ref['collision']), k
         returns = returns + ref['reward']
         episodes += ref['done']
         collisions += ref['collision']
-    assert np.array_equal(_bits(res['returns']), _bits(returns))
+    assert np.array_equal(bits(res['returns']), bits(returns))
     assert np.array_equal(res['episodes'], episodes) and np.array_equal(res['collisions'], collisions)
     assert np.array_equal(env.get_state()[0], co.state)
     # size-independent properties of the recorded trajectory
@@ -773,7 +735,7 @@ def _full_size_check(grid, nbr, A, start, goal, fail_prob, crit, ocrit, n_step, 
     ret = np.zeros(E)
     for t in range(n_roll):
         ret = ret + res['reward'][t]
-    assert np.array_equal(_bits(ret), _bits(res['returns']))          # returns == ordered sum of recorded rewards
+    assert np.array_equal(bits(ret), bits(res['returns']))          # returns == ordered sum of recorded rewards
     assert np.all((res['prob'] > 0) & (res['prob'] <= 1.0)) and np.all(res['local'] < nbr.shape[0])
     assert np.all(res['collision'] <= res['done'])                    # a collision always ends the episode
     env.close()
@@ -858,7 +820,7 @@ def test_reference_room64_maps_32agents_under_default_dispatch(monkeypatch, crit
                 local, reward, done, info = env.step(acts, auto_reset=False)
                 ref = co.step(acts, auto_reset=False)
                 assert np.array_equal(local, ref['local']) and np.array_equal(done, ref['done']), t
-                assert np.array_equal(_bits(reward), _bits(ref['reward'])) and np.array_equal(_bits(info['prob']), _bits(ref['prob'])), t
+                assert np.array_equal(bits(reward), bits(ref['reward'])) and np.array_equal(bits(info['prob']), bits(ref['prob'])), t
                 assert np.array_equal(info['collision'], ref['collision']) and np.array_equal(info['was_terminal'], ref['was_terminal']), t
             seen = env.last_kernel('step')
             assert seen.startswith(want_step.replace(',NO_TERMINAL', '').split('>')[0]) and 'NO_TERMINAL' not in seen, seen
@@ -1035,7 +997,7 @@ def _check_transition_tables_on_device(tabs):
             assert int(res['count'][q]) == len(exp), tab['name']
             for b, e in enumerate(exp):
                 assert res['next'][q, b].tolist() == e['next_local']
-                assert _bits(res['prob'][q, b]) == _bits(e['prob']) and _bits(res['reward'][q, b]) == _bits(e['reward'])
+                assert bits(res['prob'][q, b]) == bits(e['prob']) and bits(res['reward'][q, b]) == bits(e['reward'])
                 assert bool(res['done'][q, b]) == e['done'] and bool(res['collision'][q, b]) == e['collision']
         env.close()
 
@@ -1065,39 +1027,13 @@ def test_transitions_random_queries_against_oracle(n_agents, criteria):
         assert int(res['count'][q]) == len(exp), q
         for b, ((p, c), nxt, r, d) in enumerate(exp):
             assert res['next'][q, b].tolist() == list(nxt), (q, b)
-            assert _bits(res['prob'][q, b]) == _bits(p) and _bits(res['reward'][q, b]) == _bits(r), (q, b)
+            assert bits(res['prob'][q, b]) == bits(p) and bits(res['reward'][q, b]) == bits(r), (q, b)
             assert bool(res['done'][q, b]) == d and bool(res['collision'][q, b]) == c, (q, b)
     small = env.transitions(local, acts, max_branches=2, env_index=env_index)       # truncated rows, true counts
     assert np.array_equal(small['count'], res['count'])
-    assert np.array_equal(small['next'][:, 0], res['next'][:, 0]) and np.array_equal(_bits(small['prob'][:, 0]), _bits(res['prob'][:, 0]))
-    _check_compact_against_reserved(env, local, acts, env_index, res)
+    assert np.array_equal(small['next'][:, 0], res['next'][:, 0]) and np.array_equal(bits(small['prob'][:, 0]), bits(res['prob'][:, 0]))
+    check_compact_against_reserved(env, local, acts, env_index, res)
     env.close()
-
-
-def _check_compact_against_reserved(env, local, acts, env_index, res, first=0, window=None):
-    """mapf_transitions_compact: the same rows as the reserved form (already checked against the oracle), back to back
-    behind the exclusive scan of the windows' lengths; a capacity that is too small drops rows instead of overrunning."""
-    N = local.shape[0]
-    kw = dict(env_index=env_index, first_branch=first)
-    if window is not None:
-        kw['max_branches'] = window
-    cmp = env.transitions_compact(local, acts, **kw)
-    M = res['prob'].shape[1]
-    rows = np.minimum(np.maximum(res['count'].astype(np.int64) - first, 0), M)
-    assert np.array_equal(cmp['count'], res['count'])
-    assert np.array_equal(cmp['offset'].astype(np.int64), np.concatenate([[0], np.cumsum(rows)]))
-    for q in range(N):
-        o, n = int(cmp['offset'][q]), int(rows[q])
-        assert np.array_equal(cmp['next'][o:o + n], res['next'][q, :n]), q
-        assert np.array_equal(_bits(cmp['prob'][o:o + n]), _bits(res['prob'][q, :n])), q
-        assert np.array_equal(_bits(cmp['reward'][o:o + n]), _bits(res['reward'][q, :n])), q
-        assert np.array_equal(cmp['done'][o:o + n], res['done'][q, :n]) and np.array_equal(cmp['collision'][o:o + n], res['collision'][q, :n]), q
-    total = int(cmp['offset'][N])
-    if total > 3:                                                 # too small a capacity: the needed size is reported, nothing overruns
-        cap = total // 2
-        part = env.transitions_compact(local, acts, capacity=cap, **kw)
-        assert int(part['offset'][N]) == total and part['prob'].shape[0] == cap
-        assert np.array_equal(_bits(part['prob']), _bits(cmp['prob'][:cap])) and np.array_equal(part['next'], cmp['next'][:cap])
 
 
 @pytest.mark.parametrize('n_agents', [2, 4, 8])
@@ -1127,7 +1063,7 @@ def test_compacted_transitions_across_the_scan_block_boundaries(shim, n_agents):
         keep = np.arange(M)[None, :] < rows[:, None]              # the reserved form's live rows, query by query = the compacted rows
         total = int(offset[N])
         assert np.array_equal(cmp['next'][:total], res['next'][keep]), (A, N)
-        assert np.array_equal(_bits(cmp['prob'][:total]), _bits(res['prob'][keep])) and np.array_equal(_bits(cmp['reward'][:total]), _bits(res['reward'][keep])), (A, N)
+        assert np.array_equal(bits(cmp['prob'][:total]), bits(res['prob'][keep])) and np.array_equal(bits(cmp['reward'][:total]), bits(res['reward'][keep])), (A, N)
         assert np.array_equal(cmp['done'][:total], res['done'][keep]) and np.array_equal(cmp['collision'][:total], res['collision'][keep]), (A, N)
     env.close()
 
@@ -1159,7 +1095,7 @@ def test_transitions_of_large_teams_come_in_windows(slip=0.2, rewards=EXACT):
                      bool(res['collision'][0, b])) for b in range(k)]
             first += window
         for (nxt, p, r, d, c), ((ep, ec), enxt, er, ed) in zip(got, exp):
-            assert nxt == list(enxt) and _bits(p) == _bits(ep) and _bits(r) == _bits(er) and (d, c) == (ed, ec)
+            assert nxt == list(enxt) and bits(p) == bits(ep) and bits(r) == bits(er) and (d, c) == (ed, ec)
     env.close()
     # 12 agents through the scalar API: MapfEnv.P pages by itself (window 65536 < 3^12 possible branches)
     lines = ['......', '......', '......']
@@ -1174,7 +1110,7 @@ def test_transitions_of_large_teams_come_in_windows(slip=0.2, rewards=EXACT):
     assert len(got) == len(exp) > 65536
     for k in (0, 1, 65535, 65536, 65537, len(exp) - 1):
         ((p, c), s_next, r, d), ((ep, ec), enxt, er, ed) = got[k], exp[k]
-        assert _bits(p) == _bits(ep) and _bits(r) == _bits(er) and (d, c) == (ed, ec)
+        assert bits(p) == bits(ep) and bits(r) == bits(er) and (d, c) == (ed, ec)
         assert s_next == mo.encode_mixed_radix(enxt, orc.V)
     assert abs(sum(t[0][0] for t in got) - 1.0) < 1e-9
     menv.close()
@@ -1229,9 +1165,9 @@ def test_every_transitions_kernel_instance_against_oracle(n_agents, slip=0.2, re
                 for b in range(min(window, max(0, len(exp[q]) - first))):
                     (ep, ec), enxt, er, ed = exp[q][first + b]
                     assert res['next'][q, b].tolist() == list(enxt), (A, window, q, first + b)
-                    assert _bits(res['prob'][q, b]) == _bits(ep) and _bits(res['reward'][q, b]) == _bits(er), (A, window, q, first + b)
+                    assert bits(res['prob'][q, b]) == bits(ep) and bits(res['reward'][q, b]) == bits(er), (A, window, q, first + b)
                     assert (bool(res['done'][q, b]), bool(res['collision'][q, b])) == (ed, ec), (A, window, q, first + b)
-            _check_compact_against_reserved(env, local, acts, env_index, res, first=first, window=window)   # ... and the compacted rows
+            check_compact_against_reserved(env, local, acts, env_index, res, first=first, window=window)   # ... and the compacted rows
             first += window
     assert sum(1 for x in exp for t in x if t[0][1]) > 0              # collision branches were among them
     name = env.last_kernel('transitions')
@@ -1318,7 +1254,7 @@ def test_transition_rewards_of_a_batch_against_oracle(n_agents, criteria, per_en
         g = goal[which[q]].tolist()
         p, n = prev[q].tolist(), nxt[q].tolist()
         r, d, c, _ = mo.transition_reward(p, read[q].tolist(), n, g, INEXACT, OCRIT[criteria])
-        assert _bits(reward[q]) == _bits(r) and (bool(done[q]), bool(coll[q])) == (d, c), (A, criteria, q)
+        assert bits(reward[q]) == bits(r) and (bool(done[q]), bool(coll[q])) == (d, c), (A, criteria, q)
         vertex = len(set(n)) < A
         swap = any(p[i] == n[j] and p[j] == n[i] for i in range(A) for j in range(i + 1, A))
         assert c == (vertex or swap)
@@ -1334,7 +1270,7 @@ def test_transition_rewards_of_a_batch_against_oracle(n_agents, criteria, per_en
     r0, d0, c0 = env.transition_rewards(prev[:0], acts[:0], nxt[:0], env_index=None if env_index is None else env_index[:0])
     assert r0.shape == d0.shape == c0.shape == (0,)
     only, d1, c1 = env.transition_rewards(prev, acts, nxt, env_index=env_index, want_done=False, want_collision=False)
-    assert d1 is None and c1 is None and np.array_equal(_bits(only), _bits(reward))
+    assert d1 is None and c1 is None and np.array_equal(bits(only), bits(reward))
     env.close()
 
 
@@ -1381,7 +1317,7 @@ def test_mixed_map_batch_keeps_every_envs_own_stream():
         local, reward, done, info = env.step(acts, auto_reset=True)
         for e, o in enumerate(oracles):
             nxt, r, d, c, p, wt = o.step(acts[e].tolist(), u[e].tolist())
-            assert list(nxt) == local[e].tolist() and _bits(r) == _bits(reward[e]) and _bits(p) == _bits(info['prob'][e]), (t, e)
+            assert list(nxt) == local[e].tolist() and bits(r) == bits(reward[e]) and bits(p) == bits(info['prob'][e]), (t, e)
             assert (d, c, wt) == (bool(done[e]), bool(info['collision'][e]), bool(info['was_terminal'][e])), (t, e)
             if d:
                 o.reset()
@@ -1394,7 +1330,7 @@ def test_mixed_map_batch_keeps_every_envs_own_stream():
             ret, epi = ret + r, epi + int(d)
             if d:
                 o.reset()
-        assert _bits(ret) == _bits(res['returns'][e]) and epi == res['episodes'][e], e
+        assert bits(ret) == bits(res['returns'][e]) and epi == res['episodes'][e], e
     state, t_now = env.get_state()
     assert t_now == 65 and all(state[e].tolist() == list(o.local) for e, o in enumerate(oracles))
     env.close()
@@ -1427,7 +1363,7 @@ def test_mixed_map_batch_in_one_launch_through_the_union_table():
         local, reward, done, info = env.step(acts, auto_reset=True)
         for e, o in enumerate(oracles):
             nxt, r, d, c, p, wt = o.step(acts[e].tolist(), u[e].tolist())
-            assert list(nxt) == local[e].tolist() and _bits(r) == _bits(reward[e]) and _bits(p) == _bits(info['prob'][e]), (t, e)
+            assert list(nxt) == local[e].tolist() and bits(r) == bits(reward[e]) and bits(p) == bits(info['prob'][e]), (t, e)
             assert (d, c, wt) == (bool(done[e]), bool(info['collision'][e]), bool(info['was_terminal'][e])), (t, e)
             if d:
                 o.reset()
@@ -1436,7 +1372,7 @@ def test_mixed_map_batch_in_one_launch_through_the_union_table():
         for k, t in enumerate(range(40, 65)):
             a = philox.random_actions_np(8, [off + e], t, A)[0].tolist()
             nxt, r, d, c, p, wt = o.step(a, philox.slip_uniforms_np(8, [off + e], t, A)[0].tolist())
-            assert list(nxt) == res['local'][k, e].tolist() and _bits(r) == _bits(res['reward'][k, e]), (e, t)
+            assert list(nxt) == res['local'][k, e].tolist() and bits(r) == bits(res['reward'][k, e]), (e, t)
             if d:
                 o.reset()
     state, t_now = env.get_state()
@@ -1460,10 +1396,10 @@ def test_mixed_map_batch_in_one_launch_through_the_union_table():
     acts = rs.randint(0, 5, size=(6, E, A)).astype(np.uint8)
     for t in range(6):
         a, b = one.step(acts[t], auto_reset=True), many.step(acts[t], auto_reset=True)
-        assert np.array_equal(a[0], b[0]) and np.array_equal(_bits(a[1]), _bits(b[1])) and np.array_equal(a[2], b[2]), t
-        assert np.array_equal(_bits(a[3]['prob']), _bits(b[3]['prob'])) and np.array_equal(a[3]['collision'], b[3]['collision']), t
+        assert np.array_equal(a[0], b[0]) and np.array_equal(bits(a[1]), bits(b[1])) and np.array_equal(a[2], b[2]), t
+        assert np.array_equal(bits(a[3]['prob']), bits(b[3]['prob'])) and np.array_equal(a[3]['collision'], b[3]['collision']), t
     ra, rb = one.rollout(20, auto_reset=True), many.rollout(20, auto_reset=True)
-    assert np.array_equal(_bits(ra['returns']), _bits(rb['returns'])) and np.array_equal(ra['episodes'], rb['episodes'])
+    assert np.array_equal(bits(ra['returns']), bits(rb['returns'])) and np.array_equal(ra['episodes'], rb['episodes'])
     assert np.array_equal(one.get_state()[0], many.get_state()[0]) and int(ra['episodes'].sum()) > 0
     assert one.last_kernel('rollout').startswith('lq_rollout_kernel'), one.last_kernel('rollout')
     one.close(), many.close()
@@ -1476,7 +1412,7 @@ def test_mixed_map_batch_in_one_launch_through_the_union_table():
         a = dev.step(acts_t[t], auto_reset=True)
         dev.sync()
         b = ref.step(acts[t], auto_reset=True)
-        assert np.array_equal(a[0].cpu().numpy(), b[0]) and np.array_equal(_bits(a[1].cpu().numpy()), _bits(b[1])), t
+        assert np.array_equal(a[0].cpu().numpy(), b[0]) and np.array_equal(bits(a[1].cpu().numpy()), bits(b[1])), t
     dev.close(), ref.close()
 
 
@@ -1500,10 +1436,10 @@ def test_rollout_beyond_one_launch_is_issued_in_slices(monkeypatch, rewards=EXAC
     for k in ('local', 'done', 'collision', 'episodes', 'collisions'):
         assert np.array_equal(whole[k], parts[k]), k
     for k in ('reward', 'prob', 'returns'):
-        assert np.array_equal(_bits(whole[k]), _bits(parts[k])), k
+        assert np.array_equal(bits(whole[k]), bits(parts[k])), k
     co = c_oracle.COracle(nbr, A, start, goal, 0.2, *rewards, mo.SOC, seed=4)
     ref = co.rollout(T, actions=acts, auto_reset=True)
-    assert np.array_equal(_bits(parts['returns']), _bits(ref['returns'])) and np.array_equal(parts['episodes'], ref['episodes'])
+    assert np.array_equal(bits(parts['returns']), bits(ref['returns'])) and np.array_equal(parts['episodes'], ref['episodes'])
     assert sliced.t == one.t == T and np.array_equal(sliced.get_state()[0], co.state)
     more = sliced.rollout(7, auto_reset=True, accumulate_into={k: parts[k] for k in ('returns', 'episodes', 'collisions')})   # policy, no arrays: one launch
     ref2 = co.rollout(7, auto_reset=True)
@@ -1547,7 +1483,7 @@ def test_out_of_range_actions_are_stay_and_device_pointers_must_be_aligned():
     b = VecMapfEnv(grid, 2, None, None, 0.2, -1.0, 1.0, -1.0, OptimizationCriteria.SoC, seed=3, **kw)
     la, ra, da, ia = a.step(np.full((64, 2), 200, np.uint8))              # garbage action values ...
     lb, rb, db, ib = b.step(np.zeros((64, 2), np.uint8))                  # ... behave like STAY
-    assert np.array_equal(la, lb) and np.array_equal(_bits(ra), _bits(rb)) and np.array_equal(_bits(ia['prob']), _bits(ib['prob']))
+    assert np.array_equal(la, lb) and np.array_equal(bits(ra), bits(rb)) and np.array_equal(bits(ia['prob']), bits(ib['prob']))
     a.close(), b.close()
     dev = VecMapfEnv(grid, 2, None, None, 0.2, -1.0, 1.0, -1.0, OptimizationCriteria.SoC, device_arrays=True, **kw)
     buf = torch.zeros(64 * 2 + 3, dtype=torch.uint8, device='cuda')
@@ -1634,7 +1570,7 @@ def test_rollout_with_large_lds_move_table():
                          start_local=start, goal_local=goal)
         co = c_oracle.COracle(nbr, A, start, goal, 0.2, -1000.0, 100.0, -1.0, mo.SOC, seed=9)
         res, ref = env.rollout(40, auto_reset=True, record=True), co.rollout(40, auto_reset=True)
-        assert np.array_equal(_bits(res['returns']), _bits(ref['returns'])) and np.array_equal(res['episodes'], ref['episodes'])
+        assert np.array_equal(bits(res['returns']), bits(ref['returns'])) and np.array_equal(res['episodes'], ref['episodes'])
         assert np.array_equal(env.get_state()[0], co.state)
         env.close()
 
@@ -1677,7 +1613,7 @@ def test_mixed_map_batch_in_device_mode_on_one_stream():
         prob, coll, wt_ = out['prob'].cpu().numpy(), out['collision'].cpu().numpy(), out['was_terminal'].cpu().numpy()
         for e, o in enumerate(oracles):
             nxt, r, d, c, p, wt = o.step(acts[e].tolist(), u[e].tolist())
-            assert list(nxt) == local[e].tolist() and _bits(r) == _bits(reward[e]) and _bits(p) == _bits(prob[e]), (t, e)
+            assert list(nxt) == local[e].tolist() and bits(r) == bits(reward[e]) and bits(p) == bits(prob[e]), (t, e)
             assert (d, c, wt) == (bool(done[e]), bool(coll[e]), bool(wt_[e])), (t, e)
             if d:
                 o.reset()
@@ -1692,7 +1628,7 @@ def test_mixed_map_batch_in_device_mode_on_one_stream():
             ret, epi = ret + r, epi + int(d)
             if d:
                 o.reset()
-        assert _bits(ret) == _bits(returns[e]) and epi == episodes[e], e
+        assert bits(ret) == bits(returns[e]) and epi == episodes[e], e
     state, t_now = env.get_state()
     env.sync()
     state = state.cpu().numpy()

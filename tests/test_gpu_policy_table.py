@@ -12,6 +12,7 @@ from gym_mapf_amd import _native as nat
 from gym_mapf_amd.envs.grid import MapfGrid
 from gym_mapf_amd.envs.policies import shortest_path_policy, shortest_path_table
 from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
+from parity_checks import bits, to_np
 
 pytestmark = pytest.mark.gpu
 R = (-1000.0, 100.0, -1.0)
@@ -21,20 +22,12 @@ INEXACT = (-0.3, 0.7, -0.1)
 CRIT = {'Makespan': (OptimizationCriteria.Makespan, mo.MAKESPAN), 'SoC': (OptimizationCriteria.SoC, mo.SOC)}
 
 
-def _bits(x):
-    return np.asarray(x, np.float64).view(np.uint64)
-
-
-def _np(x):
-    return x.cpu().numpy() if hasattr(x, 'cpu') else np.asarray(x)
-
-
 def _state(env):
     """the handle's state on the host: in device mode get_state only ENQUEUES its copy on the env's stream, which the reader's stream
     does not wait for"""
     local = env.get_state()[0]
     env.sync()
-    return _np(local)
+    return to_np(local)
 
 
 def _random_map(seed, size=20, p=0.15):
@@ -69,10 +62,10 @@ def _oracle_steps(co, table, rows, T, auto_reset=True):
 
 def _check_record(res, refs, tag, t0=0):
     for t, ref in enumerate(refs):
-        assert np.array_equal(_np(res['local'][t0 + t]), ref['local']), (tag, t)
-        assert np.array_equal(_bits(_np(res['reward'][t0 + t])), _bits(ref['reward'])), (tag, t)
-        assert np.array_equal(_bits(_np(res['prob'][t0 + t])), _bits(ref['prob'])), (tag, t)
-        assert np.array_equal(_np(res['done'][t0 + t]), ref['done']) and np.array_equal(_np(res['collision'][t0 + t]), ref['collision']), (tag, t)
+        assert np.array_equal(to_np(res['local'][t0 + t]), ref['local']), (tag, t)
+        assert np.array_equal(bits(to_np(res['reward'][t0 + t])), bits(ref['reward'])), (tag, t)
+        assert np.array_equal(bits(to_np(res['prob'][t0 + t])), bits(ref['prob'])), (tag, t)
+        assert np.array_equal(to_np(res['done'][t0 + t]), ref['done']) and np.array_equal(to_np(res['collision'][t0 + t]), ref['collision']), (tag, t)
 
 
 def _check_totals(res, refs, tag, base=None):
@@ -83,8 +76,8 @@ def _check_totals(res, refs, tag, base=None):
         ret = ret + ref['reward']                                 # float64 adds in step order, as the kernels do
         epi = epi + ref['done'].astype(np.uint32)
         col = col + ref['collision'].astype(np.uint32)
-    assert np.array_equal(_bits(_np(res['returns'])), _bits(ret)), tag
-    assert np.array_equal(_np(res['episodes']), epi) and np.array_equal(_np(res['collisions']), col), tag
+    assert np.array_equal(bits(to_np(res['returns'])), bits(ret)), tag
+    assert np.array_equal(to_np(res['episodes']), epi) and np.array_equal(to_np(res['collisions']), col), tag
     return dict(returns=ret, episodes=epi, collisions=col)
 
 
@@ -292,7 +285,7 @@ def test_a_shard_equals_the_slice_of_the_whole():
     whole, shard = outs
     for key in ('local', 'reward', 'prob', 'done', 'collision'):
         assert np.array_equal(whole[key][:, 4096:].view(np.uint8), shard[key].view(np.uint8)), key
-    assert np.array_equal(_bits(whole['returns'][4096:]), _bits(shard['returns']))
+    assert np.array_equal(bits(whole['returns'][4096:]), bits(shard['returns']))
     co = c_oracle.COracle(nbr, A, start[4096:], goal[4096:], 0.2, *R, mo.MAKESPAN, seed=9, env_id_offset=4096)
     refs, _, _ = _oracle_steps(co, table, rows[4096:].astype(np.int64), T)
     _check_record(shard, refs, 'shard')
@@ -314,14 +307,14 @@ def test_policy_switches_restore_the_policy_stream_and_replace_tables():
     out = env.rollout(6)
     ref = co.rollout(6, auto_reset=True)
     assert 'POLICY' in env.last_kernel('rollout')
-    assert np.array_equal(_bits(out['returns']), _bits(ref['returns'])) and np.array_equal(env.get_state()[0], co.state)
+    assert np.array_equal(bits(out['returns']), bits(ref['returns'])) and np.array_equal(env.get_state()[0], co.state)
     env.set_policy('table', table=table, rows=rows)
     env.set_policy('greedy')                                      # table -> greedy -> table
     res = env.rollout(5, record=True)
     assert 'POLICY' in env.last_kernel('rollout')
     for t in range(5):
         r = co.step(co.greedy_actions(rc), auto_reset=True)
-        assert np.array_equal(res['local'][t], r['local']) and np.array_equal(_bits(res['reward'][t]), _bits(r['reward']))
+        assert np.array_equal(res['local'][t], r['local']) and np.array_equal(bits(res['reward'][t]), bits(r['reward']))
     env.set_policy('table', table=table, rows=rows)
     res = env.rollout(7, record=True)
     assert 'TABLE' in env.last_kernel('rollout')

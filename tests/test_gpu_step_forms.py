@@ -8,13 +8,10 @@ import pytest
 import step_cases as sc
 from conftest import load_json, set_tune
 from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
+from parity_checks import bits
 
 pytestmark = pytest.mark.gpu
 NAMES = load_json('lq_step_kernel_names.json')['launches']
-
-
-def _bits(x):
-    return np.asarray(x, np.float64).view(np.uint64)
 
 
 def _name(case, scen, may_be_terminal):
@@ -40,7 +37,7 @@ def _same(got, ref, tag):
     assert np.array_equal(np.asarray(local), ref['local']), tag
     assert np.array_equal(np.asarray(done), ref['done']) and np.array_equal(np.asarray(info['collision']), ref['collision']), tag
     assert np.array_equal(np.asarray(info['was_terminal']), ref['was_terminal']), tag
-    assert np.array_equal(_bits(reward), _bits(ref['reward'])) and np.array_equal(_bits(info['prob']), _bits(ref['prob'])), tag
+    assert np.array_equal(bits(reward), bits(ref['reward'])) and np.array_equal(bits(info['prob']), bits(ref['prob'])), tag
 
 
 def _run_handle(case, scen, p):

@@ -11,16 +11,13 @@ import mapf_oracle as mo
 from gym_mapf_amd import _native as nat
 from gym_mapf_amd.envs.grid import MapfGrid
 from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
+from parity_checks import bits
 
 pytestmark = pytest.mark.gpu
 R = (-1000.0, 100.0, -1.0)
 # constants on which float64 rounds (see tests/test_gpu_parity.py): a fused or re-associated r_x + (A - stayed) * r_living
 # changes bits with these, never with R
 INEXACT = (-0.3, 0.7, -0.1)
-
-
-def _bits(x):
-    return np.asarray(x, np.float64).view(np.uint64)
 
 
 def _c3_tables(n_envs, offset=0):
@@ -31,8 +28,8 @@ def _c3_tables(n_envs, offset=0):
 def _check(out, ref, tag, local=True):
     if local:
         assert np.array_equal(out['local'].cpu().numpy(), ref['local']), tag
-    assert np.array_equal(_bits(out['reward'].cpu().numpy()), _bits(ref['reward'])), tag
-    assert np.array_equal(_bits(out['prob'].cpu().numpy()), _bits(ref['prob'])), tag
+    assert np.array_equal(bits(out['reward'].cpu().numpy()), bits(ref['reward'])), tag
+    assert np.array_equal(bits(out['prob'].cpu().numpy()), bits(ref['prob'])), tag
     assert np.array_equal(out['done'].cpu().numpy(), ref['done']), tag
     assert np.array_equal(out['collision'].cpu().numpy(), ref['collision']), tag
     assert np.array_equal(out['was_terminal'].cpu().numpy(), ref['was_terminal']), tag
@@ -125,7 +122,7 @@ def test_graph_of_rollout_and_steps_and_host_side_index_moves():
         graph.launch(1)
         env.sync()
         ref = co.rollout(8, auto_reset=True)
-        assert np.array_equal(_bits(res['returns'].cpu().numpy()), _bits(ref['returns'])), rep
+        assert np.array_equal(bits(res['returns'].cpu().numpy()), bits(ref['returns'])), rep
         assert np.array_equal(res['episodes'].cpu().numpy(), ref['episodes']), rep
         for k in range(2):
             _check(outs[k], co.step(acts_host[k], auto_reset=True), 'replay %d step %d' % (rep, k))
@@ -164,8 +161,8 @@ def test_scenario_table_step_equals_plain_rows(monkeypatch, n_agents, n_envs):
             acts[t % 3::3] = ((1 + (which[t % 3::3, None] + np.arange(n_agents)[None, :]) % 4)).astype(np.uint8)   # head for the goals
             local, reward, done, info = env.step(acts, auto_reset=(t % 8 != 7))
             ref = co.step(acts, auto_reset=(t % 8 != 7))
-            assert np.array_equal(local, ref['local']) and np.array_equal(_bits(reward), _bits(ref['reward'])), (use_table, t)
-            assert np.array_equal(_bits(info['prob']), _bits(ref['prob'])) and np.array_equal(done, ref['done']), (use_table, t)
+            assert np.array_equal(local, ref['local']) and np.array_equal(bits(reward), bits(ref['reward'])), (use_table, t)
+            assert np.array_equal(bits(info['prob']), bits(ref['prob'])) and np.array_equal(done, ref['done']), (use_table, t)
             assert np.array_equal(info['collision'], ref['collision']) and np.array_equal(info['was_terminal'], ref['was_terminal']), (use_table, t)
             assert np.array_equal(env.get_state()[0], co.state), (use_table, t)
             n_done += int(done.sum())
@@ -198,8 +195,8 @@ def test_single_step_at_a_batch_larger_than_the_device_holds(monkeypatch, big, r
         acts = philox.random_actions_np(3, ids, t, A)
         local, reward, done, info = env.step(acts, auto_reset=True)
         ref = co.step(acts, auto_reset=True)
-        assert np.array_equal(local, ref['local']) and np.array_equal(_bits(reward), _bits(ref['reward'])), t
-        assert np.array_equal(_bits(info['prob']), _bits(ref['prob'])) and np.array_equal(done, ref['done']), t
+        assert np.array_equal(local, ref['local']) and np.array_equal(bits(reward), bits(ref['reward'])), t
+        assert np.array_equal(bits(info['prob']), bits(ref['prob'])) and np.array_equal(done, ref['done']), t
         assert np.array_equal(info['collision'], ref['collision']) and np.array_equal(info['was_terminal'], ref['was_terminal'])
         name = env.last_kernel('step')
         assert name.startswith(expect) and (',BIG>' in name) == (big != '0'), name
@@ -239,8 +236,8 @@ def test_big_form_of_the_single_step_at_other_team_sizes(monkeypatch, n_agents, 
         auto = t % 4 != 3
         local, reward, done, info = env.step(acts, auto_reset=auto)
         ref = co.step(acts, auto_reset=auto)
-        assert np.array_equal(local, ref['local']) and np.array_equal(_bits(reward), _bits(ref['reward'])), t
-        assert np.array_equal(_bits(info['prob']), _bits(ref['prob'])) and np.array_equal(done, ref['done']), t
+        assert np.array_equal(local, ref['local']) and np.array_equal(bits(reward), bits(ref['reward'])), t
+        assert np.array_equal(bits(info['prob']), bits(ref['prob'])) and np.array_equal(done, ref['done']), t
         assert np.array_equal(info['collision'], ref['collision']) and np.array_equal(info['was_terminal'], ref['was_terminal']), t
         assert np.array_equal(env.get_state()[0], co.state), t
         n_done += int(done.sum())
@@ -278,8 +275,8 @@ def test_step_drops_is_terminal_only_when_no_env_can_be_terminal():
         acts = co.greedy_actions(rc)
         local, reward, done, info = env.step(acts, auto_reset=what)
         ref = co.step(acts, auto_reset=what)
-        assert np.array_equal(local, ref['local']) and np.array_equal(_bits(reward), _bits(ref['reward'])), len(seen)
-        assert np.array_equal(_bits(info['prob']), _bits(ref['prob'])) and np.array_equal(done, ref['done']), len(seen)
+        assert np.array_equal(local, ref['local']) and np.array_equal(bits(reward), bits(ref['reward'])), len(seen)
+        assert np.array_equal(bits(info['prob']), bits(ref['prob'])) and np.array_equal(done, ref['done']), len(seen)
         assert np.array_equal(info['collision'], ref['collision']) and np.array_equal(info['was_terminal'], ref['was_terminal']), len(seen)
         assert np.array_equal(env.get_state()[0], co.state)
         n_terminal += int(ref['was_terminal'].sum())
@@ -330,7 +327,7 @@ def test_recording_with_the_callers_own_kernels_on_a_shared_stream():
             _check(out, ref, 'replay %d' % rep, local=False)
             assert np.array_equal(obs.cpu().numpy(), co.state), rep
             ref_total = ref_total + ref['reward']
-        assert np.array_equal(_bits(total.cpu().numpy()), _bits(ref_total)) and env.t == 40
+        assert np.array_equal(bits(total.cpu().numpy()), bits(ref_total)) and env.t == 40
         graph.close()
     env.close()
 
@@ -419,8 +416,8 @@ def test_stand_in_trajectory_buffers_cannot_move_under_a_recorded_rollout():
     env.sync()
     import philox
     ref = np.stack([co.step(philox.random_actions_np(5, np.arange(E), t, A), auto_reset=True)['reward'] for t in range(16)])
-    assert np.array_equal(_bits(first), _bits(ref[:8]))
-    assert np.array_equal(_bits(small.cpu().numpy()), _bits(ref[8:]))
+    assert np.array_equal(bits(first), bits(ref[:8]))
+    assert np.array_equal(bits(small.cpu().numpy()), bits(ref[8:]))
     assert env.t == 16
     graph.close()
     nat.check(env._lib.mapf_rollout(env._h, ctypes.byref(io16)))   # no graph left: the stand-ins may grow again

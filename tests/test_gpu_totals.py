@@ -8,12 +8,13 @@ import pytest
 import totals_cases as tc
 from conftest import set_tune
 from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
+from parity_checks import bits
 
 pytestmark = pytest.mark.gpu
 
 
 def _check(res, want, env, run, k, tag):
-    assert np.array_equal(tc._bits(res['returns']), tc._bits(want['returns'])), tag
+    assert np.array_equal(bits(res['returns']), bits(want['returns'])), tag
     assert np.array_equal(res['episodes'], want['episodes']) and np.array_equal(res['collisions'], want['collisions']), tag
     cells, t = env.get_state()
     assert t == run.after[k][1] and np.array_equal(cells, run.after[k][0]), tag
@@ -58,8 +59,8 @@ def test_totals_only_rollout_against_c_oracle(case, monkeypatch):
                 assert 'RECORD' in env.last_kernel('rollout') or case.kernel == 'thread_per_env', env.last_kernel('rollout')
                 for j, ref in enumerate(run.refs[lo:hi]):
                     assert np.array_equal(rec['local'][j], ref['local']), tag + (j,)
-                    assert np.array_equal(tc._bits(rec['reward'][j]), tc._bits(ref['reward'])), tag + (j,)
-                    assert np.array_equal(tc._bits(rec['prob'][j]), tc._bits(ref['prob'])), tag + (j,)
+                    assert np.array_equal(bits(rec['reward'][j]), bits(ref['reward'])), tag + (j,)
+                    assert np.array_equal(bits(rec['prob'][j]), bits(ref['prob'])), tag + (j,)
                     assert np.array_equal(rec['done'][j], ref['done']) and np.array_equal(rec['collision'][j], ref['collision']), tag + (j,)
                 _check(rec, run.totals(lo, hi), env, run, k, tag)
                 continue

@@ -15,9 +15,9 @@ import mapf_oracle as mo
 from gym_mapf_amd import _native as nat
 from gym_mapf_amd.envs.grid import MapfGrid
 from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
-from test_gpu_parity import EXACT, _bits, _check_compact_against_reserved
-from test_host_tables import shim  # noqa: F401  (the host shim, built once per run)
-from test_transitions_plan import declare, planned
+from host_shim import shim  # noqa: F401  (the host shim, built once per run)
+from parity_checks import EXACT, bits, check_compact_against_reserved
+from plan_sweeps import declare, planned
 
 pytestmark = pytest.mark.gpu
 LINES = ['......'] * 6                                                    # a small open map
@@ -55,7 +55,7 @@ def _check_rows(rows, exp, first, tag):
     nxt, prob, reward, done, coll = rows
     n = len(exp)
     assert np.array_equal(nxt[:n], np.array([e[1] for e in exp], np.uint16).reshape(n, -1)), tag
-    assert np.array_equal(_bits(prob[:n]), _bits([e[0][0] for e in exp])) and np.array_equal(_bits(reward[:n]), _bits([e[2] for e in exp])), tag
+    assert np.array_equal(bits(prob[:n]), bits([e[0][0] for e in exp])) and np.array_equal(bits(reward[:n]), bits([e[2] for e in exp])), tag
     assert np.array_equal(done[:n].astype(bool), np.array([e[3] for e in exp], bool)) and np.array_equal(coll[:n].astype(bool), np.array([e[0][1] for e in exp], bool)), tag
 
 
@@ -145,7 +145,7 @@ def test_larger_pieces_launch_the_planned_kernel(shim, N, rows_per_wave, scan_pa
     terminal[at] = False
     rows = offset[:N][terminal]                                           # every terminal query's single row: ((1.0, False), s, 0, True)
     assert np.array_equal(cmp['next'][rows], local[terminal])
-    assert np.array_equal(_bits(cmp['prob'][rows]), _bits(np.ones(len(rows)))) and np.array_equal(_bits(cmp['reward'][rows]), _bits(np.zeros(len(rows))))
+    assert np.array_equal(bits(cmp['prob'][rows]), bits(np.ones(len(rows)))) and np.array_equal(bits(cmp['reward'][rows]), bits(np.zeros(len(rows))))
     assert np.all(cmp['done'][rows] == 1) and np.all(cmp['collision'][rows] == 0)
     env.close()
 
@@ -166,7 +166,7 @@ def test_wide_family_launches_the_planned_kernel(shim, window, walks, groups):  
             _check_compacted(res, exp, window)
         else:
             _check_reserved(res, exp, window)
-            _check_compact_against_reserved(env, local, acts, None, res, window=window)
+            check_compact_against_reserved(env, local, acts, None, res, window=window)
     env.close()
 
 

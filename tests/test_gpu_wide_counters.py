@@ -10,16 +10,9 @@ import philox
 import wide_counter_cases as wc
 from conftest import set_tune
 from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
+from parity_checks import bits, to_np
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(x):
-    return np.asarray(x, np.float64).view(np.uint64)
-
-
-def _np(x):
-    return x.cpu().numpy() if hasattr(x, 'cpu') else np.asarray(x)
 
 
 def _exp(X):
@@ -37,9 +30,9 @@ def _env(case, X, tables):
 
 def _check_step(got, ref, tag):
     """got: (local, reward, prob, done, collision) of one step"""
-    local, reward, prob, done, collision = (_np(x) for x in got)
+    local, reward, prob, done, collision = (to_np(x) for x in got)
     assert np.array_equal(local, ref['local']), tag
-    assert np.array_equal(_bits(reward), _bits(ref['reward'])) and np.array_equal(_bits(prob), _bits(ref['prob'])), tag
+    assert np.array_equal(bits(reward), bits(ref['reward'])) and np.array_equal(bits(prob), bits(ref['prob'])), tag
     assert np.array_equal(done, ref['done']) and np.array_equal(collision, ref['collision']), tag
 
 
@@ -70,7 +63,7 @@ def test_recorded_rollouts_across_every_crossing_point(case, monkeypatch):
                     _check_step((res['local'][k], res['reward'][k], res['prob'][k], res['done'][k], res['collision'][k]), run.refs[lo + k],
                                 (case.id, _exp(X), window.name, 'step X%+d' % (window.t0 + lo + k - X)))
                 total = run.totals(lo, lo + n)
-                assert np.array_equal(_bits(res['returns']), _bits(total['returns'])), (case.id, _exp(X), window.name, lo)
+                assert np.array_equal(bits(res['returns']), bits(total['returns'])), (case.id, _exp(X), window.name, lo)
                 assert np.array_equal(res['episodes'], total['episodes']) and np.array_equal(res['collisions'], total['collisions'])
                 lo += n
             local, t = env.get_state()
@@ -134,7 +127,7 @@ def test_graph_replays_carry_the_device_side_step_index(case):
             _check_step((local, reward, info['prob'], done, info['collision']), run.refs[s], (case.id, _exp(X), 'plain step X%+d' % (run.t0 + s - X)))
         local, t = env.get_state()
         env.sync()
-        assert np.array_equal(_np(local), run.state) and t == run.t_end == X + 14
+        assert np.array_equal(to_np(local), run.state) and t == run.t_end == X + 14
         graph.close()
         env.close()
 

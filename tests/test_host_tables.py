@@ -4,103 +4,18 @@ through ctypes.  The move table is compared with the movement lists the referenc
 outcome rows with the rules re-stated here in Python (exact integer / Fraction arithmetic for the thresholds)."""
 import ctypes
 import math
-import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
 from gym_mapf_amd.envs.grid import MapfGrid
 import mapf_oracle as mo
+from host_shim import OUTCOME, SLIP, move_tables, sizes, slip_rows, step_instances
+from host_shim import shim  # noqa: F401  (the host shim, built once per run)
+from plan_sweeps import STEP_PLAN_AGENTS, STEP_PLAN_CELLS, STEP_PLAN_CUS, STEP_PLAN_ENVS, STEP_PLAN_TUNES
 
-CSRC = os.path.join(ROOT, 'gym-mapf_amd', 'csrc')
-SLIP = np.dtype([('q', '<f8', 3), ('th', '<u4', 3), ('n', '<u4'), ('thr', '<u8', 3), ('cum', '<f8', 3), ('th_biased', '<u4'), ('members', '<u4')])
-OUTCOME = np.dtype([('reward', '<f8'), ('status', '<u4'), ('pad', '<u4')])
 LDS = 160 * 1024
-
-
-_SHIM = []      # built once per run: tests/test_cabi_and_host.py and tests/test_plan_decisions.py use the fixture too
-
-
-@pytest.fixture(scope='module')
-def shim(tmp_path_factory):
-    if not _SHIM:
-        _SHIM.append(load_shim(build_shim(tmp_path_factory.mktemp('host_tables'))))
-    return _SHIM[0]
-
-
-def build_shim(out_dir, csrc=CSRC):
-    out = os.path.join(str(out_dir), 'libhost_tables_shim.so')
-    cmd = ['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-shared', '-I' + os.path.join(ROOT, 'include'),
-           '-I' + csrc, os.path.join(ROOT, 'tests', 'host_tables_shim.hip'), os.path.join(csrc, 'mapf_tables.hip'),
-           os.path.join(csrc, 'mapf_plan.hip'), '-o', out]                          # (the Makefile's flags: no FMA contraction)
-    proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert proc.returncode == 0, proc.stdout.decode('utf-8', 'replace')[-3000:]
-    return out
-
-
-def load_shim(path):
-    lib = ctypes.CDLL(path)
-    lib.shim_slip_tables.argtypes = [ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.shim_outcome_rows.argtypes = [ctypes.c_double] * 3 + [ctypes.c_void_p]
-    lib.shim_outcome_status.argtypes = [ctypes.c_uint32]
-    lib.shim_outcome_status.restype = ctypes.c_uint32
-    lib.shim_sizes.argtypes = [ctypes.c_uint32, ctypes.c_void_p]
-    lib.shim_move_tables.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 3
-    lib.shim_scen_table.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
-    lib.shim_scen_table.restype = ctypes.c_uint32
-    lib.shim_greedy_cells.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
-    lib.shim_plan_step.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p]
-    lib.shim_plan_rollout_table.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int,
-                                            ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-    lib.shim_lq_rollout_name.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p] + \
-        [ctypes.c_int] * 5 + [ctypes.c_char_p]
-    lib.shim_table_instance_count.argtypes = [ctypes.c_int]
-    if hasattr(lib, 'shim_plan_rollout_lg'):
-        lib.shim_plan_rollout_lg.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_char_p]
-        lib.shim_plan_step_lg.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p]
-    if hasattr(lib, 'shim_plan_limit_rollout_lg'):
-        lib.shim_plan_limit_rollout_lg.argtypes = lib.shim_plan_rollout_lg.argtypes
-        lib.shim_plan_limit_step_lg.argtypes = lib.shim_plan_step_lg.argtypes
-    if hasattr(lib, 'shim_rollout_instance_exists'):
-        lib.shim_rollout_instance_exists.argtypes = [ctypes.c_int] * 4
-    if hasattr(lib, 'shim_step_instance_exists'):
-        lib.shim_step_instance_exists.argtypes = [ctypes.c_int] * 3
-        lib.shim_lq_step_name.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_char_p]
-    if hasattr(lib, 'shim_route_rollout'):
-        lib.shim_route_rollout.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p] + \
-            [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_char_p]
-        lib.shim_route_step.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p] + [ctypes.c_int] * 5 + \
-            [ctypes.c_void_p, ctypes.c_char_p]
-    return lib
-
-
-def _sizes(lib, V):
-    out = np.zeros(6, np.uint64)
-    lib.shim_sizes(V, out.ctypes.data)
-    mv_cols, delta_cols, row_bias, slip_bytes, outcome_bytes, delta_words = (int(x) for x in out)
-    assert slip_bytes == SLIP.itemsize and outcome_bytes == OUTCOME.itemsize and 8 * slip_bytes + 16 * outcome_bytes == 1024
-    return mv_cols, delta_cols, row_bias, delta_words
-
-
-def _slip_rows(lib, fail_prob):
-    rows = np.zeros(8, SLIP)
-    p_cand, flags = np.zeros(3), np.zeros(2, np.uint32)
-    assert lib.shim_slip_tables(fail_prob, rows.ctypes.data, p_cand.ctypes.data, flags.ctypes.data) == 1
-    return rows, p_cand, flags
-
-
-def _move_tables(lib, nbr, fail_prob):
-    V = len(nbr)
-    mv_cols, delta_cols, row_bias, delta_words = _sizes(lib, V)
-    mv, mv8, mv4 = np.zeros((V, mv_cols, 4), np.uint32), np.zeros((V, mv_cols, 2), np.uint32), np.zeros(delta_words, np.uint32)
-    nbr = np.ascontiguousarray(nbr, np.uint16)
-    delta8 = lib.shim_move_tables(nbr.ctypes.data, V, fail_prob, mv.ctypes.data, mv8.ctypes.data, mv4.ctypes.data)
-    assert delta8 in (0, 1)
-    return mv, mv8, (mv4 if delta8 else None)
 
 
 def _decode16(mv, slip):
@@ -128,8 +43,8 @@ def test_move_table_rows_are_the_reference_movement_lists(shim, trajectory_set):
     V = len(nbr)
     assert nbr.shape == (V, 5) and V == len(g['valid_locations'])
     for fail_prob in (meta['fail_prob'], 0.0, 1.0):
-        slip, _, _ = _slip_rows(shim, fail_prob)
-        mv, mv8, mv4 = _move_tables(shim, nbr, fail_prob)
+        slip, _, _ = slip_rows(shim, fail_prob)
+        mv, mv8, mv4 = move_tables(shim, nbr, fail_prob)
         n, cells, q = _decode16(mv, slip)
         if fail_prob == meta['fail_prob']:                        # the lists the reference wrote
             _same_lists(n[:, :5], cells[:, :5], q[:, :5], g['mv_n'], g['mv_next'], g['mv_prob'])
@@ -154,7 +69,7 @@ def test_move_table_rows_are_the_reference_movement_lists(shim, trajectory_set):
         if meta['name'].startswith('berlin256'):                    # (ids run down 256-row columns: a false case)
             assert not near
         if mv4 is not None:
-            mv_cols, delta_cols, row_bias, delta_words = _sizes(shim, V)
+            mv_cols, delta_cols, row_bias, delta_words = sizes(shim, V)
             assert delta_words % 4 == 0 and 0 <= delta_words - V * delta_cols < 4 and not mv4[V * delta_cols:].any()
             rows4 = mv4[:V * delta_cols].reshape(V, delta_cols)
             own = np.arange(V, dtype=np.int64)[:, None]
@@ -190,7 +105,7 @@ def _expected_slip_row(code, p):
 
 @pytest.mark.parametrize('fail_prob', [0.0, 0.05, 0.1, 0.2, 0.3, 1.0 / 3.0, 0.5, 0.7, 0.999, 1.0])
 def test_slip_rows_thresholds_and_members(shim, fail_prob):
-    rows, p_cand, flags = _slip_rows(shim, fail_prob)
+    rows, p_cand, flags = slip_rows(shim, fail_prob)
     rf = lf = fail_prob / 2
     p = [1 - rf - lf, rf, lf]                                      # mapf_env.py:131-132, :167
     assert p_cand.tobytes() == np.asarray(p).tobytes()
@@ -293,21 +208,6 @@ def test_greedy_policy_cells(shim):
     wrong[[0, V - 1]] = wrong[[V - 1, 0]]
     assert shim.shim_greedy_cells(nbr.ctypes.data, V, wrong.ctypes.data, cells.ctypes.data, err, 256) == 0
     assert b'cell_rc does not match the neighbour table' in err.value
-
-
-# the sweep of plan_step_lq (tests/test_plan_decisions.py digests the same one)
-STEP_PLAN_CELLS = sorted(set(list(range(2, 200, 13)) + list(range(600, 900, 17)) + list(range(3000, 3400, 23)) + list(range(4000, 7200, 97)) +
-                             [682, 683, 852, 853, 3294, 3648, 6783, 6784, 6785, 14818, 47540, 65535]))
-STEP_PLAN_TUNES = [None, b'step_big=2', b'step_big=0', b'step_delta=2', b'step_delta=0', b'step_big=2,step_delta=2', b'k=2', b'k=4',
-                   b'step_block=512', b'step_block=64', b'bitmap_pairs=0', b'quad_lanes=0']
-STEP_PLAN_CUS = (256, 8)
-STEP_PLAN_AGENTS = (2, 3, 4, 6, 8, 16, 32, 64, 128)
-STEP_PLAN_ENVS = (0, 1, 64, 1000, 1024, 4096, 16384, 65536, 131072, 262144, 1 << 20, 1 << 22)
-
-
-def step_instances(lib):
-    """the (Q, K, form) of MAPF_LQ_STEP_INSTANCES (csrc/mapf_layout.hpp): the list the planner asks and the launcher walks"""
-    return {(Q, K, form) for K in (2, 4, 8) for Q in range(1, 17) for form in range(4) if lib.shim_step_instance_exists(K, Q, form) == 1}
 
 
 def test_packed_step_plan_stays_within_the_lds_and_its_residency(shim):

@@ -2,25 +2,15 @@
 the tuning key, the limited form of plan_rollout_lq_table over the case table of tests/limit_packed_cases.py, the device listings
 of the limit unit, and the outcomes the reference shows for every case.  No compute is launched here."""
 import ctypes
-import os
-import sys
 
 import pytest
 
 import episode_limit_cases as ec
 import limit_packed_cases as lp
-from conftest import ROOT
 from gym_mapf_amd import _native as nat
-from test_cabi_and_host import ROLLOUT_PLAN_CELLS
-from test_host_tables import shim  # noqa: F401  (the host shim, built once per run)
-from test_plan_decisions import TABLE_AGENTS, TABLE_BYTES, TABLE_ENVS, TABLE_TUNES
-
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-try:
-    import device_listings
-    import kernel_meta
-finally:
-    sys.path.pop(0)
+from host_shim import device_listings, kernel_meta
+from host_shim import shim  # noqa: F401  (the host shim, built once per run)
+from plan_sweeps import ROLLOUT_PLAN_CELLS, TABLE_AGENTS, TABLE_BYTES, TABLE_ENVS, TABLE_TUNES
 
 LDS = 160 * 1024
 

@@ -8,12 +8,9 @@ import numpy as np
 import mapf_oracle as mo
 import philox
 from conftest import load_json
+from parity_checks import bits
 
 CRIT = {'Makespan': mo.MAKESPAN, 'SoC': mo.SOC}
-
-
-def _bits(x):
-    return np.asarray(x, np.float64).view(np.uint64)
 
 
 def test_scripted_cases_match_reference():
@@ -28,9 +25,9 @@ def test_scripted_cases_match_reference():
             nxt, r, done, coll, prob, was_term = env.step(st['actions'], st['uniforms'])
             tag = '%s step %d' % (case['name'], k)
             assert list(nxt) == st['next_local'], tag
-            assert _bits(r) == _bits(st['reward']), tag
+            assert bits(r) == bits(st['reward']), tag
             assert done == st['done'], tag
-            assert _bits(prob) == _bits(st['prob']), tag
+            assert bits(prob) == bits(st['prob']), tag
             assert (None if was_term else coll) == st['collision'], tag
             assert st['draws'] == (0 if was_term else len(st['actions'])), tag
             assert str(env.s) == st['s'], tag
@@ -45,10 +42,10 @@ def test_transition_tables_match_reference():
             got = env.transitions(tuple(row['local']), row['actions'])
             assert len(got) == len(row['transitions']), tab['name']
             for ((p, c), nxt, r, d), exp in zip(got, row['transitions']):
-                assert _bits(p) == _bits(exp['prob'])
+                assert bits(p) == bits(exp['prob'])
                 assert c == exp['collision'] and d == exp['done']
                 assert list(nxt) == exp['next_local']
-                assert _bits(r) == _bits(exp['reward'])
+                assert bits(r) == bits(exp['reward'])
                 assert str(mo.encode_mixed_radix(nxt, env.V)) == exp['s']
 
 
@@ -68,10 +65,10 @@ def test_inexact_transition_tables_match_reference():
             got = env.transitions(tuple(row['local']), row['actions'])
             assert len(got) == len(row['transitions']), tab['name']
             for ((p, c), nxt, r, d), exp in zip(got, row['transitions']):
-                assert _bits(p) == _bits(exp['prob'])
+                assert bits(p) == bits(exp['prob'])
                 assert c == exp['collision'] and d == exp['done']
                 assert list(nxt) == exp['next_local']
-                assert _bits(r) == _bits(exp['reward'])
+                assert bits(r) == bits(exp['reward'])
                 assert str(mo.encode_mixed_radix(nxt, env.V)) == exp['s']
 
 
@@ -92,7 +89,7 @@ def test_transition_reward_restatement_matches_reference():
             acts = mo.decode_mixed_radix(c['action'], mo.N_ACTIONS, 3)             # vector_action_to_integer: first agent least significant
             r, d, coll, living = mo.transition_reward(c['prev_local'], acts, c['next_local'], env.goal, case['rewards'],
                                                       CRIT[case['criteria']])
-            assert _bits(r) == _bits(c['reward']) and _bits(living) == _bits(c['living']), (case['rewards'], c)
+            assert bits(r) == bits(c['reward']) and bits(living) == bits(c['living']), (case['rewards'], c)
             assert (d, coll) == (c['done'], c['collision']) and coll == c['is_collision']
             assert (r, d, coll) == env.transition_reward(tuple(c['prev_local']), acts, tuple(c['next_local']))
 
@@ -109,12 +106,12 @@ def test_inexact_constants_survive_the_json_round_trip():
         meta = load_json(name + '.json')
         assert meta['criteria'] == crit, name
         for key, value in (('fail_prob', fp), ('r_clash', rc), ('r_goal', rg), ('r_living', rl)):
-            assert isinstance(meta[key], float) and _bits(meta[key]) == _bits(value), (name, key, meta[key])
+            assert isinstance(meta[key], float) and bits(meta[key]) == bits(value), (name, key, meta[key])
     sub = load_json('inexact_goals_a16_slip13_soc_noreset.json')
     assert sub['r_living'] != 0.0 and sub['r_living'] == -2.0 ** -1074 and sub['r_living'] / 2 == 0.0
     assert sub['fail_prob'] == 1.0 / 3.0 and sub['auto_reset'] is False
     helper = load_json('inexact_cases.json')['transition_reward_helpers']
-    assert len(helper) == 1 and helper[0]['criteria'] == 'SoC' and [_bits(x) for x in helper[0]['rewards']] == [_bits(x) for x in (-0.3, 0.7, -0.1)]
+    assert len(helper) == 1 and helper[0]['criteria'] == 'SoC' and [bits(x) for x in helper[0]['rewards']] == [bits(x) for x in (-0.3, 0.7, -0.1)]
 
 
 def test_trajectories_match_reference(trajectory_set):
@@ -131,7 +128,7 @@ def test_trajectories_match_reference(trajectory_set):
             n = int(g['mv_n'][v, a])
             assert len(dist) == n
             assert [c for c, _ in dist] == list(g['mv_next'][v, a, :n])
-            assert np.array_equal(_bits([p for _, p in dist]), _bits(g['mv_prob'][v, a, :n]))
+            assert np.array_equal(bits([p for _, p in dist]), bits(g['mv_prob'][v, a, :n]))
     for j, env_id in enumerate(g['env_ids']):
         env = mo.OracleEnv(meta['lines'], A, g['start_loc'][j].tolist(), g['goal_loc'][j].tolist(),
                            meta['fail_prob'], meta['r_clash'], meta['r_goal'], meta['r_living'], crit)
@@ -139,7 +136,7 @@ def test_trajectories_match_reference(trajectory_set):
         assert list(env.goal) == list(g['goal_local'][j])
         us = np.stack([philox.slip_uniforms_np(meta['seed'], [env_id], t, A)[0] for t in range(T)])
         nu = g['uniforms'].shape[0]
-        assert np.array_equal(_bits(us[:nu]), _bits(g['uniforms'][:, j]))
+        assert np.array_equal(bits(us[:nu]), bits(g['uniforms'][:, j]))
         acts = np.stack([philox.random_actions_np(meta['seed'], [env_id], t, A)[0] for t in range(T)])
         scripted = 'actions_from' in meta            # goal-seeking sets: only every fifth step is the policy stream
         if scripted:
@@ -155,8 +152,8 @@ def test_trajectories_match_reference(trajectory_set):
             nxt, r, done, coll, prob, was_term = env.step(acts[t].tolist(), us[t].tolist())
             tag = '%s env %d t %d' % (meta['name'], int(env_id), t)
             assert list(nxt) == list(g['next_local'][t, j]), tag
-            assert _bits(r) == _bits(g['reward'][t, j]), tag
-            assert _bits(prob) == _bits(g['prob'][t, j]), tag
+            assert bits(r) == bits(g['reward'][t, j]), tag
+            assert bits(prob) == bits(g['prob'][t, j]), tag
             assert done == bool(g['done'][t, j]) and coll == bool(g['collision'][t, j]), tag
             assert was_term == bool(g['was_terminal'][t, j]), tag
             if t < 4:
@@ -176,8 +173,8 @@ def _c_oracle_for(meta, g, env_sel, env_id_offset, use_seed=True):
 
 def _compare_step(out, g, t, sel, tag):
     assert np.array_equal(out['local'], g['next_local'][t][sel]), tag
-    assert np.array_equal(_bits(out['reward']), _bits(g['reward'][t][sel])), tag
-    assert np.array_equal(_bits(out['prob']), _bits(g['prob'][t][sel])), tag
+    assert np.array_equal(bits(out['reward']), bits(g['reward'][t][sel])), tag
+    assert np.array_equal(bits(out['prob']), bits(g['prob'][t][sel])), tag
     assert np.array_equal(out['done'], g['done'][t][sel]), tag
     assert np.array_equal(out['collision'], g['collision'][t][sel]), tag
     assert np.array_equal(out['was_terminal'], g['was_terminal'][t][sel]), tag
@@ -217,7 +214,7 @@ def test_c_oracle_rollout_returns(trajectory_set):
         ret = 0.0
         for t in range(T):
             ret = ret + g['reward'][t, j]
-        assert _bits(out['returns'][0]) == _bits(ret)
+        assert bits(out['returns'][0]) == bits(ret)
         assert out['episodes'][0] == g['done'][:, j].sum() and out['collisions'][0] == g['collision'][:, j].sum()
 
 

@@ -7,7 +7,7 @@ change of any decision names its group here.
 
 The lane-group planners -- plan_rollout_lg and plan_step_lg -- take every launch the packed kernels decline.  Their recorded
 decisions are those of the commit before they existed, when the launchers decided inline and only mapf_last_kernel showed what
-they decided: every shape of the sweep below was launched once on an MI355X (a one-step rollout, a step) and the kernel's name
+they decided: every shape of the LG_* sweep (tests/plan_sweeps.py) was launched once on an MI355X (a one-step rollout, a step) and the kernel's name
 parsed into the fields a plan holds.  The fixture keeps them per shape ('-' = a packed kernel took the launch), and the full name
 of one shape per distinct name.  The comparison involves no GPU; one GPU test launches a shape of every kind.
 
@@ -18,7 +18,7 @@ built from the tree's sources); `packed` / `lane_group` alone re-records those g
 `lane_group` needs a GPU.
 
 The limit instances of the lane-group family (mapf_lg_limit.hip) are named by the same two planners, asked for a limit plan.  Their
-plans and full names over LIMIT_* below are compared with tests/golden/plan_decisions_limit.json, recorded on the CPU from the
+plans and full names over LIMIT_* (tests/plan_sweeps.py) are compared with tests/golden/plan_decisions_limit.json, recorded on the CPU from the
 commit that still had a planner and name functions of their own for them (tests/golden/generation_info.json says how):
 
     python tests/test_plan_decisions.py --record-limit [OUT.json]
@@ -31,7 +31,7 @@ whose launchers still formatted these names themselves (MAPF_HIP_LIB; generation
     python tests/test_plan_decisions.py --record-lq-names [OUT.json]
 
 The packed single step is named by lq_step_kernel_name.  tests/golden/lq_step_kernel_names.json holds what mapf_last_kernel said after
-a step of every launch of LQ_STEP_LAUNCHES below -- every entry of the step's instance list, with and without the scenario table, a step
+a step of every launch of LQ_STEP_LAUNCHES (tests/plan_sweeps.py) -- every entry of the step's instance list, with and without the scenario table, a step
 that may meet a terminal env and one that cannot -- on an MI355X, from the library of the commit whose launcher still formatted these
 names itself:
 
@@ -46,61 +46,27 @@ import tempfile
 
 import pytest
 
-if __name__ == '__main__':
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from conftest import GOLDEN
-from test_cabi_and_host import ROLLOUT_PLAN_AGENTS, ROLLOUT_PLAN_CELLS, ROLLOUT_PLAN_ENVS, ROLLOUT_PLAN_TUNES
-from test_host_tables import STEP_PLAN_AGENTS, STEP_PLAN_CELLS, STEP_PLAN_CUS, STEP_PLAN_ENVS, STEP_PLAN_TUNES, build_shim, load_shim
-from test_host_tables import shim  # noqa: F401  (the host shim, built once per run)
+from host_shim import build_shim, load_shim, step_instances
+from host_shim import shim  # noqa: F401  (the host shim, built once per run)
+from plan_sweeps import (FIXTURE, FIXTURE_LQ_NAMES, FIXTURE_LQ_STEP_NAMES, KERNEL_NAME_BYTES, LG_AGENTS, LG_ENVS, LG_MAPS, LG_PACKED, LG_ROLLOUTS, LG_STEPS, LIMIT_AGENTS,
+                         LIMIT_CELLS, LIMIT_ENVS, LQ_STEP_LAUNCHES, LQ_TABLE_ROWS, PACKED, PREFER_LG, ROLLOUT_PLAN_AGENTS, ROLLOUT_PLAN_CELLS, ROLLOUT_PLAN_ENVS,
+                         ROLLOUT_PLAN_TUNES, STEP_PLAN_AGENTS, STEP_PLAN_CELLS, STEP_PLAN_CUS, STEP_PLAN_ENVS, STEP_PLAN_TUNES, TABLE_AGENTS, TABLE_BYTES, TABLE_ENVS,
+                         TABLE_TUNES, LaneGroupLauncher, launch_lq, lg_key, lg_shapes, lq_fixture, lq_step_fixture, parse_lg_key, plan_fixture, planned_rollout_lg,
+                         planned_step_lg, routed_rollout, routed_step, tune_name, tuned_env)
 
-FIXTURE = os.path.join(GOLDEN, 'plan_decisions.json')
 NOT_PACKED = b'-'
-TABLE_AGENTS, TABLE_ENVS = (4, 8, 16, 32, 64), (1024, 16384, 65536, 262144)
-TABLE_BYTES = (1, 8, 64)                                               # policy tables of V, 8 V and 64 V action bytes
-TABLE_TUNES = (None, b'policy_table_lds=0', b'policy_table_lds=1')
-# the lane-group sweep: the smallest shapes at which each rule can go wrong -- odd teams and every group size; batches around one
-# wave, the 64 * 256 threads the LDS table needs, the 2^17 threads of the four-wave block and whole / ragged blocks; maps whose
-# move table leaves >= 4, 2, 2 and 1 copies per CU (the last only with the limit lifted)
-LG_AGENTS = (1, 2, 3, 5, 8, 16, 17, 31, 32, 33, 128)
-LG_ENVS = (1, 63, 64, 257, 4096, 8191, 8192, 16384, 65536)
-LG_MAPS = ((10, 10), (22, 31), (25, 40), (30, 50))                     # empty maps of 100, 682, 1000 and 1500 free cells
-LG_TUNES = (None, b'quad_lanes=0', b'quad_lanes=0,mv_lds_max_bytes=163840', b'mv_lds_max_bytes=0')
-LG_ROLLOUTS = tuple((record, policy) for record in (0, 1) for policy in (0, 1, 2))   # policy: streamed actions, policy stream, table policy
-LG_STEPS = (0, 1)                                                      # caller uniforms
-LG_PACKED = '-'
 LG_ROLLOUT_NAME = re.compile(r'^lg_rollout_kernel(_table)?<L=(\d+),(FULL|RAGGED),(MV_LDS|MV_GLOBAL),(RECORD|TOTALS),(STREAM|POLICY|TABLE),(DENSE|GUARDED)> block=(\d+) ')
 LG_STEP_NAME = re.compile(r'^lg_step_kernel<L=(\d+),(FULL|RAGGED),(EXT_UNIFORMS|PHILOX)> block=(\d+) ')
 LG_ROLLOUT_CODE, LG_STEP_CODE = re.compile(r'^(\d+)([FR])([LG])([DG])(\d+)$'), re.compile(r'^(\d+)([FR])(\d+)$')   # (lg_rollout_code, lg_step_code)
-# the limit instances: every L, full and ragged; one-wave and four-wave blocks, MV_GLOBAL and MV_LDS, ragged and full last blocks; a
-# table of 4 copies per CU, of 2, and one no LDS holds
 FIXTURE_LIMIT = os.path.join(GOLDEN, 'plan_decisions_limit.json')
-LIMIT_AGENTS = (1, 2, 3, 5, 8, 16, 17, 32, 33, 64, 128)
-LIMIT_ENVS = (1, 63, 64, 4096, 65536)
-LIMIT_CELLS = (16, 683, 3300)
-KERNEL_NAME_BYTES = 160                                                # what mapf_last_kernel keeps of a name (the terminator included)
-# the packed names: every launch on the 20 x 20 map of the limit cases (V = 341, delta rows present), a table of LQ_TABLE_ROWS rows
-FIXTURE_LQ_NAMES = os.path.join(GOLDEN, 'lq_kernel_names.json')
-LQ_TABLE_ROWS = 64
 # (criteria, auto-reset): no env of these launches starts terminal, so a launch may meet a terminal env exactly without auto-reset
 LQ_VARIANTS = {'SOC': ('SoC', True), 'MAKESPAN': ('Makespan', False), 'NO_TERMINAL': ('Makespan', True)}
 LQ_POLICIES = ('STREAM', 'POLICY', 'TABLE')
-# the packed step's names: every instance on the same map at the smallest batch of full blocks its form accepts -- the plain step in
-# one-wave blocks (two agents per lane: k=2), the LDS-table form in its 1024-thread blocks (eight agents per lane unless k=4), the
-# delta-row forms in 512-thread blocks
-FIXTURE_LQ_STEP_NAMES = os.path.join(GOLDEN, 'lq_step_kernel_names.json')
-STEP_FORMS = ('Plain', 'FullRows', 'DeltaRows', 'DeltaRowsBitmap')   # StepForm's numbers; what a name says of each: its tag, its block
-STEP_FORM_TAG, STEP_FORM_BLOCK = ('', ',BIG', ',DELTA', ',DELTA,BITMAP'), (64, 1024, 512, 512)
-LQ_STEP_LAUNCHES = {'%s-K%d-Q%d' % (STEP_FORMS[form], K, Q): (form, K, Q, E, tune) for form, K, Q, E, tune in
-                    [(0, 4, Q, max(64, 512 // Q), '') for Q in (1, 2, 4, 8, 16)] + [(0, 2, Q, max(64, 512 // Q), 'k=2') for Q in (2, 4, 8, 16)] +
-                    [(1, 4, Q, 1024 // Q, 'step_big=2,k=4') for Q in (1, 2, 4, 8)] + [(1, 8, Q, 1024 // Q, 'step_big=2') for Q in (1, 2, 4)] +
-                    [(2, 4, Q, 512 // Q, 'step_delta=2,bitmap_pairs=0') for Q in (1, 2, 4, 8)] + [(3, 4, 8, 64, 'step_delta=2')]}
+STEP_FORM_TAG, STEP_FORM_BLOCK = ('', ',BIG', ',DELTA', ',DELTA,BITMAP'), (64, 1024, 512, 512)   # what a name says of each StepForm: its tag, its block
 # (scenario table, may be terminal): the handles' rows come from five scenarios, so MAPF_TUNE scen_table=0 is what leaves the table out;
 # no env starts terminal, so a step may meet a terminal env exactly when the step before it ran without auto-reset
 LQ_STEP_VARIANTS = {'%s %s' % ('SCEN' if scen else 'ROWS', 'TERMINAL' if term else 'NO_TERMINAL'): (scen, term) for scen in (True, False) for term in (True, False)}
-
-
-def _name(tune):
-    return tune.decode() if tune else 'default'
 
 
 def rollout_digests(lib):
@@ -121,7 +87,7 @@ def rollout_digests(lib):
                                     rc = plan(V, A, E, T, streamed, delta, n_cu, tune, out)
                                     assert rc in (0, 1), (rc, tune)
                                     h.update(bytes(out) if rc else NOT_PACKED)
-                            digests['%s A=%d streamed=%d delta=%d n_cu=%d T=%d' % (_name(tune), A, streamed, delta, n_cu, T)] = h.hexdigest()
+                            digests['%s A=%d streamed=%d delta=%d n_cu=%d T=%d' % (tune_name(tune), A, streamed, delta, n_cu, T)] = h.hexdigest()
     return digests
 
 
@@ -132,7 +98,7 @@ def table_plans(shim_lib):
         for A in TABLE_AGENTS:
             for mult in TABLE_BYTES:
                 for delta in (0, 1):
-                    group = '%s A=%d table_bytes=%dV delta=%d' % (_name(tune), A, mult, delta)
+                    group = '%s A=%d table_bytes=%dV delta=%d' % (tune_name(tune), A, mult, delta)
                     for E in TABLE_ENVS:
                         for V in ROLLOUT_PLAN_CELLS:
                             rc = shim_lib.shim_plan_rollout_table(V, A, E, 64, delta, mult * V, 256, tune, 0, out, None)
@@ -161,20 +127,8 @@ def step_digests(shim_lib):
                             rc = shim_lib.shim_plan_step(V, A, E, delta, n_cu, tune, out)
                             assert rc in (0, 1), (rc, tune)
                             h.update(bytes(out) if rc else NOT_PACKED)
-                digests['%s n_cu=%d A=%d' % (_name(tune), n_cu, A)] = h.hexdigest()
+                digests['%s n_cu=%d A=%d' % (tune_name(tune), n_cu, A)] = h.hexdigest()
     return digests
-
-
-def lg_key(tune, V, A, E):
-    return '%s V=%d A=%d E=%d' % (_name(tune), V, A, E)
-
-
-def lg_shapes():
-    for tune in LG_TUNES:
-        for rows, cols in LG_MAPS:
-            for A in LG_AGENTS:
-                for E in LG_ENVS:
-                    yield tune, rows, cols, A, E
 
 
 def lg_rollout_code(name, record, policy):
@@ -199,44 +153,6 @@ def lg_step_code(name, uniforms):
     L, full, ext, block = m.groups()
     assert ext == ('EXT_UNIFORMS' if uniforms else 'PHILOX'), name
     return '%s%s%s' % (L, full[0], block)
-
-
-def planned_rollout_lg(shim_lib, tune, V, A, E, record, policy):
-    """plan_rollout_lg through the shim: (code, grid, lds_bytes, the name the launcher notes)"""
-    out, name = (ctypes.c_uint64 * 7)(), ctypes.create_string_buffer(2 * KERNEL_NAME_BYTES)
-    rc = shim_lib.shim_plan_rollout_lg(V, A, E, record, policy, tune, out, name)
-    assert rc == 1, (rc, tune)
-    L, full, mv_lds, dense, block, grid, lds_bytes = out
-    return '%d%s%s%s%d' % (L, 'F' if full else 'R', 'L' if mv_lds else 'G', 'D' if dense else 'G', block), grid, lds_bytes, name.value.decode()
-
-
-def planned_step_lg(shim_lib, A, E, uniforms):
-    out, name = (ctypes.c_uint64 * 4)(), ctypes.create_string_buffer(2 * KERNEL_NAME_BYTES)
-    assert shim_lib.shim_plan_step_lg(A, E, uniforms, out, name) == 1
-    L, full, block, grid = out
-    return '%d%s%d' % (L, 'F' if full else 'R', block), grid, name.value.decode()
-
-
-# the route (route_rollout, route_step: tests/test_route.py has their tests)
-AUTO, PREFER_TPE, PREFER_LG = 0, 1, 2                                  # FamilyPreference's numbers (csrc/mapf_kernels.hpp)
-TPE, PACKED, LG = 0, 1, 2                                              # KernelFamily's numbers (csrc/mapf_plan.hpp)
-N_CU = 256                                                             # the MI355X the fixtures were recorded on
-
-
-def routed_rollout(shim_lib, V, A, E, prefer, policy, tune=None, *, delta=1, table_bytes=None, n_cu=N_CU, limited=0, budgeted=0, record=0, soc=0, term=0):
-    """route_rollout over a one-step launch, through the shim: (family, the plan's nine fields, the name its launcher notes)"""
-    out, name = (ctypes.c_uint64 * 9)(), ctypes.create_string_buffer(2 * KERNEL_NAME_BYTES)
-    table_bytes = (V if policy == 2 else 0) if table_bytes is None else table_bytes
-    family = shim_lib.shim_route_rollout(V, A, E, delta, table_bytes, n_cu, tune, prefer, policy, limited, budgeted, record, soc, term, out, name)
-    assert family in (TPE, PACKED, LG), (family, tune)
-    return family, tuple(out), name.value.decode()
-
-
-def routed_step(shim_lib, V, A, E, prefer, uniforms, tune=None, *, delta=1, n_cu=N_CU, limited=0, scen=0, term=0):
-    out, name = (ctypes.c_uint64 * 8)(), ctypes.create_string_buffer(2 * KERNEL_NAME_BYTES)
-    family = shim_lib.shim_route_step(V, A, E, delta, n_cu, tune, prefer, limited, uniforms, scen, term, out, name)
-    assert family in (TPE, PACKED, LG), (family, tune)
-    return family, tuple(out), name.value.decode()
 
 
 def limit_plans(shim_lib):
@@ -269,38 +185,6 @@ def lq_launches():
                 tune = c.tune_bytes(table_lds, limit_packed=limited).decode()
                 parts = c.name_parts(table_lds) if limited else ('lq_rollout_kernel_table<Q=%d,K=%d,' % (c.Q, c.K),) + c.name_parts(table_lds)[1:2] + c.name_parts(table_lds)[3:]
                 yield '%s lds=%d limit=%d' % (c.id, table_lds, limited), 'table', c.A, c.E, tune, 'TABLE', limited, parts
-
-
-def tuned_env(grid, A, E, tune, criteria, start, goal):
-    """a handle created under MAPF_TUNE = `tune` (read when the handle is created)"""
-    from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
-    outer_tune = os.environ.pop('MAPF_TUNE', None)
-    os.environ['MAPF_TUNE'] = tune
-    try:
-        return VecMapfEnv(grid, A, None, None, 0.2, -1000.0, 100.0, -1.0, OptimizationCriteria[criteria], n_envs=E, start_local=start, goal_local=goal)
-    finally:
-        os.environ.pop('MAPF_TUNE', None)
-        if outer_tune is not None:
-            os.environ['MAPF_TUNE'] = outer_tune
-
-
-def launch_lq(grid, A, E, tune, policy, limited, criteria, runs):
-    """a handle of that shape under `tune`, and the names of its one-step rollouts `runs` = [(auto_reset, record), ...]"""
-    import numpy as np
-    V = len(grid.tables()[0])
-    env = tuned_env(grid, A, E, tune, criteria, np.arange(A), np.arange(A) + 1)
-    try:
-        if policy == 'TABLE':
-            env.set_policy('table', table=np.zeros((LQ_TABLE_ROWS, V), np.uint8), rows=np.zeros(A, np.uint16))
-        if limited:
-            env.set_episode_limit(4)
-        names = []
-        for auto_reset, record in runs:
-            env.rollout(1, actions=np.zeros((1, E, A), np.uint8) if policy == 'STREAM' else None, auto_reset=auto_reset, record=record)
-            names.append(env.last_kernel('rollout'))
-        return names
-    finally:
-        env.close()
 
 
 def record_lq_names(n_cu):
@@ -381,53 +265,6 @@ def planned_lq_step(shim_lib, n_cu, launch, scen, term):
     return ((out[1], out[0], out[2]), name.value.decode()) if rc else None
 
 
-class LaneGroupLauncher:
-    """Launches the shapes of the lane-group sweep on the GPU and reads mapf_last_kernel: device-mode handles of the lane-group
-    family on empty maps, rows broadcast, inputs shared by all shapes."""
-
-    def __init__(self):
-        import numpy as np
-        import torch
-        from gym_mapf_amd.envs.grid import MapfGrid
-        from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv
-        self.np, self.torch, self.make_grid, self.make_env, self.criteria = np, torch, MapfGrid, VecMapfEnv, OptimizationCriteria.Makespan
-        n = max(LG_ENVS) * max(LG_AGENTS)
-        self.actions = torch.zeros(n, dtype=torch.uint8, device='cuda')
-        self.uniforms = torch.full((n,), 0.5, dtype=torch.float64, device='cuda')
-        self.grids = {}
-
-    def names(self, tune, rows, cols, A, E):
-        """the kernel names of the shape's six one-step rollouts (LG_ROLLOUTS) and two steps (LG_STEPS)"""
-        np, outer_tune = self.np, os.environ.pop('MAPF_TUNE', None)
-        if tune:
-            os.environ['MAPF_TUNE'] = tune.decode()             # (read when the handle is created)
-        if (rows, cols) not in self.grids:
-            self.grids[rows, cols] = self.make_grid(['.' * cols] * rows)
-        V = rows * cols
-        env = self.make_env(self.grids[rows, cols], A, None, None, 0.2, -1000.0, 100.0, -1.0, self.criteria, n_envs=E, device_arrays=True,
-                            start_local=np.arange(A) % V, goal_local=(np.arange(A) + 1) % V, kernel='lane_group')
-        try:
-            rollouts = {}
-            for table in (False, True):
-                if table:
-                    env.set_policy('table', table=np.zeros((1, V), dtype=np.uint8), rows=np.zeros(A, dtype=np.uint16))
-                for record, policy in LG_ROLLOUTS:
-                    if (policy == 2) == table:
-                        env.rollout(1, actions=self.actions[:E * A].view(1, E, A) if policy == 0 else None, record=bool(record))
-                        rollouts[record, policy] = env.last_kernel('rollout')
-            steps = []
-            for uniforms in LG_STEPS:
-                env.step(self.actions[:E * A].view(E, A), uniforms=self.uniforms[:E * A].view(E, A) if uniforms else None)
-                steps.append(env.last_kernel('step'))
-            env.sync()
-        finally:
-            env.close()
-            os.environ.pop('MAPF_TUNE', None)
-            if outer_tune is not None:
-                os.environ['MAPF_TUNE'] = outer_tune
-        return [rollouts[r] for r in LG_ROLLOUTS], steps
-
-
 def record_lane_group():
     """the two lane-group groups and the kept names: of every distinct name, the smallest shape that printed it"""
     launcher = LaneGroupLauncher()
@@ -442,13 +279,8 @@ def record_lane_group():
                 if name.startswith('lg_') and (name not in kept or E * A < kept[name][0]):
                     kept[name] = (E * A, '%s|%d|%s' % (planner, i, key))
         if E == LG_ENVS[-1] and A == LG_AGENTS[-1]:
-            print('launched %s V=%d' % (_name(tune), rows * cols), flush=True)
+            print('launched %s V=%d' % (tune_name(tune), rows * cols), flush=True)
     return rollouts, steps, {name: where for name, (_, where) in kept.items()}
-
-
-def parse_lg_key(key):
-    tune, V, A, E = key.split(' ')
-    return (None if tune == 'default' else tune.encode()), int(V[2:]), int(A[2:]), int(E[2:])
 
 
 def _compare(planner, found):
@@ -489,17 +321,12 @@ def test_step_plan_decisions_are_the_recorded_ones(shim):  # noqa: F811
     _compare('plan_step_lq', step_digests(shim))
 
 
-def _fixture():
-    with open(FIXTURE) as f:
-        return json.load(f)
-
-
 def test_lane_group_plans_are_the_recorded_ones(shim):  # noqa: F811
     """plan_rollout_lg and plan_step_lg decide what the inline launchers decided on the GPU, shape by shape; the grid follows from
     block, L and E, the dynamic LDS segment is the move table or nothing; the kept names are formatted byte for byte.  Where a
     packed kernel took the launch there is no lane-group plan to compare: the route must say packed there (tests/test_route.py
     compares the route with every entry) -- none with the packed layout off, and no more than half of the sweep in all."""
-    recorded = _fixture()
+    recorded = plan_fixture()
     rollouts, steps, names = recorded['plan_rollout_lg'], recorded['plan_step_lg'], recorded['lg_kernel_names']
     keys = [lg_key(tune, rows * cols, A, E) for tune, rows, cols, A, E in lg_shapes()]
     assert len(keys) == 4 * 4 * 11 * 9 and sorted(keys) == sorted(rollouts) == sorted(steps)
@@ -562,15 +389,10 @@ def test_limit_plans_and_names_are_the_recorded_ones(shim):  # noqa: F811
         assert fields.split(' ')[3] == '0' and '_limit_guarded<' in name and ',LIMIT> ' in name and len(name) < KERNEL_NAME_BYTES, line
 
 
-def _lq_fixture():
-    with open(FIXTURE_LQ_NAMES) as f:
-        return json.load(f)
-
-
 def test_packed_rollout_names_are_the_recorded_ones(shim):  # noqa: F811
     """the planner and lq_rollout_kernel_name, asked for every launch of the fixture, against what the launchers' own format strings
     printed on the GPU before the name had one function: byte for byte, and shorter than what mapf_last_kernel keeps"""
-    recorded = _lq_fixture()
+    recorded = lq_fixture()
     launches, n = recorded['launches'], 0
     wanted = list(lq_launches())
     assert sorted(launches) == sorted(w[0] for w in wanted) and len(wanted) == 20 * 2 + 9 * 2 * 2
@@ -597,7 +419,7 @@ def test_packed_launches_print_the_recorded_names():
     """the launcher that takes a plan notes the name the plan's name function gives: a launch of every packed family, without terminal
     handling and totals only, then with it and recording, each compared in full with the recorded name"""
     import episode_limit_cases as ec
-    launches, grid = _lq_fixture()['launches'], ec.random_map(3)
+    launches, grid = lq_fixture()['launches'], ec.random_map(3)
     for key in LQ_GPU_LAUNCHES:
         launch = launches[key]
         assert (launch['A'], launch['E']) in ((32, 1024), (32, 2048), (4, 512), (32, 128)) and launch['V'] == len(grid.tables()[0]), key
@@ -605,16 +427,10 @@ def test_packed_launches_print_the_recorded_names():
         assert found == [launch['names']['NO_TERMINAL TOTALS'], launch['names']['MAKESPAN RECORD']], (key, found)
 
 
-def _lq_step_fixture():
-    with open(FIXTURE_LQ_STEP_NAMES) as f:
-        return json.load(f)
-
-
 def test_packed_step_names_are_the_recorded_ones(shim):  # noqa: F811
     """plan_step_lq and lq_step_kernel_name, asked for every step of the fixture, against what the launcher's own format strings printed
     on the GPU before the name had a function: byte for byte, shorter than what mapf_last_kernel keeps, every instance of the list"""
-    from test_host_tables import step_instances
-    recorded = _lq_step_fixture()
+    recorded = lq_step_fixture()
     launches, names, seen = recorded['launches'], set(), set()
     assert sorted(launches) == sorted(LQ_STEP_LAUNCHES) and len(launches) == 21
     for key, (form, K, Q, E, tune) in LQ_STEP_LAUNCHES.items():
@@ -640,7 +456,7 @@ def test_packed_step_launches_print_the_recorded_names():
     """the step's launcher notes the name the plan's name function gives: a launch of every form, a step that may be terminal and then
     one after an auto-reset step, each compared in full with the recorded name"""
     import episode_limit_cases as ec
-    launches, grid = _lq_step_fixture()['launches'], ec.random_map(3)
+    launches, grid = lq_step_fixture()['launches'], ec.random_map(3)
     for key, scen in LQ_STEP_GPU_LAUNCHES:
         launch, rows = launches[key], 'SCEN' if scen else 'ROWS'
         assert launch['E'] <= 1024 and launch['V'] == len(grid.tables()[0]), key
@@ -675,7 +491,7 @@ def lg_kinds(recorded):
 def test_lane_group_launches_print_the_recorded_names():
     """the launcher that takes a plan launches the instance the plan names: a shape of every kind of the sweep, each compared with
     the name recorded for it"""
-    kinds = lg_kinds(_fixture())
+    kinds = lg_kinds(plan_fixture())
     assert len(kinds) == 13, sorted(kinds, key=str)              # FULL: 2 x 2 x 2, RAGGED (never dense): 2 x 2, the cap
     launcher = LaneGroupLauncher()
     for kind, (key, i, name) in sorted(kinds.items(), key=str):

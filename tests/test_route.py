@@ -19,13 +19,11 @@ import sys
 
 import pytest
 
-if __name__ == '__main__':
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from conftest import GOLDEN
-from test_host_tables import shim  # noqa: F401  (the host shim, built once per run)
-from test_plan_decisions import (AUTO, KERNEL_NAME_BYTES, LG, LG_MAPS, LG_PACKED, LG_ROLLOUTS, LG_STEPS, LIMIT_AGENTS, LIMIT_CELLS, LIMIT_ENVS, N_CU, PACKED, PREFER_LG,
-                                 PREFER_TPE, TPE, LaneGroupLauncher, _fixture, _lq_fixture, launch_lq, lg_key, lg_shapes, parse_lg_key, planned_rollout_lg,
-                                 planned_step_lg, routed_rollout, routed_step)
+from host_shim import shim  # noqa: F401  (the host shim, built once per run)
+from plan_sweeps import (AUTO, KERNEL_NAME_BYTES, LG, LG_MAPS, LG_PACKED, LG_ROLLOUTS, LG_STEPS, LIMIT_AGENTS, LIMIT_CELLS, LIMIT_ENVS, N_CU, PACKED, PREFER_LG,
+                         PREFER_TPE, TPE, LaneGroupLauncher, launch_lq, lg_key, lg_shapes, lq_fixture, parse_lg_key, plan_fixture, planned_rollout_lg, planned_step_lg,
+                         routed_rollout, routed_step)
 
 FIXTURE_TPE = os.path.join(GOLDEN, 'tpe_kernel_names.json')
 TPE_ENVS = (1 << 18, (1 << 18) + 1)                                    # the block rule: 64 threads up to 2^18 envs, 256 beyond
@@ -37,7 +35,7 @@ def test_routes_of_the_lane_group_sweep_are_the_recorded_ones(shim):  # noqa: F8
     """every launch of the recorded sweep (handles that prefer the lane-group family, 256 CUs, the table policy's table of V bytes, delta
     rows as every one of these empty maps of at most 127 rows has them): packed exactly where a packed kernel took the launch on the GPU,
     elsewhere lane-group with the very plan and name plan_rollout_lg / plan_step_lg give"""
-    recorded = _fixture()
+    recorded = plan_fixture()
     rollouts, steps = recorded['plan_rollout_lg'], recorded['plan_step_lg']
     assert all(rows <= 127 for rows, _ in LG_MAPS)
     n, n_packed, wrong = 0, 0, []
@@ -226,7 +224,7 @@ def test_every_route_branch_launches_what_the_route_names(shim):  # noqa: F811
     finally:
         empty.close()
     # packed rollout and packed step: the smallest shapes of the lane-group sweep whose fixture code is '-'
-    recorded, launcher = _fixture(), LaneGroupLauncher()
+    recorded, launcher = plan_fixture(), LaneGroupLauncher()
     index_of = {lg_key(tune, rows * cols, A, E): i for i, (tune, rows, cols, A, E) in enumerate(lg_shapes())}
     for codes, kind in ((recorded['plan_rollout_lg'], 'rollout'), (recorded['plan_step_lg'], 'step')):
         key, i = smallest_packed(codes, index_of)
@@ -241,7 +239,7 @@ def test_every_route_branch_launches_what_the_route_names(shim):  # noqa: F811
             family, _, name = routed_step(shim, V_key, A, E, PREFER_LG, 0, tune, n_cu=n_cu)
             assert i == 0 and family == PACKED and step_names[0] == name and A * E <= 32768, (key, i, step_names[0], name)
     # packed under a limit: the smallest case of tests/limit_packed_cases.py, as the packed-name fixture launches it
-    launch = _lq_fixture()['launches']['k2-4x512 lds=0 limit=1']
+    launch = lq_fixture()['launches']['k2-4x512 lds=0 limit=1']
     found = launch_lq(ec.random_map(3), launch['A'], launch['E'], launch['tune'], 'TABLE', True, 'Makespan', [(True, False)])
     family, out, name = routed_rollout(shim, launch['V'], launch['A'], launch['E'], AUTO, 2, launch['tune'].encode(), table_bytes=launch['table_bytes'], n_cu=n_cu,
                                        limited=1)

@@ -7,9 +7,9 @@ import numpy as np
 import pytest
 
 import step_cases as sc
-from test_host_tables import _move_tables, _slip_rows
-from test_host_tables import shim  # noqa: F401  (the host shim, built once per run)
-from test_plan_decisions import KERNEL_NAME_BYTES, LQ_STEP_LAUNCHES, PACKED, _lq_step_fixture, routed_step
+from host_shim import move_tables, slip_rows
+from host_shim import shim  # noqa: F401  (the host shim, built once per run)
+from plan_sweeps import KERNEL_NAME_BYTES, LQ_STEP_LAUNCHES, PACKED, lq_step_fixture, routed_step
 
 SHAPES = list({(c.key, c.E): c for c in sc.CASES}.values())               # (the three grids of a chunk walk share their runs)
 
@@ -39,8 +39,8 @@ def test_the_instance_cases_are_the_recorded_launches(shim):  # noqa: F811
     for c in sc.INSTANCE_CASES:
         form, K, Q, E, tune = LQ_STEP_LAUNCHES[c.key]
         assert (c.form, c.K, c.Q, c.tune) == (form, K, Q, tune) and c.E in (E, 2 * E) and 64 <= c.E <= 1024, c.id
-    assert the_cells() == 341 == _lq_step_fixture()['launches']['Plain-K4-Q1']['V']
-    assert _move_tables(shim, sc.the_map()[1], 0.2)[2] is not None
+    assert the_cells() == 341 == lq_step_fixture()['launches']['Plain-K4-Q1']['V']
+    assert move_tables(shim, sc.the_map()[1], 0.2)[2] is not None
     assert len({c.id for c in sc.CASES}) == len(sc.CASES)
     for c in sc.CASES:
         assert all(s in sc.SEEDS_SEARCHED for s in c.seeds), c.id
@@ -50,7 +50,7 @@ def test_every_case_plans_its_instance_and_the_table_names_all_84_kernels(shim):
     """route_step, asked at the fixture's CU count as the dispatcher asks it: the packed family and exactly the case's (Q, K, form),
     with and without the scenario table, terminal test or not; the names are the fixture's in full (a name says nothing of the batch
     or the grid), and over the table they are all 84"""
-    recorded = _lq_step_fixture()
+    recorded = lq_step_fixture()
     names = set()
     for case in sc.CASES:
         for scen in (True, False):
@@ -69,7 +69,7 @@ def test_every_case_plans_its_instance_and_the_table_names_all_84_kernels(shim):
 @pytest.mark.parametrize('case', sc.WALK_CASES, ids=lambda c: c.id)
 def test_chunk_walk_geometry(case, shim):  # noqa: F811
     """seven chunks; step_grid blocks under the key, seven without it (one chunk per block: what the suite ran before the key)"""
-    n_cu = _lq_step_fixture()['n_cu']
+    n_cu = lq_step_fixture()['n_cu']
     for scen in (True, False):
         instance, grid, n_chunks, _ = _planned(shim, n_cu, case, scen, True)
         assert (n_chunks, grid) == (sc.WALK_CHUNKS, case.step_grid), (case.id, grid, n_chunks)
@@ -99,7 +99,7 @@ def slip_thresholds(shim):  # noqa: F811
     """per slip rate: (the top 16 bits of every threshold a list compares against, the thresholds as 53-bit integers)"""
     found = {}
     for p in sc.PASSES:
-        rows = _slip_rows(shim, p.fail_prob)[0]
+        rows = slip_rows(shim, p.fail_prob)[0]
         th16 = sorted({int(row['th'][k]) for row in rows for k in range(int(row['n']) - 1)})
         th53 = sc.exact_thresholds(row['cum'][k] for row in rows for k in range(int(row['n']) - 1))
         assert th53 == sorted({int(row['thr'][k]) for row in rows for k in range(int(row['n']) - 1)})   # (what the host built: ceil(cum * 2^53))

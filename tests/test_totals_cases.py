@@ -7,10 +7,11 @@ import numpy as np
 import pytest
 
 import totals_cases as tc
-from test_host_tables import _move_tables, _slip_rows
-from test_host_tables import shim  # noqa: F401  (the host shim, built once per run)
+from host_shim import move_tables, slip_rows
+from host_shim import shim  # noqa: F401  (the host shim, built once per run)
+from parity_checks import bits
+from plan_sweeps import KERNEL_NAME_BYTES
 
-KERNEL_NAME_BYTES = 160
 T_VALUES = sorted(set(tc.LENGTHS + tc.LENGTHS_CHAIN + (tc.OVERWRITE_STEPS, tc.RECORD_STEPS)))
 
 
@@ -34,7 +35,7 @@ def thresholds16(shim):  # noqa: F811
     """the top 16 bits of every threshold a slip rate's lists compare against (a list's last threshold is never compared)"""
     found = {}
     for fail_prob in set(tc.SLIP.values()):
-        rows = _slip_rows(shim, fail_prob)[0]
+        rows = slip_rows(shim, fail_prob)[0]
         found[fail_prob] = sorted({int(row['th'][k]) for row in rows for k in range(int(row['n']) - 1)})
         assert len(found[fail_prob]) == 2, found
     return found
@@ -51,7 +52,7 @@ def test_case_reaches_its_kernel_and_its_inputs_can_show_an_error(case, shim, th
     for family in ('R', 'G') if case.packed else ('R',):
         nbr = getattr(tables, family)[1]
         V = nbr.shape[0]
-        delta = int(_move_tables(shim, nbr, 0.2)[2] is not None)
+        delta = int(move_tables(shim, nbr, 0.2)[2] is not None)
         assert family != 'R' or delta == 1                           # (delta rows apply on the random maps)
         for streamed in (1, 0):
             for T in T_VALUES:
@@ -86,7 +87,7 @@ def test_case_reaches_its_kernel_and_its_inputs_can_show_an_error(case, shim, th
         lo, hi = run.steps_of(len(p.lengths))
         over = run.totals(lo, hi)
         added = run.totals(lo, hi, base=total)
-        assert not np.array_equal(tc._bits(over['returns']), tc._bits(added['returns'])), tag
+        assert not np.array_equal(bits(over['returns']), bits(added['returns'])), tag
         assert not np.array_equal(over['episodes'], added['episodes']), tag
         if p.rewards == tc.INEXACT and not p.auto_reset and case.ends_at_once_without_reset:
             assert not p.soc or len(tc.soc_counts(run, n)) >= 3, tag     # (what is left of the conditions below: see the property)
@@ -99,7 +100,7 @@ def test_case_reaches_its_kernel_and_its_inputs_can_show_an_error(case, shim, th
             for k in range(1, len(p.lengths)):
                 first, last = sum(p.lengths[:k]), sum(p.lengths[:k + 1])
                 restarted = run.totals(0, first)['returns'] + run.totals(first, last)['returns']
-                shows += int((tc._bits(restarted) != tc._bits(run.totals(0, last)['returns'])).sum())
+                shows += int((bits(restarted) != bits(run.totals(0, last)['returns'])).sum())
             assert shows > 0, tag
     assert many_episodes > 0 and goal_episodes > 0 and clash_episodes > 0 and r_collisions > 0, \
         (case.id, many_episodes, goal_episodes, clash_episodes, r_collisions)

@@ -11,7 +11,6 @@ layout, outputs) group for the dense sweep.  Recorded without a device by tools/
 
 A call that is refused is recorded as its return code alone: the old launchers had by then noted a name or launched the scan, the
 planner declines before anything is launched."""
-import ctypes
 import hashlib
 import json
 import os
@@ -19,13 +18,11 @@ import re
 import subprocess
 import sys
 
-if __name__ == '__main__':
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from conftest import GOLDEN
-from test_host_tables import shim  # noqa: F401  (the host shim, built once per run)
+from host_shim import shim  # noqa: F401  (the host shim, built once per run)
+from plan_sweeps import KERNEL_NAME_BYTES, declare, planned
 
 FIXTURE = os.path.join(GOLDEN, 'transitions_plans.json')
-KERNEL_NAME_BYTES = 160
 AGENTS = range(1, 17)
 # both sides of every threshold of the arithmetic: the scan block (256) and the fused scan (256 blocks); the wave supply rule
 # (16384 waves of 8, 16, 32 queries); the piece sizes at 8 agents and a full window (est. rows / 2048 >= 24576, / 4096 likewise)
@@ -97,33 +94,6 @@ def row_of_line(line):
     else:
         assert m.group('tn') is None, line
     return '%s|%s<%s,%s> %s %s %s %s' % (scan, m.group('kind'), m.group('n'), m.group('flag'), grid, block, lds, m.group('args')), m.group('name')
-
-
-_PLAN_FIELDS = ('wide', 'max_a', 'all_out', 'qw_log2', 'pieces_max', 'rows_per_wave', 'unscanned_blocks', 'lanes_log2', 'walks', 'chunk', 'chunks_per_query',
-                'scan_passes', 'scan_blocks', 'block', 'grid', 'lds_bytes')
-
-
-def declare(lib):
-    shape = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_int]
-    lib.shim_plan_transitions.argtypes = shape + [ctypes.c_void_p]
-    lib.shim_transitions_kernel_name.argtypes = shape + [ctypes.c_char_p]
-    lib.shim_transitions_wave_lds_bytes.argtypes = [ctypes.c_int, ctypes.c_uint32]
-    lib.shim_transitions_wave_lds_bytes.restype = ctypes.c_uint64
-    lib.shim_transitions_scan_blocks.argtypes = [ctypes.c_uint64]
-    lib.shim_transitions_scan_blocks.restype = ctypes.c_uint64
-    return lib
-
-
-_out, _name = (ctypes.c_uint64 * 16)(), ctypes.create_string_buffer(KERNEL_NAME_BYTES)
-
-
-def planned(lib, shape):
-    """(plan as a dict, name), or (None, None) where the planner declines"""
-    if lib.shim_plan_transitions(*shape, _out) != 1:
-        assert lib.shim_transitions_kernel_name(*shape, _name) == 0
-        return None, None
-    assert lib.shim_transitions_kernel_name(*shape, _name) == 1
-    return dict(zip(_PLAN_FIELDS, _out)), _name.value.decode()
 
 
 def row_of_plan(plan, compact):

@@ -6,7 +6,7 @@ import pytest
 from gym_mapf_amd import _native as nat
 from gym_mapf_amd.envs.grid import MapfGrid
 from gym_mapf_amd.envs.vec_env import OptimizationCriteria, VecMapfEnv, array_ptr, checked_ptr, coerce_array
-from test_host_call_trace import Recorder
+from native_recorder import Recorder
 
 
 def test_host_mode_output_arrays_are_checked_not_converted():

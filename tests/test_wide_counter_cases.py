@@ -13,16 +13,11 @@ import c_oracle
 import mapf_oracle as mo
 import philox
 import wide_counter_cases as wc
-from test_host_tables import _move_tables
-from test_host_tables import shim  # noqa: F401  (the host shim, built once per run)
+from host_shim import move_tables
+from host_shim import shim  # noqa: F401  (the host shim, built once per run)
+from parity_checks import bits
+from plan_sweeps import KERNEL_NAME_BYTES, N_CU
 from totals_cases import _random_map_tables
-
-KERNEL_NAME_BYTES = 160
-N_CU = 256
-
-
-def _bits(x):
-    return np.asarray(x, np.float64).view(np.uint64)
 
 
 @pytest.mark.parametrize('n_agents', [8, 5])
@@ -50,7 +45,7 @@ def test_the_three_oracles_agree_on_every_window(X, n_agents):
             acts = philox.random_actions_np(seed, ids, t, A)
             assert acts.tolist() == [[philox.random_action(seed, i, t, a) for a in range(A)] for i in ids], (seed, t)
             u = np.asarray([[philox.slip_uniform(seed, i, t, a) for a in range(A)] for i in ids])
-            assert np.array_equal(_bits(u), _bits(philox.slip_uniforms_np(seed, ids, t, A))), (seed, t)
+            assert np.array_equal(bits(u), bits(philox.slip_uniforms_np(seed, ids, t, A))), (seed, t)
             a, b = own.step(acts, auto_reset=True), fed.step(acts, uniforms=u, auto_reset=True)
             for name in a:
                 assert np.array_equal(a[name].view(np.uint8), b[name].view(np.uint8)), (seed, t, name)
@@ -64,7 +59,7 @@ def test_the_three_oracles_agree_on_every_window(X, n_agents):
             done_total += int(a['done'].sum())
         assert np.array_equal(own.state, fed.state) and done_total > 0
         total = whole.rollout(T, auto_reset=True)
-        assert np.array_equal(_bits(total['returns']), _bits(ret)) and np.array_equal(whole.state, own.state), seed
+        assert np.array_equal(bits(total['returns']), bits(ret)) and np.array_equal(whole.state, own.state), seed
 
 
 def _windows(case, X):
@@ -120,19 +115,12 @@ def test_every_fill_random_actions_window_shows_a_narrowed_policy_counter():
 
 
 # ----------------------------------------------------------------------- the ledger
-def _goal_rows():
-    import test_gpu_parity
-    marks = [m for m in test_gpu_parity.test_goal_reaching_episodes_against_c_oracle.pytestmark if m.name == 'parametrize']
-    assert len(marks) == 1 and marks[0].args[0] == 'n_agents,n_envs,layout,env_vars'
-    return marks[0].args[1]
-
-
 def test_the_case_tables_name_every_form_once_and_follow_the_goal_tests_list():
     for table in (wc.ROLLOUT_CASES, wc.STEP_CASES, wc.GRAPH_CASES):
         assert len({c.id for c in table}) == len(table) and len({c.layout for c in table}) == len(table)
         assert [c.index for c in table] == list(range(len(table)))
         assert all(c.E <= 16512 for c in table)
-    rows = {(A, E, layout, tuple(sorted(tune.items()))) for A, E, layout, tune in _goal_rows()}
+    rows = {(A, E, layout, tuple(sorted(tune.items()))) for A, E, layout, tune in wc.GOAL_ROWS}
     mine = {(c.A, c.E, c.layout, tuple(sorted(c.tune.items()))) for c in wc.ROLLOUT_CASES if not c.table}
     assert mine <= rows, sorted(mine - rows)
     assert {(A, E) for A, E, _, _ in rows - mine} == wc.GOAL_ROWS_LEFT_OUT
@@ -161,7 +149,7 @@ def test_rollout_case_plans_the_form_it_names(case, shim):  # noqa: F811
     lib = _native.load()
     grid, nbr, start, goal, policy = wc.tables_of(case)
     V, tune = nbr.shape[0], case.tune_text().encode() or None
-    delta = int(_move_tables(shim, nbr, wc.SLIP)[2] is not None)
+    delta = int(move_tables(shim, nbr, wc.SLIP)[2] is not None)
     out = (ctypes.c_uint64 * 9)()
     launches = [(n, 0 if w.mode == 'policy' else 1) for w in wc.rollout_windows(wc.CROSSINGS[0], case.table) for n in w.lengths]
     assert launches == ([(5, 1), (7, 1)] if case.table else [(5, 1), (7, 1), (12, 0)])
@@ -191,7 +179,7 @@ def test_rollout_case_plans_the_form_it_names(case, shim):  # noqa: F811
 def test_step_case_plans_the_form_it_names(case, shim):  # noqa: F811
     grid, nbr, start, goal, _ = wc.tables_of(case)
     V, tune = nbr.shape[0], case.tune_text().encode() or None
-    delta = int(_move_tables(shim, nbr, wc.SLIP)[2] is not None)
+    delta = int(move_tables(shim, nbr, wc.SLIP)[2] is not None)
     out = (ctypes.c_uint64 * 8)()
     rc = shim.shim_plan_step(V, case.A, case.E, delta, N_CU, tune, out)
     if case.kernel == 'thread_per_env':

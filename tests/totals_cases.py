@@ -15,13 +15,8 @@ import c_oracle
 import mapf_oracle as mo
 import philox
 from gym_mapf_amd.envs.grid import MapfGrid
+from parity_checks import EXACT, INEXACT, bits
 
-# reward constants (clash, goal, living): EXACT -- every product n * living and every sum of rewards is exact in float64, in
-# any order; INEXACT -- they round: fl(fl(n * living) + goal) differs from the correctly rounded n * living + goal at
-# n = 3, 5, 6, 7, 9, 10, 12, 15, 20, 23..26, 28, 30, 31 (the same with clash), n-fold addition of living differs from n * living
-# from n = 6 on, ten left-to-right additions of -0.1 give -0.9999999999999999: a fused multiply-add, a repeated add, a
-# reordered or re-associated sum each change bits (tests/golden/inexact_* were recorded from the reference with such constants)
-EXACT, INEXACT = (-1000.0, 100.0, -1.0), (-0.3, 0.7, -0.1)
 SLIP = {EXACT: 0.2, INEXACT: 0.15}
 
 # the ABI's form numbers (mapf_layout.hpp TableForm) and what a packed kernel's name says about each: (COMPACT, the form's tag)
@@ -34,10 +29,6 @@ LENGTHS = (1, 6, 9)                   # a plain launch, then two that accumulate
 LENGTHS_CHAIN = (8, 1, 16)            # ... of the systolic RECORD instances' chain length, one shorter and two chains (32 agents, Q = 16)
 OVERWRITE_STEPS, RECORD_STEPS = 5, 4  # a plain launch with out= the accumulated totals; pass 1's last launch records
 MIN_TIES, TIE_EXEMPT_BELOW = 4, 250000
-
-
-def _bits(x):
-    return np.asarray(x, np.float64).view(np.uint64)
 
 
 class Case:
@@ -304,7 +295,7 @@ def _assert_a_wrong_rounding_would_show(refs, prevs, acts, goal, rewards, soc, f
             for k in np.unique(n[sel]).tolist():
                 exact = float(Fraction(k) * Fraction(r_living) + Fraction(base))   # n * r_living + r_x, rounded once
                 got = refs[t]['reward'][sel & (n == k)]
-                assert np.array_equal(_bits(got), _bits(np.full(got.shape, base + float(k) * r_living))), (tag, t, k)   # n is the oracle's n
+                assert np.array_equal(bits(got), bits(np.full(got.shape, base + float(k) * r_living))), (tag, t, k)   # n is the oracle's n
                 two_roundings += int((got != exact).sum())
     assert two_roundings > 0 and len(counts) >= 3, (tag, two_roundings, sorted(counts))       # (no waiver: see the caller)
 

@@ -90,6 +90,37 @@ def _r(id, n_agents, n_envs, layout, form=None, **tune):
     return Case(id, n_agents, n_envs, layout, {k: str(v) for k, v in tune.items()}, kernel=kernel, form=form)
 
 
+# the rows of test_goal_reaching_episodes_against_c_oracle (tests/test_gpu_parity.py): (agents, envs, what the kernel's name must hold, MAPF_TUNE)
+GOAL_ROWS = [
+    (4, 16384, 'lq_rollout_kernel<Q=1,K=4', {'k': '4'}), (4, 16512, 'lq_rollout_kernel<Q=2,K=2', {'k': '2'}),
+    (8, 8192, 'lq_rollout_kernel<Q=2,K=4', {'k': '4'}), (8, 16448, 'lq_rollout_kernel<Q=4,K=2', {'k': '2'}),
+    (8, 16448, 'lg_rollout_kernel<L=4,FULL,MV_LDS', {'quad_lanes': '0'}),
+    (16, 4096, 'lq_rollout_kernel<Q=4,K=4', {'k': '4'}), (16, 4128, 'lq_rollout_kernel<Q=8,K=2', {'k': '2'}),
+    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,NO_TERMINAL> block=', {'k': '4', 'bitmap_pairs': '0'}),
+    # (32 agents, full table rows in LDS: occupancy bitmaps behind them -- what MAPF_TUNE k=4 or a batch of one wave per SIMD gets)
+    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,NO_TERMINAL,BITMAP> block=', {'k': '4'}),
+    (32, 1024, 'lq_rollout_kernel<Q=16,K=2', {'k': '2'}),
+    (32, 1024, 'lg_rollout_kernel<L=16,FULL,MV_GLOBAL', {'mv_lds_max_bytes': '0'}),
+    # eight agents per lane (the default only for batches of two waves per SIMD and more)
+    (8, 8192, 'lq_rollout_kernel<Q=1,K=8', {'k': '8'}), (16, 4096, 'lq_rollout_kernel<Q=2,K=8', {'k': '8'}),
+    (32, 2048, 'lq_rollout_kernel<Q=4,K=8', {'k': '8'}),
+    (32, 2048, 'lq_rollout_kernel<Q=4,K=8,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL> block=512', {'mv_lds_max_bytes': '2048', 'k': '8'}),
+    # (a full table "too large" for the LDS budget: the 8-byte-row form of the packed kernel, 512- and 1024-thread blocks)
+    (16, 4096, 'lq_rollout_kernel<Q=4,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL> block=512', {'mv_lds_max_bytes': '2048'}),
+    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL> block=512', {'mv_lds_max_bytes': '2048', 'bitmap_pairs': '0'}),
+    # (32 agents, 8-byte rows: collisions through per-env LDS occupancy bitmaps instead of the 496 agent pairs -- the default)
+    # (five-column table where it leaves room for the bitmaps -- here it does -- else four columns and a made-up STAY row)
+    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL,BITMAP5> block=512', {'mv_lds_max_bytes': '2048', 'bitmap_delta': '0'}),
+    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL,BITMAP> block=512', {'mv_lds_max_bytes': '2048', 'bitmap_staycol': '0', 'bitmap_delta': '0'}),
+    # (... in 1024-thread blocks, 128 bitmaps behind the table: what a batch that fills every CU with such a block gets)
+    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL,BITMAP> block=1024', {'mv_lds_max_bytes': '2048', 'bitmap_block': '1024', 'bitmap_staycol': '0', 'bitmap_delta': '0'}),
+    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL,BITMAP5> block=1024', {'mv_lds_max_bytes': '2048', 'bitmap_block': '1024', 'bitmap_delta': '0'}),
+    # (... behind 4-byte delta rows -- the default wherever a map's neighbour ids lie within +-127 of their cell's)
+    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL,BITMAPD> block=512', {'mv_lds_max_bytes': '2048'}),
+    (32, 2048, 'lq_rollout_kernel<Q=8,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL,BITMAPD> block=1024', {'mv_lds_max_bytes': '2048', 'bitmap_block': '1024'}),
+    (64, 16384, 'lq_rollout_kernel<Q=16,K=4,RECORD,STREAM,MAKESPAN,COMPACT,NO_TERMINAL> block=1024', {'mv_lds_max_bytes': '2048'}),
+    (8, 300, 'lg_rollout_kernel<L=4,FULL,MV_GLOBAL', {}), (5, 600, 'lg_rollout_kernel<L=4,RAGGED', {}),
+    (8, 16417, 'lg_rollout_kernel<L=4,FULL,MV_LDS', {}), (6, 512, 'rollout_kernel<A=6>', {})]
 _FULL = 'lq_rollout_kernel<Q=%d,K=%d,RECORD,STREAM,MAKESPAN%s,NO_TERMINAL%s> block=%s'
 # The fused rollout: (agents, envs, the kernel's name, MAPF_TUNE) as test_goal_reaching_episodes_against_c_oracle has them -- the
 # smallest batch that reaches each form (tests/test_wide_counter_cases.py holds every row against that list).  `form`: the
