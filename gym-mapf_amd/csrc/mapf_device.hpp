@@ -9,9 +9,24 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mapf_kernels.hpp"
+#include <type_traits>
 
 namespace mapf {
 
+// ---------------------------------------------------------------- optional kernel arguments
+// A kernel template whose instances differ in what they are handed takes the optional blocks as a trailing pack `Extra... extra`
+// (the kernarg layout is the pack's order).  has_kernel_arg<T, Extra...>: the instance has a T; kernel_arg<T>(extra...): that
+// argument BY VALUE (a reference into the pack changes the register allocation), or an empty tag where there is none.
+struct NoKernelArg {};
+template <class T, class... Extra>
+constexpr bool has_kernel_arg = (std::is_same_v<T, Extra> || ...);
+template <class T>
+__device__ __forceinline__ NoKernelArg kernel_arg() { return {}; }
+template <class T, class First, class... Rest>
+__device__ __forceinline__ auto kernel_arg(const First &first, const Rest &...rest) {
+    if constexpr (std::is_same_v<T, First>) return first;
+    else return kernel_arg<T>(rest...);
+}
 
 // ---------------------------------------------------------------- Philox4x32-10
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,

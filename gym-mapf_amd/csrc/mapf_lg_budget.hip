@@ -8,28 +8,18 @@
 // and zeros.  Any other step is the limit kernels' step (with max_steps == 0: the step without a limit); it counts as a live step
 // unless the env was terminal on entry, and takes one from the env's episodes left when it reports done or truncated.
 #include "mapf_lg_launch.hpp"
+#include "mapf_lg_rollout_kernel.hpp"
 
 namespace mapf {
 
-// lg_rollout_kernel_budget_guarded (streamed actions, the policy stream, the greedy policy) and
-// lg_rollout_kernel_table_budget_guarded (the table policy): the body of the rollout kernels with its limit and budget sections
-#define MAPF_ROLLOUT_LIMIT 1
-#define MAPF_ROLLOUT_BUDGET 1
-#define MAPF_ROLLOUT_TABLE_KERNEL 0
-#include "mapf_lg_rollout_kernel.inc"
-#undef MAPF_ROLLOUT_TABLE_KERNEL
-#define MAPF_ROLLOUT_TABLE_KERNEL 1
-#include "mapf_lg_rollout_kernel.inc"
-#undef MAPF_ROLLOUT_TABLE_KERNEL
-#undef MAPF_ROLLOUT_BUDGET
-#undef MAPF_ROLLOUT_LIMIT
-
-// the budget instances: guarded only, as the limit instances are.  7 group sizes x FULL x MV_LDS x RECORD x (STREAM | table)
+// the budget instances of lg_rollout_kernel (mapf_lg_rollout_kernel.hpp): its EpisodeLimit and EpisodeBudget arguments, behind the
+// table policy where the launch follows one; guarded only, as the limit instances are.
+// 7 group sizes x FULL x MV_LDS x RECORD x (STREAM | table)
 struct LgRolloutBudgetFamily {
     template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM, bool TABLE>
     static auto kernel(bool) {
-        if constexpr (TABLE) return lg_rollout_kernel_table_budget_guarded<L, FULL, MV_LDS, RECORD>;
-        else return lg_rollout_kernel_budget_guarded<L, FULL, MV_LDS, RECORD, STREAM>;
+        if constexpr (TABLE) return lg_rollout_kernel<L, FULL, MV_LDS, RECORD, false, false, TablePolicy, EpisodeLimit, EpisodeBudget>;
+        else return lg_rollout_kernel<L, FULL, MV_LDS, RECORD, STREAM, false, EpisodeLimit, EpisodeBudget>;
     }
 };
 

@@ -1,14 +1,11 @@
 // Lane-group family: single-step kernel, run-time-A helper kernels and their launchers (device code: mapf_lg.hpp; the step's
 // plan: the route's, mapf_plan.hip; its launcher proper: mapf_lg_launch.hpp).
 #include "mapf_lg_launch.hpp"
+#include "mapf_lg_step_kernel.hpp"
 
 namespace mapf {
 
-// lg_step_kernel: the body of the single-step kernels without its limit sections
-#define MAPF_STEP_LIMIT 0
-#include "mapf_lg_step_kernel.inc"
-#undef MAPF_STEP_LIMIT
-
+// the plain instances of lg_step_kernel (mapf_lg_step_kernel.hpp): no argument behind (args, A)
 struct LgStepFamily {
     template <int L, bool FULL, bool EXT_UNIFORMS>
     static auto kernel() { return lg_step_kernel<L, FULL, EXT_UNIFORMS>; }

@@ -1,11 +1,11 @@
 // Lane-group family: the launchers of its fused rollout and single-step kernels, once for every family of instances.  A launcher
 // takes ONE plan (mapf_plan.hpp) and launches the instance it names; which kernels those instances are is the including unit's
 // say, through a family type:
-//   rollout -- Family::kernel<L, FULL, MV_LDS, RECORD, STREAM, TABLE>(dense) returns the kernel's address (mapf_lg_rollout.hip:
-//              lg_rollout_kernel / lg_rollout_kernel_table, DENSE for full groups only; mapf_lg_limit.hip: the limit instances,
-//              guarded only; mapf_lg_budget.hip: the budget instances, guarded only);
-//   step    -- Family::kernel<L, FULL, EXT_UNIFORMS>() likewise (mapf_lg_kernels.hip: lg_step_kernel; mapf_lg_limit.hip:
-//              lg_step_kernel_limit).
+//   rollout -- Family::kernel<L, FULL, MV_LDS, RECORD, STREAM, TABLE>(dense) returns the address of an instance of lg_rollout_kernel
+//              (mapf_lg_rollout_kernel.hpp).  mapf_lg_rollout.hip: the plain and the table instances, DENSE for full groups only;
+//              mapf_lg_limit.hip: the limit instances, guarded only; mapf_lg_budget.hip: the budget instances, guarded only;
+//   step    -- Family::kernel<L, FULL, EXT_UNIFORMS>() likewise, of lg_step_kernel (mapf_lg_step_kernel.hpp).  mapf_lg_kernels.hip:
+//              the plain instances; mapf_lg_limit.hip: the limit instances.
 // `extra` are the kernel's arguments behind (args, A): nothing, the table policy, the episode limit, or both in that order; the
 // budget instances take the episode budget behind the limit.
 #pragma once

@@ -9,37 +9,25 @@
 // age is kept and the env reports truncated on every later live step.  Nothing else of the step changes: reward, prob, done,
 // collision, the totals and every Philox counter are those of the kernels without the limit.
 #include "mapf_lg_launch.hpp"
+#include "mapf_lg_rollout_kernel.hpp"
+#include "mapf_lg_step_kernel.hpp"
 
 namespace mapf {
 
-// lg_rollout_kernel_limit_guarded (streamed actions, the policy stream, the greedy policy) and
-// lg_rollout_kernel_table_limit_guarded (the table policy): the body of the rollout kernels with its limit sections
-#define MAPF_ROLLOUT_LIMIT 1
-#define MAPF_ROLLOUT_TABLE_KERNEL 0
-#include "mapf_lg_rollout_kernel.inc"
-#undef MAPF_ROLLOUT_TABLE_KERNEL
-#define MAPF_ROLLOUT_TABLE_KERNEL 1
-#include "mapf_lg_rollout_kernel.inc"
-#undef MAPF_ROLLOUT_TABLE_KERNEL
-#undef MAPF_ROLLOUT_LIMIT
-
-// lg_step_kernel_limit: the body of the single-step kernels (mapf_lg_kernels.hip has lg_step_kernel) with its limit sections
-#define MAPF_STEP_LIMIT 1
-#include "mapf_lg_step_kernel.inc"
-#undef MAPF_STEP_LIMIT
-
-// the limit instances: guarded only, whatever the plan's `dense` (plan_rollout_lg clears it for them)
+// the limit instances of lg_rollout_kernel (mapf_lg_rollout_kernel.hpp): its EpisodeLimit argument, behind the table policy where
+// the launch follows one; guarded only, whatever the plan's `dense` (plan_rollout_lg clears it for them)
 struct LgRolloutLimitFamily {
     template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM, bool TABLE>
     static auto kernel(bool) {
-        if constexpr (TABLE) return lg_rollout_kernel_table_limit_guarded<L, FULL, MV_LDS, RECORD>;
-        else return lg_rollout_kernel_limit_guarded<L, FULL, MV_LDS, RECORD, STREAM>;
+        if constexpr (TABLE) return lg_rollout_kernel<L, FULL, MV_LDS, RECORD, false, false, TablePolicy, EpisodeLimit>;
+        else return lg_rollout_kernel<L, FULL, MV_LDS, RECORD, STREAM, false, EpisodeLimit>;
     }
 };
 
+// the limit instances of lg_step_kernel (mapf_lg_step_kernel.hpp; mapf_lg_kernels.hip has the plain ones)
 struct LgStepLimitFamily {
     template <int L, bool FULL, bool EXT_UNIFORMS>
-    static auto kernel() { return lg_step_kernel_limit<L, FULL, EXT_UNIFORMS>; }
+    static auto kernel() { return lg_step_kernel<L, FULL, EXT_UNIFORMS, EpisodeLimit>; }
 };
 
 // mapf_reset(mask) on a handle with a limit: the ages of the envs it resets go to 0 (one thread per env)

@@ -1,6 +1,7 @@
 // Lane-group family: fused T-step rollout kernel and the launcher of its instances without an episode limit (device code:
 // mapf_lg.hpp; the launch's plan: the route's, mapf_plan.hip; the launcher proper: mapf_lg_launch.hpp).
 #include "mapf_lg_launch.hpp"
+#include "mapf_lg_rollout_kernel.hpp"
 
 namespace mapf {
 
@@ -15,20 +16,14 @@ namespace mapf {
 // identical data), so the
 // loop contains no exec-masked memory operation and the compiler can wait for the prefetched action word with a
 // counted vmcnt(N) instead of draining every store.  Start cells stay in two registers per lane, so an
-// auto-reset touches no memory.
-#define MAPF_ROLLOUT_TABLE_KERNEL 0
-#include "mapf_lg_rollout_kernel.inc"
-#undef MAPF_ROLLOUT_TABLE_KERNEL
-#define MAPF_ROLLOUT_TABLE_KERNEL 1
-#include "mapf_lg_rollout_kernel.inc"
-#undef MAPF_ROLLOUT_TABLE_KERNEL
+// auto-reset touches no memory.  (The kernel: mapf_lg_rollout_kernel.hpp.)
 
-// The instances without an episode limit: lg_rollout_kernel, or lg_rollout_kernel_table (TABLE: then STREAM is false); DENSE
-// exists for full groups only.
+// The instances without an episode limit: lg_rollout_kernel with no further argument, or with the table policy (TABLE: then STREAM
+// is false); DENSE exists for full groups only.
 struct LgRolloutFamily {
     template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM, bool TABLE>
     static auto kernel(bool dense) {
-        if constexpr (TABLE) return dense ? lg_rollout_kernel_table<L, FULL, MV_LDS, RECORD, FULL> : lg_rollout_kernel_table<L, FULL, MV_LDS, RECORD, false>;
+        if constexpr (TABLE) return dense ? lg_rollout_kernel<L, FULL, MV_LDS, RECORD, false, FULL, TablePolicy> : lg_rollout_kernel<L, FULL, MV_LDS, RECORD, false, false, TablePolicy>;
         else return dense ? lg_rollout_kernel<L, FULL, MV_LDS, RECORD, STREAM, FULL> : lg_rollout_kernel<L, FULL, MV_LDS, RECORD, STREAM, false>;
     }
 };

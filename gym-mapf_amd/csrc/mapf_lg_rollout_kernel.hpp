@@ -1,45 +1,32 @@
-// The body of the lane-group rollout kernels of mapf_lg_rollout.hip, which includes this file twice:
-//   MAPF_ROLLOUT_TABLE_KERNEL 0 -- lg_rollout_kernel: streamed actions, the policy stream, the greedy policy;
-//   MAPF_ROLLOUT_TABLE_KERNEL 1 -- lg_rollout_kernel_table: the table policy (MAPF_POLICY_TABLE): agent i of env e on cell c takes
-//     tp.table[tp.rows[e * A + i] * V + c], gathered from global memory; the row bases wait in two registers per lane as the
-//     greedy policy's goal coordinates do.
-// Textual inclusion, not a shared function template: the first kernel's token stream is what it was before the table policy
-// existed, so its instances compile to the same code.
-// mapf_lg_limit.hip includes it twice more with MAPF_ROLLOUT_LIMIT 1 (the episode step limit, include/mapf_hip.h
-// mapf_set_episode_limit): lg_rollout_kernel_limit_guarded and lg_rollout_kernel_table_limit_guarded carry the env's age in a
-// register beside `terminal`, count truncations like episodes, store the truncated byte with the delayed flag bytes and go
-// back to the start cells on done OR truncated.  They have no DENSE form (the name says so): always the guarded one.
-// mapf_lg_budget.hip includes it twice again with MAPF_ROLLOUT_LIMIT 1 and MAPF_ROLLOUT_BUDGET 1 (the episode budget, include/mapf_hip.h
-// mapf_set_episode_budget): lg_rollout_kernel_budget_guarded and lg_rollout_kernel_table_budget_guarded are the limit kernels with a
-// per-env count of episodes left beside the age.  An env whose count is 0 is PARKED: it folds into the `terminal` the transition is
-// told, so its step draws and moves nothing, and its done bit is cleared before anything counts or records it.
-#if MAPF_ROLLOUT_BUDGET && MAPF_ROLLOUT_TABLE_KERNEL
-template <int L, bool FULL, bool MV_LDS, bool RECORD, bool TABLE = true>
-__global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel_table_budget_guarded(const RolloutArgs p, const uint32_t n_agents, const TablePolicy tp,
-                                                                                                 const EpisodeLimit lim, const EpisodeBudget bud) {
-    constexpr bool STREAM = false, DENSE = false;
-#elif MAPF_ROLLOUT_BUDGET
-template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM>
-__global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel_budget_guarded(const RolloutArgs p, const uint32_t n_agents, const EpisodeLimit lim,
-                                                                                           const EpisodeBudget bud) {
-    constexpr bool DENSE = false;
-#elif MAPF_ROLLOUT_LIMIT && MAPF_ROLLOUT_TABLE_KERNEL
-template <int L, bool FULL, bool MV_LDS, bool RECORD, bool TABLE = true>
-__global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel_table_limit_guarded(const RolloutArgs p, const uint32_t n_agents, const TablePolicy tp,
-                                                                                                const EpisodeLimit lim) {
-    constexpr bool STREAM = false, DENSE = false;
-#elif MAPF_ROLLOUT_LIMIT
-template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM>
-__global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel_limit_guarded(const RolloutArgs p, const uint32_t n_agents, const EpisodeLimit lim) {
-    constexpr bool DENSE = false;
-#elif MAPF_ROLLOUT_TABLE_KERNEL
-template <int L, bool FULL, bool MV_LDS, bool RECORD, bool DENSE, bool TABLE = true>
-__global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel_table(const RolloutArgs p, const uint32_t n_agents, const TablePolicy tp) {
-    constexpr bool STREAM = false;   // (a table instance runs the launches without streamed actions)
-#else
-template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM, bool DENSE>
-__global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(const RolloutArgs p, const uint32_t n_agents) {
-#endif
+// The lane-group rollout kernel: one template for every instance of mapf_lg_rollout.hip, mapf_lg_limit.hip and mapf_lg_budget.hip.
+// What an instance does beyond the plain rollout is read from the types of its trailing arguments (kernel_arg, mapf_device.hpp),
+// which follow (p, n_agents) in this order:
+//   TablePolicy   -- the table policy (MAPF_POLICY_TABLE): agent i of env e on cell c takes tp.table[tp.rows[e * A + i] * V + c],
+//     gathered from global memory; the row bases wait in two registers per lane as the greedy policy's goal coordinates do.  Such an
+//     instance runs the launches without streamed actions: STREAM is false.
+//   EpisodeLimit  -- the episode step limit (include/mapf_hip.h mapf_set_episode_limit): the env's age is carried in a register
+//     beside `terminal`, truncations are counted like episodes, the truncated byte is stored with the delayed flag bytes, and the
+//     env goes back to its start cells on done OR truncated.  These instances have no DENSE form: always the guarded one.
+//   EpisodeBudget -- the episode budget (include/mapf_hip.h mapf_set_episode_budget), behind the limit: a per-env count of episodes
+//     left beside the age.  An env whose count is 0 is PARKED: it folds into the `terminal` the transition is told, so its step
+//     draws and moves nothing, and its done bit is cleared before anything counts or records it.
+// A mode's sections are `if constexpr`: an instance without the mode compiles to the code it had when the modes were separate
+// kernels (tools/compare_kernels.py, profiles/kernel_templates_device_listings.txt).  Which instances exist is each unit's say,
+// through its family struct.
+#pragma once
+#include "mapf_lg.hpp"
+
+namespace mapf {
+
+template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM, bool DENSE, class... Extra>
+__global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(const RolloutArgs p, const uint32_t n_agents, const Extra... extra) {
+    constexpr bool TABLE = has_kernel_arg<TablePolicy, Extra...>, LIMIT = has_kernel_arg<EpisodeLimit, Extra...>,
+                   BUDGET = has_kernel_arg<EpisodeBudget, Extra...>;
+    static_assert(!(TABLE && STREAM), "a table instance runs the launches without streamed actions");
+    static_assert(!(LIMIT && DENSE) && (LIMIT || !BUDGET), "the limit instances are guarded; a budget instance takes the limit block too");
+    const auto tp = kernel_arg<TablePolicy>(extra...);       // by value: an empty tag where the instance has no such argument
+    const auto lim = kernel_arg<EpisodeLimit>(extra...);
+    const auto bud = kernel_arg<EpisodeBudget>(extra...);
     __shared__ SlipRow slip[8];
     __shared__ OutcomeRow outcome[16];
     extern __shared__ __attribute__((aligned(16))) MoveEntry lds_mv[];
@@ -97,26 +84,30 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
     double ret = (p.accumulate && ret_p && leader) ? *ret_p : 0.0;
     uint32_t episodes = (p.accumulate && epi_p && leader) ? *epi_p : 0u;
     uint32_t collisions = (p.accumulate && col_p && leader) ? *col_p : 0u;
-#if MAPF_ROLLOUT_LIMIT
-    // the env's age: read once by every lane of the group (one address per group: each lane decides `back` itself), written
-    // back once by the leader; lanes past the last env read env 0's and write nothing
-    gu32 age_p = (gu32)at(lim.age, e);
-    gu32 trn_p = (gu32)(lim.out_truncations ? at(lim.out_truncations, e) : nullptr);
-    gu8 trunc_lane = (gu8)(RECORD ? lim.rec_truncated : nullptr) + e;      // the delayed step's row
-    asm volatile("" : "+v"(age_p), "+v"(trn_p), "+v"(trunc_lane));
-    uint32_t age = *age_p;
-    uint32_t truncations = (p.accumulate && trn_p && leader) ? *trn_p : 0u;
-    const uint32_t max_steps = lim.max_steps;
-#endif
-#if MAPF_ROLLOUT_BUDGET
-    // the env's episodes left: read and written back like the age (lanes past the last env are parked: they write nothing anyway)
-    gu32 left_p = (gu32)at(bud.left, e);
-    gu32 liv_p = (gu32)(bud.out_live_steps ? at(bud.out_live_steps, e) : nullptr);
-    asm volatile("" : "+v"(left_p), "+v"(liv_p));
-    uint32_t left = live ? *left_p : 0u;
-    uint32_t live_steps = (p.accumulate && liv_p && leader) ? *liv_p : 0u;
-    uint32_t idle = 0u;                    // steps that were parked or terminal on entry: live steps = n_steps - idle
-#endif
+    // what only a mode's sections use: dead, and gone from the code, in an instance without the mode
+    gu32 age_p = nullptr, trn_p = nullptr, left_p = nullptr, liv_p = nullptr;
+    gu8 trunc_lane = nullptr;
+    uint32_t age = 0u, truncations = 0u, max_steps = 0u, left = 0u, live_steps = 0u;
+    uint32_t idle = 0u;                        // budget: steps that were parked or terminal on entry: live steps = n_steps - idle
+    if constexpr (LIMIT) {
+        // the env's age: read once by every lane of the group (one address per group: each lane decides `back` itself), written
+        // back once by the leader; lanes past the last env read env 0's and write nothing
+        age_p = (gu32)at(lim.age, e);
+        trn_p = (gu32)(lim.out_truncations ? at(lim.out_truncations, e) : nullptr);
+        trunc_lane = (gu8)(RECORD ? lim.rec_truncated : nullptr) + e;      // the delayed step's row
+        asm volatile("" : "+v"(age_p), "+v"(trn_p), "+v"(trunc_lane));
+        age = *age_p;
+        truncations = (p.accumulate && trn_p && leader) ? *trn_p : 0u;
+        max_steps = lim.max_steps;
+    }
+    if constexpr (BUDGET) {
+        // the env's episodes left: read and written back like the age (lanes past the last env are parked: they write nothing anyway)
+        left_p = (gu32)at(bud.left, e);
+        liv_p = (gu32)(bud.out_live_steps ? at(bud.out_live_steps, e) : nullptr);
+        asm volatile("" : "+v"(left_p), "+v"(liv_p));
+        left = live ? *left_p : 0u;
+        live_steps = (p.accumulate && liv_p && leader) ? *liv_p : 0u;
+    }
     const uint64_t env_id = p.env_id_offset + e;
     const uint32_t n_envs = uint32_t(p.n_envs);
 
@@ -175,9 +166,7 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
                 *reward_lane = d_reward;
                 *done_lane = uint8_t(d_flags & 1u);
                 *coll_lane = uint8_t(d_flags >> 8);
-#if MAPF_ROLLOUT_LIMIT
-                *trunc_lane = uint8_t(d_flags >> 24);          // byte 3 truncated
-#endif
+                if constexpr (LIMIT) *trunc_lane = uint8_t(d_flags >> 24);   // byte 3 truncated
             }
         }
     };
@@ -186,29 +175,26 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
         reward_lane += step_rows;
         done_lane += step_rows;
         if (!(DENSE && L > 1)) { prob_lane += step_rows; coll_lane += step_rows; }
-#if MAPF_ROLLOUT_LIMIT
-        trunc_lane += step_rows;
-#endif
+        if constexpr (LIMIT) trunc_lane += step_rows;
     };
     const uint8_t *act_lane = STREAM ? p.actions + lane_cell : nullptr;   // the row being prefetched
 
     uint32_t goal_rc0 = 0u, goal_rc1 = 0u;   // greedy policy: my agents' goal coordinates
     if (!STREAM && p.policy_cells) { goal_rc0 = p.policy_cells[goal0].x; goal_rc1 = p.policy_cells[goal1].x; }
 
-#if MAPF_ROLLOUT_TABLE_KERNEL
-    uint32_t row_base0, row_base1;   // table policy: my agents' rows (ghost slots: row 0, whose bytes are never used)
-    load_pair<uint16_t>(tp.rows, tp.rows_broadcast ? 0 : e, n_agents, x.g, x.v0, x.v1, row_base0, row_base1);
-    row_base0 *= p.c.n_cells;
-    row_base1 *= p.c.n_cells;
-#endif
+    uint32_t row_base0 = 0u, row_base1 = 0u;   // table policy: my agents' rows (ghost slots: row 0, whose bytes are never used)
+    if constexpr (TABLE) {
+        load_pair<uint16_t>(tp.rows, tp.rows_broadcast ? 0 : e, n_agents, x.g, x.v0, x.v1, row_base0, row_base1);
+        row_base0 *= p.c.n_cells;
+        row_base1 *= p.c.n_cells;
+    }
 
     const uint64_t t_first = first_step_index(p);
     for (uint32_t s = 0; s < p.n_steps; ++s) {
         const uint64_t t = t_first + s;
-#if MAPF_ROLLOUT_BUDGET
-        const bool parked = left == 0u;
-        const bool no_op = parked || terminal != 0u;       // a parked step is the terminal no-op: nothing drawn, nothing moved ...
-#endif
+        // budget: a parked step is the terminal no-op: nothing drawn, nothing moved ...
+        const bool parked = BUDGET && left == 0u;
+        const bool no_op = parked || terminal != 0u;
         uint32_t act0, act1;
         if (STREAM) {
             act0 = raw & 0xFFu; act1 = (raw >> 8) & 0xFFu;   // only the low half-word of `raw` is defined
@@ -220,14 +206,10 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
                 act_lane += step_cells;
                 raw = load_actions_raw<FULL>(act_lane, 0u, 0u, 0u, x.v0, x.v1);
             }
-        }
-#if MAPF_ROLLOUT_TABLE_KERNEL
-        else if constexpr (TABLE) {   // table policy: the byte of (my row, my cell) -- ghost slots read byte 0 of row 0
+        } else if constexpr (TABLE) {   // table policy: the byte of (my row, my cell) -- ghost slots read byte 0 of row 0
             act0 = tp.table[row_base0 + cur0];
             act1 = tp.table[row_base1 + cur1];
-        }
-#endif
-        else if (p.policy_cells) {   // greedy policy (ghost slots read cell 0: their actions are never used)
+        } else if (p.policy_cells) {   // greedy policy (ghost slots read cell 0: their actions are never used)
             act0 = greedy_action(p.policy_cells, p.c.n_cells, cur0, goal_rc0);
             act1 = greedy_action(p.policy_cells, p.c.n_cells, cur1, goal_rc1);
         } else {   // policy stream: one Philox call covers agents 4q..4q+3 for the four steps of a block; this lane's
@@ -247,50 +229,48 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
         // my pair's words of a four-step block (one slip-stream call per lane, traded with the neighbour lane): refresh when
         // t is a multiple of 4 (and at the first step)
         if (p.c.need_rng && ((t & 3u) == 0u || s == 0u)) rng = pair_block_words<(L > 1)>(p.c, env_id, t, x.g);
-#if MAPF_ROLLOUT_BUDGET
         lg_transition<L, FULL, false, true, MV_LDS, true>(p.c, mv, slip, outcome, x, n_agents, cur0, cur1, goal0, goal1, act0, act1, 0.0, 0.0,
                                             env_id, t, step_word(rng, t), no_op, next0, next1, o STAMP_ARG);
-        // ... but it reports no done: a no-op's status is kTerminalStatus, whose byte 0 goes and whose byte 2 stays (the carried `terminal`
-        // is 1 from here on).  Its reward is +0.0, and ret + 0.0 would turn an accumulated -0.0 into +0.0: what is added is -0.0
-        o.status -= parked ? 1u : 0u;
-        ret = __dadd_rn(ret, __hiloint2double(parked ? int(0x80000000u) : __double2hiint(o.reward), __double2loint(o.reward)));
-#else
-        lg_transition<L, FULL, false, true, MV_LDS, true>(p.c, mv, slip, outcome, x, n_agents, cur0, cur1, goal0, goal1, act0, act1, 0.0, 0.0,
-                                            env_id, t, step_word(rng, t), terminal != 0u, next0, next1, o STAMP_ARG);
-        STAMP(6);   // reward / selects
-        ret = __dadd_rn(ret, o.reward);
-#endif
+        if constexpr (BUDGET) {
+            // ... but it reports no done: a no-op's status is kTerminalStatus, whose byte 0 goes and whose byte 2 stays (the carried `terminal`
+            // is 1 from here on).  Its reward is +0.0, and ret + 0.0 would turn an accumulated -0.0 into +0.0: what is added is -0.0
+            o.status -= parked ? 1u : 0u;
+            ret = __dadd_rn(ret, __hiloint2double(parked ? int(0x80000000u) : __double2hiint(o.reward), __double2loint(o.reward)));
+        } else {
+            STAMP(6);   // reward / selects
+            ret = __dadd_rn(ret, o.reward);
+        }
         episodes += o.status & 0xFFu;
         collisions += (o.status >> 8) & 0xFFu;
         if (RECORD) {
             d_next0 = next0; d_next1 = next1; d_reward = o.reward; d_prob = o.prob;
             d_flags = o.status;                            // byte 0 done, byte 1 collision
         }
-#if MAPF_ROLLOUT_BUDGET
-        // the limit's rules below, switched off as a whole by max_steps == 0 (a budget without a limit: the ages stay zero); a step
-        // that was neither parked nor terminal on entry is a live step, and one that reports done or truncated takes an episode
-        // from the env's count (a parked step reports neither, so the count stops at 0)
-        const bool ageing = !no_op && max_steps != 0u;
-        const uint32_t aged = ageing ? (age + (age != 0xFFFFFFFFu ? 1u : 0u)) : age;
-        const uint32_t truncated = (ageing && (o.status & 0xFFu) == 0u && aged >= max_steps) ? 1u : 0u;
-        idle += no_op ? 1u : 0u;
-#elif MAPF_ROLLOUT_LIMIT
-        // a live step ages the episode (saturating); it is truncated when it did not end the episode and the age has reached
-        // the limit.  A step from a terminal state (a no-op) leaves the age alone and is never truncated.
-        const uint32_t aged = terminal != 0u ? age : (age + (age != 0xFFFFFFFFu ? 1u : 0u));
-        const uint32_t truncated = (terminal == 0u && (o.status & 0xFFu) == 0u && aged >= max_steps) ? 1u : 0u;
-#endif
-#if MAPF_ROLLOUT_LIMIT
-        truncations += truncated;
-        if (RECORD) d_flags |= truncated << 24;
-        const bool back = p.auto_reset && ((o.status & 0xFFu) != 0u || truncated != 0u);   // done or truncated: start cells, age 0
-        age = back ? 0u : aged;
-#if MAPF_ROLLOUT_BUDGET
-        left -= back ? 1u : 0u;                // (the budget instances run auto-reset launches only: back == done || truncated)
-#endif
-#else
-        const bool back = p.auto_reset && (o.status & 0xFFu) != 0u;   // MapfEnv.reset(): start cells, no reseed
-#endif
+        bool back;
+        if constexpr (LIMIT) {
+            uint32_t aged, truncated;
+            if constexpr (BUDGET) {
+                // the limit's rules below, switched off as a whole by max_steps == 0 (a budget without a limit: the ages stay zero); a step
+                // that was neither parked nor terminal on entry is a live step, and one that reports done or truncated takes an episode
+                // from the env's count (a parked step reports neither, so the count stops at 0)
+                const bool ageing = !no_op && max_steps != 0u;
+                aged = ageing ? (age + (age != 0xFFFFFFFFu ? 1u : 0u)) : age;
+                truncated = (ageing && (o.status & 0xFFu) == 0u && aged >= max_steps) ? 1u : 0u;
+                idle += no_op ? 1u : 0u;
+            } else {
+                // a live step ages the episode (saturating); it is truncated when it did not end the episode and the age has reached
+                // the limit.  A step from a terminal state (a no-op) leaves the age alone and is never truncated.
+                aged = terminal != 0u ? age : (age + (age != 0xFFFFFFFFu ? 1u : 0u));
+                truncated = (terminal == 0u && (o.status & 0xFFu) == 0u && aged >= max_steps) ? 1u : 0u;
+            }
+            truncations += truncated;
+            if (RECORD) d_flags |= truncated << 24;
+            back = p.auto_reset && ((o.status & 0xFFu) != 0u || truncated != 0u);   // done or truncated: start cells, age 0
+            age = back ? 0u : aged;
+            if constexpr (BUDGET) left -= back ? 1u : 0u;   // (the budget instances run auto-reset launches only: back == done || truncated)
+        } else {
+            back = p.auto_reset && (o.status & 0xFFu) != 0u;   // MapfEnv.reset(): start cells, no reseed
+        }
         cur0 = back ? start0 : next0;
         cur1 = back ? start1 : next1;
         terminal = back ? start_terminal : (o.status >> 16);
@@ -309,14 +289,15 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
         if (ret_p) *ret_p = ret;
         if (epi_p) *epi_p = episodes;
         if (col_p) *col_p = collisions;
-#if MAPF_ROLLOUT_LIMIT
-        *age_p = age;
-        if (trn_p) *trn_p = truncations;
-#endif
-#if MAPF_ROLLOUT_BUDGET
-        *left_p = left;
-        if (liv_p) *liv_p = live_steps + (p.n_steps - idle);
-#endif
+        if constexpr (LIMIT) {
+            *age_p = age;
+            if (trn_p) *trn_p = truncations;
+        }
+        if constexpr (BUDGET) {
+            *left_p = left;
+            if (liv_p) *liv_p = live_steps + (p.n_steps - idle);
+        }
     }
 }
 
+}  // namespace mapf

@@ -1,20 +1,20 @@
-// The body of the lane-group single-step kernels, included once by each of two units:
-//   MAPF_STEP_LIMIT 0 -- mapf_lg_kernels.hip: lg_step_kernel;
-//   MAPF_STEP_LIMIT 1 -- mapf_lg_limit.hip: lg_step_kernel_limit, the step under an episode step limit (include/mapf_hip.h
-//     mapf_set_episode_limit; EpisodeLimit in mapf_kernels.hpp).
-// Textual inclusion, as in mapf_lg_rollout_kernel.inc: each kernel's token stream is what it was when the two were separate
-// copies, so their instances compile to the same code.
+// The lane-group single-step kernel: one template for the instances of mapf_lg_kernels.hip (the plain step) and of
+// mapf_lg_limit.hip, whose trailing EpisodeLimit argument (kernel_arg, mapf_device.hpp; include/mapf_hip.h mapf_set_episode_limit)
+// makes them the step under an episode step limit.  The limit's sections are `if constexpr`: the plain step compiles to the code
+// it had as a kernel of its own (tools/compare_kernels.py, profiles/kernel_templates_device_listings.txt).
 // The limit sections: every lane of the group reads the env's age; a step from a terminal state leaves it alone, any other step
 // ages the episode by one (saturating) and is TRUNCATED when it did not return done and the age has reached lim.max_steps; the
 // leader writes the age back (0 when the env goes back to its start cells) and reports the step's truncated byte
 // (lim.rec_truncated: [E] or null); with auto-reset the env goes back on done OR truncated.
-#if MAPF_STEP_LIMIT
-template <int L, bool FULL, bool EXT_UNIFORMS>
-__global__ void __launch_bounds__(256) lg_step_kernel_limit(const StepArgs p, const uint32_t n_agents, const EpisodeLimit lim) {
-#else
-template <int L, bool FULL, bool EXT_UNIFORMS>
-__global__ void __launch_bounds__(256) lg_step_kernel(const StepArgs p, const uint32_t n_agents) {
-#endif
+#pragma once
+#include "mapf_lg.hpp"
+
+namespace mapf {
+
+template <int L, bool FULL, bool EXT_UNIFORMS, class... Extra>
+__global__ void __launch_bounds__(256) lg_step_kernel(const StepArgs p, const uint32_t n_agents, const Extra... extra) {
+    constexpr bool LIMIT = has_kernel_arg<EpisodeLimit, Extra...>;
+    const auto lim = kernel_arg<EpisodeLimit>(extra...);   // by value: an empty tag in the plain step
     bool live;
     const LaneCtx<L> x = lane_ctx<L>(n_agents, p.n_envs, live);
     const uint32_t e = x.e;
@@ -23,9 +23,8 @@ __global__ void __launch_bounds__(256) lg_step_kernel(const StepArgs p, const ui
     load_pair<uint16_t>(p.state, e, n_agents, x.g, x.v0, x.v1, cur0, cur1);
     load_pair<uint16_t>(p.goal, p.goal_broadcast ? 0 : e, n_agents, x.g, x.v0, x.v1, goal0, goal1);
     load_pair<uint8_t>(p.actions, e, n_agents, x.g, x.v0, x.v1, act0, act1);
-#if MAPF_STEP_LIMIT
-    const uint32_t age = *at(lim.age, e);   // (lanes past the last env: env 0's, never written back)
-#endif
+    uint32_t age = 0u;
+    if constexpr (LIMIT) age = *at(lim.age, e);   // (lanes past the last env: env 0's, never written back)
     double u0 = 0.0, u1 = 0.0;
     if (EXT_UNIFORMS) {
         const double *up = at(p.uniforms, e * n_agents + 2u * x.g);
@@ -49,13 +48,13 @@ __global__ void __launch_bounds__(256) lg_step_kernel(const StepArgs p, const ui
                                                 u0, u1, p.env_id_offset + e, t, word, false, next0, next1, o STAMP_ARG);
     if (!live) return;
 
-#if MAPF_STEP_LIMIT
-    const uint32_t aged = o.was_terminal ? age : (age + (age != 0xFFFFFFFFu ? 1u : 0u));
-    const bool truncated = !o.was_terminal && !o.done() && aged >= lim.max_steps;
+    uint32_t aged = 0u;
+    bool truncated = false;
+    if constexpr (LIMIT) {
+        aged = o.was_terminal ? age : (age + (age != 0xFFFFFFFFu ? 1u : 0u));
+        truncated = !o.was_terminal && !o.done() && aged >= lim.max_steps;
+    }
     const bool back = p.auto_reset && (o.done() || truncated);
-#else
-    const bool back = p.auto_reset && o.done();
-#endif
 
     if (p.out_local) store_cells(p.out_local, e, n_agents, x.g, x.v0, x.v1, next0, next1);
     if (x.g == uint32_t(L - 1) && p.out_prob) *at(p.out_prob, e) = o.prob;   // the product chain ends in the last lane
@@ -64,10 +63,10 @@ __global__ void __launch_bounds__(256) lg_step_kernel(const StepArgs p, const ui
         if (p.out_done) *at(p.out_done, e) = o.done() ? 1 : 0;
         if (p.out_collision) *at(p.out_collision, e) = o.collision() ? 1 : 0;
         if (p.out_was_terminal) *at(p.out_was_terminal, e) = o.was_terminal ? 1 : 0;
-#if MAPF_STEP_LIMIT
-        if (lim.rec_truncated) *at(lim.rec_truncated, e) = truncated ? 1 : 0;
-        *at(lim.age, e) = back ? 0u : aged;
-#endif
+        if constexpr (LIMIT) {
+            if (lim.rec_truncated) *at(lim.rec_truncated, e) = truncated ? 1 : 0;
+            *at(lim.age, e) = back ? 0u : aged;
+        }
     }
     if (back) {
         uint32_t s0, s1;
@@ -78,3 +77,5 @@ __global__ void __launch_bounds__(256) lg_step_kernel(const StepArgs p, const ui
     }
     signal_step_done(p.done_flag, p.done_seq);
 }
+
+}  // namespace mapf

@@ -360,7 +360,7 @@ __device__ __forceinline__ double packed_prob_product(const double (&q)[K]) {
     return run;
 }
 
-// ---- constants of the packed rollout kernels' body (mapf_lq_rollout_kernel.inc), for the units that include it: mapf_lq_rollout.hip, mapf_lq_limit.hip
+// ---- constants of the packed rollout kernel (mapf_lq_rollout_kernel.hpp), whose instances are mapf_lq_rollout.hip's and mapf_lq_limit.hip's
 // The LDS copy of a table row carries its slip row's byte offset PLUS kRowBias, so that sample_slot_packed's probability
 // address -- that operand minus 8 per threshold not passed -- is never negative and packs into an unsigned field (the
 // systolic probability chain of the rollout files four of them per word); the immediates of the LDS reads absorb the bias.

@@ -1,9 +1,9 @@
 // Packed family: the launcher of its fused rollout kernels, once for every family of instances.  The launcher takes ONE plan
 // (mapf_plan.hpp) and launches the instance it names; which kernels those instances are is the including unit's say, through a
 // family type:
-//   Family::kernel<Q, K, RECORD, STREAM, SOC, COMPACT, TERM, BITMAP, TABLE>() returns the kernel's address (mapf_lq_rollout.hip:
-//       lq_rollout_kernel, which has no TABLE, and lq_rollout_kernel_table, which has no STREAM; mapf_lq_limit.hip:
-//       lq_rollout_kernel_table_limit);
+//   Family::kernel<Q, K, RECORD, STREAM, SOC, COMPACT, TERM, BITMAP, TABLE>() returns the address of an instance of
+//       lq_rollout_kernel (mapf_lq_rollout_kernel.hpp).  mapf_lq_rollout.hip: the plain instances, whose TABLE is 0, and the table
+//       instances, whose STREAM is false; mapf_lq_limit.hip: the table instances under an episode step limit;
 //   Family::kTable -- the instances follow the table policy: MAPF_LQ_ROLLOUT_TABLE_INSTANCES, built for 512 threads, TABLE = 1
 //       (action bytes gathered from global memory) or 2 (staged into LDS); Family::kLimit -- ... under an episode step limit.
 // The kernels' arguments are (args, A, where the bitmaps begin[, the table policy, where its LDS copy begins[, extra...]]): the

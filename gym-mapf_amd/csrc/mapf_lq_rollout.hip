@@ -44,6 +44,7 @@
 // beyond the LDS budget, single steps) stays with mapf_lg_rollout.hip; route_rollout (mapf_plan.hip) picks.  Same stream,
 // same arithmetic, same outputs: the parity tests run all layouts against the oracle.
 #include "mapf_lq_launch.hpp"
+#include "mapf_lq_rollout_kernel.hpp"
 
 namespace mapf {
 
@@ -69,25 +70,19 @@ namespace {
 // row is made up) take half the room of the five 8-byte ones: 128 bitmaps fit behind them on the 64x64 maps.
 // (the four-column form with the in-kernel policy holds its actions across the table reads -- the made-up STAY row asks for
 // them -- and does not fit the 128 registers of a 1024-thread block: launched with 512 threads, see plan_rollout_lq)
-#define MAPF_ROLLOUT_TABLE_KERNEL 0
-#include "mapf_lq_rollout_kernel.inc"
-#undef MAPF_ROLLOUT_TABLE_KERNEL
-#define MAPF_ROLLOUT_TABLE_KERNEL 1
-#include "mapf_lq_rollout_kernel.inc"
-#undef MAPF_ROLLOUT_TABLE_KERNEL
+// (The kernel: mapf_lq_rollout_kernel.hpp.)
 
-#undef env_id
-
-// The instances without an episode limit: lq_rollout_kernel (streamed actions, the in-kernel policies) and lq_rollout_kernel_table
+// The instances of lq_rollout_kernel without an episode limit: the plain ones (streamed actions, the in-kernel policies: TABLE is 0
+// whatever the launcher asks for) and those that follow the table policy (its block and where its LDS copy begins as arguments)
 struct LqFamily {
     static constexpr bool kTable = false, kLimit = false;
     template <int Q, int K, bool RECORD, bool STREAM, bool SOC, bool COMPACT, bool TERM, int BITMAP, int TABLE>
-    static auto kernel() { return lq_rollout_kernel<Q, K, RECORD, STREAM, SOC, COMPACT, TERM, BITMAP>; }
+    static auto kernel() { return lq_rollout_kernel<Q, K, RECORD, STREAM, SOC, COMPACT, TERM, BITMAP, 0>; }
 };
 struct LqTableFamily {
     static constexpr bool kTable = true, kLimit = false;
     template <int Q, int K, bool RECORD, bool STREAM, bool SOC, bool COMPACT, bool TERM, int BITMAP, int TABLE>
-    static auto kernel() { return lq_rollout_kernel_table<Q, K, RECORD, SOC, COMPACT, TERM, BITMAP, TABLE>; }
+    static auto kernel() { return lq_rollout_kernel<Q, K, RECORD, false, SOC, COMPACT, TERM, BITMAP, TABLE, TablePolicy, uint32_t>; }
 };
 
 }  // namespace

@@ -1,34 +1,39 @@
-// The body of the packed rollout kernels of mapf_lq_rollout.hip, which includes this file twice:
-//   MAPF_ROLLOUT_TABLE_KERNEL 0 -- lq_rollout_kernel: streamed actions, the policy stream, the greedy policy;
-//   MAPF_ROLLOUT_TABLE_KERNEL 1 -- lq_rollout_kernel_table: the table policy (MAPF_POLICY_TABLE).  An agent's action is the byte
+// The packed rollout kernel: one template for every instance of mapf_lq_rollout.hip and mapf_lq_limit.hip (each unit's family
+// structs say which exist).  The plain instances -- streamed actions, the policy stream, the greedy policy -- have TABLE == 0 and
+// no argument behind (p, n_agents, bitmap_base).  What an instance does beyond them is read from the types of its trailing
+// arguments (kernel_arg, mapf_device.hpp), which follow in this order:
+//   TablePolicy, uint32_t table_at -- the table policy (MAPF_POLICY_TABLE), TABLE != 0.  An agent's action is the byte
 //     table[row * V + cell] of the row it follows: one dependent lookup in front of the move-table read.  TABLE == 1 gathers the
 //     byte from global memory; TABLE == 2 stages the policy table into the launch's LDS segment at `table_at`, behind the image
 //     (and the bitmaps), and reads it with a ds_read_u8.  The agents' row bases are loaded once per launch and wait in
 //     registers, as goal_rc[] does for greedy.  Launched with at most 512 threads: 256 vector registers per lane, so the row
 //     bases and the table's address cost no spill in any instance (the 1024-thread bound of the others leaves 128, which the
-//     policy instances fill).
-// Textual inclusion, not a shared function template: the first kernel's token stream is what it was before the table policy
-// existed, so its instances (which sit at the edge of their register budgets) compile to the same code.
-// mapf_lq_limit.hip includes it once more with MAPF_ROLLOUT_TABLE_KERNEL 1 and MAPF_ROLLOUT_LIMIT 1 (the episode step limit,
-// include/mapf_hip.h mapf_set_episode_limit): lq_rollout_kernel_table_limit carries the env's age in a register beside `terminal`,
-// counts truncations in a register beside `counts`, stores the truncated byte with the pending step's other flags and goes back
-// to the start cells on done OR truncated.  Its 512-thread bound leaves the registers for that; the other packed kernels have
-// no limit form.
-#if MAPF_ROLLOUT_TABLE_KERNEL
-template <int Q, int K, bool RECORD, bool SOC, bool COMPACT, bool TERM, int BITMAP, int TABLE>
-#if MAPF_ROLLOUT_LIMIT
-__global__ void __launch_bounds__(512) lq_rollout_kernel_table_limit(const RolloutArgs p, const uint32_t n_agents, const uint32_t bitmap_base, const TablePolicy tp,
-                                                                     const uint32_t table_at, const EpisodeLimit lim) {
-#else
-__global__ void __launch_bounds__(512) lq_rollout_kernel_table(const RolloutArgs p, const uint32_t n_agents, const uint32_t bitmap_base, const TablePolicy tp,
-                                                               const uint32_t table_at) {
-#endif
-    static_assert(TABLE == 1 || TABLE == 2, "1: action bytes from global memory, 2: from the LDS copy");
-    constexpr bool STREAM = false;   // (a table instance runs the launches without streamed actions)
-#else
-template <int Q, int K, bool RECORD, bool STREAM, bool SOC, bool COMPACT, bool TERM, int BITMAP = 0>
-__global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)) ? 512 : 1024) lq_rollout_kernel(const RolloutArgs p, const uint32_t n_agents, const uint32_t bitmap_base) {
-#endif
+//     policy instances fill).  Such an instance runs the launches without streamed actions: STREAM is false.
+//   EpisodeLimit -- the episode step limit (include/mapf_hip.h mapf_set_episode_limit), for table instances only: the env's age is
+//     carried in a register beside `terminal`, truncations are counted in a register beside `counts`, the truncated byte is stored
+//     with the pending step's other flags, and the env goes back to the start cells on done OR truncated.  The 512-thread bound
+//     leaves the registers for that; the plain instances have no limit form.
+// A mode's sections are `if constexpr`: the plain instances (which sit at the edge of their register budgets) compile to the code
+// they had when the modes were separate kernels (tools/compare_kernels.py, profiles/kernel_templates_device_listings.txt).
+#pragma once
+#include "mapf_lq.hpp"
+
+#include <type_traits>
+
+namespace mapf {
+namespace {
+
+template <int Q, int K, bool RECORD, bool STREAM, bool SOC, bool COMPACT, bool TERM, int BITMAP, int TABLE, class... Extra>
+__global__ void __launch_bounds__((TABLE != 0 || K == 8 || (COMPACT && BITMAP == 1 && !STREAM)) ? 512 : 1024)
+lq_rollout_kernel(const RolloutArgs p, const uint32_t n_agents, const uint32_t bitmap_base, const Extra... extra) {
+    constexpr bool LIMIT = has_kernel_arg<EpisodeLimit, Extra...>;
+    static_assert(TABLE == 0 || TABLE == 1 || TABLE == 2, "0: no table policy, 1: action bytes from global memory, 2: from the LDS copy");
+    static_assert((TABLE != 0) == has_kernel_arg<TablePolicy, Extra...> && (TABLE != 0) == has_kernel_arg<uint32_t, Extra...>,
+                  "a table instance takes the table policy and where its LDS copy begins");
+    static_assert(!(TABLE != 0 && STREAM) && (TABLE != 0 || !LIMIT), "a table instance streams no actions; only table instances have a limit form");
+    const auto tp = kernel_arg<TablePolicy>(extra...);       // by value: an empty tag where the instance has no such argument
+    const auto table_at = kernel_arg<uint32_t>(extra...);
+    const auto lim = kernel_arg<EpisodeLimit>(extra...);
     constexpr int P = K / 2;   // packed dwords per lane
     static_assert(K == 2 || K == 4 || K == 8, "two, four or eight agents per lane");
     constexpr TableFormTraits kForm = table_form_traits(table_form_of<COMPACT, BITMAP>());   // the table form this instance reads (mapf_layout.hpp)
@@ -61,12 +66,14 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
 #pragma unroll
         for (int i = 0; i < P; ++i) { c[i] = cells.v[i]; g[i] = gl.v[i]; start_c[i] = sc.v[i]; }
     }
-#if MAPF_ROLLOUT_LIMIT
-    // the env's age: read once by every lane of the group (one address per group: each lane decides `back` itself), written
-    // back once by the leader
-    uint32_t age = *at(lim.age, e);
-    const uint32_t max_steps = lim.max_steps;
-#endif
+    // What only the limit's sections use is dead, and gone from the code, in an instance without it.  The env's age: read once by
+    // every lane of the group (one address per group: each lane decides `back` itself), written back once by the leader.
+    // (Each declared where the limit kernel declared it: declared together, ahead of the two assignments, the limit instances
+    // with two agents per lane come out with other registers.)
+    uint32_t age = 0u;
+    if constexpr (LIMIT) age = *at(lim.age, e);
+    uint32_t max_steps = 0u;
+    if constexpr (LIMIT) max_steps = lim.max_steps;
     // (requested HERE, with the state / goal / start rows and ahead of the table copy: a launch's fixed cost -- 8-12 us, a third
     // of a T = 32 launch, profiles/r05_rollout_T_sweep.txt -- is mostly memory round trips in a row, so they travel together)
     const uint8_t *act_lane = STREAM ? p.actions + lane_cell : nullptr;
@@ -170,9 +177,8 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
         const uint32_t n_words = (blockDim.x / uint32_t(Q)) * (stride >> 2);
         for (uint32_t w = threadIdx.x; w < n_words; w += blockDim.x) *(lds_u32)lds_addr(lds, bitmap_base + 4u * w) = 0u;
     }
-#if MAPF_ROLLOUT_TABLE_KERNEL
-    uint32_t row_base[K];   // table policy: my agents' rows (byte offsets of their first cells; in the LDS form from LDS address 0)
-    {
+    uint32_t row_base[K] = {};   // table policy: my agents' rows (byte offsets of their first cells; in the LDS form from LDS address 0)
+    if constexpr (TABLE != 0) {
         const Packed<P> rows = Packed<P>::load(at(tp.rows, tp.rows_broadcast ? fixed_cell : lane_cell));
 #pragma unroll
         for (int k = 0; k < K; ++k) row_base[k] = ((k & 1) ? rows.v[k / 2] >> 16 : rows.v[k / 2] & 0xFFFFu) * p.c.n_cells + (TABLE == 2 ? table_at : 0u);
@@ -191,7 +197,6 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
                 if (w0 + k * blockDim.x < n_vec) *(__attribute__((address_space(3))) u32x4 *)lds_addr(lds, table_at + 16u * (w0 + k * blockDim.x)) = part[k];
         }
     }
-#endif
     stage_outcome_table(p.c, outcome);
     stage_slip_table(p.slip, slip);   // ends with __syncthreads()
 
@@ -221,8 +226,8 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
     }
     double ret = 0.0;
     if (p.accumulate && p.out_returns && leader) ret = *(gf64)at(p.out_returns, e);
-    // (formed where it is used -- the slip refresh, one step in four, and the tie path: not held across the loop)
-#define env_id (p.env_id_offset + x.e)
+    // (the env's id, p.env_id_offset + x.e, is formed where it is used -- the slip refresh, one step in four, and the tie path: not
+    // held across the loop)
     const uint64_t t_first = first_step_index(p);
     const uint32_t n_envs = uint32_t(p.n_envs);
 
@@ -244,13 +249,14 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
         rec_lane = (gu16)p.rec_local + lane_cell;
     }
     asm volatile("" : "+v"(wide_lane), "+v"(prob_lane), "+v"(narrow_lane), "+v"(coll_lane), "+v"(rec_lane));
-#if MAPF_ROLLOUT_LIMIT
-    // the truncated byte of a step: EVERY lane of the group stores it through its own pointer (same byte, same address), as the
-    // reward is stored by all lanes but the last -- no exec-masked store in the step loop
-    gu8 trunc_lane = RECORD ? (gu8)lim.rec_truncated + e : nullptr;
-    asm volatile("" : "+v"(trunc_lane));
-    uint32_t p_trunc = 0u, truncs = 0u;   // p_trunc: truncated (0 / 1) of the pending step; truncs: the launch's count
-#endif
+    gu8 trunc_lane = nullptr;
+    uint32_t p_trunc = 0u, truncs = 0u;   // limit: p_trunc: truncated (0 / 1) of the pending step; truncs: the launch's count
+    if constexpr (LIMIT) {
+        // the truncated byte of a step: EVERY lane of the group stores it through its own pointer (same byte, same address), as the
+        // reward is stored by all lanes but the last -- no exec-masked store in the step loop
+        trunc_lane = RECORD ? (gu8)lim.rec_truncated + e : nullptr;
+        asm volatile("" : "+v"(trunc_lane));
+    }
 #pragma unroll
     for (uint32_t j = 0; j < kAhead; ++j) asm volatile("" : "+v"(raw[j]));   // consumed here: the loop's waits are counted ones
     asm volatile("" : "+v"(raw_first), "+v"(raw_head[0]), "+v"(raw_head[1]));
@@ -352,10 +358,10 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
                 *prob_lane = prob;
                 *coll_lane = uint8_t(p_status >> 16);
             }
-#if MAPF_ROLLOUT_LIMIT
-            asm volatile("" : "+v"(p_trunc));
-            *trunc_lane = uint8_t(p_trunc);
-#endif
+            if constexpr (LIMIT) {
+                asm volatile("" : "+v"(p_trunc));
+                *trunc_lane = uint8_t(p_trunc);
+            }
         }
     };
 
@@ -397,9 +403,9 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
         odd_pair = __umul24(odd, 5u << kColShift) & (0x00070007u << (8 + kColShift));
     };
     auto refresh_policy = [&](const uint64_t m) __attribute__((always_inline)) {
-        if constexpr (K == 8) policy_words_x2(__builtin_amdgcn_readfirstlane(pol_key_lo), __builtin_amdgcn_readfirstlane(pol_key_hi), env_id, m,
+        if constexpr (K == 8) policy_words_x2(__builtin_amdgcn_readfirstlane(pol_key_lo), __builtin_amdgcn_readfirstlane(pol_key_hi), p.env_id_offset + x.e, m,
                                               2u * x.g, 2u * x.g + 1u, pol[0], pol[1]);
-        else pol[0] = policy_words(p.c, env_id, m, K == 4 ? x.g : x.g >> 1);
+        else pol[0] = policy_words(p.c, p.env_id_offset + x.e, m, K == 4 ? x.g : x.g >> 1);
         if constexpr (PRECOL) {
 #pragma unroll
             for (int j = 0; j < kPolicyCalls; ++j) {
@@ -457,18 +463,14 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
                 act_lane += (!TAIL || s + kAhead <= last_row) ? step_cells : 0u;   // row min(s + kAhead, last)
                 raw = load_raw();
             }
-        }
-#if MAPF_ROLLOUT_TABLE_KERNEL
-        else if constexpr (TABLE != 0) {   // table policy: the byte of (my row, my cell); the host has checked that it is 0..4
+        } else if constexpr (TABLE != 0) {   // table policy: the byte of (my row, my cell); the host has checked that it is 0..4
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 if constexpr (TABLE == 2) act[k] = lds_at<uint8_t>(lds, row_base[k] + cur[k]);
                 else act[k] = tp.table[row_base[k] + cur[k]];
             }
             if constexpr (FAST_POLICY) columns_from_actions();
-        }
-#endif
-        else if (p.policy_cells) {   // greedy policy
+        } else if (p.policy_cells) {   // greedy policy
 #pragma unroll
             for (int k = 0; k < K; ++k) act[k] = greedy_action(p.policy_cells, p.c.n_cells, cur[k], goal_rc[k]);
             if constexpr (FAST_POLICY) columns_from_actions();
@@ -532,9 +534,7 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
                 else wide_lane += step_rows;
                 narrow_lane += step_rows;
                 if (Q == 1) { prob_lane += step_rows; coll_lane += step_rows; }
-#if MAPF_ROLLOUT_LIMIT
-                trunc_lane += step_rows;                       // (not delayed with SYS: only prob trails)
-#endif
+                if constexpr (LIMIT) trunc_lane += step_rows;   // (not delayed with SYS: only prob trails)
             }
         }
         STAMP(1);   // previous step: probability chain, totals, trajectory stores
@@ -565,13 +565,13 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
         if (refresh && p.c.need_rng) {
             const uint64_t h0 = block_first_call(t);
             if constexpr (P == 1) {
-                rng[0] = pair_block_words<true>(p.c, env_id, t, x.g);
+                rng[0] = pair_block_words<true>(p.c, p.env_id_offset + x.e, t, x.g);
             } else {
 #pragma unroll
                 for (int j = 0; j < P / 2; ++j) {
                     const uint32_t quad = uint32_t(P / 2) * x.g + uint32_t(j);
                     Words4 a, b;
-                    slip_words_x2(p.c, env_id, h0, quad, h0 | 1u, quad, a, b);
+                    slip_words_x2(p.c, p.env_id_offset + x.e, h0, quad, h0 | 1u, quad, a, b);
                     rng[2 * j] = block_words(a, b, 0u);
                     rng[2 * j + 1] = block_words(a, b, 1u);
                 }
@@ -579,9 +579,9 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
         }
         // ... and the policy stream's call of the NEXT block is made in the block's last step (its words are free by then:
         // this step's actions were taken from them at the top), so a block's first step finds its actions ready
-#if !MAPF_ROLLOUT_TABLE_KERNEL   // (the table policy draws nothing from the policy stream)
-        if (!STREAM && !p.policy_cells && (W == 3 || (W < 0 && (t & 3u) == 3u))) refresh_policy((t >> 2) + 1u);
-#endif
+        if constexpr (TABLE == 0) {   // (the table policy draws nothing from the policy stream)
+            if (!STREAM && !p.policy_cells && (W == 3 || (W < 0 && (t & 3u) == 3u))) refresh_policy((t >> 2) + 1u);
+        }
         STAMP(2);   // slip Philox (1 step in 4)
         double q[K];
         uint32_t n[P], word[P], d[K], q_at[K], tie_all = 0u;   // q_at: byte offset of the sampled slot's probability from kSlipAt
@@ -627,7 +627,7 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
                     if (COMPACT) full.y = (full.y & 0xFFFFu) | (((full.w - kRowBias) / uint32_t(sizeof(SlipRow))) << 16);   // the code, where entry_code() looks
                     const uint32_t hi = (k & 1) ? word[k / 2] >> 16 : word[k / 2] & 0xFFFFu;
                     uint32_t nx;
-                    const uint64_t mant = refine_mantissa(p.c, env_id, t, uint32_t(K) * x.g + uint32_t(k), hi);
+                    const uint64_t mant = refine_mantissa(p.c, p.env_id_offset + x.e, t, uint32_t(K) * x.g + uint32_t(k), hi);
                     if (SYS) {
                         const uint32_t slot = slip_slot_exact(slip, full, mant);
                         nx = entry_cell(full, slot);
@@ -714,22 +714,23 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
         // the episode; the returned state is terminal after a vertex collision or on goal (mapf_env.py:210-223), a swap
         // alone is not: bits 0 (vertex), 2 (flipped: on goal) and 3 (was terminal) of code ^ 4
         const uint32_t ended = code16 ^ (4u * 16u);
-#if MAPF_ROLLOUT_LIMIT
-        // The episode step limit, from the group-uniform code (the outcome row is still on its way): a live step ages the episode
-        // (saturating); it is truncated when it did not end the episode -- code 4 is the one code that does not -- and the age has
-        // reached the limit.  A step from a terminal state leaves the age alone and is never truncated.  Done or truncated: start
-        // cells, age 0 (with auto-reset; without it the age is kept and every later live step is truncated again).
-        const uint32_t aged = was_terminal ? age : age + (age != 0xFFFFFFFFu ? 1u : 0u);
-        const uint32_t truncated = (!was_terminal && code16 == 4u * 16u && aged >= max_steps) ? 1u : 0u;
-        truncs += truncated;
-        if (RECORD) p_trunc = truncated;
-        // (as below: one compare of an integer against a wave-uniform constant; the NO_TERMINAL instance runs with auto-reset only)
-        const bool back = MAYBE_TERMINAL ? (ended | truncated) > reset_above : (ended | truncated) != 0u;
-        age = back ? 0u : aged;
-#else
-        // (the instance without terminal handling only runs with auto-reset on: one compare against the code itself)
-        const bool back = MAYBE_TERMINAL ? ended > reset_above : code16 != 4u * 16u;   // never with auto-reset off
-#endif
+        bool back;
+        if constexpr (LIMIT) {
+            // The episode step limit, from the group-uniform code (the outcome row is still on its way): a live step ages the episode
+            // (saturating); it is truncated when it did not end the episode -- code 4 is the one code that does not -- and the age has
+            // reached the limit.  A step from a terminal state leaves the age alone and is never truncated.  Done or truncated: start
+            // cells, age 0 (with auto-reset; without it the age is kept and every later live step is truncated again).
+            const uint32_t aged = was_terminal ? age : age + (age != 0xFFFFFFFFu ? 1u : 0u);
+            const uint32_t truncated = (!was_terminal && code16 == 4u * 16u && aged >= max_steps) ? 1u : 0u;
+            truncs += truncated;
+            if (RECORD) p_trunc = truncated;
+            // (as below: one compare of an integer against a wave-uniform constant; the NO_TERMINAL instance runs with auto-reset only)
+            back = MAYBE_TERMINAL ? (ended | truncated) > reset_above : (ended | truncated) != 0u;
+            age = back ? 0u : aged;
+        } else {
+            // (the instance without terminal handling only runs with auto-reset on: one compare against the code itself)
+            back = MAYBE_TERMINAL ? ended > reset_above : code16 != 4u * 16u;   // never with auto-reset off
+        }
 #pragma unroll
         for (int i = 0; i < P; ++i) c[i] = back ? start_c[i] : n[i];
         if (MAYBE_TERMINAL) terminal = back ? start_terminal : min(ended & (13u * 16u), 1u);
@@ -863,10 +864,13 @@ __global__ void __launch_bounds__((K == 8 || (COMPACT && BITMAP == 1 && !STREAM)
         if (ret_p) *ret_p = ret;
         if (epi_p) *epi_p = (p.accumulate ? *epi_p : 0u) + (counts & 0xFFFFu);
         if (col_p) *col_p = (p.accumulate ? *col_p : 0u) + (counts >> 16);
-#if MAPF_ROLLOUT_LIMIT
-        *at(lim.age, e) = age;
-        if (lim.out_truncations) *at(lim.out_truncations, e) = (p.accumulate ? *at(lim.out_truncations, e) : 0u) + truncs;
-#endif
+        if constexpr (LIMIT) {
+            *at(lim.age, e) = age;
+            if (lim.out_truncations) *at(lim.out_truncations, e) = (p.accumulate ? *at(lim.out_truncations, e) : 0u) + truncs;
+        }
     }
 }
+
+}  // namespace
+}  // namespace mapf
 

@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tools'))
 try:
     import device_listings  # noqa: F401
     import kernel_meta  # noqa: F401
+    import compare_kernels  # noqa: F401
 finally:
     sys.path.pop(0)
 

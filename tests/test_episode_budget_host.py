@@ -67,8 +67,9 @@ def budget_listing():
 
 def test_the_budget_unit_holds_its_declared_instances_free_of_spills_and_scratch(budget_listing):
     kernels = kernel_meta.kernels(budget_listing)
-    rollout = [k for k in kernels if 'lg_rollout_kernel_budget_guarded' in k['name']]
-    table = [k for k in kernels if 'lg_rollout_kernel_table_budget_guarded' in k['name']]
+    # the instances of the kernel template by the argument types behind (args, A), as the mangled names spell the pack
+    rollout = [k for k in kernels if 'lg_rollout_kernelI' in k['name'] and 'JNS_12EpisodeLimitENS_13EpisodeBudgetEEE' in k['name']]
+    table = [k for k in kernels if 'lg_rollout_kernelI' in k['name'] and 'JNS_11TablePolicyENS_12EpisodeLimitENS_13EpisodeBudgetEEE' in k['name']]
     # 7 group sizes x FULL x MV_LDS x RECORD x (STREAM | table), as the unit's family comment declares; nothing else
     assert re.search(r'7 group sizes x FULL x MV_LDS x RECORD x \(STREAM \| table\)', open(os.path.join(CSRC, 'mapf_lg_budget.hip')).read())
     assert (len(rollout), len(table), len(kernels)) == (112, 56, 168)

@@ -87,9 +87,10 @@ def limit_listing():
 
 def test_the_limit_instances_are_free_of_register_spills(limit_listing):
     kernels = kernel_meta.kernels(limit_listing)
-    rollout = [k for k in kernels if 'lg_rollout_kernel_limit_guarded' in k['name']]
-    table = [k for k in kernels if 'lg_rollout_kernel_table_limit_guarded' in k['name']]
-    step = [k for k in kernels if 'lg_step_kernel_limit' in k['name']]
+    # the instances of the two kernel templates by the argument types behind (args, A), as the mangled names spell the pack
+    rollout = [k for k in kernels if 'lg_rollout_kernelI' in k['name'] and 'JNS_12EpisodeLimitEEE' in k['name']]
+    table = [k for k in kernels if 'lg_rollout_kernelI' in k['name'] and 'JNS_11TablePolicyENS_12EpisodeLimitEEE' in k['name']]
+    step = [k for k in kernels if 'lg_step_kernelI' in k['name'] and 'JNS_12EpisodeLimitEEE' in k['name']]
     # 7 group sizes x FULL x MV_LDS x RECORD x (STREAM | table); 7 x FULL x EXT_UNIFORMS; the ages' reset
     assert (len(rollout), len(table), len(step), len(kernels)) == (112, 56, 28, 197)
     for k in kernels:

@@ -106,7 +106,10 @@ def test_the_limit_listings_hold_108_kernels_free_of_register_spills(limit_listi
     for (K, record), text in limit_listings.items():
         kernels = kernel_meta.kernels(text)
         # per (K, Q, form) triple: {SOC, MAKESPAN, MAKESPAN NO_TERMINAL} x {TABLE_GLOBAL, TABLE_LDS}
-        assert len(kernels) == (30 if K == 4 else 24) and all('lq_rollout_kernel_table_limit' in k['name'] for k in kernels), (K, record, len(kernels))
+        # (instances of the kernel template with the table policy's two arguments and the limit behind (args, A, bitmap_base), as the
+        # mangled names spell the pack)
+        limit_form = lambda name: 'lq_rollout_kernelI' in name and 'JNS_11TablePolicyEjNS_12EpisodeLimitEEE' in name
+        assert len(kernels) == (30 if K == 4 else 24) and all(limit_form(k['name']) for k in kernels), (K, record, len(kernels))
         assert len({k['name'] for k in kernels}) == len(kernels)
         for k in kernels:
             assert (k['sgpr_spill'], k['vgpr_spill'], k['scratch']) == (0, 0, 0) and k['vgpr'] <= 256, k

@@ -6,6 +6,9 @@
 #
 #   tools/compare_device_listings.sh OLD_TREE NEW_TREE WORK_DIR [JOBS]     (trees: repository roots; exit 0 = all identical)
 #
+# A unit whose bytes differ is compared again kernel by kernel (tools/compare_kernels.py): a change that renames or merges kernels
+# moves symbols, function numbers and the kernels' order, and still leaves every instance its code, descriptor and metadata
+# entry.  Such a unit is reported as "same code" with its count of paired kernels; anything else as DIFFERENT, pair by pair.
 # Translation units of NEW_TREE that are not in the table must hold no kernel: their listings are checked for an empty
 # kernel list as well.  A unit of the table that OLD_TREE does not have yet is compiled from NEW_TREE alone and reported as new.
 set -u
@@ -27,12 +30,14 @@ build old "$OLD" $(echo "$UNITS" | while read -r name unit; do [ -f "$OLD/gym-ma
 build new "$NEW" $(echo "$UNITS" | cut -d' ' -f1) $HOST
 
 status=0
-echo "device listings, hipcc -S --cuda-device-only, __hip_cuid_* masked: old tree vs new tree"
+echo "device listings, hipcc -S --cuda-device-only, __hip_cuid_* masked: old tree vs new tree (identical: byte for byte; same code: kernel by kernel)"
 while read -r name unit; do
     if [ ! -f "$OLD/gym-mapf_amd/csrc/$unit.hip" ] && [ -s "$WORK/new/$name.s" ]; then
         echo "new unit   $name.s  $(wc -l < "$WORK/new/$name.s") lines  $(grep -c '^  - .agpr_count:' "$WORK/new/$name.s") kernels"
     elif cmp -s "$WORK/old/$name.s" "$WORK/new/$name.s" && [ -s "$WORK/new/$name.s" ]; then
         echo "identical  $name.s  $(wc -l < "$WORK/new/$name.s") lines  $(grep -c '^  - .agpr_count:' "$WORK/new/$name.s") kernels"
+    elif [ -s "$WORK/old/$name.s" ] && [ -s "$WORK/new/$name.s" ]; then
+        python3 "$NEW/tools/compare_kernels.py" "$WORK/old/$name.s" "$WORK/new/$name.s" "$name.s" || status=1
     else
         echo "DIFFERENT  $name.s"; status=1
     fi

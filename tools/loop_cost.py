@@ -3,7 +3,7 @@
 usage: python loop_cost.py /tmp/ro.s [mangled-name-substring]   (default: the L=4 DENSE recording kernel)"""
 import re, sys, collections
 s = open(sys.argv[1]).read()
-key = sys.argv[2] if len(sys.argv) > 2 else 'lg_rollout_kernelILi4ELb1ELb1ELb1ELb1ELb1EE'
+key = sys.argv[2] if len(sys.argv) > 2 else 'lg_rollout_kernelILi4ELb1ELb1ELb1ELb1ELb1EJEE'
 m = re.search(r'^(_ZN4mapf\w*%s\w*):' % re.escape(key), s, re.M)
 body = s[m.end():s.index('.Lfunc_end', m.end())].split('\n')
 hdr = [i for i, l in enumerate(body) if 'Inner Loop Header' in l and 'Depth=1' in l][-1]

@@ -44,7 +44,7 @@ def classify(line):
 
 def mix_of(listing, instance_re):
     text = device_listings.listings(listing)[listing]            # one compilation per translation unit, not per instance
-    m = re.search(r'^(_ZN4mapf\S*lq_rollout_kernel' + instance_re + r'\S*):', text, re.M)
+    m = re.search(r'^(_ZN4mapf\S*lq_rollout_kernel' + instance_re + r'E\S*):', text, re.M)
     body = text[m.end():text.index('.Lfunc_end', m.end())].split('\n')
     counts = {'fast': 0, 'ordinary': 0, 'wide': 0}
     for line in body:
@@ -56,15 +56,16 @@ def mix_of(listing, instance_re):
 
 def main():
     import bench
-    # (rocprofv3's spelling of the instance, the listing of its compilation, mangled template arguments)
+    # (rocprofv3's spelling of the instance, the listing of its compilation, ALL its mangled template arguments: the plain instances of
+    # the kernel template end in TABLE = 0 and an empty argument pack -- a table instance may share every argument before those)
     instances = [
-        ('lq_rollout_kernel<2, 4, true, true, false, false, false, 0>', 'mapf_lq_rollout_k4_r1', 'ILi2ELi4ELb1ELb1ELb0ELb0ELb0ELi0E'),
-        ('lq_rollout_kernel<2, 4, true, false, false, false, false, 0>', 'mapf_lq_rollout_k4_r1', 'ILi2ELi4ELb1ELb0ELb0ELb0ELb0ELi0E'),   # ... with the in-kernel policy
-        ('lq_rollout_kernel<8, 4, true, true, false, true, false, 2>', 'mapf_lq_rollout_k4_r1', 'ILi8ELi4ELb1ELb1ELb0ELb1ELb0ELi2E'),
-        ('lq_rollout_kernel<8, 4, true, true, false, true, false, 1>', 'mapf_lq_rollout_k4_r1', 'ILi8ELi4ELb1ELb1ELb0ELb1ELb0ELi1E'),
-        ('lq_rollout_kernel<8, 4, true, true, false, true, false, 3>', 'mapf_lq_rollout_k4_r1', 'ILi8ELi4ELb1ELb1ELb0ELb1ELb0ELi3E'),
-        ('lq_rollout_kernel<4, 8, true, true, false, true, false, 0>', 'mapf_lq_rollout_k8_r1', 'ILi4ELi8ELb1ELb1ELb0ELb1ELb0ELi0E'),
-        ('lq_rollout_kernel<1, 8, true, true, false, false, false, 0>', 'mapf_lq_rollout_k8_r1', 'ILi1ELi8ELb1ELb1ELb0ELb0ELb0ELi0E'),
+        ('lq_rollout_kernel<2, 4, true, true, false, false, false, 0, 0>', 'mapf_lq_rollout_k4_r1', 'ILi2ELi4ELb1ELb1ELb0ELb0ELb0ELi0ELi0EJEE'),
+        ('lq_rollout_kernel<2, 4, true, false, false, false, false, 0, 0>', 'mapf_lq_rollout_k4_r1', 'ILi2ELi4ELb1ELb0ELb0ELb0ELb0ELi0ELi0EJEE'),   # ... with the in-kernel policy
+        ('lq_rollout_kernel<8, 4, true, true, false, true, false, 2, 0>', 'mapf_lq_rollout_k4_r1', 'ILi8ELi4ELb1ELb1ELb0ELb1ELb0ELi2ELi0EJEE'),
+        ('lq_rollout_kernel<8, 4, true, true, false, true, false, 1, 0>', 'mapf_lq_rollout_k4_r1', 'ILi8ELi4ELb1ELb1ELb0ELb1ELb0ELi1ELi0EJEE'),
+        ('lq_rollout_kernel<8, 4, true, true, false, true, false, 3, 0>', 'mapf_lq_rollout_k4_r1', 'ILi8ELi4ELb1ELb1ELb0ELb1ELb0ELi3ELi0EJEE'),
+        ('lq_rollout_kernel<4, 8, true, true, false, true, false, 0, 0>', 'mapf_lq_rollout_k8_r1', 'ILi4ELi8ELb1ELb1ELb0ELb1ELb0ELi0ELi0EJEE'),
+        ('lq_rollout_kernel<1, 8, true, true, false, false, false, 0, 0>', 'mapf_lq_rollout_k8_r1', 'ILi1ELi8ELb1ELb1ELb0ELb0ELb0ELi0ELi0EJEE'),
     ]
     doc = {'_how': ' '.join(__doc__.split('\n\n')[0].split()), 'csrc_hash': bench.csrc_hash(), 'instances': {}}
     for name, listing, mangled in instances:
