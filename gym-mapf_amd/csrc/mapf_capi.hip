@@ -166,6 +166,12 @@ struct mapf_handle_s : StreamAndEvents {
     uint32_t episode_budget = 0;
     DevicePtr<uint32_t> left;
     DeviceBuf s_live;                 // staging of out_live_steps
+    // conflict matrix (mapf_set_conflict_pairs): the counts u64[n_slots * A * A] and the envs' slots (null: all in slot 0);
+    // n_slots 0 = the mode is off and both are null.  Only the kernels that count, mapf_set_conflict_pairs and mapf_conflict_pairs write M
+    uint32_t pair_slots = 0;
+    DevicePtr<unsigned long long> pair_counts;
+    DevicePtr<uint32_t> pair_slot_of_env;
+    size_t pair_bytes() const { return size_t(pair_slots) * A * A * sizeof(unsigned long long); }
     // host-pointer mode staging
     DeviceBuf s_actions, s_uniforms, s_local, s_reward, s_prob, s_done, s_coll, s_term, s_mask, s_ret, s_epi, s_ncoll;
     DeviceBuf x_local, x_reward, x_prob, x_done, x_coll;   // stand-ins for trajectory arrays the caller left out
@@ -699,6 +705,9 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
     mapf::EpisodeBudget bud{h->left, nullptr};
     const mapf::EpisodeBudget *budget = h->episode_budget ? &bud : nullptr;
     const mapf::EpisodeLimit *limit = (h->episode_limit || budget) ? &lim : nullptr;
+    // (... and the conflict matrix last: the lane-group instances that count, in the form the limit and the budget name)
+    const mapf::ConflictPairs cp{h->pair_counts, h->pair_slot_of_env, h->pair_slots};
+    const mapf::ConflictPairs *pairs = h->pair_slots ? &cp : nullptr;
     // (the totals are inputs too when the call accumulates)
     const CallArray arrays[] = {input(h->s_actions, io->actions, TEA, &a.actions, "actions"),
                                 output(h->s_ret, io->out_returns, E, &a.out_returns, "out_returns", a.accumulate),
@@ -720,7 +729,7 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
         if (int rc = reserve_stand_in(h, h->x_trunc, TE, "rec_truncated")) return rc;
         lim.rec_truncated = static_cast<uint8_t *>(h->x_trunc.ptr);
     }
-    HIP_TRY(mapf::launch_rollout(int(h->A), a, h->tune, h->prefer, h->stream, table, limit, budget));
+    HIP_TRY(mapf::launch_rollout(int(h->A), a, h->tune, h->prefer, h->stream, table, limit, budget, pairs));
     after_launch(h, h->last_rollout_kernel, io->n_steps, a.auto_reset);
     if (int rc = fetch_arrays(h, arrays)) return rc;
     if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
@@ -737,6 +746,44 @@ int mapf_rollout_limited(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *o
 
 int mapf_rollout_budgeted(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_truncations, uint8_t *rec_truncated, uint32_t *out_live_steps) {
     return rollout_impl(h, io, out_truncations, rec_truncated, out_live_steps);
+}
+
+int mapf_set_conflict_pairs(mapf_handle_t h, uint32_t n_slots, const uint32_t *slot_of_env) {
+    if (!h) return fail(MAPF_EINVAL, "set_conflict_pairs: null handle");
+    if (int rc = check_not_recording(h, "mapf_set_conflict_pairs")) return rc;
+    if (!h->graphs.empty()) return fail(MAPF_EINVAL, "set_conflict_pairs: recorded graphs hold launches without a conflict matrix (destroy them first)");
+    const uint64_t entries = uint64_t(n_slots) * h->A * h->A;
+    if (entries * sizeof(uint64_t) > (uint64_t(1) << 30)) return fail(MAPF_EINVAL, "set_conflict_pairs: n_slots * A * A * 8 bytes must not exceed 2^30");
+    if (n_slots && slot_of_env)
+        for (uint64_t e = 0; e < h->E; ++e)
+            if (slot_of_env[e] >= n_slots) return fail(MAPF_EINVAL, "set_conflict_pairs: slot_of_env[" + std::to_string(e) + "] is not below n_slots");
+    if (int rc = check_handle(h)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // (no launch may still count into what is freed here)
+    h->pair_slots = 0;
+    h->pair_counts.reset();
+    h->pair_slot_of_env.reset();
+    if (n_slots == 0) return MAPF_OK;
+    HIP_TRY(h->pair_counts.alloc(size_t(entries)));
+    if (slot_of_env && h->E) HIP_TRY(h->pair_slot_of_env.upload(slot_of_env, size_t(h->E)));
+    HIP_TRY(hipMemsetAsync(h->pair_counts, 0, size_t(entries) * sizeof(uint64_t), h->stream));   // every call: counts from zero
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->pair_slots = n_slots;
+    return MAPF_OK;
+}
+
+int mapf_conflict_pairs(mapf_handle_t h, uint64_t *out, int zero) {
+    if (!h) return fail(MAPF_EINVAL, "conflict_pairs: null handle");
+    if (!out && !zero) return fail(MAPF_EINVAL, "conflict_pairs: out is null and zero is 0");
+    if (!h->pair_slots) return fail(MAPF_EINVAL, "conflict_pairs: the handle has no conflict matrix (mapf_set_conflict_pairs)");
+    if (int rc = check_not_recording(h, "mapf_conflict_pairs")) return rc;
+    if (h->device_ptrs && misaligned(out)) return fail(MAPF_EINVAL, "conflict_pairs: device pointer must be 16-byte aligned");
+    if (int rc = check_handle(h)) return rc;
+    const size_t bytes = h->pair_bytes();
+    // (out receives the counts as they are before they are zeroed)
+    if (out && bytes) HIP_TRY(hipMemcpyAsync(out, h->pair_counts, bytes, h->device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    if (zero && bytes) HIP_TRY(hipMemsetAsync(h->pair_counts, 0, bytes, h->stream));
+    if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
+    return MAPF_OK;
 }
 
 int mapf_set_episode_budget(mapf_handle_t h, uint32_t n_episodes) {
@@ -1036,6 +1083,7 @@ int mapf_graph_begin(mapf_handle_t h) {
     if (h->capturing) return fail(MAPF_EINVAL, "graph_begin: already recording");
     if (h->episode_limit) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with an episode limit cannot be recorded (mapf_set_episode_limit(h, 0) first)");
     if (h->episode_budget) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with an episode budget cannot be recorded (mapf_set_episode_budget(h, 0) first)");
+    if (h->pair_slots) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with a conflict matrix cannot be recorded (mapf_set_conflict_pairs(h, 0, NULL) first)");
     HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed));
     h->capturing = true;
     h->cap_steps = 0;

@@ -177,6 +177,15 @@ struct EpisodeBudget {
     uint32_t *out_live_steps;      // [E] or null (RolloutArgs::accumulate applies): steps neither parked nor terminal on entry
 };
 
+// Conflict matrix (include/mapf_hip.h mapf_set_conflict_pairs): the handle's per-slot counts of vertex conflicts (upper triangle) and
+// swaps (lower triangle) per agent pair, and the slot of every env.  One more block beside the others: the instances that count
+// (pairs/mapf_lg_pairs.hip) take it last, behind the table policy, the limit and the budget where the launch has those.
+struct ConflictPairs {
+    unsigned long long *matrix;    // [n_slots * A * A] counts, row-major per slot; the diagonal is never written
+    const uint32_t *slot;          // [E] the env's slot, < n_slots; null = every env in slot 0
+    uint32_t n_slots;              // >= 1, n_slots * A * A * 8 <= 2^30 bytes (so an entry's index fits 32 bits)
+};
+
 // Every launcher names the kernel instance (and block size) that took the launch; the C ABI keeps the name of a
 // handle's last step / rollout launch (mapf_last_kernel) so a benchmark labels its numbers with what actually ran.
 constexpr size_t kKernelNameBytes = 160;   // what is kept of a name, the terminator included
@@ -280,10 +289,11 @@ enum class FamilyPreference { Auto, ThreadPerEnv, LaneGroup };
 // (table: the table policy of an actions == null launch, or null: streamed actions take precedence over it as over the other
 // policies, and the C ABI, which applies that rule, never passes both.  A recording launch names all five rec_* arrays: the C ABI
 // substitutes scratch for absent ones.  limit / budget: those of a handle that has them, or null; with a budget `limit` is
-// non-null too, max_steps 0 on a handle without a limit)
+// non-null too, max_steps 0 on a handle without a limit.  pairs: the conflict matrix of a handle that counts, or null)
 hipError_t launch_step(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, hipStream_t stream, const EpisodeLimit *limit = nullptr);
 hipError_t launch_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, hipStream_t stream,
-                          const TablePolicy *table = nullptr, const EpisodeLimit *limit = nullptr, const EpisodeBudget *budget = nullptr);
+                          const TablePolicy *table = nullptr, const EpisodeLimit *limit = nullptr, const EpisodeBudget *budget = nullptr,
+                          const ConflictPairs *pairs = nullptr);
 // is the step launch_step would launch a thread-per-env one (one thread per env), else lg_group_size(A) threads per env?
 bool step_is_thread_per_env(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, const EpisodeLimit *limit);
 
@@ -297,6 +307,12 @@ hipError_t launch_rollout_lg(const LgRolloutPlan &plan, int n_agents, const Roll
 hipError_t launch_rollout_lg_limit(const LgRolloutPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table, const EpisodeLimit &limit);
 hipError_t launch_rollout_lg_budget(const LgRolloutPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table,
                                     const EpisodeLimit &limit, const EpisodeBudget &budget);
+// ... and the instances of the three that count conflicting pairs: pairs/mapf_lg_pairs.hip, compiled once per form (plain, limit, budget)
+hipError_t launch_rollout_lg_pairs(const LgRolloutPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table, const ConflictPairs &pairs);
+hipError_t launch_rollout_lg_pairs_limit(const LgRolloutPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table, const EpisodeLimit &limit,
+                                         const ConflictPairs &pairs);
+hipError_t launch_rollout_lg_pairs_budget(const LgRolloutPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table,
+                                          const EpisodeLimit &limit, const EpisodeBudget &budget, const ConflictPairs &pairs);
 hipError_t launch_step_lg(const LgStepPlan &plan, int n_agents, const StepArgs &args, hipStream_t stream);
 hipError_t launch_step_lg_limit(const LgStepPlan &plan, int n_agents, const StepArgs &args, hipStream_t stream, const EpisodeLimit &limit);
 hipError_t launch_reset_ages(uint32_t *age, const uint8_t *mask, uint64_t n_envs, hipStream_t stream);

@@ -4,10 +4,11 @@
 //   rollout -- Family::kernel<L, FULL, MV_LDS, RECORD, STREAM, TABLE>(dense) returns the address of an instance of lg_rollout_kernel
 //              (mapf_lg_rollout_kernel.hpp).  mapf_lg_rollout.hip: the plain and the table instances, DENSE for full groups only;
 //              mapf_lg_limit.hip: the limit instances, guarded only; mapf_lg_budget.hip: the budget instances, guarded only;
+//              pairs/mapf_lg_pairs.hip: the instances of the three that count conflicting pairs, guarded only;
 //   step    -- Family::kernel<L, FULL, EXT_UNIFORMS>() likewise, of lg_step_kernel (mapf_lg_step_kernel.hpp).  mapf_lg_kernels.hip:
 //              the plain instances; mapf_lg_limit.hip: the limit instances.
 // `extra` are the kernel's arguments behind (args, A): nothing, the table policy, the episode limit, or both in that order; the
-// budget instances take the episode budget behind the limit.
+// budget instances take the episode budget behind the limit, the instances that count pairs the conflict matrix last.
 #pragma once
 #include "mapf_lg.hpp"
 #include "mapf_plan.hpp"
@@ -21,7 +22,8 @@ hipError_t launch_lg_rollout_instance(const LgRolloutPlan &plan, const RolloutAr
     const auto kern = plan.mv_lds ? Family::template kernel<L, FULL, true, RECORD, STREAM, TABLE>(plan.dense)
                                   : Family::template kernel<L, FULL, false, RECORD, STREAM, TABLE>(plan.dense);
     if (plan.lds_bytes > 32 * 1024) {
-        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(kLdsBytes - kLdsReserve))) return e;
+        // (the most a CU has beside the instance's static LDS: kLdsReserve, and kPairsLdsBytes more in the instances that count pairs)
+        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(kLdsBytes - kLdsReserve - (plan.pairs ? kPairsLdsBytes : 0)))) return e;
     }
     char name[kKernelNameBytes];
     lg_rollout_kernel_name(name, plan, RECORD, STREAM, TABLE);

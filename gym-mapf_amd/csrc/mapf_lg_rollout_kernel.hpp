@@ -10,6 +10,9 @@
 //   EpisodeBudget -- the episode budget (include/mapf_hip.h mapf_set_episode_budget), behind the limit: a per-env count of episodes
 //     left beside the age.  An env whose count is 0 is PARKED: it folds into the `terminal` the transition is told, so its step
 //     draws and moves nothing, and its done bit is cleared before anything counts or records it.
+//   ConflictPairs -- the conflict matrix (include/mapf_hip.h mapf_set_conflict_pairs), last: the step's fast path is the one of the
+//     instance without it; a wave in which some env's step collided then takes the attributed pass (lg_count_pairs below), which
+//     finds the pairs the minima folded away and counts them with atomic adds.  Guarded instances only (pairs/mapf_lg_pairs.hip).
 // A mode's sections are `if constexpr`: an instance without the mode compiles to the code it had when the modes were separate
 // kernels (tools/compare_kernels.py, profiles/kernel_templates_device_listings.txt).  Which instances exist is each unit's say,
 // through its family struct.
@@ -18,17 +21,77 @@
 
 namespace mapf {
 
+// The attributed pass of a step under the conflict matrix: which agent pairs of (prev, next) conflict, counted into the env's
+// slot of the matrix.  Entered by the WHOLE wave (the cross-lane reads need every lane) when some env of the wave reports a
+// collision; only the lanes of such an env (`collided`) test and count.  The pair tests of pair_tests, unmerged: my own pair, then
+// rotations 1 .. L/2 against group position og, whose agents 2og, 2og+1 are known; a ghost slot's index is n_agents or more and
+// drops out by that (pair_apply masks the same slots).  A
+// rotation below L/2 meets every lane pair once; the half rotation meets it from both sides (a group of two lanes has only that
+// one), so there the lower position counts.  One rolled loop of ds_bpermute reads at every group size: this path runs on a few
+// steps in a thousand, and a rolled loop keeps its registers out of the step loop's budget.
+// Every hit is one 64-bit atomic add without a return value (relaxed, agent scope) on M[slot][min][max] (vertex) or
+// M[slot][max][min] (swap): integer adds commute, so the matrix does not depend on the order the waves run in.
+template <int L>
+__device__ __forceinline__ void lg_count_pairs(const LaneCtx<L> &x, const uint32_t n_agents, const bool collided, const uint32_t e,
+                                               const uint32_t cur0, const uint32_t cur1, const uint32_t next0, const uint32_t next1,
+                                               const ConflictPairs &cp_lds) {
+    using gu64 = __attribute__((address_space(1))) unsigned long long *;
+    using gslot = const __attribute__((address_space(1))) uint32_t *;
+    const ConflictPairs cp = cp_lds;   // (the kernel keeps the block in LDS; what it points to is global memory)
+    // per-lane facts as integers, not wave masks: the step loop around this pass has no scalar register pair to spare
+    uint32_t counting = collided ? 1u : 0u;
+    asm volatile("" : "+v"(counting));
+    // the slot is loaded here, not held across the step loop (a slot past the matrix -- the host has refused those -- is clamped)
+    uint32_t slot_base = 0u;
+    if (counting != 0u && cp.slot) slot_base = min(*(gslot)at(cp.slot, e), cp.n_slots - 1u) * n_agents * n_agents;
+    const gu64 m = (gu64)cp.matrix + slot_base;
+    // agents i and j (an index from n_agents on: a ghost slot, or a pair that the other side counts) with their cells
+    auto count = [&](uint32_t i, uint32_t j, uint32_t prev_i, uint32_t next_i, uint32_t prev_j, uint32_t next_j) __attribute__((always_inline)) {
+        const uint32_t lo = min(i, j), hi = max(i, j);
+        const bool both = counting != 0u && hi < n_agents;
+        if (both && next_i == next_j)   // vertex conflict (mapf_env.py:386-387): the upper triangle
+            (void)__hip_atomic_fetch_add(m + (lo * n_agents + hi), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (both && prev_i == next_j && prev_j == next_i)   // swap (:382-384): the lower triangle
+            (void)__hip_atomic_fetch_add(m + (hi * n_agents + lo), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    count(2u * x.g, 2u * x.g + 1u, cur0, next0, cur1, next1);
+    if constexpr (L > 1) {
+        const uint32_t pk_prev = cur0 | (cur1 << 16), pk_next = next0 | (next1 << 16);
+#pragma unroll 1
+        for (uint32_t s = 1; s <= uint32_t(L / 2); ++s) {
+            const uint32_t og = (x.g + s) & uint32_t(L - 1);
+            const int src = int(x.base + og);
+            const uint32_t o_prev = uint32_t(__shfl(int(pk_prev), src, 64)), o_next = uint32_t(__shfl(int(pk_next), src, 64));
+            const uint32_t j0 = (s < uint32_t(L / 2) || x.g < og) ? 2u * og : 0xFFFFu;   // the half rotation: the lower position counts
+            count(2u * x.g, j0, cur0, next0, o_prev & 0xFFFFu, o_next & 0xFFFFu);
+            count(2u * x.g, j0 + 1u, cur0, next0, o_prev >> 16, o_next >> 16);
+            count(2u * x.g + 1u, j0, cur1, next1, o_prev & 0xFFFFu, o_next & 0xFFFFu);
+            count(2u * x.g + 1u, j0 + 1u, cur1, next1, o_prev >> 16, o_next >> 16);
+        }
+    }
+}
+
 template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM, bool DENSE, class... Extra>
 __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(const RolloutArgs p, const uint32_t n_agents, const Extra... extra) {
     constexpr bool TABLE = has_kernel_arg<TablePolicy, Extra...>, LIMIT = has_kernel_arg<EpisodeLimit, Extra...>,
-                   BUDGET = has_kernel_arg<EpisodeBudget, Extra...>;
+                   BUDGET = has_kernel_arg<EpisodeBudget, Extra...>, PAIRS = has_kernel_arg<ConflictPairs, Extra...>;
     static_assert(!(TABLE && STREAM), "a table instance runs the launches without streamed actions");
     static_assert(!(LIMIT && DENSE) && (LIMIT || !BUDGET), "the limit instances are guarded; a budget instance takes the limit block too");
+    static_assert(!(PAIRS && DENSE), "the instances that count conflicting pairs are guarded");
     const auto tp = kernel_arg<TablePolicy>(extra...);       // by value: an empty tag where the instance has no such argument
     const auto lim = kernel_arg<EpisodeLimit>(extra...);
     const auto bud = kernel_arg<EpisodeBudget>(extra...);
     __shared__ SlipRow slip[8];
     __shared__ OutcomeRow outcome[16];
+    // the conflict matrix's block waits in LDS (kPairsLdsBytes behind the table image: the planner leaves room), not in five scalar
+    // registers across the step loop, which has none to spare: the attributed pass reads it back
+    const ConflictPairs *cp = nullptr;
+    if constexpr (PAIRS) {
+        __shared__ ConflictPairs cp_lds;
+        static_assert(sizeof(ConflictPairs) <= kPairsLdsBytes, "the room plan_rollout_lg leaves");
+        if (threadIdx.x == 0u) cp_lds = kernel_arg<ConflictPairs>(extra...);   // (the staging below ends with __syncthreads())
+        cp = &cp_lds;
+    }
     extern __shared__ __attribute__((aligned(16))) MoveEntry lds_mv[];
     bool live_rt;
     LaneCtx<L> x = lane_ctx<L>(n_agents, p.n_envs, live_rt);
@@ -231,6 +294,12 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
         if (p.c.need_rng && ((t & 3u) == 0u || s == 0u)) rng = pair_block_words<(L > 1)>(p.c, env_id, t, x.g);
         lg_transition<L, FULL, false, true, MV_LDS, true>(p.c, mv, slip, outcome, x, n_agents, cur0, cur1, goal0, goal1, act0, act1, 0.0, 0.0,
                                             env_id, t, step_word(rng, t), no_op, next0, next1, o STAMP_ARG);
+        if constexpr (PAIRS) {
+            // status byte 1 is the collision of a step that was not a no-op (a no-op reports kTerminalStatus).  __any: the branch is
+            // the wave's, as the cross-lane reads of the pass need it; cur and next are still the cells on entry and the sampled ones
+            const bool collided = live && (o.status & 0xFF00u) != 0u;
+            if (__builtin_expect(__any(collided), 0)) lg_count_pairs<L>(x, n_agents, collided, e, cur0, cur1, next0, next1, *cp);
+        }
         if constexpr (BUDGET) {
             // ... but it reports no done: a no-op's status is kTerminalStatus, whose byte 0 goes and whose byte 2 stays (the carried `terminal`
             // is 1 from here on).  Its reward is +0.0, and ret + 0.0 would turn an accumulated -0.0 into +0.0: what is added is -0.0

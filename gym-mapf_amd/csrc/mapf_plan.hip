@@ -361,9 +361,9 @@ void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, 
     const char *family = plan.budget ? "_budget_guarded" : (plan.limit ? "_limit_guarded" : "");
     const char *form = plan.budget ? "BUDGET" : (plan.limit ? "LIMIT" : (plan.dense ? "DENSE" : "GUARDED"));
     const char *note = plan.budget ? "; episode budget" : (plan.limit ? "; episode step limit" : "");
-    snprintf(name, kKernelNameBytes, "lg_rollout_kernel%s%s<L=%d,%s,%s,%s,%s,%s> block=%u (pair layout: 2 agents per lane%s%s)", table_policy ? "_table" : "",
-             family, plan.L, plan.full ? "FULL" : "RAGGED", plan.mv_lds ? "MV_LDS" : "MV_GLOBAL", record ? "RECORD" : "TOTALS",
-             table_policy ? "TABLE" : (streamed ? "STREAM" : "POLICY"), form, plan.block, note,
+    snprintf(name, kKernelNameBytes, "lg_rollout_kernel%s%s%s<L=%d,%s,%s,%s,%s,%s%s> block=%u (pair layout: 2 agents per lane%s%s%s)", table_policy ? "_table" : "",
+             family, plan.pairs ? "_pairs" : "", plan.L, plan.full ? "FULL" : "RAGGED", plan.mv_lds ? "MV_LDS" : "MV_GLOBAL", record ? "RECORD" : "TOTALS",
+             table_policy ? "TABLE" : (streamed ? "STREAM" : "POLICY"), form, plan.pairs ? ",PAIRS" : "", plan.block, note, plan.pairs ? "; conflict matrix" : "",
              table_policy ? "; table policy: action bytes gathered from global memory" : "");
 }
 
@@ -488,8 +488,17 @@ static bool prefers_tpe(FamilyPreference prefer, int n_agents) {
 }
 
 RolloutRoute route_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool table_policy, size_t table_bytes,
-                           bool limited, bool budgeted) {
+                           bool limited, bool budgeted, bool pairs) {
     RolloutRoute r;
+    if (pairs) {   // the instances that count exist in the lane-group family only, guarded, one form per (limit, budget)
+        RolloutTuning t = tune;   // (kPairsLdsBytes of static LDS more than the others: the largest tables stay in global memory)
+        t.mv_lds_max_bytes = std::min(t.mv_lds_max_bytes, kLdsBytes - kPairsLdsBytes);
+        r.lg = plan_rollout_lg(n_agents, args, t, limited || budgeted);
+        r.lg.budget = budgeted;
+        r.lg.dense = false;
+        r.lg.pairs = true;
+        return r;
+    }
     if (budgeted) {   // the budget instances exist in the lane-group family only -- no packed plan, whatever the tuning says
         r.lg = plan_rollout_lg(n_agents, args, tune, true);
         r.lg.budget = true;

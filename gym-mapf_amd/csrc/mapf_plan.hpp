@@ -64,6 +64,9 @@ int lg_group_size(int n_agents);
 // Largest block of a rollout kernel: groups of 16 lanes unroll 8 rotation rounds and need more than the 128 registers a
 // 1024-thread block leaves per lane.  The kernels' __launch_bounds__ (rollout_max_block, mapf_lg_rollout.hip) read it too.
 constexpr unsigned kLgRolloutMaxBlock = 1024u, kLgRolloutMaxBlock16 = 512u;
+// static LDS the instances that count conflicting pairs keep beyond kLdsReserve (their ConflictPairs block): a pairs plan stages the
+// move table into LDS only where this fits as well
+constexpr size_t kPairsLdsBytes = 32;
 // The instance lg_rollout_kernel<L, full, mv_lds, ., ., dense> (or lg_rollout_kernel_table<L, full, mv_lds, ., dense>) and its geometry;
 // under `limit` the instance of the same fields among the limit kernels (mapf_lg_limit.hip), which are never dense
 struct LgRolloutPlan {
@@ -73,6 +76,7 @@ struct LgRolloutPlan {
     bool dense = false;              // full groups and the env count fills every block: no per-lane predicates
     bool limit = false;              // the family the plan names: the instances under an episode step limit, or those without
     bool budget = false;             // ... or, of a limit plan, the instances under an episode budget (mapf_lg_budget.hip): their launcher sets it
+    bool pairs = false;              // ... and, of any of the three, the instances that count conflicting pairs (pairs/mapf_lg_pairs.hip): never dense
     unsigned block = 0, grid = 0;
     size_t lds_bytes = 0;            // dynamic LDS segment: the move table, or 0 (the launcher raises the limit beyond 32 KB)
 };
@@ -85,6 +89,7 @@ struct LgStepPlan { int L = 0; bool full = false; bool limit = false; unsigned b
 LgStepPlan plan_step_lg(int n_agents, const StepArgs &args, bool limited = false);
 // The names the launchers note for these plans (mapf_last_kernel; at most kKernelNameBytes with the terminator).  A limit plan's
 // name says _limit_guarded (the step: _limit) and LIMIT, and has no DENSE / GUARDED field; a budget plan's says _budget_guarded and BUDGET.
+// A pairs plan's name says _pairs behind the kernel's name and PAIRS behind the form (GUARDED, LIMIT or BUDGET).
 void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy);
 void lg_step_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms);
 
@@ -119,6 +124,8 @@ void transitions_kernel_name(char *name, const TransitionsPlan &plan, uint32_t n
 // ------------------------------------------------------------------- the route
 // Which family takes a launch, with that family's plan (the other plans stay as constructed).  The rules, each written once, in
 // route_rollout / route_step, in this order:
+//   a conflict matrix takes the lane-group plan of its form (plain, limit or budget), marked `pairs` and never dense, before
+//     anything else: whatever the handle prefers and whatever limit_packed says;
 //   a budget takes the lane-group budget plan (a limit plan marked `budget`) before anything else;
 //   a limit never goes to thread-per-env, and the step under a limit has the lane-group limit instance only;
 //   thread-per-env takes what the handle prefers it for (FamilyPreference; Auto: A <= 2) where its kernels exist: steps up to
@@ -130,9 +137,9 @@ enum class KernelFamily { ThreadPerEnv, Packed, LaneGroup };
 struct RolloutRoute { KernelFamily family = KernelFamily::LaneGroup; TpePlan tpe; LqPlan lq; LgRolloutPlan lg; };
 struct StepRoute { KernelFamily family = KernelFamily::LaneGroup; TpePlan tpe; StepPlan lq; LgStepPlan lg; };
 // (table_policy: the launch follows the table policy, of table_bytes action bytes; limited / budgeted: it runs under an episode
-// step limit / an episode budget.  args is never dereferenced)
+// step limit / an episode budget; pairs: the handle counts conflicting pairs.  args is never dereferenced)
 RolloutRoute route_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool table_policy, size_t table_bytes,
-                           bool limited, bool budgeted);
+                           bool limited, bool budgeted, bool pairs = false);
 // (ext_uniforms: the caller supplies the uniforms)
 StepRoute route_step(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool limited, bool ext_uniforms);
 

@@ -57,6 +57,8 @@ SIGNATURES = {
     'mapf_rollout_budgeted': (c_int, [c_void_p, POINTER(MapfRolloutIO), c_void_p, c_void_p, c_void_p]),
     'mapf_set_episode_budget': (c_int, [c_void_p, c_uint32]),
     'mapf_episodes_left': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'mapf_set_conflict_pairs': (c_int, [c_void_p, c_uint32, c_void_p]),
+    'mapf_conflict_pairs': (c_int, [c_void_p, c_void_p, c_int]),
     'mapf_fill_random_actions': (c_int, [c_void_p, c_void_p, c_uint64, c_uint32]),
     'mapf_set_policy': (c_int, [c_void_p, c_int, c_void_p]),
     'mapf_set_policy_table': (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),

@@ -94,13 +94,18 @@ def evaluate(env, n_episodes, max_steps, chunk=256):
     ``returns`` f64 (the rewards of the ``n_episodes`` episodes, no cut-off episode among them), ``goal_ends`` (= episodes -
     collisions: episodes that ended on the goals, a terminal start state included), ``collisions``, ``truncations`` and
     ``live_steps`` (the steps those episodes took), uint32 -- ``goal_ends + collisions + truncations == n_episodes`` everywhere.
-    Not covered: the multi-map and union-map wrappers and the scalar ``MapfEnv``."""
+    On an env that counts conflicting pairs (``set_conflict_pairs``) the matrix is zeroed before the first launch and returned as
+    ``pair_conflicts`` uint64 [n_slots, A, A] (``conflicts`` and ``conflicting_pairs`` read it): which agents got in each other's
+    way during those episodes.  Not covered: the multi-map and union-map wrappers and the scalar ``MapfEnv``."""
     n_episodes, max_steps, chunk = int(n_episodes), int(max_steps), int(chunk)
     if n_episodes < 1 or max_steps < 1 or chunk < 1:
         raise ValueError('evaluate needs n_episodes >= 1, max_steps >= 1 and chunk >= 1')
     env.set_episode_limit(max_steps)
     env.set_episode_budget(n_episodes)
     env.reset()
+    counting = bool(getattr(env, 'conflict_slots', 0))
+    if counting:
+        cleared = env.conflict_pairs(zero=True)   # (kept until the sync below: in device mode the read is only enqueued)
     totals = None
     for _ in range(-(-n_episodes * max_steps // chunk)):
         totals = env.rollout(chunk, auto_reset=True, accumulate_into=totals)
@@ -111,4 +116,32 @@ def evaluate(env, n_episodes, max_steps, chunk=256):
     assert int(left.max(initial=0)) == 0, 'after n_episodes * max_steps steps every env is parked'
     out = {k: host(totals[k]) for k in ('returns', 'collisions', 'truncations', 'live_steps')}
     out['goal_ends'] = host(totals['episodes']) - out['collisions']
+    if counting:
+        del cleared
+        pairs = env.conflict_pairs()
+        env.sync()
+        out['pair_conflicts'] = host(pairs)
     return out
+
+
+def conflicts(M):
+    """The count per UNORDERED agent pair of a conflict matrix ``M`` [..., A, A] (``VecMapfEnv.conflict_pairs``): vertex conflicts
+    (the upper triangle) plus swaps (the lower one), as a symmetric matrix of the same shape with a zero diagonal."""
+    M = np.asarray(M.cpu() if hasattr(M, 'cpu') else M, dtype=np.uint64)
+    if M.ndim < 2 or M.shape[-1] != M.shape[-2]:
+        raise ValueError('a conflict matrix is [..., A, A], got shape %r' % (M.shape,))
+    upper, lower = np.triu(M, 1), np.tril(M, -1)
+    both = upper + np.swapaxes(lower, -1, -2)
+    return both + np.swapaxes(both, -1, -2)
+
+
+def conflicting_pairs(M):
+    """The rows ``(i, j, vertex, swap)``, i < j, of the agent pairs with a nonzero count in the conflict matrix ``M`` [A, A] or
+    [n_slots, A, A] (the slots are summed), sorted by (i, j): the pairs a decomposing planner merges into one group and replans."""
+    M = np.asarray(M.cpu() if hasattr(M, 'cpu') else M, dtype=np.uint64)
+    if M.ndim == 3:
+        M = M.sum(axis=0, dtype=np.uint64)
+    if M.ndim != 2 or M.shape[0] != M.shape[1]:
+        raise ValueError('a conflict matrix is [A, A] or [n_slots, A, A], got shape %r' % (M.shape,))
+    vertex, swap = np.triu(M, 1), np.tril(M, -1).T
+    return [(int(i), int(j), int(vertex[i, j]), int(swap[i, j])) for i, j in zip(*np.nonzero(vertex + swap))]

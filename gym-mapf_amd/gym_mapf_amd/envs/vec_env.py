@@ -180,6 +180,7 @@ class VecMapfEnv:
         self._rollout_io = None        # rollout(out=...): the _RolloutIO of the last such call
         self.episode_limit = 0         # set_episode_limit: steps per episode, 0 = no limit
         self.episode_budget = 0        # set_episode_budget: episodes per env, 0 = no budget
+        self.conflict_slots = 0        # set_conflict_pairs: slots of the conflict matrix, 0 = the mode is off
 
     # ------------------------------------------------------------------ construction
     def _as_local(self, locations, local_ids, what):
@@ -546,6 +547,40 @@ class VecMapfEnv:
         if out is None:
             out = self._empty(shape, np.uint32)
         nat.check(self._lib.mapf_episodes_left(self._h, self._ptr(out, np.uint32, shape, 'out'), self._ptr(set, np.uint32, shape, 'set')))
+        return out
+
+    def set_conflict_pairs(self, n_slots=1, slots=None):
+        """Conflict matrix: from now on every ``rollout`` counts, per agent pair, the vertex conflicts and the swaps of its live steps
+        into ``M`` uint64 [n_slots, A, A] on the device (``conflict_pairs`` reads it): ``M[slot, i, j]``, i < j, counts the steps on
+        which agents i and j moved onto one cell, ``M[slot, j, i]`` the steps on which they traded cells; all conflicting pairs of a
+        step count.  ``slots`` uint32 [E] (a HOST array in both modes; copied) names every env's slot, ``None`` puts all envs in slot
+        0.  ``n_slots`` ``None`` or 0 switches the mode off (the default); every call zeroes ``M``.  Nothing else of a rollout
+        changes; it runs the lane-group kernels' instances that count (``last_kernel`` says PAIRS), ``step`` counts nothing and
+        ``graph_begin`` is refused.  Not covered: the multi-map and union-map wrappers and the scalar ``MapfEnv``."""
+        n_slots = 0 if n_slots is None else n_slots
+        if isinstance(n_slots, bool) or not isinstance(n_slots, (int, np.integer)) or not 0 <= int(n_slots) <= 0xFFFFFFFF:
+            raise ValueError('n_slots must be None or an integer 0 .. 2**32 - 1, got %r' % (n_slots,))
+        ptr = None
+        if slots is not None:
+            slots = self._host_ints(slots, 'slots')
+            if slots.shape != (self.n_envs,) or (slots.size and (slots.min() < 0 or slots.max() > 0xFFFFFFFF)):
+                raise ValueError('slots must be %d non-negative integers below n_slots' % self.n_envs)
+            slots = np.ascontiguousarray(slots, dtype=np.uint32)
+            ptr = slots.ctypes.data
+        nat.check(self._lib.mapf_set_conflict_pairs(self._h, int(n_slots), ptr))
+        self._rollout_io = None
+        self.conflict_slots = int(n_slots)
+
+    def conflict_pairs(self, out=None, zero=False):
+        """The conflict matrix, uint64 [n_slots, A, A] (``set_conflict_pairs``): the upper triangle counts vertex conflicts, the lower
+        one swaps, the diagonal is zero.  ``zero=True`` clears the device's counts after the read.  A host array, or a CUDA tensor in
+        device mode (then only enqueued).  ``policies.conflicts`` and ``policies.conflicting_pairs`` read it."""
+        if not self.conflict_slots:
+            raise ValueError('the env has no conflict matrix (set_conflict_pairs)')
+        shape = (self.conflict_slots, self.n_agents, self.n_agents)
+        if out is None:
+            out = self._empty(shape, np.uint64)
+        nat.check(self._lib.mapf_conflict_pairs(self._h, self._ptr(out, np.uint64, shape, 'out'), 1 if zero else 0))
         return out
 
     def episode_steps(self, out=None, set=None):

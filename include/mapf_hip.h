@@ -257,6 +257,42 @@ int mapf_set_episode_budget(mapf_handle_t h, uint32_t n_episodes);
 int mapf_episodes_left(mapf_handle_t h, uint32_t *out_left, const uint32_t *set_left);
 int mapf_rollout_budgeted(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_truncations, uint8_t *rec_truncated, uint32_t *out_live_steps);
 
+/*
+ * Conflict matrix (ABI 6, new symbols only): fused rollouts that count WHICH agent pairs collide -- what a planner that solves
+ * agents or groups apart and joins their policies needs to know before it merges groups and replans.  A totals-only rollout
+ * reports one collisions count per env; the pairs behind it otherwise cost a recording rollout and an O(T * E * A^2) pass over it.
+ * THE DEFINITION.  A handle has a conflict matrix M, or none (the default).  M is u64[n_slots, A, A] in device memory, and every env
+ * has a slot, slot[e] < n_slots.  For every env e and every step of a mapf_rollout, mapf_rollout_limited or mapf_rollout_budgeted
+ * launch -- any action source, recording or not, auto-reset or not -- that is not a no-op on entry (a no-op: an env that is
+ * terminal on entry, mapf_env.py:239-240, or parked by the budget), with prev the cells on entry and next the sampled cells
+ * before any reset, for every i < j < A:
+ *   next[i] == next[j], a vertex conflict (mapf_env.py:386-387):            M[slot[e]][i][j] += 1  (the upper triangle);
+ *   prev[i] == next[j] && prev[j] == next[i], a swap (mapf_env.py:382-384): M[slot[e]][j][i] += 1  (the lower triangle).
+ * ALL conflicting pairs of a step count, not the first one only; the diagonal is never written.  A non-terminal state has
+ * distinct cells, so a pair is never both, and a live step reports collision exactly when it adds at least one count.
+ * The mode changes nothing else: state, outputs, totals, ages, left, both Philox streams and the step index are bit for bit those
+ * of the same launch with the mode off.  Counts of shards add: the matrices of two handles that split a batch by env_id_offset
+ * sum to the whole batch's matrix.
+ *
+ * mapf_set_conflict_pairs: n_slots == 0 switches the mode off and frees M; otherwise it allocates M, and slot_of_env u32[E] -- a
+ *   HOST pointer in every handle mode -- is copied (NULL: every env in slot 0).  Every call zeroes M.  MAPF_EINVAL for a null
+ *   handle, a slot >= n_slots, or n_slots * A * A * 8 > 2^30 bytes; refused (MAPF_EINVAL) while recording and while recorded
+ *   graphs live, as mapf_set_episode_limit is.  A handle with the mode on refuses mapf_graph_begin with MAPF_EUNSUPPORTED.
+ * mapf_conflict_pairs: out u64[n_slots * A * A] receives M -- a HOST pointer, or a DEVICE pointer on a MAPF_FLAG_DEVICE_PTRS
+ *   handle (then only enqueued) -- and then M is zeroed if zero != 0.  out == NULL is allowed with zero; both absent, or the mode
+ *   off, is MAPF_EINVAL.
+ * mapf_step* count nothing and stay as they are (a single step hands back the cells: the caller can count for itself).
+ *   mapf_reset, mapf_set_state, mapf_set_episode_limit and mapf_set_episode_budget leave M alone.
+ * Everything is validated on the host before any device work.  Launches of a handle with the mode on run the lane-group kernels'
+ * instances that count, whatever the handle's family flag or limit_packed, and mapf_last_kernel says PAIRS, next to LIMIT or
+ * BUDGET where those apply; with the mode off every launch, kernel instance and name is what it is without this feature.
+ * Out of scope: packed (lq_*) and thread-per-env forms (a handle with the mode on takes the lane-group speed, as one with a budget
+ * does), the single step and recorded graphs, the multi-map / union-map wrappers and the scalar MapfEnv, per-step or per-episode
+ * logs of conflicts, anything that merges groups or replans on the device.
+ */
+int mapf_set_conflict_pairs(mapf_handle_t h, uint32_t n_slots, const uint32_t *slot_of_env);
+int mapf_conflict_pairs(mapf_handle_t h, uint64_t *out, int zero);
+
 /* Synthetic policy used by bench/rollout: fills actions u8[n_steps*E*A] for step indices
  * t0 .. t0+n_steps-1 from the policy stream (oracle/philox.py random_actions_np; ABI 5: key seed + 1, ONE Philox
  * call per agent quad per FOUR steps -- counter (env, t >> 2, quad), word t & 3, byte agent & 3, action =

@@ -14,7 +14,7 @@
 set -u
 OLD=$(cd "$1" && pwd); NEW=$(cd "$2" && pwd); mkdir -p "$3"; WORK=$(cd "$3" && pwd); JOBS=${4:-8}
 MK="$NEW/gym-mapf_amd/csrc/Makefile"
-UNITS=$(make -s --no-print-directory -f "$MK" print-kernel-units)        # name, source unit
+UNITS=$(make -s --no-print-directory -f "$MK" print-kernel-units print-added-kernel-units 2>/dev/null || make -s --no-print-directory -f "$MK" print-kernel-units)   # name, source unit: both tables
 HOST=$(for f in "$NEW"/gym-mapf_amd/csrc/*.hip; do unit=$(basename "$f" .hip); echo "$UNITS" | grep -q " $unit\$" || echo "$unit"; done)
 
 build() {   # side, tree, names: the listings into $WORK/side/raw, their masked copies into $WORK/side

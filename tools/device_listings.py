@@ -28,6 +28,11 @@ def units():
     return dict(line.split() for line in _make('print-kernel-units').splitlines())
 
 
+def added_units():
+    """{name: source unit} of the Makefile's second table: the kernel-holding compilations that entered the library after the first"""
+    return dict(line.split() for line in _make('print-added-kernel-units').splitlines())
+
+
 def listings(*names):
     """{name: listing text} for the named compilations (a kernel-holding one or a host unit); for all kernel-holding ones if none is named"""
     names = names or tuple(units())
