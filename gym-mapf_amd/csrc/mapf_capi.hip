@@ -155,6 +155,12 @@ struct mapf_handle_s : StreamAndEvents {
     DevicePtr<uint8_t> table_bytes;
     DevicePtr<uint16_t> table_rows;
     mapf::TablePolicy table{};
+    // joint table policy (mapf_set_policy_joint): device copies of the action bytes, the agents' segment offsets and partners, and
+    // the view of them the kernels are handed; joint.table null = off.  At most one of table / joint is on
+    DevicePtr<uint8_t> joint_bytes;
+    DevicePtr<uint32_t> joint_offset;
+    DevicePtr<uint16_t> joint_partner;
+    mapf::JointPolicy joint{};
     DevicePtr<uint16_t> state, start, goal;
     // episode step limit (mapf_set_episode_limit): N (0 = none) and the per-env ages, which are all zero while N == 0 -- only the
     // limit kernels and mapf_episode_steps write them, and only a handle with a limit runs those
@@ -197,6 +203,12 @@ struct mapf_handle_s : StreamAndEvents {
         table_bytes.reset();
         table_rows.reset();
         table = mapf::TablePolicy{};
+    }
+    void drop_policy_joint() {
+        joint_bytes.reset();
+        joint_offset.reset();
+        joint_partner.reset();
+        joint = mapf::JointPolicy{};
     }
     // Teardown: the stream drains, then the recordings go (they name the handle's buffers), then the members -- every
     // buffer -- and last the base: events, and the stream if the handle created it.
@@ -693,6 +705,7 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
     // (the table policy travels beside the argument block: its kernels are instances of their own; streamed actions take
     // precedence over it, as over the other policies -- the ONE place that rule is applied: no launcher sees both)
     const mapf::TablePolicy *table = (h->table.table && !io->actions) ? &h->table : nullptr;
+    const mapf::JointPolicy *joint = (h->joint.table && !io->actions) ? &h->joint : nullptr;   // (the joint table policy likewise)
     a.auto_reset = io->step_flags & MAPF_STEP_AUTO_RESET;
     a.accumulate = io->accumulate != 0;
     a.start_terminal_any = h->start_terminal_any;
@@ -729,7 +742,7 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
         if (int rc = reserve_stand_in(h, h->x_trunc, TE, "rec_truncated")) return rc;
         lim.rec_truncated = static_cast<uint8_t *>(h->x_trunc.ptr);
     }
-    HIP_TRY(mapf::launch_rollout(int(h->A), a, h->tune, h->prefer, h->stream, table, limit, budget, pairs));
+    HIP_TRY(mapf::launch_rollout(int(h->A), a, h->tune, h->prefer, h->stream, table, limit, budget, pairs, joint));
     after_launch(h, h->last_rollout_kernel, io->n_steps, a.auto_reset);
     if (int rc = fetch_arrays(h, arrays)) return rc;
     if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
@@ -861,6 +874,7 @@ int mapf_set_policy_table(mapf_handle_t h, const uint8_t *table, uint32_t n_rows
             return fail(MAPF_EINVAL, "set_policy_table: row_index[" + std::to_string(i) + "] = " + std::to_string(unsigned(row_index[i])) + " is not below n_rows");
     HIP_TRY(hipStreamSynchronize(h->stream));   // no launch may still be reading the old copies
     h->drop_policy_table();
+    h->drop_policy_joint();
     h->policy_cells.reset();   // (one policy at a time)
     // the table's allocation is padded to whole 16-byte words (the LDS form stages it sixteen bytes at a time); the row indices
     // by one agent row (the packed kernels load an agent pair's two indices as one word)
@@ -883,15 +897,75 @@ int mapf_set_policy_table(mapf_handle_t h, const uint8_t *table, uint32_t n_rows
     return MAPF_OK;
 }
 
+int mapf_set_policy_joint(mapf_handle_t h, const uint8_t *table, uint64_t table_bytes, const uint32_t *offset, const uint16_t *partner, uint32_t flags) {
+    if (!h) return fail(MAPF_EINVAL, "set_policy_joint: null handle");
+    if (!table) return fail(MAPF_EINVAL, "set_policy_joint: table is null");
+    if (!offset) return fail(MAPF_EINVAL, "set_policy_joint: offset is null");
+    if (!partner) return fail(MAPF_EINVAL, "set_policy_joint: partner is null");
+    if (table_bytes == 0 || table_bytes > 0x7FFFFFFFull) return fail(MAPF_EINVAL, "set_policy_joint: table_bytes must be 1..2^31-1");
+    if (flags & ~MAPF_POLICY_ROWS_BROADCAST) return fail(MAPF_EINVAL, "set_policy_joint: unknown bits in flags");
+    if (int rc = check_handle(h)) return rc;
+    if (int rc = check_not_recording(h, "mapf_set_policy")) return rc;
+    if (!h->graphs.empty()) return fail(MAPF_EINVAL, "set_policy: recorded graphs hold the current policy table (destroy them first)");
+    // the kernels index the move table with these bytes unclamped, and the policy table with offset + cell * V + cell: all checked here
+    for (uint64_t i = 0; i < table_bytes; ++i)
+        if (table[i] > 4u)
+            return fail(MAPF_EINVAL, "set_policy_joint: table[" + std::to_string(i) + "] = " + std::to_string(unsigned(table[i])) + " is not an action (0..4)");
+    const bool broadcast = (flags & MAPF_POLICY_ROWS_BROADCAST) != 0u;
+    const uint64_t A = h->A, V = h->V, n_index = broadcast ? A : uint64_t(h->E) * A;
+    for (uint64_t i = 0; i < n_index; ++i) {
+        const uint64_t row = i - i % A, me = i % A, other = partner[i];
+        if (other >= A)
+            return fail(MAPF_EINVAL, "set_policy_joint: partner[" + std::to_string(i) + "] = " + std::to_string(other) + " is not below n_agents");
+        if (partner[row + other] != me)
+            return fail(MAPF_EINVAL, "set_policy_joint: partner[" + std::to_string(i) + "] = " + std::to_string(other) + " but partner[" + std::to_string(row + other) +
+                                         "] = " + std::to_string(unsigned(partner[row + other])) + ": the merge is not mutual");
+        const uint64_t segment = other == me ? V : V * V;
+        if (uint64_t(offset[i]) + segment > table_bytes)
+            return fail(MAPF_EINVAL, "set_policy_joint: offset[" + std::to_string(i) + "] = " + std::to_string(offset[i]) + ": the segment of " + std::to_string(segment) +
+                                         " bytes ends past table_bytes");
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));   // no launch may still be reading the old copies
+    // the allocations are padded as the table policy's are: the table to whole 16-byte words, the index arrays by one agent row
+    const size_t padded = (size_t(table_bytes) + 15u) & ~size_t(15), n_padded = size_t(n_index) + 16u;
+    DevicePtr<uint8_t> d_table;
+    DevicePtr<uint32_t> d_offset;
+    DevicePtr<uint16_t> d_partner;
+    HIP_TRY(d_table.alloc(padded));
+    if (hipError_t e = d_offset.alloc(n_padded)) return hip_fail(e, "hipMalloc");
+    if (hipError_t e = d_partner.alloc(n_padded)) return hip_fail(e, "hipMalloc");
+    hipError_t e = hipMemset(d_table, 0, padded);
+    if (e == hipSuccess) e = hipMemset(d_offset, 0, n_padded * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(d_partner, 0, n_padded * sizeof(uint16_t));
+    if (e == hipSuccess) e = hipMemcpy(d_table, table, size_t(table_bytes), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_offset, offset, size_t(n_index) * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_partner, partner, size_t(n_index) * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(e, "set_policy_joint: copying the table");   // (the previous policy stays in force)
+    h->drop_policy_table();    // (one policy at a time)
+    h->drop_policy_joint();
+    h->policy_cells.reset();
+    h->joint_bytes = std::move(d_table);
+    h->joint_offset = std::move(d_offset);
+    h->joint_partner = std::move(d_partner);
+    h->joint.table = h->joint_bytes;
+    h->joint.offset = h->joint_offset;
+    h->joint.partner = h->joint_partner;
+    h->joint.table_bytes = uint32_t(table_bytes);
+    h->joint.broadcast = broadcast ? 1u : 0u;
+    return MAPF_OK;
+}
+
 int mapf_set_policy(mapf_handle_t h, int policy, const uint32_t *cell_rc) {
     if (int rc = check_handle(h)) return rc;
     if (int rc = check_not_recording(h, "mapf_set_policy")) return rc;
     if (!h->graphs.empty()) return fail(MAPF_EINVAL, "set_policy: recorded graphs hold the current policy table (destroy them first)");
     if (policy == MAPF_POLICY_TABLE) return fail(MAPF_EINVAL, "set_policy: MAPF_POLICY_TABLE is set through mapf_set_policy_table (it takes the table and the row indices)");
+    if (policy == MAPF_POLICY_JOINT) return fail(MAPF_EINVAL, "set_policy: MAPF_POLICY_JOINT is set through mapf_set_policy_joint (it takes the table, the offsets and the partners)");
     if (policy != MAPF_POLICY_RANDOM && policy != MAPF_POLICY_GREEDY) return fail(MAPF_EINVAL, "set_policy: unknown policy");
     if (policy == MAPF_POLICY_GREEDY && !cell_rc) return fail(MAPF_EINVAL, "set_policy: the greedy policy needs cell_rc");
     HIP_TRY(hipStreamSynchronize(h->stream));   // no launch may still be reading the old table
     h->drop_policy_table();                     // either policy leaves table mode
+    h->drop_policy_joint();                     // ... and joint mode
     if (policy == MAPF_POLICY_RANDOM) {
         h->policy_cells.reset();
         return MAPF_OK;
@@ -1084,6 +1158,7 @@ int mapf_graph_begin(mapf_handle_t h) {
     if (h->episode_limit) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with an episode limit cannot be recorded (mapf_set_episode_limit(h, 0) first)");
     if (h->episode_budget) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with an episode budget cannot be recorded (mapf_set_episode_budget(h, 0) first)");
     if (h->pair_slots) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with a conflict matrix cannot be recorded (mapf_set_conflict_pairs(h, 0, NULL) first)");
+    if (h->joint.table) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle under the joint table policy cannot be recorded (mapf_set_policy or mapf_set_policy_table first)");
     HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed));
     h->capturing = true;
     h->cap_steps = 0;

@@ -45,17 +45,26 @@ static hipError_t launch_rollout_lq(const LqPlan &plan, int n_agents, const Roll
 }
 
 hipError_t launch_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, hipStream_t stream, const TablePolicy *table,
-                          const EpisodeLimit *limit, const EpisodeBudget *budget, const ConflictPairs *pairs) {
-    if (n_agents < 1) return hipErrorInvalidValue;
+                          const EpisodeLimit *limit, const EpisodeBudget *budget, const ConflictPairs *pairs, const JointPolicy *joint) {
+    if (n_agents < 1 || (joint && (table || args.actions))) return hipErrorInvalidValue;   // (one policy per launch: the C ABI passes at most one)
     if (args.n_envs == 0) return hipSuccess;
     const RolloutRoute r = route_rollout(n_agents, args, tune, prefer, table != nullptr, table ? table->table_bytes : 0u, limit != nullptr, budget != nullptr,
-                                         pairs != nullptr);
+                                         pairs != nullptr, joint != nullptr);
     if (!limit_block_complete(limit, budget, true, args.rec_local != nullptr, args.auto_reset)) return hipErrorInvalidValue;
     if (pairs && !(pairs->matrix && pairs->n_slots != 0u)) return hipErrorInvalidValue;
     switch (r.family) {
         case KernelFamily::ThreadPerEnv: MAPF_TPE_GROUP(launch_rollout, n_agents, r.tpe, n_agents, args, stream, table)
         case KernelFamily::Packed: return launch_rollout_lq(r.lq, n_agents, args, stream, table, limit);
         case KernelFamily::LaneGroup: break;
+    }
+    if (joint) {   // the route took the lane-group plan of the launch's form, marked `joint`: the unit of that form
+        if (!(joint->table && joint->offset && joint->partner && joint->table_bytes != 0u)) return hipErrorInvalidValue;
+        if (pairs) return budget ? launch_rollout_lg_joint_pairs_budget(r.lg, n_agents, args, stream, *joint, limit, budget, pairs)
+                          : (limit ? launch_rollout_lg_joint_pairs_limit(r.lg, n_agents, args, stream, *joint, limit, budget, pairs)
+                                   : launch_rollout_lg_joint_pairs_plain(r.lg, n_agents, args, stream, *joint, limit, budget, pairs));
+        return budget ? launch_rollout_lg_joint_budget(r.lg, n_agents, args, stream, *joint, limit, budget, pairs)
+                      : (limit ? launch_rollout_lg_joint_limit(r.lg, n_agents, args, stream, *joint, limit, budget, pairs)
+                               : launch_rollout_lg_joint_plain(r.lg, n_agents, args, stream, *joint, limit, budget, pairs));
     }
     if (pairs) {   // the route took the lane-group plan of the launch's form, marked `pairs`
         if (budget) return launch_rollout_lg_pairs_budget(r.lg, n_agents, args, stream, table, *limit, *budget, *pairs);

@@ -159,6 +159,18 @@ struct TablePolicy {
     uint32_t rows_broadcast;       // rows is [A]
 };
 
+// Joint table policy (include/mapf_hip.h MAPF_POLICY_JOINT): the device copies mapf_set_policy_joint made.  A solo agent i of env e
+// (partner[e,i] == i) on cell c takes table[offset[e,i] + c]; an agent merged with j = partner[e,i], which stands on c_j, takes
+// table[offset[e,i] + c * V + c_j].  One more block beside the others: the joint instances (csrc_joint/mapf_lg_joint.hip) take it
+// first, where the table instances take TablePolicy -- never both.
+struct JointPolicy {
+    const uint8_t *table;          // [table_bytes] action bytes 0..4 (the allocation is padded to a multiple of 16 bytes)
+    const uint32_t *offset;        // [E*A] or [A]: where the agent's segment begins (V bytes solo, V*V bytes merged)
+    const uint16_t *partner;       // [E*A] or [A]: the agent it is merged with, or itself
+    uint32_t table_bytes;          // < 2^31
+    uint32_t broadcast;            // offset and partner are [A]
+};
+
 // Episode step limit (include/mapf_hip.h mapf_set_episode_limit): the handle's per-env ages, the limit and where a launch
 // reports its truncations.  Travels beside the argument blocks as the table policy does -- StepArgs, RolloutArgs, and with them
 // every kernel that exists without the limit, stay as they are; the limit instances are kernels of their own (mapf_lg_limit.hip).
@@ -289,11 +301,12 @@ enum class FamilyPreference { Auto, ThreadPerEnv, LaneGroup };
 // (table: the table policy of an actions == null launch, or null: streamed actions take precedence over it as over the other
 // policies, and the C ABI, which applies that rule, never passes both.  A recording launch names all five rec_* arrays: the C ABI
 // substitutes scratch for absent ones.  limit / budget: those of a handle that has them, or null; with a budget `limit` is
-// non-null too, max_steps 0 on a handle without a limit.  pairs: the conflict matrix of a handle that counts, or null)
+// non-null too, max_steps 0 on a handle without a limit.  pairs: the conflict matrix of a handle that counts, or null.
+// joint: the joint table policy of an actions == null launch, or null -- never beside `table`)
 hipError_t launch_step(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, hipStream_t stream, const EpisodeLimit *limit = nullptr);
 hipError_t launch_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, hipStream_t stream,
                           const TablePolicy *table = nullptr, const EpisodeLimit *limit = nullptr, const EpisodeBudget *budget = nullptr,
-                          const ConflictPairs *pairs = nullptr);
+                          const ConflictPairs *pairs = nullptr, const JointPolicy *joint = nullptr);
 // is the step launch_step would launch a thread-per-env one (one thread per env), else lg_group_size(A) threads per env?
 bool step_is_thread_per_env(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, const EpisodeLimit *limit);
 
@@ -313,6 +326,15 @@ hipError_t launch_rollout_lg_pairs_limit(const LgRolloutPlan &plan, int n_agents
                                          const ConflictPairs &pairs);
 hipError_t launch_rollout_lg_pairs_budget(const LgRolloutPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table,
                                           const EpisodeLimit &limit, const EpisodeBudget &budget, const ConflictPairs &pairs);
+// ... and the instances that follow a joint table policy: csrc_joint/mapf_lg_joint.hip, compiled once per form (plain, limit, budget;
+// each with and without the conflict matrix).  ONE signature: a form is handed the blocks it takes and refuses a launch that
+// lacks one of them or brings another
+#define MAPF_LG_JOINT_LAUNCHERS(X) X(plain) X(limit) X(budget) X(pairs_plain) X(pairs_limit) X(pairs_budget)
+#define X(form)                                                                                                                              \
+    hipError_t launch_rollout_lg_joint_##form(const LgRolloutPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const JointPolicy &joint, \
+                                              const EpisodeLimit *limit, const EpisodeBudget *budget, const ConflictPairs *pairs);
+MAPF_LG_JOINT_LAUNCHERS(X)
+#undef X
 hipError_t launch_step_lg(const LgStepPlan &plan, int n_agents, const StepArgs &args, hipStream_t stream);
 hipError_t launch_step_lg_limit(const LgStepPlan &plan, int n_agents, const StepArgs &args, hipStream_t stream, const EpisodeLimit &limit);
 hipError_t launch_reset_ages(uint32_t *age, const uint8_t *mask, uint64_t n_envs, hipStream_t stream);

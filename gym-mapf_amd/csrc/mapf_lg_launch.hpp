@@ -5,10 +5,13 @@
 //              (mapf_lg_rollout_kernel.hpp).  mapf_lg_rollout.hip: the plain and the table instances, DENSE for full groups only;
 //              mapf_lg_limit.hip: the limit instances, guarded only; mapf_lg_budget.hip: the budget instances, guarded only;
 //              pairs/mapf_lg_pairs.hip: the instances of the three that count conflicting pairs, guarded only;
+//              ../csrc_joint/mapf_lg_joint.hip: the instances that follow a joint table policy, guarded only and never streamed -- it
+//              launches through the TABLE arm (no streamed actions) and its plan is marked `joint`, which the name reads;
 //   step    -- Family::kernel<L, FULL, EXT_UNIFORMS>() likewise, of lg_step_kernel (mapf_lg_step_kernel.hpp).  mapf_lg_kernels.hip:
 //              the plain instances; mapf_lg_limit.hip: the limit instances.
 // `extra` are the kernel's arguments behind (args, A): nothing, the table policy, the episode limit, or both in that order; the
-// budget instances take the episode budget behind the limit, the instances that count pairs the conflict matrix last.
+// budget instances take the episode budget behind the limit, the instances that count pairs the conflict matrix last; the joint
+// instances take the joint table policy first, in the table policy's place.
 #pragma once
 #include "mapf_lg.hpp"
 #include "mapf_plan.hpp"

@@ -4,6 +4,11 @@
 //   TablePolicy   -- the table policy (MAPF_POLICY_TABLE): agent i of env e on cell c takes tp.table[tp.rows[e * A + i] * V + c],
 //     gathered from global memory; the row bases wait in two registers per lane as the greedy policy's goal coordinates do.  Such an
 //     instance runs the launches without streamed actions: STREAM is false.
+//   JointPolicy   -- the joint table policy (MAPF_POLICY_JOINT), in TablePolicy's place and never beside it: an agent merged with a
+//     partner takes jp.table[jp.offset[e * A + i] + c_i * V + c_j], a solo agent jp.table[jp.offset[e * A + i] + c_i].  Per agent a
+//     segment base, a row stride (V, or 0 when solo) and a selector -- the lane that holds the partner and which half of its cell
+//     word -- wait in registers; the step reads the partner lane's cells with one ds_bpermute per agent (a solo agent is its own
+//     partner, so one formula serves both), then gathers the byte from global memory.  STREAM is false.
 //   EpisodeLimit  -- the episode step limit (include/mapf_hip.h mapf_set_episode_limit): the env's age is carried in a register
 //     beside `terminal`, truncations are counted like episodes, the truncated byte is stored with the delayed flag bytes, and the
 //     env goes back to its start cells on done OR truncated.  These instances have no DENSE form: always the guarded one.
@@ -74,11 +79,14 @@ __device__ __forceinline__ void lg_count_pairs(const LaneCtx<L> &x, const uint32
 template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM, bool DENSE, class... Extra>
 __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(const RolloutArgs p, const uint32_t n_agents, const Extra... extra) {
     constexpr bool TABLE = has_kernel_arg<TablePolicy, Extra...>, LIMIT = has_kernel_arg<EpisodeLimit, Extra...>,
-                   BUDGET = has_kernel_arg<EpisodeBudget, Extra...>, PAIRS = has_kernel_arg<ConflictPairs, Extra...>;
+                   BUDGET = has_kernel_arg<EpisodeBudget, Extra...>, PAIRS = has_kernel_arg<ConflictPairs, Extra...>,
+                   JOINT = has_kernel_arg<JointPolicy, Extra...>;
     static_assert(!(TABLE && STREAM), "a table instance runs the launches without streamed actions");
+    static_assert(!(JOINT && (TABLE || STREAM || DENSE)), "a joint instance: no table policy beside it, no streamed actions, guarded");
     static_assert(!(LIMIT && DENSE) && (LIMIT || !BUDGET), "the limit instances are guarded; a budget instance takes the limit block too");
     static_assert(!(PAIRS && DENSE), "the instances that count conflicting pairs are guarded");
     const auto tp = kernel_arg<TablePolicy>(extra...);       // by value: an empty tag where the instance has no such argument
+    const auto jp = kernel_arg<JointPolicy>(extra...);
     const auto lim = kernel_arg<EpisodeLimit>(extra...);
     const auto bud = kernel_arg<EpisodeBudget>(extra...);
     __shared__ SlipRow slip[8];
@@ -252,6 +260,27 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
         row_base1 *= p.c.n_cells;
     }
 
+    // joint table policy: per agent the segment's base, the row stride (V merged, 0 solo) and the selector: the lane that holds
+    // the partner's cell | the half of that lane's cell word << 10 (so that sel >> 6 is the shift, 0 or 16; __shfl keeps the low
+    // six bits).  A solo agent is its own partner: base + cur * 0 + its own cell.  Ghost slots and the lanes past the last env are
+    // solo on offset 0 (their cell is 0: byte 0, never used).  Integers in VGPRs: the step loop has no scalar registers to spare
+    uint32_t jbase0 = 0u, jbase1 = 0u, jstride0 = 0u, jstride1 = 0u, jsel0 = 0u, jsel1 = 0u;
+    if constexpr (JOINT) {
+        const uint32_t me0 = 2u * x.g, me1 = 2u * x.g + 1u, jrow = (jp.broadcast ? 0u : e) * n_agents + me0;
+        uint32_t partner0, partner1;
+        load_pair<uint16_t>(jp.partner, jp.broadcast ? 0 : e, n_agents, x.g, x.v0, x.v1, partner0, partner1);
+        if (x.v0) jbase0 = *at(jp.offset, jrow);
+        if (x.v1) jbase1 = *at(jp.offset, jrow + 1u);
+        // (a partner the host has refused -- not below A -- would name a lane outside the group: such an agent is solo here)
+        partner0 = (x.v0 && partner0 < n_agents) ? partner0 : me0;
+        partner1 = (x.v1 && partner1 < n_agents) ? partner1 : me1;
+        jstride0 = partner0 != me0 ? p.c.n_cells : 0u;
+        jstride1 = partner1 != me1 ? p.c.n_cells : 0u;
+        jsel0 = (x.base + (partner0 >> 1)) | ((partner0 & 1u) << 10);
+        jsel1 = (x.base + (partner1 >> 1)) | ((partner1 & 1u) << 10);
+        asm volatile("" : "+v"(jbase0), "+v"(jbase1), "+v"(jstride0), "+v"(jstride1), "+v"(jsel0), "+v"(jsel1));
+    }
+
     const uint64_t t_first = first_step_index(p);
     for (uint32_t s = 0; s < p.n_steps; ++s) {
         const uint64_t t = t_first + s;
@@ -272,6 +301,17 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
         } else if constexpr (TABLE) {   // table policy: the byte of (my row, my cell) -- ghost slots read byte 0 of row 0
             act0 = tp.table[row_base0 + cur0];
             act1 = tp.table[row_base1 + cur1];
+        } else if constexpr (JOINT) {   // joint table policy: the byte of (my segment, my cell, my partner's cell)
+            // every lane is active here (the loop bound is the wave's): the cross-lane read needs that.  The partner lane is a run-time
+            // value, so ds_bpermute (no DPP control word fits); a group of one lane holds both cells itself
+            const uint32_t pk = cur0 | (cur1 << 16);
+            uint32_t o0 = pk, o1 = pk;
+            if constexpr (L > 1) {
+                o0 = uint32_t(__shfl(int(pk), int(jsel0), 64));
+                o1 = uint32_t(__shfl(int(pk), int(jsel1), 64));
+            }
+            act0 = jp.table[jbase0 + cur0 * jstride0 + ((o0 >> (jsel0 >> 6)) & 0xFFFFu)];
+            act1 = jp.table[jbase1 + cur1 * jstride1 + ((o1 >> (jsel1 >> 6)) & 0xFFFFu)];
         } else if (p.policy_cells) {   // greedy policy (ghost slots read cell 0: their actions are never used)
             act0 = greedy_action(p.policy_cells, p.c.n_cells, cur0, goal_rc0);
             act1 = greedy_action(p.policy_cells, p.c.n_cells, cur1, goal_rc1);

@@ -361,10 +361,11 @@ void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, 
     const char *family = plan.budget ? "_budget_guarded" : (plan.limit ? "_limit_guarded" : "");
     const char *form = plan.budget ? "BUDGET" : (plan.limit ? "LIMIT" : (plan.dense ? "DENSE" : "GUARDED"));
     const char *note = plan.budget ? "; episode budget" : (plan.limit ? "; episode step limit" : "");
-    snprintf(name, kKernelNameBytes, "lg_rollout_kernel%s%s%s<L=%d,%s,%s,%s,%s,%s%s> block=%u (pair layout: 2 agents per lane%s%s%s)", table_policy ? "_table" : "",
+    const bool joint = plan.joint && table_policy;   // (the joint launcher passes table_policy: a launch without streamed actions)
+    snprintf(name, kKernelNameBytes, "lg_rollout_kernel%s%s%s<L=%d,%s,%s,%s,%s,%s%s> block=%u (pair layout: 2 agents per lane%s%s%s)", joint ? "_joint" : (table_policy ? "_table" : ""),
              family, plan.pairs ? "_pairs" : "", plan.L, plan.full ? "FULL" : "RAGGED", plan.mv_lds ? "MV_LDS" : "MV_GLOBAL", record ? "RECORD" : "TOTALS",
-             table_policy ? "TABLE" : (streamed ? "STREAM" : "POLICY"), form, plan.pairs ? ",PAIRS" : "", plan.block, note, plan.pairs ? "; conflict matrix" : "",
-             table_policy ? "; table policy: action bytes gathered from global memory" : "");
+             joint ? "JOINT" : (table_policy ? "TABLE" : (streamed ? "STREAM" : "POLICY")), form, plan.pairs ? ",PAIRS" : "", plan.block, note, plan.pairs ? "; conflict matrix" : "",
+             joint ? "; joint policy: action bytes gathered from global memory" : (table_policy ? "; table policy: action bytes gathered from global memory" : ""));
 }
 
 void lg_step_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms) {
@@ -488,8 +489,18 @@ static bool prefers_tpe(FamilyPreference prefer, int n_agents) {
 }
 
 RolloutRoute route_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool table_policy, size_t table_bytes,
-                           bool limited, bool budgeted, bool pairs) {
+                           bool limited, bool budgeted, bool pairs, bool joint) {
     RolloutRoute r;
+    if (joint) {   // the joint instances exist in the lane-group family only, guarded, one form per (limit, budget, pairs)
+        RolloutTuning t = tune;   // (with the matrix: its block's static LDS, as below)
+        if (pairs) t.mv_lds_max_bytes = std::min(t.mv_lds_max_bytes, kLdsBytes - kPairsLdsBytes);
+        r.lg = plan_rollout_lg(n_agents, args, t, limited || budgeted);
+        r.lg.budget = budgeted;
+        r.lg.pairs = pairs;
+        r.lg.dense = false;
+        r.lg.joint = true;
+        return r;
+    }
     if (pairs) {   // the instances that count exist in the lane-group family only, guarded, one form per (limit, budget)
         RolloutTuning t = tune;   // (kPairsLdsBytes of static LDS more than the others: the largest tables stay in global memory)
         t.mv_lds_max_bytes = std::min(t.mv_lds_max_bytes, kLdsBytes - kPairsLdsBytes);

@@ -77,6 +77,7 @@ struct LgRolloutPlan {
     bool limit = false;              // the family the plan names: the instances under an episode step limit, or those without
     bool budget = false;             // ... or, of a limit plan, the instances under an episode budget (mapf_lg_budget.hip): their launcher sets it
     bool pairs = false;              // ... and, of any of the three, the instances that count conflicting pairs (pairs/mapf_lg_pairs.hip): never dense
+    bool joint = false;              // ... and, of any of the six, the instances that follow a joint table policy (csrc_joint/mapf_lg_joint.hip): never dense
     unsigned block = 0, grid = 0;
     size_t lds_bytes = 0;            // dynamic LDS segment: the move table, or 0 (the launcher raises the limit beyond 32 KB)
 };
@@ -90,6 +91,7 @@ LgStepPlan plan_step_lg(int n_agents, const StepArgs &args, bool limited = false
 // The names the launchers note for these plans (mapf_last_kernel; at most kKernelNameBytes with the terminator).  A limit plan's
 // name says _limit_guarded (the step: _limit) and LIMIT, and has no DENSE / GUARDED field; a budget plan's says _budget_guarded and BUDGET.
 // A pairs plan's name says _pairs behind the kernel's name and PAIRS behind the form (GUARDED, LIMIT or BUDGET).
+// A joint plan's name (its launcher passes table_policy) says _joint and JOINT where a table launch says _table and TABLE, and ends with the joint policy's note.
 void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy);
 void lg_step_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms);
 
@@ -124,6 +126,8 @@ void transitions_kernel_name(char *name, const TransitionsPlan &plan, uint32_t n
 // ------------------------------------------------------------------- the route
 // Which family takes a launch, with that family's plan (the other plans stay as constructed).  The rules, each written once, in
 // route_rollout / route_step, in this order:
+//   a joint table policy takes the lane-group plan of its form (plain, limit or budget; with the conflict matrix or without), marked
+//     `joint` and never dense, before anything else: whatever the handle prefers, limit_packed and the tuning say;
 //   a conflict matrix takes the lane-group plan of its form (plain, limit or budget), marked `pairs` and never dense, before
 //     anything else: whatever the handle prefers and whatever limit_packed says;
 //   a budget takes the lane-group budget plan (a limit plan marked `budget`) before anything else;
@@ -137,9 +141,10 @@ enum class KernelFamily { ThreadPerEnv, Packed, LaneGroup };
 struct RolloutRoute { KernelFamily family = KernelFamily::LaneGroup; TpePlan tpe; LqPlan lq; LgRolloutPlan lg; };
 struct StepRoute { KernelFamily family = KernelFamily::LaneGroup; TpePlan tpe; StepPlan lq; LgStepPlan lg; };
 // (table_policy: the launch follows the table policy, of table_bytes action bytes; limited / budgeted: it runs under an episode
-// step limit / an episode budget; pairs: the handle counts conflicting pairs.  args is never dereferenced)
+// step limit / an episode budget; pairs: the handle counts conflicting pairs; joint: the launch follows the joint table policy.
+// args is never dereferenced)
 RolloutRoute route_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool table_policy, size_t table_bytes,
-                           bool limited, bool budgeted, bool pairs = false);
+                           bool limited, bool budgeted, bool pairs = false, bool joint = false);
 // (ext_uniforms: the caller supplies the uniforms)
 StepRoute route_step(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool limited, bool ext_uniforms);
 

@@ -16,7 +16,7 @@ MAPF_MAKESPAN, MAPF_SOC = 0, 1
 MAPF_FLAG_DEVICE_PTRS, MAPF_FLAG_START_BROADCAST, MAPF_FLAG_GOAL_BROADCAST = 0x1, 0x2, 0x4
 MAPF_FLAG_THREAD_PER_ENV, MAPF_FLAG_LANE_GROUP = 0x10, 0x20
 MAPF_TPE_MAX_AGENTS = 16
-MAPF_POLICY_RANDOM, MAPF_POLICY_GREEDY, MAPF_POLICY_TABLE = 0, 1, 2
+MAPF_POLICY_RANDOM, MAPF_POLICY_GREEDY, MAPF_POLICY_TABLE, MAPF_POLICY_JOINT = 0, 1, 2, 3
 MAPF_POLICY_ROWS_BROADCAST = 0x1
 MAPF_STEP_AUTO_RESET = 0x1
 MAPF_KERNEL_STEP, MAPF_KERNEL_ROLLOUT, MAPF_KERNEL_TRANSITIONS = 0, 1, 2
@@ -62,6 +62,7 @@ SIGNATURES = {
     'mapf_fill_random_actions': (c_int, [c_void_p, c_void_p, c_uint64, c_uint32]),
     'mapf_set_policy': (c_int, [c_void_p, c_int, c_void_p]),
     'mapf_set_policy_table': (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
+    'mapf_set_policy_joint': (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32]),
     'mapf_transitions': (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
     'mapf_transitions_window': (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p,

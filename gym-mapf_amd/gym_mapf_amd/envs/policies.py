@@ -3,8 +3,16 @@
 A table policy is what the reference's planning workflow ends with: every agent (or small group) is solved on its own
 local view (``utils.get_local_view``) and the single-agent policies are joined.  A single-agent policy of a local view
 is a function ``cell -> action``, i.e. one row of ``V`` bytes; the fused rollout follows ``table[rows[e, i], cell]``
-for agent ``i`` of env ``e`` (include/mapf_hip.h, MAPF_POLICY_TABLE).  Nothing here needs a GPU.
+for agent ``i`` of env ``e`` (include/mapf_hip.h, MAPF_POLICY_TABLE).
+
+When a decomposing planner has found two agents in each other's way (``conflicting_pairs``) it merges them and replans the pair
+on ``get_local_view(env, [i, j])``: that plan is a function of BOTH cells.  ``set_policy('joint', ...)`` follows it (include/mapf_hip.h,
+MAPF_POLICY_JOINT): each merged agent has a ``[V, V]`` byte array indexed by (own cell, partner's cell).  ``pair_rows_from_policy``
+and ``pair_shortest_path_rows`` build a pair's two arrays, ``join_plan`` lays solo rows and pair arrays out as the three arrays
+``set_policy('joint')`` takes.  Nothing here needs a GPU.
 """
+import itertools
+
 import numpy as np
 
 from gym_mapf_amd.envs import ACTIONS
@@ -84,9 +92,121 @@ def row_from_policy(local_env, policy):
     return row
 
 
+def pair_rows_from_policy(local_env, policy):
+    """The two arrays uint8 [V, V] ``(rows_0, rows_1)`` of a reference-style ``policy(s) -> a`` of a TWO-agent ``MapfEnv`` (for instance a
+    ``get_local_view(env, [i, j])`` the caller planned on): ``rows_k[own cell, partner's cell]`` is agent k's action code.  States and
+    actions are decoded through the env's own ``state_to_locations`` / ``integer_action_to_vector`` (agent 0 least significant)."""
+    from gym_mapf_amd.envs.mapf_env import integer_action_to_vector
+    if local_env.n_agents != 2:
+        raise ValueError('pair_rows_from_policy needs a two-agent env (the local view of a merged pair), got %d agents' % local_env.n_agents)
+    V = len(local_env.valid_locations)
+    rows_0, rows_1 = np.empty((V, V), dtype=np.uint8), np.empty((V, V), dtype=np.uint8)
+    for s in range(V * V):
+        a = int(policy(s))
+        if not 0 <= a < len(ACTIONS) ** 2:
+            raise ValueError('policy(%d) = %d is not a joint action code 0..%d' % (s, a, len(ACTIONS) ** 2 - 1))
+        c0, c1 = (local_env.loc_to_int[tuple(loc)] for loc in local_env.state_to_locations(s))
+        a0, a1 = (ACTIONS.index(name) for name in integer_action_to_vector(a, 2))
+        rows_0[c0, c1] = a0
+        rows_1[c1, c0] = a1
+    return rows_0, rows_1
+
+
+def pair_shortest_path_rows(grid, goal_i, goal_j):
+    """``(rows_i, rows_j)`` uint8 [V, V] for a pair merged on ``grid`` with goal cells ``goal_i``, ``goal_j`` (local ids): the noise-free
+    shortest JOINT path.  Breadth-first search over the ``V * V`` joint cells (c_i, c_j) and the 25 joint actions; a move that makes a
+    vertex conflict (both on one cell) or a swap is forbidden, and a joint cell with both agents on one cell is never entered.  In a
+    joint cell the pair takes the first joint action in ``itertools.product(ACTIONS, repeat=2)`` order whose target is one step closer to
+    the joint goal; STAY / STAY on the joint goal and on joint cells that cannot reach it.  ``rows_i[c_i, c_j]`` is agent i's action,
+    ``rows_j[c_j, c_i]`` agent j's: each array is indexed by (own cell, partner's cell), as ``join_plan`` takes them."""
+    _, _, nbr = grid.tables()
+    nbr = np.asarray(nbr, dtype=np.int64)
+    V = nbr.shape[0]
+    goal_i, goal_j = int(goal_i), int(goal_j)
+    if not (0 <= goal_i < V and 0 <= goal_j < V) or goal_i == goal_j:
+        raise ValueError('goal_i and goal_j must be two different local ids 0..%d' % (V - 1))
+    joint_actions = list(itertools.product(range(len(ACTIONS)), repeat=2))
+
+    def targets(ci, cj, a_i, a_j):
+        """the joint cell a joint action leads to, and whether the move is allowed"""
+        ni, nj = nbr[ci, a_i], nbr[cj, a_j]
+        return ni, nj, (ni != nj) & ~((ni == cj) & (nj == ci))
+
+    # joint moves are symmetric (every allowed move has an allowed reverse), so the cells one move from the frontier are the
+    # frontier's own targets
+    dist = np.full(V * V, -1, dtype=np.int64)
+    dist[goal_i * V + goal_j] = 0
+    frontier = np.asarray([goal_i * V + goal_j], dtype=np.int64)
+    d = 0
+    while frontier.size:
+        d += 1
+        ci, cj = frontier // V, frontier % V
+        found = []
+        for a_i, a_j in joint_actions:
+            ni, nj, ok = targets(ci, cj, a_i, a_j)
+            found.append((ni * V + nj)[ok])
+        nxt = np.unique(np.concatenate(found))
+        nxt = nxt[dist[nxt] < 0]
+        dist[nxt] = d
+        frontier = nxt
+    act_i = np.full(V * V, _STAY, dtype=np.uint8)
+    act_j = np.full(V * V, _STAY, dtype=np.uint8)
+    cells = np.arange(V * V, dtype=np.int64)
+    ci, cj = cells // V, cells % V
+    undecided = dist > 0
+    for a_i, a_j in joint_actions:
+        ni, nj, ok = targets(ci, cj, a_i, a_j)
+        take = undecided & ok & (dist[ni * V + nj] == dist - 1)
+        act_i[take] = a_i
+        act_j[take] = a_j
+        undecided &= ~take
+    return act_i.reshape(V, V), np.ascontiguousarray(act_j.reshape(V, V).T)
+
+
+def join_plan(V, n_agents, solo, pairs):
+    """``(table uint8 [N], offsets uint32 [A], partners uint16 [A])`` for ``env.set_policy('joint', table=, offsets=, partners=)`` from a
+    decomposed plan: ``solo`` is ``{agent: row uint8 [V]}`` (a row of ``shortest_path_table`` or ``row_from_policy``), ``pairs`` is
+    ``{(i, j): (rows_i [V, V], rows_j [V, V])}`` (``pair_shortest_path_rows`` or ``pair_rows_from_policy``).  Every agent 0..A-1 appears
+    exactly once.  The arrays are shared by all envs (the broadcast form)."""
+    V, n_agents = int(V), int(n_agents)
+    seen, segments = [], {}
+    for agent, row in solo.items():
+        row = np.asarray(row)
+        if row.shape != (V,):
+            raise ValueError('the row of solo agent %r must be [V] = (%d,), got %r' % (agent, V, row.shape))
+        seen.append(int(agent))
+        segments[int(agent)] = (row, int(agent))
+    for (i, j), (rows_i, rows_j) in pairs.items():
+        rows_i, rows_j = np.asarray(rows_i), np.asarray(rows_j)
+        if rows_i.shape != (V, V) or rows_j.shape != (V, V):
+            raise ValueError('the arrays of pair %r must both be [V, V] = (%d, %d), got %r and %r' % ((i, j), V, V, rows_i.shape, rows_j.shape))
+        seen += [int(i), int(j)]
+        segments[int(i)] = (rows_i, int(j))
+        segments[int(j)] = (rows_j, int(i))
+    for agent in seen:
+        if not 0 <= agent < n_agents:
+            raise ValueError('agent %d is not one of the %d agents' % (agent, n_agents))
+        if seen.count(agent) > 1:
+            raise ValueError('agent %d appears %d times in the plan' % (agent, seen.count(agent)))
+    missing = sorted(set(range(n_agents)) - set(seen))
+    if missing:
+        raise ValueError('agent %d appears nowhere in the plan' % missing[0])
+    offsets, partners, parts, at = np.zeros(n_agents, dtype=np.uint32), np.zeros(n_agents, dtype=np.uint16), [], 0
+    for agent in range(n_agents):
+        segment, partner = segments[agent]
+        if segment.size and (segment.min() < 0 or segment.max() >= len(ACTIONS)):
+            raise ValueError('the plan of agent %d holds a value that is not an action code 0..%d' % (agent, len(ACTIONS) - 1))
+        offsets[agent], partners[agent] = at, partner
+        parts.append(np.ascontiguousarray(segment, dtype=np.uint8).ravel())
+        at += segment.size
+        if at > 0x7FFFFFFF:
+            raise ValueError('the joint table exceeds 2**31 - 1 bytes')
+    return np.concatenate(parts), offsets, partners
+
+
 def evaluate(env, n_episodes, max_steps, chunk=256):
-    """Monte-Carlo evaluation of whatever drives ``env``'s ``rollout(actions=None)`` -- a table policy, the greedy policy or the
-    random stream: EXACTLY ``n_episodes`` episodes of at most ``max_steps`` steps in every env of a ``VecMapfEnv``, inside
+    """Monte-Carlo evaluation of whatever drives ``env``'s ``rollout(actions=None)`` -- a table policy, a joint table policy (a plan with
+    merged pairs, ``join_plan``), the greedy policy or the random stream: EXACTLY ``n_episodes`` episodes of at most ``max_steps`` steps in every env of a ``VecMapfEnv``, inside
     totals-only fused rollouts.  Sets the episode limit and the episode budget (``set_episode_limit``, ``set_episode_budget``; both
     stay set), resets, then issues ``ceil(n_episodes * max_steps / chunk)`` launches of ``chunk`` steps that accumulate into one set
     of totals.  Every episode ends within ``max_steps`` steps, so after that many steps every env is parked by construction: nothing

@@ -469,7 +469,7 @@ class VecMapfEnv:
                                                      int(t0), int(n_steps)))
         return out
 
-    def set_policy(self, policy='random', table=None, rows=None):
+    def set_policy(self, policy='random', table=None, rows=None, offsets=None, partners=None):
         """On-device policy of ``rollout(actions=None)``: ``'random'`` (default; the uniform-random action stream),
         ``'greedy'`` -- every agent takes the first action in ACTIONS order whose intended target is closest
         (Manhattan distance) to its goal, i.e. the first unblocked move one step closer, else STAY -- or ``'table'``:
@@ -477,9 +477,18 @@ class VecMapfEnv:
         that follows row ``r`` does on ``cell``), ``rows`` [E, A] or [A] = the row every agent follows; both HOST arrays
         (numpy or CPU torch) in either handle mode, copied.  ``envs/policies.py`` builds such tables (shortest paths,
         or the row of a single-agent policy planned on a ``get_local_view``).  The reference has no policy; this
-        stands in for the caller-side ``a = policy(s)`` of the loop around ``step`` (mapf_env.py:237-266)."""
-        if policy != 'table' and (table is not None or rows is not None):
-            raise ValueError("table= and rows= belong to policy='table'")
+        stands in for the caller-side ``a = policy(s)`` of the loop around ``step`` (mapf_env.py:237-266).
+
+        ``'joint'``: a plan in which some agent PAIRS were merged and replanned jointly (include/mapf_hip.h MAPF_POLICY_JOINT).
+        ``table`` uint8 [N] of action codes, ``offsets`` [E, A] or [A] = where every agent's segment begins, ``partners`` [E, A]
+        or [A] = the agent it is merged with, or itself; HOST arrays, copied.  A solo agent on cell ``c`` takes
+        ``table[offsets[e, i] + c]``, an agent merged with ``j`` takes ``table[offsets[e, i] + c_i * V + c_j]``.
+        ``envs/policies.py`` builds the three (``pair_shortest_path_rows``, ``pair_rows_from_policy``, ``join_plan``).  Joint
+        launches always run a lane-group kernel (``last_kernel`` says JOINT); ``graph_begin`` is refused in this mode."""
+        if (policy not in ('table', 'joint') and table is not None) or (policy != 'table' and rows is not None):
+            raise ValueError("table= and rows= belong to policy='table'" + (" (policy='joint' takes table=, offsets= and partners=)" if policy == 'joint' else ''))
+        if policy != 'joint' and (offsets is not None or partners is not None):
+            raise ValueError("offsets= and partners= belong to policy='joint'")
         if policy == 'random':
             nat.check(self._lib.mapf_set_policy(self._h, nat.MAPF_POLICY_RANDOM, None))
         elif policy == 'greedy':
@@ -502,10 +511,49 @@ class VecMapfEnv:
             table8, rows16 = np.ascontiguousarray(table, dtype=np.uint8), np.ascontiguousarray(rows, dtype=np.uint16)
             nat.check(self._lib.mapf_set_policy_table(self._h, table8.ctypes.data, table8.shape[0], rows16.ctypes.data,
                                                       nat.MAPF_POLICY_ROWS_BROADCAST if rows16.ndim == 1 else 0))
+        elif policy == 'joint':
+            V = len(self.grid.tables()[0])
+            table8, offsets32, partners16 = self._joint_arguments(V, self.n_envs, self.n_agents, table, offsets, partners)
+            nat.check(self._lib.mapf_set_policy_joint(self._h, table8.ctypes.data, table8.size, offsets32.ctypes.data, partners16.ctypes.data,
+                                                      nat.MAPF_POLICY_ROWS_BROADCAST if offsets32.ndim == 1 else 0))
         else:
-            raise ValueError("policy must be 'random', 'greedy' or 'table'")
+            raise ValueError("policy must be 'random', 'greedy', 'table' or 'joint'")
         self._rollout_io = None            # (a cached argument block must not outlive a policy change)
         self.policy = policy
+
+    @staticmethod
+    def _joint_arguments(V, n_envs, n_agents, table, offsets, partners):
+        """The three arrays of ``set_policy('joint')`` as the library takes them -- (uint8 [N], uint32, uint16) -- after the checks
+        the library repeats (include/mapf_hip.h MAPF_POLICY_JOINT); a ``ValueError`` names the offending entry.  Needs no handle."""
+        if table is None or offsets is None or partners is None:
+            raise ValueError("policy='joint' needs table= [N], offsets= and partners= [E, A] or [A]")
+        table, offsets, partners = (VecMapfEnv._host_ints(a, name) for a, name in ((table, 'table'), (offsets, 'offsets'), (partners, 'partners')))
+        if table.ndim != 1 or not 1 <= table.size <= 0x7FFFFFFF:
+            raise ValueError('table must be [N] with 1 <= N <= 2**31 - 1, got %r' % (tuple(table.shape),))
+        shapes = ((n_envs, n_agents), (n_agents,))
+        if tuple(offsets.shape) not in shapes or tuple(partners.shape) != tuple(offsets.shape):
+            raise ValueError('offsets and partners must both be [E, A] = %r or both [A], got %r and %r' % (shapes[0], tuple(offsets.shape), tuple(partners.shape)))
+        bad = np.flatnonzero((table < 0) | (table > 4))
+        if bad.size:
+            raise ValueError('table holds action codes 0..4 (STAY, UP, RIGHT, DOWN, LEFT), found table[%d] = %d' % (bad[0], table[bad[0]]))
+        part = partners.reshape(-1, n_agents).astype(np.int64)
+        off = offsets.reshape(-1, n_agents).astype(np.int64)
+        where = lambda k: '[%d, %d]' % (k[0], k[1]) if offsets.ndim == 2 else '[%d]' % k[1]   # (the entry's name: [e, i], or [i] of shared arrays)
+        bad = np.argwhere((part < 0) | (part >= n_agents))
+        if bad.size:
+            raise ValueError('partners%s = %d is not an agent 0..%d' % (where(bad[0]), part[tuple(bad[0])], n_agents - 1))
+        me = np.arange(n_agents, dtype=np.int64)[None, :]
+        bad = np.argwhere(np.take_along_axis(part, part, axis=1) != me)
+        if bad.size:
+            e, i = bad[0]
+            raise ValueError('partners%s = %d, but agent %d is merged with %d: the merge is not mutual' % (where(bad[0]), part[e, i], part[e, i], part[e, part[e, i]]))
+        if off.min() < 0 or off.max() > 0xFFFFFFFF:
+            raise ValueError('offsets must be 0 .. 2**32 - 1')
+        bad = np.argwhere(off + np.where(part == me, V, V * V) > table.size)
+        if bad.size:
+            raise ValueError('offsets%s = %d: the segment of %d bytes ends past the table of %d' % (where(bad[0]), off[tuple(bad[0])],
+                                                                                               V if part[tuple(bad[0])] == bad[0][1] else V * V, table.size))
+        return (np.ascontiguousarray(table, dtype=np.uint8), np.ascontiguousarray(offsets, dtype=np.uint32), np.ascontiguousarray(partners, dtype=np.uint16))
 
     def set_episode_limit(self, n):
         """Episode step limit: an episode that has taken ``n`` steps without ending is TRUNCATED -- with ``auto_reset`` the env goes

@@ -330,12 +330,44 @@ int mapf_set_policy(mapf_handle_t h, int policy, const uint32_t *cell_rc);
  * mapf_set_policy(h, MAPF_POLICY_RANDOM | MAPF_POLICY_GREEDY, ...) leaves table mode and frees the copies.
  * mapf_last_kernel(h, MAPF_KERNEL_ROLLOUT) of a table launch says TABLE where a streamed one says STREAM.
  * Out of scope: a policy argument for the single mapf_step, the multi-map / union-map wrappers and the scalar MapfEnv
- * of the Python package, tables over joint states of agent groups, anything that COMPUTES a policy on the device.
+ * of the Python package, anything that COMPUTES a policy on the device.  Tables over the joint states of merged agent
+ * PAIRS are MAPF_POLICY_JOINT, below.
  */
 #define MAPF_POLICY_TABLE 2
 #define MAPF_POLICY_ROWS_BROADCAST 0x1u      /* row_index is [A], shared by all envs */
 int mapf_set_policy_table(mapf_handle_t h, const uint8_t *table, uint32_t n_rows,
                           const uint16_t *row_index, uint32_t flags);
+
+/*
+ * MAPF_POLICY_JOINT: the table policy for plans in which some agent pairs were merged and replanned jointly (the
+ * reference's get_local_view(env, [i, j])): a merged agent's action is a function of its own cell AND its partner's.
+ *   table u8[table_bytes]: action codes 0..4.  1 <= table_bytes <= 2^31 - 1.
+ *   offset u32[E * A] (u32[A] with MAPF_POLICY_ROWS_BROADCAST): where the segment of agent i of local env e begins.
+ *   partner u16[E * A] (u16[A] likewise): the agent that i is merged with, or i itself.
+ * All three are HOST pointers in every handle mode and are copied, as in mapf_set_policy_table.
+ *   Solo agent: partner[e,i] == i.  On cell c it takes table[offset[e,i] + c]; its segment is V bytes.
+ *   Merged agent: partner[e,i] == j != i.  On cell c_i, with j on c_j, it takes table[offset[e,i] + c_i * V + c_j]; its
+ *     segment is V * V bytes.
+ * Each agent has its own segment: a pair's joint plan is two [V, V] byte arrays, each indexed by (own cell, partner's
+ * cell).  Segments may be shared between agents and envs, and they may overlap.
+ * Everything else is as under MAPF_POLICY_TABLE: the cells are those on entry to the step, after any auto-reset; slip,
+ * collisions, reward, termination, both Philox streams' counters, the episode limit, the episode budget and the conflict
+ * matrix are exactly those of a mapf_step with these actions; the policy stream is not drawn; a terminal or parked step
+ * is a no-op.  A rollout with streamed actions ignores the policy; mapf_step* are unaffected.
+ * Validated on the host before any device work, MAPF_EINVAL with a mapf_last_error that names the offending index: null
+ * handle or pointer; table_bytes 0 or above 2^31 - 1; a table byte above 4; partner[e,i] >= A;
+ * partner[e, partner[e,i]] != i; a segment that ends past table_bytes (computed in 64 bits); unknown flag bits.  Refused
+ * while recording and while recorded graphs live; mapf_graph_begin refuses a handle in joint mode.
+ * mapf_set_policy(h, MAPF_POLICY_RANDOM | MAPF_POLICY_GREEDY, ...) and mapf_set_policy_table leave joint mode and free
+ * the copies; mapf_set_policy_joint leaves table mode.  mapf_set_policy(h, MAPF_POLICY_JOINT, ...) is MAPF_EINVAL.
+ * mapf_last_kernel(h, MAPF_KERNEL_ROLLOUT) of a joint launch says _joint and JOINT: always a lane-group kernel.
+ * Out of scope: groups of three or more (V^3 bytes), a policy argument for mapf_step, packed and thread-per-env forms,
+ * the multi-map / union-map wrappers and the scalar MapfEnv, graph recording of joint launches, anything that computes
+ * a policy on the device.
+ */
+#define MAPF_POLICY_JOINT 3
+int mapf_set_policy_joint(mapf_handle_t h, const uint8_t *table, uint64_t table_bytes,
+                          const uint32_t *offset, const uint16_t *partner, uint32_t flags);
 
 /*
  * MapfEnv.P[s][a] (mapf_env.py:448-478 _get_transitions): for each of n_queries (state, joint action) pairs,

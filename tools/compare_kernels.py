@@ -17,8 +17,8 @@ registers on both sides."""
 import re
 import sys
 
-TABLE, LIMIT, BUDGET = 'table', 'limit', 'budget'
-PACK_MODES = {'TablePolicy': TABLE, 'EpisodeLimit': LIMIT, 'EpisodeBudget': BUDGET}
+TABLE, LIMIT, BUDGET, JOINT = 'table', 'limit', 'budget', 'joint'
+PACK_MODES = {'TablePolicy': TABLE, 'EpisodeLimit': LIMIT, 'EpisodeBudget': BUDGET, 'JointPolicy': JOINT}
 
 
 def parse(symbol):

@@ -33,6 +33,11 @@ def added_units():
     return dict(line.split() for line in _make('print-added-kernel-units').splitlines())
 
 
+def joint_units():
+    """{name: source unit} of the Makefile's third table: the compilations that follow a joint table policy, whose source lies beside csrc"""
+    return dict(line.split() for line in _make('print-joint-kernel-units').splitlines())
+
+
 def listings(*names):
     """{name: listing text} for the named compilations (a kernel-holding one or a host unit); for all kernel-holding ones if none is named"""
     names = names or tuple(units())
