@@ -178,6 +178,15 @@ struct mapf_handle_s : StreamAndEvents {
     DevicePtr<unsigned long long> pair_counts;
     DevicePtr<uint32_t> pair_slot_of_env;
     size_t pair_bytes() const { return size_t(pair_slots) * A * A * sizeof(unsigned long long); }
+    // episode log (mapf_set_episode_log): the capacity C (0 = the mode is off and both are null), the per-env partials with the counts
+    // behind them in one allocation (EpisodeLog, mapf_kernels.hpp), and the records [E * C].  Only the log kernels and the entry points
+    // the header names write them
+    uint32_t log_capacity = 0;
+    DevicePtr<uint4> log_heads;       // E partials of 16 bytes, then E counts of 4: E * 20 bytes, as uint4 words (rounded up)
+    DevicePtr<uint4> log_records;
+    mapf::EpisodeLogPartial *log_partials() const { return reinterpret_cast<mapf::EpisodeLogPartial *>(log_heads.ptr); }
+    uint32_t *log_counts() const { return mapf::episode_log_counts(log_partials(), E); }
+    size_t log_record_bytes() const { return size_t(E) * log_capacity * sizeof(mapf_episode_record); }
     // host-pointer mode staging
     DeviceBuf s_actions, s_uniforms, s_local, s_reward, s_prob, s_done, s_coll, s_term, s_mask, s_ret, s_epi, s_ncoll;
     DeviceBuf x_local, x_reward, x_prob, x_done, x_coll;   // stand-ins for trajectory arrays the caller left out
@@ -564,6 +573,7 @@ int mapf_reset(mapf_handle_t h, const uint8_t *mask) {
     if (int rc = stage_arrays(h, io)) return rc;
     HIP_TRY(mapf::launch_reset(int(h->A), h->state, h->start, h->start_broadcast, d_mask, h->E, h->stream));
     if (h->episode_limit) HIP_TRY(mapf::launch_reset_ages(h->age, d_mask, h->E, h->stream));   // a reset env's episode begins again
+    if (h->log_capacity) HIP_TRY(mapf::launch_reset_log_partials(h->log_partials(), d_mask, h->E, h->stream));   // ... and its running record is dropped
     if (!mask) h->terminal_possible() = h->start_terminal_any;
     if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
     return MAPF_OK;
@@ -721,6 +731,9 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
     // (... and the conflict matrix last: the lane-group instances that count, in the form the limit and the budget name)
     const mapf::ConflictPairs cp{h->pair_counts, h->pair_slot_of_env, h->pair_slots};
     const mapf::ConflictPairs *pairs = h->pair_slots ? &cp : nullptr;
+    // (... and the episode log beside the budget: the lane-group budget instances that keep one)
+    const mapf::EpisodeLog lg{h->log_partials(), h->log_records, h->log_capacity};
+    const mapf::EpisodeLog *log = (h->log_capacity && budget) ? &lg : nullptr;
     // (the totals are inputs too when the call accumulates)
     const CallArray arrays[] = {input(h->s_actions, io->actions, TEA, &a.actions, "actions"),
                                 output(h->s_ret, io->out_returns, E, &a.out_returns, "out_returns", a.accumulate),
@@ -742,7 +755,7 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
         if (int rc = reserve_stand_in(h, h->x_trunc, TE, "rec_truncated")) return rc;
         lim.rec_truncated = static_cast<uint8_t *>(h->x_trunc.ptr);
     }
-    HIP_TRY(mapf::launch_rollout(int(h->A), a, h->tune, h->prefer, h->stream, table, limit, budget, pairs, joint));
+    HIP_TRY(mapf::launch_rollout(int(h->A), a, h->tune, h->prefer, h->stream, table, limit, budget, pairs, joint, log));
     after_launch(h, h->last_rollout_kernel, io->n_steps, a.auto_reset);
     if (int rc = fetch_arrays(h, arrays)) return rc;
     if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
@@ -803,11 +816,54 @@ int mapf_set_episode_budget(mapf_handle_t h, uint32_t n_episodes) {
     if (!h) return fail(MAPF_EINVAL, "set_episode_budget: null handle");
     if (int rc = check_not_recording(h, "mapf_set_episode_budget")) return rc;
     if (!h->graphs.empty()) return fail(MAPF_EINVAL, "set_episode_budget: recorded graphs hold launches without a budget (destroy them first)");
+    if (n_episodes == 0 && h->log_capacity) return fail(MAPF_EINVAL, "set_episode_budget: the handle keeps an episode log, which needs a budget (mapf_set_episode_log(h, 0) first)");
     if (int rc = check_handle(h)) return rc;
     // every call re-arms every env: left[e] = n_episodes (state and ages stay)
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->left.ptr), int(n_episodes), h->E ? size_t(h->E) : 1, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->episode_budget = n_episodes;
+    return MAPF_OK;
+}
+
+int mapf_set_episode_log(mapf_handle_t h, uint32_t capacity) {
+    if (!h) return fail(MAPF_EINVAL, "set_episode_log: null handle");
+    if (int rc = check_not_recording(h, "mapf_set_episode_log")) return rc;
+    if (!h->graphs.empty()) return fail(MAPF_EINVAL, "set_episode_log: recorded graphs hold launches without an episode log (destroy them first)");
+    if (capacity && !h->episode_budget) return fail(MAPF_EINVAL, "set_episode_log: a handle without an episode budget (mapf_set_episode_budget first)");
+    if (uint64_t(h->E) * capacity * sizeof(mapf_episode_record) > (uint64_t(1) << 31))
+        return fail(MAPF_EINVAL, "set_episode_log: E * capacity * 16 bytes must not exceed 2^31");
+    if (int rc = check_handle(h)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // (no launch may still log into what is freed here)
+    h->log_capacity = 0;
+    h->log_heads.reset();
+    h->log_records.reset();
+    if (capacity == 0) return MAPF_OK;
+    const size_t E = size_t(h->E), head_words = (E * (sizeof(mapf::EpisodeLogPartial) + sizeof(uint32_t)) + 15u) / 16u, record_words = E * capacity;
+    HIP_TRY(h->log_heads.alloc(head_words ? head_words : 1));
+    HIP_TRY(h->log_records.alloc(record_words ? record_words : 1));
+    // every call: no episode running, none counted, no record
+    HIP_TRY(hipMemsetAsync(h->log_heads, 0, (head_words ? head_words : 1) * sizeof(uint4), h->stream));
+    HIP_TRY(hipMemsetAsync(h->log_records, 0, (record_words ? record_words : 1) * sizeof(uint4), h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->log_capacity = capacity;
+    return MAPF_OK;
+}
+
+int mapf_episode_log(mapf_handle_t h, mapf_episode_record *out_records, uint32_t *out_count, int clear) {
+    if (!h) return fail(MAPF_EINVAL, "episode_log: null handle");
+    if (!out_records && !out_count && !clear) return fail(MAPF_EINVAL, "episode_log: out_records and out_count are null and clear is 0");
+    if (!h->log_capacity) return fail(MAPF_EINVAL, "episode_log: the handle has no episode log (mapf_set_episode_log)");
+    if (int rc = check_not_recording(h, "mapf_episode_log")) return rc;
+    if (h->device_ptrs && (misaligned(out_records) || misaligned(out_count))) return fail(MAPF_EINVAL, "episode_log: device pointer must be 16-byte aligned");
+    if (int rc = check_handle(h)) return rc;
+    const size_t record_bytes = h->log_record_bytes(), count_bytes = size_t(h->E) * sizeof(uint32_t);
+    const hipMemcpyKind kind = h->device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    // (the outputs receive the log as it is before it is cleared; the partials -- the running episodes -- stay)
+    if (out_records && record_bytes) HIP_TRY(hipMemcpyAsync(out_records, h->log_records, record_bytes, kind, h->stream));
+    if (out_count && count_bytes) HIP_TRY(hipMemcpyAsync(out_count, h->log_counts(), count_bytes, kind, h->stream));
+    if (clear && record_bytes) HIP_TRY(hipMemsetAsync(h->log_records, 0, record_bytes, h->stream));
+    if (clear && count_bytes) HIP_TRY(hipMemsetAsync(h->log_counts(), 0, count_bytes, h->stream));
+    if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
     return MAPF_OK;
 }
 
@@ -1130,6 +1186,7 @@ int mapf_set_state(mapf_handle_t h, const uint16_t *local, uint64_t t) {
                                h->device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
         h->may_be_terminal = true;   // (an arbitrary state)
         if (h->episode_limit) HIP_TRY(hipMemsetAsync(h->age, 0, size_t(h->E) * sizeof(uint32_t), h->stream));   // (... of new episodes)
+        if (h->log_capacity) HIP_TRY(mapf::launch_reset_log_partials(h->log_partials(), nullptr, h->E, h->stream));   // (... whose running records begin again)
         if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
     }
     h->t = t;
@@ -1157,6 +1214,7 @@ int mapf_graph_begin(mapf_handle_t h) {
     if (h->capturing) return fail(MAPF_EINVAL, "graph_begin: already recording");
     if (h->episode_limit) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with an episode limit cannot be recorded (mapf_set_episode_limit(h, 0) first)");
     if (h->episode_budget) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with an episode budget cannot be recorded (mapf_set_episode_budget(h, 0) first)");
+    if (h->log_capacity) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with an episode log cannot be recorded (mapf_set_episode_log(h, 0) first)");
     if (h->pair_slots) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with a conflict matrix cannot be recorded (mapf_set_conflict_pairs(h, 0, NULL) first)");
     if (h->joint.table) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle under the joint table policy cannot be recorded (mapf_set_policy or mapf_set_policy_table first)");
     HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed));

@@ -198,6 +198,20 @@ struct ConflictPairs {
     uint32_t n_slots;              // >= 1, n_slots * A * A * 8 <= 2^30 bytes (so an entry's index fits 32 bits)
 };
 
+// Episode log (include/mapf_hip.h mapf_set_episode_log): the handle's per-env partial episode -- the running return and its live
+// steps -- its count of ended episodes and the records of the first `capacity` of them.  One more block beside the others: the
+// log instances (../csrc_log/mapf_lg_log.hip) take it behind the budget and before the conflict matrix.  Two pointers, so that the
+// step loop carries two addresses per lane: the counts lie behind the partials in ONE allocation.
+struct EpisodeLogPartial { double acc; uint32_t len, pad; };   // the running return (+0.0 when an episode begins) and its live steps
+static_assert(sizeof(EpisodeLogPartial) == 16, "read and written as one 16-byte word");
+struct EpisodeLog {
+    EpisodeLogPartial *partial;    // [E] partials, then u32 count[E] at byte E * 16: episodes ended since the last clear, saturating
+    uint4 *records;                // [E * capacity] mapf_episode_record {f64 ret, u32 steps, u32 outcome}: env e's k-th ended episode at e * capacity + k
+    uint32_t capacity;             // C >= 1, E * C * 16 <= 2^31 bytes (so a record's byte offset fits 32 bits)
+};
+// where the counts of a log of n_envs envs begin
+__host__ __device__ inline uint32_t *episode_log_counts(EpisodeLogPartial *partial, uint64_t n_envs) { return reinterpret_cast<uint32_t *>(partial + n_envs); }
+
 // Every launcher names the kernel instance (and block size) that took the launch; the C ABI keeps the name of a
 // handle's last step / rollout launch (mapf_last_kernel) so a benchmark labels its numbers with what actually ran.
 constexpr size_t kKernelNameBytes = 160;   // what is kept of a name, the terminator included
@@ -302,11 +316,12 @@ enum class FamilyPreference { Auto, ThreadPerEnv, LaneGroup };
 // policies, and the C ABI, which applies that rule, never passes both.  A recording launch names all five rec_* arrays: the C ABI
 // substitutes scratch for absent ones.  limit / budget: those of a handle that has them, or null; with a budget `limit` is
 // non-null too, max_steps 0 on a handle without a limit.  pairs: the conflict matrix of a handle that counts, or null.
-// joint: the joint table policy of an actions == null launch, or null -- never beside `table`)
+// joint: the joint table policy of an actions == null launch, or null -- never beside `table`.  log: the episode log of a handle
+// that keeps one, or null; only beside a budget)
 hipError_t launch_step(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, hipStream_t stream, const EpisodeLimit *limit = nullptr);
 hipError_t launch_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, hipStream_t stream,
                           const TablePolicy *table = nullptr, const EpisodeLimit *limit = nullptr, const EpisodeBudget *budget = nullptr,
-                          const ConflictPairs *pairs = nullptr, const JointPolicy *joint = nullptr);
+                          const ConflictPairs *pairs = nullptr, const JointPolicy *joint = nullptr, const EpisodeLog *log = nullptr);
 // is the step launch_step would launch a thread-per-env one (one thread per env), else lg_group_size(A) threads per env?
 bool step_is_thread_per_env(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, const EpisodeLimit *limit);
 
@@ -335,6 +350,18 @@ hipError_t launch_rollout_lg_pairs_budget(const LgRolloutPlan &plan, int n_agent
                                               const EpisodeLimit *limit, const EpisodeBudget *budget, const ConflictPairs *pairs);
 MAPF_LG_JOINT_LAUNCHERS(X)
 #undef X
+// ... and the budget instances that keep an episode log: ../csrc_log/mapf_lg_log.hip, compiled once per (policy arm, conflict matrix):
+// streamed actions / in-kernel policy / table policy, or the joint table policy; each without and with the matrix.  ONE signature,
+// as the joint launchers have: a unit refuses a launch that lacks one of its blocks or brings another.  The masked zeroing of the
+// partials (mapf_reset) lives in the first of them
+#define MAPF_LG_LOG_LAUNCHERS(X) X(budget) X(pairs_budget) X(joint_budget) X(joint_pairs_budget)
+#define X(form)                                                                                                                                \
+    hipError_t launch_rollout_lg_log_##form(const LgRolloutPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const TablePolicy *table, \
+                                            const JointPolicy *joint, const EpisodeLimit *limit, const EpisodeBudget *budget, const EpisodeLog *log,       \
+                                            const ConflictPairs *pairs);
+MAPF_LG_LOG_LAUNCHERS(X)
+#undef X
+hipError_t launch_reset_log_partials(EpisodeLogPartial *partial, const uint8_t *mask, uint64_t n_envs, hipStream_t stream);
 hipError_t launch_step_lg(const LgStepPlan &plan, int n_agents, const StepArgs &args, hipStream_t stream);
 hipError_t launch_step_lg_limit(const LgStepPlan &plan, int n_agents, const StepArgs &args, hipStream_t stream, const EpisodeLimit &limit);
 hipError_t launch_reset_ages(uint32_t *age, const uint8_t *mask, uint64_t n_envs, hipStream_t stream);

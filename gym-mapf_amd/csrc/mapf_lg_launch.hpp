@@ -25,8 +25,9 @@ hipError_t launch_lg_rollout_instance(const LgRolloutPlan &plan, const RolloutAr
     const auto kern = plan.mv_lds ? Family::template kernel<L, FULL, true, RECORD, STREAM, TABLE>(plan.dense)
                                   : Family::template kernel<L, FULL, false, RECORD, STREAM, TABLE>(plan.dense);
     if (plan.lds_bytes > 32 * 1024) {
-        // (the most a CU has beside the instance's static LDS: kLdsReserve, and kPairsLdsBytes more in the instances that count pairs)
-        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(kLdsBytes - kLdsReserve - (plan.pairs ? kPairsLdsBytes : 0)))) return e;
+        // (the most a CU has beside the instance's static LDS: kLdsReserve, and kPairsLdsBytes more in the instances that count pairs,
+        // kLogLdsBytes more in those that keep an episode log)
+        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(kLdsBytes - kLdsReserve - (plan.pairs ? kPairsLdsBytes : 0) - (plan.log ? kLogLdsBytes : 0)))) return e;
     }
     char name[kKernelNameBytes];
     lg_rollout_kernel_name(name, plan, RECORD, STREAM, TABLE);

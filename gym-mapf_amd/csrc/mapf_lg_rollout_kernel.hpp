@@ -15,6 +15,11 @@
 //   EpisodeBudget -- the episode budget (include/mapf_hip.h mapf_set_episode_budget), behind the limit: a per-env count of episodes
 //     left beside the age.  An env whose count is 0 is PARKED: it folds into the `terminal` the transition is told, so its step
 //     draws and moves nothing, and its done bit is cleared before anything counts or records it.
+//   EpisodeLog    -- the episode log (include/mapf_hip.h mapf_set_episode_log), behind the budget: the env's running return, its live
+//     steps and its count of ended episodes are carried in the leader lane's registers as the age and the episodes left are, and a
+//     step that reports done or truncated stores the finished episode's 16-byte record with ONE global store (while the env's count
+//     is below the capacity).  The block itself waits in LDS, as the conflict matrix's does.  Budget instances only
+//     (../csrc_log/mapf_lg_log.hip).
 //   ConflictPairs -- the conflict matrix (include/mapf_hip.h mapf_set_conflict_pairs), last: the step's fast path is the one of the
 //     instance without it; a wave in which some env's step collided then takes the attributed pass (lg_count_pairs below), which
 //     finds the pairs the minima folded away and counts them with atomic adds.  Guarded instances only (pairs/mapf_lg_pairs.hip).
@@ -80,7 +85,8 @@ template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM, bool DENSE, c
 __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(const RolloutArgs p, const uint32_t n_agents, const Extra... extra) {
     constexpr bool TABLE = has_kernel_arg<TablePolicy, Extra...>, LIMIT = has_kernel_arg<EpisodeLimit, Extra...>,
                    BUDGET = has_kernel_arg<EpisodeBudget, Extra...>, PAIRS = has_kernel_arg<ConflictPairs, Extra...>,
-                   JOINT = has_kernel_arg<JointPolicy, Extra...>;
+                   JOINT = has_kernel_arg<JointPolicy, Extra...>, LOG = has_kernel_arg<EpisodeLog, Extra...>;
+    static_assert(BUDGET || !LOG, "a log instance is a budget instance");
     static_assert(!(TABLE && STREAM), "a table instance runs the launches without streamed actions");
     static_assert(!(JOINT && (TABLE || STREAM || DENSE)), "a joint instance: no table policy beside it, no streamed actions, guarded");
     static_assert(!(LIMIT && DENSE) && (LIMIT || !BUDGET), "the limit instances are guarded; a budget instance takes the limit block too");
@@ -99,6 +105,19 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
         static_assert(sizeof(ConflictPairs) <= kPairsLdsBytes, "the room plan_rollout_lg leaves");
         if (threadIdx.x == 0u) cp_lds = kernel_arg<ConflictPairs>(extra...);   // (the staging below ends with __syncthreads())
         cp = &cp_lds;
+    }
+    // the episode log's block waits there too (kLogLdsBytes, planned likewise): a step that ends an episode reads where the record
+    // goes, the launch's end where the partials and the counts lie -- no address of the log occupies a register across the step loop.
+    // A log instance carries four registers per lane more than its budget instance (the running return, its steps, the count); it
+    // gets them back, and more, from the addresses of the ages, the episodes left and their two totals, which wait here as well
+    // and are formed again at the launch's end instead of being parked in eight VGPRs
+    struct LogLds { EpisodeLog log; uint32_t *age, *out_truncations, *left, *out_live_steps; };
+    const LogLds *lg = nullptr;
+    if constexpr (LOG) {
+        __shared__ LogLds lg_lds;
+        static_assert(sizeof(LogLds) <= kLogLdsBytes, "the room plan_rollout_lg leaves");
+        if (threadIdx.x == 0u) lg_lds = LogLds{kernel_arg<EpisodeLog>(extra...), lim.age, lim.out_truncations, bud.left, bud.out_live_steps};   // (the staging below ends with __syncthreads())
+        lg = &lg_lds;
     }
     extern __shared__ __attribute__((aligned(16))) MoveEntry lds_mv[];
     bool live_rt;
@@ -178,6 +197,21 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
         asm volatile("" : "+v"(left_p), "+v"(liv_p));
         left = live ? *left_p : 0u;
         live_steps = (p.accumulate && liv_p && leader) ? *liv_p : 0u;
+    }
+    // the episode log: the leader's partial episode (one 16-byte word) and the env's count, read once here and written back once at
+    // the end like the age and the episodes left -- four registers across the step loop; the other lanes carry zeros and store nothing
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    using gw4 = __attribute__((address_space(1))) u32x4 *;
+    double log_acc = 0.0;
+    uint32_t log_len = 0u, log_count = 0u;
+    if constexpr (LOG) {
+        if (leader) {
+            const EpisodeLog la = kernel_arg<EpisodeLog>(extra...);
+            const u32x4 part = *(gw4)at(la.partial, e);
+            log_acc = __hiloint2double(int(part.y), int(part.x));
+            log_len = part.z;
+            log_count = *(gu32)at(episode_log_counts(la.partial, p.n_envs), e);
+        }
     }
     const uint64_t env_id = p.env_id_offset + e;
     const uint32_t n_envs = uint32_t(p.n_envs);
@@ -377,6 +411,23 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
             back = p.auto_reset && ((o.status & 0xFFu) != 0u || truncated != 0u);   // done or truncated: start cells, age 0
             age = back ? 0u : aged;
             if constexpr (BUDGET) left -= back ? 1u : 0u;   // (the budget instances run auto-reset launches only: back == done || truncated)
+            if constexpr (LOG) {
+                // the running episode takes the step's reward (a parked step: -0.0, which changes no sum; a terminal-on-entry no-op its
+                // +0.0) and, if the step was live, one step; a step that ends it (never a parked one: `back` is false there) stores
+                // the record while the env has room, counts it, and begins the next episode from +0.0
+                log_acc = __dadd_rn(log_acc, __hiloint2double(parked ? int(0x80000000u) : __double2hiint(o.reward), __double2loint(o.reward)));
+                log_len += no_op ? 0u : 1u;
+                if (back) {
+                    // (index e * C + count < E * C: the host keeps E * C * 16 within 2^31 bytes, so the byte offset fits 32 bits)
+                    if (const uint32_t cap = lg->log.capacity; leader && log_count < cap) {
+                        const uint32_t how = (o.status & 1u) | ((o.status >> 7) & 2u) | (truncated << 2);   // done | collision << 1 | truncated << 2
+                        *(gw4)at(lg->log.records, e * cap + log_count) = u32x4{uint32_t(__double2loint(log_acc)), uint32_t(__double2hiint(log_acc)), log_len, how};
+                    }
+                    log_count += log_count != 0xFFFFFFFFu ? 1u : 0u;
+                    log_acc = 0.0;
+                    log_len = 0u;
+                }
+            }
         } else {
             back = p.auto_reset && (o.status & 0xFFu) != 0u;   // MapfEnv.reset(): start cells, no reseed
         }
@@ -395,6 +446,12 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
     if (!live) return;
     store_cells<FULL>(p.state, e, n_agents, x.g, x.v0, x.v1, cur0, cur1);
     if (leader) {
+        if constexpr (LOG) {   // (the addresses the step loop did not carry)
+            age_p = (gu32)at(lg->age, e);
+            trn_p = (gu32)(lg->out_truncations ? at(lg->out_truncations, e) : nullptr);
+            left_p = (gu32)at(lg->left, e);
+            liv_p = (gu32)(lg->out_live_steps ? at(lg->out_live_steps, e) : nullptr);
+        }
         if (ret_p) *ret_p = ret;
         if (epi_p) *epi_p = episodes;
         if (col_p) *col_p = collisions;
@@ -405,6 +462,11 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
         if constexpr (BUDGET) {
             *left_p = left;
             if (liv_p) *liv_p = live_steps + (p.n_steps - idle);
+        }
+        if constexpr (LOG) {
+            EpisodeLogPartial *const partial = lg->log.partial;
+            *(gw4)at(partial, e) = u32x4{uint32_t(__double2loint(log_acc)), uint32_t(__double2hiint(log_acc)), log_len, 0u};
+            *(gu32)at(episode_log_counts(partial, p.n_envs), e) = log_count;
         }
     }
 }

@@ -356,11 +356,13 @@ LgStepPlan plan_step_lg(int n_agents, const StepArgs &args, bool limited) {
     return plan;
 }
 
-// (a limit plan: _limit_guarded and LIMIT where the others say DENSE or GUARDED, and the note; a budget plan: _budget_guarded, BUDGET)
+// (a limit plan: _limit_guarded and LIMIT where the others say DENSE or GUARDED, and the note; a budget plan: _budget_guarded, BUDGET;
+// a budget plan that keeps an episode log: _budget_guarded_log, BUDGET,LOG)
 void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy) {
-    const char *family = plan.budget ? "_budget_guarded" : (plan.limit ? "_limit_guarded" : "");
-    const char *form = plan.budget ? "BUDGET" : (plan.limit ? "LIMIT" : (plan.dense ? "DENSE" : "GUARDED"));
-    const char *note = plan.budget ? "; episode budget" : (plan.limit ? "; episode step limit" : "");
+    const bool log = plan.log && plan.budget;
+    const char *family = plan.budget ? (log ? "_budget_guarded_log" : "_budget_guarded") : (plan.limit ? "_limit_guarded" : "");
+    const char *form = plan.budget ? (log ? "BUDGET,LOG" : "BUDGET") : (plan.limit ? "LIMIT" : (plan.dense ? "DENSE" : "GUARDED"));
+    const char *note = plan.budget ? (log ? "; episode budget; episode log" : "; episode budget") : (plan.limit ? "; episode step limit" : "");
     const bool joint = plan.joint && table_policy;   // (the joint launcher passes table_policy: a launch without streamed actions)
     snprintf(name, kKernelNameBytes, "lg_rollout_kernel%s%s%s<L=%d,%s,%s,%s,%s,%s%s> block=%u (pair layout: 2 agents per lane%s%s%s)", joint ? "_joint" : (table_policy ? "_table" : ""),
              family, plan.pairs ? "_pairs" : "", plan.L, plan.full ? "FULL" : "RAGGED", plan.mv_lds ? "MV_LDS" : "MV_GLOBAL", record ? "RECORD" : "TOTALS",
@@ -489,30 +491,36 @@ static bool prefers_tpe(FamilyPreference prefer, int n_agents) {
 }
 
 RolloutRoute route_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool table_policy, size_t table_bytes,
-                           bool limited, bool budgeted, bool pairs, bool joint) {
+                           bool limited, bool budgeted, bool pairs, bool joint, bool logged) {
     RolloutRoute r;
+    logged = logged && budgeted;   // (a log launch is a budget launch: one of the three branches below, whose plan takes the mark)
+    RolloutTuning with_log = tune;   // (kLogLdsBytes of static LDS more than the others, as the matrix has: the largest tables stay in global memory)
+    if (logged) with_log.mv_lds_max_bytes = std::min(tune.mv_lds_max_bytes, kLdsBytes - kPairsLdsBytes - kLogLdsBytes);
     if (joint) {   // the joint instances exist in the lane-group family only, guarded, one form per (limit, budget, pairs)
-        RolloutTuning t = tune;   // (with the matrix: its block's static LDS, as below)
+        RolloutTuning t = logged ? with_log : tune;   // (with the matrix: its block's static LDS, as below)
         if (pairs) t.mv_lds_max_bytes = std::min(t.mv_lds_max_bytes, kLdsBytes - kPairsLdsBytes);
         r.lg = plan_rollout_lg(n_agents, args, t, limited || budgeted);
         r.lg.budget = budgeted;
         r.lg.pairs = pairs;
+        r.lg.log = logged;
         r.lg.dense = false;
         r.lg.joint = true;
         return r;
     }
     if (pairs) {   // the instances that count exist in the lane-group family only, guarded, one form per (limit, budget)
-        RolloutTuning t = tune;   // (kPairsLdsBytes of static LDS more than the others: the largest tables stay in global memory)
+        RolloutTuning t = logged ? with_log : tune;   // (kPairsLdsBytes of static LDS more than the others: the largest tables stay in global memory)
         t.mv_lds_max_bytes = std::min(t.mv_lds_max_bytes, kLdsBytes - kPairsLdsBytes);
         r.lg = plan_rollout_lg(n_agents, args, t, limited || budgeted);
         r.lg.budget = budgeted;
         r.lg.dense = false;
         r.lg.pairs = true;
+        r.lg.log = logged;
         return r;
     }
     if (budgeted) {   // the budget instances exist in the lane-group family only -- no packed plan, whatever the tuning says
-        r.lg = plan_rollout_lg(n_agents, args, tune, true);
+        r.lg = plan_rollout_lg(n_agents, args, logged ? with_log : tune, true);
         r.lg.budget = true;
+        r.lg.log = logged;
         return r;
     }
     // (the thread-per-env rollout specialisations beyond kTpeRolloutMaxAgents need SGPR spills and are not dispatched)

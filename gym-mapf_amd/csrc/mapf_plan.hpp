@@ -67,6 +67,8 @@ constexpr unsigned kLgRolloutMaxBlock = 1024u, kLgRolloutMaxBlock16 = 512u;
 // static LDS the instances that count conflicting pairs keep beyond kLdsReserve (their ConflictPairs block): a pairs plan stages the
 // move table into LDS only where this fits as well
 constexpr size_t kPairsLdsBytes = 32;
+// ... and the instances that keep an episode log (their EpisodeLog block and four addresses of the limit and the budget), likewise
+constexpr size_t kLogLdsBytes = 64;
 // The instance lg_rollout_kernel<L, full, mv_lds, ., ., dense> (or lg_rollout_kernel_table<L, full, mv_lds, ., dense>) and its geometry;
 // under `limit` the instance of the same fields among the limit kernels (mapf_lg_limit.hip), which are never dense
 struct LgRolloutPlan {
@@ -80,6 +82,7 @@ struct LgRolloutPlan {
     bool joint = false;              // ... and, of any of the six, the instances that follow a joint table policy (csrc_joint/mapf_lg_joint.hip): never dense
     unsigned block = 0, grid = 0;
     size_t lds_bytes = 0;            // dynamic LDS segment: the move table, or 0 (the launcher raises the limit beyond 32 KB)
+    bool log = false;                // ... and, of a budget plan, the instances that keep an episode log (csrc_log/mapf_lg_log.hip): never dense
 };
 // (limited: the launch runs under an episode step limit (EpisodeLimit, mapf_kernels.hpp).  Apart from the packed table instances
 // behind MAPF_TUNE limit_packed=1 (LqPlan::limit) the limit instances exist in the lane-group family only, so no other packed plan
@@ -91,6 +94,7 @@ LgStepPlan plan_step_lg(int n_agents, const StepArgs &args, bool limited = false
 // The names the launchers note for these plans (mapf_last_kernel; at most kKernelNameBytes with the terminator).  A limit plan's
 // name says _limit_guarded (the step: _limit) and LIMIT, and has no DENSE / GUARDED field; a budget plan's says _budget_guarded and BUDGET.
 // A pairs plan's name says _pairs behind the kernel's name and PAIRS behind the form (GUARDED, LIMIT or BUDGET).
+// A log plan's name says _log behind _budget_guarded and LOG behind BUDGET.
 // A joint plan's name (its launcher passes table_policy) says _joint and JOINT where a table launch says _table and TABLE, and ends with the joint policy's note.
 void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy);
 void lg_step_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms);
@@ -131,6 +135,8 @@ void transitions_kernel_name(char *name, const TransitionsPlan &plan, uint32_t n
 //   a conflict matrix takes the lane-group plan of its form (plain, limit or budget), marked `pairs` and never dense, before
 //     anything else: whatever the handle prefers and whatever limit_packed says;
 //   a budget takes the lane-group budget plan (a limit plan marked `budget`) before anything else;
+//   an episode log comes with a budget only and marks that launch's plan -- the budget's, with the conflict matrix and the joint
+//     table policy where the launch has those -- `log`: same geometry, the instances of csrc_log/mapf_lg_log.hip;
 //   a limit never goes to thread-per-env, and the step under a limit has the lane-group limit instance only;
 //   thread-per-env takes what the handle prefers it for (FamilyPreference; Auto: A <= 2) where its kernels exist: steps up to
 //     kTpeMaxAgents, rollouts up to kTpeRolloutMaxAgents;
@@ -141,10 +147,10 @@ enum class KernelFamily { ThreadPerEnv, Packed, LaneGroup };
 struct RolloutRoute { KernelFamily family = KernelFamily::LaneGroup; TpePlan tpe; LqPlan lq; LgRolloutPlan lg; };
 struct StepRoute { KernelFamily family = KernelFamily::LaneGroup; TpePlan tpe; StepPlan lq; LgStepPlan lg; };
 // (table_policy: the launch follows the table policy, of table_bytes action bytes; limited / budgeted: it runs under an episode
-// step limit / an episode budget; pairs: the handle counts conflicting pairs; joint: the launch follows the joint table policy.
-// args is never dereferenced)
+// step limit / an episode budget; pairs: the handle counts conflicting pairs; joint: the launch follows the joint table policy;
+// logged: the handle keeps an episode log (beside a budget only).  args is never dereferenced)
 RolloutRoute route_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool table_policy, size_t table_bytes,
-                           bool limited, bool budgeted, bool pairs = false, bool joint = false);
+                           bool limited, bool budgeted, bool pairs = false, bool joint = false, bool logged = false);
 // (ext_uniforms: the caller supplies the uniforms)
 StepRoute route_step(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool limited, bool ext_uniforms);
 

@@ -43,6 +43,16 @@ class MapfRolloutIO(Structure):
                 ('rec_done', c_void_p), ('rec_collision', c_void_p), ('rec_prob', c_void_p)]
 
 
+class MapfEpisodeRecord(Structure):
+    """mapf_episode_record: one finished episode of the episode log (mapf_set_episode_log)"""
+    _fields_ = [('ret', c_double), ('steps', c_uint32), ('outcome', c_uint32)]
+
+
+# the same 16 bytes as a numpy structured dtype
+EPISODE_RECORD_DTYPE = [('ret', '<f8'), ('steps', '<u4'), ('outcome', '<u4')]
+MAPF_EPISODE_DONE, MAPF_EPISODE_COLLISION, MAPF_EPISODE_TRUNCATED = 0x1, 0x2, 0x4
+
+
 # every symbol include/mapf_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     'mapf_create': (c_int, [POINTER(MapfDesc), POINTER(c_void_p)]),
@@ -59,6 +69,8 @@ SIGNATURES = {
     'mapf_episodes_left': (c_int, [c_void_p, c_void_p, c_void_p]),
     'mapf_set_conflict_pairs': (c_int, [c_void_p, c_uint32, c_void_p]),
     'mapf_conflict_pairs': (c_int, [c_void_p, c_void_p, c_int]),
+    'mapf_set_episode_log': (c_int, [c_void_p, c_uint32]),
+    'mapf_episode_log': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     'mapf_fill_random_actions': (c_int, [c_void_p, c_void_p, c_uint64, c_uint32]),
     'mapf_set_policy': (c_int, [c_void_p, c_int, c_void_p]),
     'mapf_set_policy_table': (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),

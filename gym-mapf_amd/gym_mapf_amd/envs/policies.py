@@ -204,7 +204,7 @@ def join_plan(V, n_agents, solo, pairs):
     return np.concatenate(parts), offsets, partners
 
 
-def evaluate(env, n_episodes, max_steps, chunk=256):
+def evaluate(env, n_episodes, max_steps, chunk=256, log=False):
     """Monte-Carlo evaluation of whatever drives ``env``'s ``rollout(actions=None)`` -- a table policy, a joint table policy (a plan with
     merged pairs, ``join_plan``), the greedy policy or the random stream: EXACTLY ``n_episodes`` episodes of at most ``max_steps`` steps in every env of a ``VecMapfEnv``, inside
     totals-only fused rollouts.  Sets the episode limit and the episode budget (``set_episode_limit``, ``set_episode_budget``; both
@@ -216,12 +216,17 @@ def evaluate(env, n_episodes, max_steps, chunk=256):
     ``live_steps`` (the steps those episodes took), uint32 -- ``goal_ends + collisions + truncations == n_episodes`` everywhere.
     On an env that counts conflicting pairs (``set_conflict_pairs``) the matrix is zeroed before the first launch and returned as
     ``pair_conflicts`` uint64 [n_slots, A, A] (``conflicts`` and ``conflicting_pairs`` read it): which agents got in each other's
-    way during those episodes.  Not covered: the multi-map and union-map wrappers and the scalar ``MapfEnv``."""
+    way during those episodes.  With ``log=True`` the episodes themselves come back too (``set_episode_log(n_episodes)``, which stays
+    set; the log is cleared before the first launch and ``count == n_episodes`` is asserted everywhere): ``episode_returns`` f64,
+    ``episode_steps`` uint32 and ``episode_outcomes`` uint8 (1 on the goals, 3 by a collision, 4 truncated), each [E, n_episodes] in
+    the order the episodes ended -- ``episode_statistics`` reads them.  Not covered: the multi-map and union-map wrappers and the scalar ``MapfEnv``."""
     n_episodes, max_steps, chunk = int(n_episodes), int(max_steps), int(chunk)
     if n_episodes < 1 or max_steps < 1 or chunk < 1:
         raise ValueError('evaluate needs n_episodes >= 1, max_steps >= 1 and chunk >= 1')
     env.set_episode_limit(max_steps)
     env.set_episode_budget(n_episodes)
+    if log:
+        env.set_episode_log(n_episodes)            # (every call empties the log and drops the partial sums)
     env.reset()
     counting = bool(getattr(env, 'conflict_slots', 0))
     if counting:
@@ -241,7 +246,49 @@ def evaluate(env, n_episodes, max_steps, chunk=256):
         pairs = env.conflict_pairs()
         env.sync()
         out['pair_conflicts'] = host(pairs)
+    if log:
+        episodes = env.episode_log()
+        env.sync()
+        assert (host(episodes['count']) == n_episodes).all(), 'every env has ended exactly n_episodes episodes'
+        out['episode_returns'], out['episode_steps'] = host(episodes['returns']), host(episodes['steps'])
+        out['episode_outcomes'] = host(episodes['outcome'])
     return out
+
+
+def episode_statistics(log):
+    """Host-side statistics of an episode log: ``log`` is what ``evaluate(..., log=True)`` returns (``episode_returns``,
+    ``episode_steps``, ``episode_outcomes``), or what ``VecMapfEnv.episode_log`` returns (``returns``, ``steps``, ``outcome`` and
+    ``count``: then only the first ``min(count, C)`` columns of an env are read).  Returns ``{'per_env': {...}, 'pooled': {...}}``;
+    per env the values are arrays [E], pooled over all logged episodes they are scalars: ``n`` (episodes read), ``mean``, ``std``
+    (the SAMPLE standard deviation, ddof = 1; nan below two episodes) and ``stderr`` (= std / sqrt(n)) of the episode returns,
+    ``goal_share``, ``collision_share`` and ``truncated_share`` (outcomes 1, 3 and 4 -- they sum to 1), ``mean_steps`` and
+    ``max_steps`` (0 without an episode)."""
+    host = lambda a: np.asarray(a.cpu() if hasattr(a, 'cpu') else a)
+    pick = lambda *names: next(host(log[n]) for n in names if n in log)
+    returns = pick('episode_returns', 'returns').astype(np.float64, copy=False)
+    steps, outcome = pick('episode_steps', 'steps').astype(np.int64), pick('episode_outcomes', 'outcome').astype(np.int64)
+    if returns.ndim != 2 or steps.shape != returns.shape or outcome.shape != returns.shape:
+        raise ValueError('an episode log holds three [E, C] arrays, got shapes %r, %r, %r' % (returns.shape, steps.shape, outcome.shape))
+    E, C = returns.shape
+    n = np.minimum(host(log['count']).astype(np.int64), C) if 'count' in log else np.full(E, C, np.int64)
+    if n.shape != (E,):
+        raise ValueError('count must be [E]')
+    valid = np.arange(C)[None, :] < n[:, None]
+
+    def stats(valid, axis):
+        k = valid.sum(axis=axis)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            mean = np.where(valid, returns, 0.0).sum(axis=axis) / k
+            centred = np.where(valid, returns - (mean[:, None] if axis == 1 else mean), 0.0)
+            std = np.sqrt((centred * centred).sum(axis=axis) / (k - 1))
+            std = np.where(k > 1, std, np.nan)
+            share = lambda code: (valid & (outcome == code)).sum(axis=axis) / k
+            res = {'n': k, 'mean': mean, 'std': std, 'stderr': std / np.sqrt(k), 'goal_share': share(1), 'collision_share': share(3),
+                   'truncated_share': share(4), 'mean_steps': np.where(valid, steps, 0).sum(axis=axis) / k,
+                   'max_steps': np.where(valid, steps, 0).max(axis=axis, initial=0)}
+        return res if axis == 1 else {key: (int(v) if key in ('n', 'max_steps') else float(v)) for key, v in res.items()}
+
+    return {'per_env': stats(valid, 1), 'pooled': stats(valid, None)}
 
 
 def conflicts(M):

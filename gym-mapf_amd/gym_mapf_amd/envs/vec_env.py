@@ -181,6 +181,7 @@ class VecMapfEnv:
         self.episode_limit = 0         # set_episode_limit: steps per episode, 0 = no limit
         self.episode_budget = 0        # set_episode_budget: episodes per env, 0 = no budget
         self.conflict_slots = 0        # set_conflict_pairs: slots of the conflict matrix, 0 = the mode is off
+        self.episode_log_capacity = 0  # set_episode_log: records per env, 0 = the mode is off
 
     # ------------------------------------------------------------------ construction
     def _as_local(self, locations, local_ids, what):
@@ -630,6 +631,62 @@ class VecMapfEnv:
             out = self._empty(shape, np.uint64)
         nat.check(self._lib.mapf_conflict_pairs(self._h, self._ptr(out, np.uint64, shape, 'out'), 1 if zero else 0))
         return out
+
+    def set_episode_log(self, capacity):
+        """Episode log: from now on every ``rollout`` under the episode budget (``set_episode_budget`` first) records each finished
+        episode per env -- its return, its live steps and how it ended -- for the first ``capacity`` episodes an env ends after a
+        clear; later ones are counted only (``count > capacity``).  ``None`` or 0 switches the mode off (the default); every call
+        empties the log and drops the running episodes' partial sums.  Nothing else of a rollout changes; it runs the lane-group
+        kernels' log instances (``last_kernel`` says LOG next to BUDGET) and ``graph_begin`` is refused.  ``reset`` and ``set_state``
+        with cells drop the running partial sums of the envs they touch; a clear and a re-armed budget do not, so an episode that
+        spans them is logged whole.  Not covered: the multi-map and union-map wrappers and the scalar ``MapfEnv``."""
+        capacity = 0 if capacity is None else capacity
+        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 0 <= int(capacity) <= 0xFFFFFFFF:
+            raise ValueError('the capacity of the episode log must be None or an integer 0 .. 2**32 - 1, got %r' % (capacity,))
+        nat.check(self._lib.mapf_set_episode_log(self._h, int(capacity)))
+        self._rollout_io = None
+        self.episode_log_capacity = int(capacity)
+
+    def episode_log(self, out=None, clear=False):
+        """The episode log (``set_episode_log``) as a dict: ``returns`` float64 [E, C], ``steps`` uint32 [E, C], ``outcome`` uint8
+        [E, C] (bit 0 done, bit 1 collision, bit 2 truncated: 1 = on the goals, 3 = by a collision, 4 = cut by the step limit) and
+        ``count`` uint32 [E], the episodes each env has ended since the last clear -- columns from ``min(count, C)`` on are zero.
+        ``clear=True`` empties the log after the read (the running episodes' partial sums stay).  ``out`` may hold ``records``
+        (the raw 16-byte records: a numpy array of ``_native.EPISODE_RECORD_DTYPE`` [E, C], in device mode a uint8 CUDA tensor
+        [E, C, 16]) and ``count`` to read into.  Host arrays, or CUDA tensors in device mode (the call then waits for the env's stream
+        before it cuts the records into columns)."""
+        C = self.episode_log_capacity
+        if not C:
+            raise ValueError('the env has no episode log (set_episode_log)')
+        E, out = self.n_envs, ({} if out is None else out)
+        count = out.get('count')
+        if count is None:
+            count = self._empty((E,), np.uint32)
+        records = out.get('records')
+        if self.device_arrays:
+            if records is None:
+                records = self._empty((E, C, 16), np.uint8)
+            rec_ptr = self._ptr(records, np.uint8, (E, C, 16), 'records')
+        else:
+            if records is None:
+                records = np.empty((E, C), dtype=nat.EPISODE_RECORD_DTYPE)
+            if not isinstance(records, np.ndarray) or records.dtype != np.dtype(nat.EPISODE_RECORD_DTYPE) or records.shape != (E, C) \
+                    or not records.flags['C_CONTIGUOUS']:
+                raise ValueError('records must be a C-contiguous numpy array of _native.EPISODE_RECORD_DTYPE with shape %r' % ((E, C),))
+            rec_ptr = records.ctypes.data
+        nat.check(self._lib.mapf_episode_log(self._h, rec_ptr, self._ptr(count, np.uint32, (E,), 'count'), 1 if clear else 0))
+        if self.device_arrays:
+            torch = self._torch
+            self.sync()                                            # (the columns are cut on torch's stream: the raw records must have landed)
+            words = records.view(torch.int32)                     # [E, C, 4]: ret lo, ret hi, steps, outcome
+            res = {'returns': records[:, :, :8].contiguous().view(torch.float64).reshape(E, C),
+                   'steps': words[:, :, 2].contiguous().view(torch.uint32), 'outcome': records[:, :, 12].contiguous()}
+        else:
+            res = {'returns': np.ascontiguousarray(records['ret']), 'steps': np.ascontiguousarray(records['steps']),
+                   'outcome': records['outcome'].astype(np.uint8)}
+        res['count'] = count
+        res['records'] = records
+        return res
 
     def episode_steps(self, out=None, set=None):
         """The steps every env's current episode has taken since it began, uint32 [E] (all zero without a limit); ``set`` uint32 [E]

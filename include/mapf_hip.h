@@ -250,7 +250,8 @@ int mapf_step_limited(mapf_handle_t h, const uint8_t *actions, const double *uni
  * whatever the handle's family flag or limit_packed, and mapf_last_kernel says BUDGET; with B == 0 every launch, kernel instance
  * and name is what it is without this feature.
  * Out of scope: budget forms of the packed (lq_*) and thread-per-env kernels (a handle with a budget takes the lane-group speed),
- * the single step and recorded graphs, the multi-map / union-map wrappers and the scalar MapfEnv, a per-episode log, discounting.
+ * the single step and recorded graphs, the multi-map / union-map wrappers and the scalar MapfEnv, discounting.  (The per-episode
+ * log is mapf_set_episode_log, below.)
  * No policy is computed on the device.
  */
 int mapf_set_episode_budget(mapf_handle_t h, uint32_t n_episodes);
@@ -287,11 +288,56 @@ int mapf_rollout_budgeted(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *
  * instances that count, whatever the handle's family flag or limit_packed, and mapf_last_kernel says PAIRS, next to LIMIT or
  * BUDGET where those apply; with the mode off every launch, kernel instance and name is what it is without this feature.
  * Out of scope: packed (lq_*) and thread-per-env forms (a handle with the mode on takes the lane-group speed, as one with a budget
- * does), the single step and recorded graphs, the multi-map / union-map wrappers and the scalar MapfEnv, per-step or per-episode
- * logs of conflicts, anything that merges groups or replans on the device.
+ * does), the single step and recorded graphs, the multi-map / union-map wrappers and the scalar MapfEnv, per-step logs of
+ * conflicts, anything that merges groups or replans on the device.  (How each episode ended -- by a collision or not -- is in the
+ * episode log, below; which pair collided in which episode is not.)
  */
 int mapf_set_conflict_pairs(mapf_handle_t h, uint32_t n_slots, const uint32_t *slot_of_env);
 int mapf_conflict_pairs(mapf_handle_t h, uint64_t *out, int zero);
+
+/*
+ * Episode log (ABI 6, new symbols only): fused rollouts that record EVERY FINISHED EPISODE per env -- its return, its length and
+ * how it ended -- where the totals of a budgeted evaluation keep one sum per env.  What comparing two plans needs: the spread of
+ * the returns (a standard error per start state), the distribution of the episode lengths, which episode ended how.  The route to
+ * those is otherwise a recording rollout and a pass over its [T, E] arrays.
+ * THE DEFINITION.  A handle has an episode log of capacity C (0 = none, the default).  Per env it keeps acc, an f64 running return;
+ * len, a u32 count of running live steps; count, a u32 count of episodes ended since the last clear; and C records of 16 bytes.
+ * The log applies to the launches the budget applies to: mapf_rollout* with MAPF_STEP_AUTO_RESET on a handle with B > 0.  For
+ * every env and step, after the budget's rules have produced the step's reward, done, collision and truncated:
+ *   parked on entry: nothing changes.
+ *   otherwise: acc = acc + reward -- ONE float64 add, in step order; the terminal-on-entry no-op adds its +0.0 -- and len += 1 if
+ *     the step was live (neither parked nor terminal on entry).
+ *   if the step reports done or truncated: the record {acc, len, done | collision << 1 | truncated << 2} is stored at
+ *     records[e][count] if count < C; then count += 1 (saturating), acc = +0.0, len = 0.  Episodes beyond C are counted and not
+ *     stored: the caller sees count > C.
+ * A terminal-start no-op therefore logs {+0.0, 0, 1}.  An env's record returns, summed, need not be bit-equal to the totals'
+ * out_returns: the additions associate differently.
+ * The log changes nothing else: state, outputs, totals, ages, left, the conflict matrix, both Philox streams and the step index
+ * are bit for bit those of the same launch with the log off.  Records of shards (env_id_offset) concatenate.
+ * acc and len are zeroed in every mapf_set_episode_log call, for the envs a mapf_reset(mask) resets, and for all envs in
+ * mapf_set_state with cells.  mapf_set_episode_limit, mapf_set_episode_budget, mapf_episodes_left(set_left) and a clear leave them
+ * alone: an episode that spans a clear or a re-arm is logged whole.
+ *
+ * mapf_set_episode_log: allocates and zeroes the records, the counts and the partials; capacity 0 frees them and switches the mode
+ *   off.  MAPF_EINVAL for a null handle, capacity > 0 on a handle without a budget, E * C * 16 > 2^31 bytes; refused (MAPF_EINVAL)
+ *   while recording and while recorded graphs live, as mapf_set_episode_budget is.  With a log on, mapf_set_episode_budget(h, 0) is
+ *   MAPF_EINVAL (switch the log off first) and mapf_graph_begin is MAPF_EUNSUPPORTED.
+ * mapf_episode_log: out_records [E * C] and out_count u32[E] receive the records (env e's k-th at e * C + k; the slots from
+ *   count on are zero) and the counts -- HOST pointers, or DEVICE pointers on a MAPF_FLAG_DEVICE_PTRS handle (then only enqueued),
+ *   the rules of mapf_conflict_pairs; either may be NULL.  With clear != 0 records and counts are then zeroed; the partials are not.
+ *   All three absent, or the mode off, is MAPF_EINVAL.
+ * Everything is validated on the host before any device work, pointers first.  Launches of a handle with the mode on run the
+ * lane-group kernels' log instances -- always the budget plan -- and mapf_last_kernel says LOG next to BUDGET; with the mode off
+ * every launch, kernel instance and name is what it is without this feature.
+ * Out of scope, as for the budget: packed and thread-per-env forms, the single step and recorded graphs, the multi-map /
+ * union-map wrappers and the scalar MapfEnv, discounting.
+ */
+typedef struct mapf_episode_record { double ret; uint32_t steps; uint32_t outcome; } mapf_episode_record;
+#define MAPF_EPISODE_DONE      0x1u          /* outcome bits: the last step reported done ... */
+#define MAPF_EPISODE_COLLISION 0x2u          /* ... by a collision (3 = done | collision; 1 alone: on the goals) */
+#define MAPF_EPISODE_TRUNCATED 0x4u          /* the episode step limit cut it */
+int mapf_set_episode_log(mapf_handle_t h, uint32_t capacity);
+int mapf_episode_log(mapf_handle_t h, mapf_episode_record *out_records, uint32_t *out_count, int clear);
 
 /* Synthetic policy used by bench/rollout: fills actions u8[n_steps*E*A] for step indices
  * t0 .. t0+n_steps-1 from the policy stream (oracle/philox.py random_actions_np; ABI 5: key seed + 1, ONE Philox

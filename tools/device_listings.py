@@ -38,6 +38,11 @@ def joint_units():
     return dict(line.split() for line in _make('print-joint-kernel-units').splitlines())
 
 
+def log_units():
+    """{name: source unit} of the Makefile's fourth table: the budget compilations that keep an episode log, whose source lies beside csrc"""
+    return dict(line.split() for line in _make('print-log-kernel-units').splitlines())
+
+
 def listings(*names):
     """{name: listing text} for the named compilations (a kernel-holding one or a host unit); for all kernel-holding ones if none is named"""
     names = names or tuple(units())
