@@ -161,6 +161,14 @@ struct mapf_handle_s : StreamAndEvents {
     DevicePtr<uint32_t> joint_offset;
     DevicePtr<uint16_t> joint_partner;
     mapf::JointPolicy joint{};
+    // group policy (mapf_set_policy_group): device copies of the solo rows, the agents' row indices, member lists and books, and of the
+    // open-addressing table of all books, and the view of them the kernels are handed; group.table null = off.  At most one of
+    // table / joint / group is on
+    DevicePtr<uint8_t> group_bytes;
+    DevicePtr<uint16_t> group_rows, group_members;
+    DevicePtr<uint32_t> group_book;
+    DevicePtr<mapf::GroupSlot> group_slots;
+    mapf::GroupPolicy group{};
     DevicePtr<uint16_t> state, start, goal;
     // episode step limit (mapf_set_episode_limit): N (0 = none) and the per-env ages, which are all zero while N == 0 -- only the
     // limit kernels and mapf_episode_steps write them, and only a handle with a limit runs those
@@ -218,6 +226,14 @@ struct mapf_handle_s : StreamAndEvents {
         joint_offset.reset();
         joint_partner.reset();
         joint = mapf::JointPolicy{};
+    }
+    void drop_policy_group() {
+        group_bytes.reset();
+        group_rows.reset();
+        group_members.reset();
+        group_book.reset();
+        group_slots.reset();
+        group = mapf::GroupPolicy{};
     }
     // Teardown: the stream drains, then the recordings go (they name the handle's buffers), then the members -- every
     // buffer -- and last the base: events, and the stream if the handle created it.
@@ -716,6 +732,7 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
     // precedence over it, as over the other policies -- the ONE place that rule is applied: no launcher sees both)
     const mapf::TablePolicy *table = (h->table.table && !io->actions) ? &h->table : nullptr;
     const mapf::JointPolicy *joint = (h->joint.table && !io->actions) ? &h->joint : nullptr;   // (the joint table policy likewise)
+    const mapf::GroupPolicy *group = (h->group.table && !io->actions) ? &h->group : nullptr;   // (and the group policy)
     a.auto_reset = io->step_flags & MAPF_STEP_AUTO_RESET;
     a.accumulate = io->accumulate != 0;
     a.start_terminal_any = h->start_terminal_any;
@@ -755,7 +772,7 @@ int rollout_impl(mapf_handle_t h, const mapf_rollout_io *io, uint32_t *out_trunc
         if (int rc = reserve_stand_in(h, h->x_trunc, TE, "rec_truncated")) return rc;
         lim.rec_truncated = static_cast<uint8_t *>(h->x_trunc.ptr);
     }
-    HIP_TRY(mapf::launch_rollout(int(h->A), a, h->tune, h->prefer, h->stream, table, limit, budget, pairs, joint, log));
+    HIP_TRY(mapf::launch_rollout(int(h->A), a, h->tune, h->prefer, h->stream, table, limit, budget, pairs, joint, log, group));
     after_launch(h, h->last_rollout_kernel, io->n_steps, a.auto_reset);
     if (int rc = fetch_arrays(h, arrays)) return rc;
     if (!h->device_ptrs) HIP_TRY(hipStreamSynchronize(h->stream));
@@ -931,6 +948,7 @@ int mapf_set_policy_table(mapf_handle_t h, const uint8_t *table, uint32_t n_rows
     HIP_TRY(hipStreamSynchronize(h->stream));   // no launch may still be reading the old copies
     h->drop_policy_table();
     h->drop_policy_joint();
+    h->drop_policy_group();
     h->policy_cells.reset();   // (one policy at a time)
     // the table's allocation is padded to whole 16-byte words (the LDS form stages it sixteen bytes at a time); the row indices
     // by one agent row (the packed kernels load an agent pair's two indices as one word)
@@ -999,6 +1017,7 @@ int mapf_set_policy_joint(mapf_handle_t h, const uint8_t *table, uint64_t table_
     if (e != hipSuccess) return hip_fail(e, "set_policy_joint: copying the table");   // (the previous policy stays in force)
     h->drop_policy_table();    // (one policy at a time)
     h->drop_policy_joint();
+    h->drop_policy_group();
     h->policy_cells.reset();
     h->joint_bytes = std::move(d_table);
     h->joint_offset = std::move(d_offset);
@@ -1011,17 +1030,125 @@ int mapf_set_policy_joint(mapf_handle_t h, const uint8_t *table, uint64_t table_
     return MAPF_OK;
 }
 
+// what mapf_set_policy_group and mapf_debug_policy_group share: the pointer and range checks that need no handle, the header's rules
+// about the arrays, and the table of all books -- all on the host
+static int group_plan_checked(const mapf::GroupPlanArrays &g, uint32_t flags, mapf::GroupTable *built) {
+    if (!g.table) return fail(MAPF_EINVAL, "set_policy_group: table is null");
+    if (!g.row_index) return fail(MAPF_EINVAL, "set_policy_group: row_index is null");
+    if (!g.members) return fail(MAPF_EINVAL, "set_policy_group: members is null");
+    if (!g.book) return fail(MAPF_EINVAL, "set_policy_group: book is null");
+    if (!g.entries && !(g.n_entries == 0 && g.n_books == 0)) return fail(MAPF_EINVAL, "set_policy_group: entries is null (allowed only with n_entries == 0 and n_books == 0)");
+    if (!g.book_begin && !(g.n_entries == 0 && g.n_books == 0)) return fail(MAPF_EINVAL, "set_policy_group: book_begin is null (allowed only with n_entries == 0 and n_books == 0)");
+    if (flags & ~MAPF_POLICY_ROWS_BROADCAST) return fail(MAPF_EINVAL, "set_policy_group: unknown bits in flags");
+    if (g.V > 65535u) return fail(MAPF_EUNSUPPORTED, "set_policy_group: the mode needs V <= 65535 (cell 0xFFFF is the padding of keys)");
+    std::string error;
+    if (!mapf::validate_group_plan(g, &error)) return fail(MAPF_EINVAL, error);
+    if (!mapf::build_group_table(reinterpret_cast<const mapf::GroupEntry *>(g.entries), g.n_entries, g.book_begin, g.n_books, built, &error)) return fail(MAPF_EINVAL, error);
+    return MAPF_OK;
+}
+
+int mapf_set_policy_group(mapf_handle_t h, const uint8_t *table, uint32_t n_rows, const uint16_t *row_index, const uint16_t *members, const uint32_t *book,
+                          const mapf_group_entry *entries, uint64_t n_entries, const uint32_t *book_begin, uint32_t n_books, uint32_t flags) {
+    static_assert(sizeof(mapf_group_entry) == sizeof(mapf::GroupEntry) && sizeof(mapf_group_entry) == 12, "one layout");
+    if (!h) return fail(MAPF_EINVAL, "set_policy_group: null handle");
+    mapf::GroupPlanArrays g;
+    g.table = table; g.n_rows = n_rows; g.row_index = row_index; g.members = members; g.book = book;
+    g.entries = reinterpret_cast<const mapf::GroupEntry *>(entries); g.n_entries = n_entries; g.book_begin = book_begin; g.n_books = n_books;
+    g.broadcast = (flags & MAPF_POLICY_ROWS_BROADCAST) != 0u;
+    if (!table || !row_index || !members || !book || (flags & ~MAPF_POLICY_ROWS_BROADCAST)) return group_plan_checked(g, flags, nullptr);   // (fails before the handle is read)
+    g.V = h->V; g.A = h->A; g.E = h->E;
+    if (int rc = check_not_recording(h, "mapf_set_policy")) return rc;
+    if (!h->graphs.empty()) return fail(MAPF_EINVAL, "set_policy: recorded graphs hold the current policy table (destroy them first)");
+    mapf::GroupTable built;
+    if (int rc = group_plan_checked(g, flags, &built)) return rc;   // all of it on the host, before any device work
+    if (int rc = check_handle(h)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // no launch may still be reading the old copies
+    // the allocations are padded as the table policy's are: the table to whole 16-byte words, the index arrays by one agent row
+    const uint64_t bytes = uint64_t(n_rows) * h->V, n_index = g.broadcast ? uint64_t(h->A) : uint64_t(h->E) * h->A;
+    const size_t padded = (size_t(bytes) + 15u) & ~size_t(15), n_padded = size_t(n_index) + 16u;
+    DevicePtr<uint8_t> d_table;
+    DevicePtr<uint16_t> d_rows, d_members;
+    DevicePtr<uint32_t> d_book;
+    DevicePtr<mapf::GroupSlot> d_slots;
+    HIP_TRY(d_table.alloc(padded));
+    if (hipError_t e = d_rows.alloc(n_padded)) return hip_fail(e, "hipMalloc");
+    if (hipError_t e = d_members.alloc(n_padded * 4u)) return hip_fail(e, "hipMalloc");
+    if (hipError_t e = d_book.alloc(n_padded)) return hip_fail(e, "hipMalloc");
+    if (hipError_t e = d_slots.alloc(built.slots.size())) return hip_fail(e, "hipMalloc");
+    hipError_t e = hipMemset(d_table, 0, padded);
+    if (e == hipSuccess) e = hipMemset(d_rows, 0, n_padded * sizeof(uint16_t));
+    if (e == hipSuccess) e = hipMemset(d_members, 0xFF, n_padded * 4u * sizeof(uint16_t));
+    if (e == hipSuccess) e = hipMemset(d_book, 0, n_padded * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpy(d_table, table, size_t(bytes), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_rows, row_index, size_t(n_index) * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_members, members, size_t(n_index) * 4u * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_book, book, size_t(n_index) * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_slots, built.slots.data(), built.slots.size() * sizeof(mapf::GroupSlot), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(e, "set_policy_group: copying the plan");   // (the previous policy stays in force)
+    h->drop_policy_table();    // (one policy at a time)
+    h->drop_policy_joint();
+    h->drop_policy_group();
+    h->policy_cells.reset();
+    h->group_bytes = std::move(d_table);
+    h->group_rows = std::move(d_rows);
+    h->group_members = std::move(d_members);
+    h->group_book = std::move(d_book);
+    h->group_slots = std::move(d_slots);
+    h->group.table = h->group_bytes;
+    h->group.rows = h->group_rows;
+    h->group.members = h->group_members;
+    h->group.book = h->group_book;
+    h->group.slots = h->group_slots;
+    h->group.mask = uint32_t(built.slots.size() - 1u);
+    h->group.max_probe = built.max_probe;
+    h->group.broadcast = g.broadcast ? 1u : 0u;
+    return MAPF_OK;
+}
+
+int mapf_policy_group_stats(mapf_handle_t h, uint64_t *slots, uint32_t *max_probe) {
+    if (!h) return fail(MAPF_EINVAL, "policy_group_stats: null handle");
+    if (!h->group.table) return fail(MAPF_EINVAL, "policy_group_stats: the handle is not under the group policy (mapf_set_policy_group)");
+    if (slots) *slots = uint64_t(h->group.mask) + 1u;
+    if (max_probe) *max_probe = h->group.max_probe;
+    return MAPF_OK;
+}
+
+int mapf_debug_policy_group(uint32_t n_cells, uint32_t n_agents, uint64_t n_envs, const uint8_t *table, uint32_t n_rows, const uint16_t *row_index,
+                            const uint16_t *members, const uint32_t *book, const mapf_group_entry *entries, uint64_t n_entries, const uint32_t *book_begin,
+                            uint32_t n_books, uint32_t flags, uint64_t n_keys, const uint16_t *key_cells, const uint32_t *key_book, uint32_t *out_actions,
+                            uint32_t *out_probes, uint64_t *out_slots, uint32_t *out_max_probe) {
+    mapf::GroupPlanArrays g;
+    g.V = n_cells; g.A = n_agents; g.E = n_envs;
+    g.table = table; g.n_rows = n_rows; g.row_index = row_index; g.members = members; g.book = book;
+    g.entries = reinterpret_cast<const mapf::GroupEntry *>(entries); g.n_entries = n_entries; g.book_begin = book_begin; g.n_books = n_books;
+    g.broadcast = (flags & MAPF_POLICY_ROWS_BROADCAST) != 0u;
+    if (n_agents < 1 || n_agents > MAPF_MAX_AGENTS) return fail(MAPF_EINVAL, "debug_policy_group: n_agents must be 1..MAPF_MAX_AGENTS");
+    if (n_keys != 0 && (!key_cells || !key_book || !out_actions)) return fail(MAPF_EINVAL, "debug_policy_group: key_cells, key_book or out_actions is null");
+    mapf::GroupTable built;
+    if (int rc = group_plan_checked(g, flags, &built)) return rc;
+    if (out_slots) *out_slots = built.slots.size();
+    if (out_max_probe) *out_max_probe = built.max_probe;
+    for (uint64_t k = 0; k < n_keys; ++k) {
+        uint32_t probes = 0;
+        out_actions[k] = mapf::lookup_group_table(built, key_cells + 4u * k, key_book[k], &probes);
+        if (out_probes) out_probes[k] = probes;
+    }
+    return MAPF_OK;
+}
+
 int mapf_set_policy(mapf_handle_t h, int policy, const uint32_t *cell_rc) {
     if (int rc = check_handle(h)) return rc;
     if (int rc = check_not_recording(h, "mapf_set_policy")) return rc;
     if (!h->graphs.empty()) return fail(MAPF_EINVAL, "set_policy: recorded graphs hold the current policy table (destroy them first)");
     if (policy == MAPF_POLICY_TABLE) return fail(MAPF_EINVAL, "set_policy: MAPF_POLICY_TABLE is set through mapf_set_policy_table (it takes the table and the row indices)");
     if (policy == MAPF_POLICY_JOINT) return fail(MAPF_EINVAL, "set_policy: MAPF_POLICY_JOINT is set through mapf_set_policy_joint (it takes the table, the offsets and the partners)");
+    if (policy == MAPF_POLICY_GROUP) return fail(MAPF_EINVAL, "set_policy: MAPF_POLICY_GROUP is set through mapf_set_policy_group (it takes the rows, the groups and the books)");
     if (policy != MAPF_POLICY_RANDOM && policy != MAPF_POLICY_GREEDY) return fail(MAPF_EINVAL, "set_policy: unknown policy");
     if (policy == MAPF_POLICY_GREEDY && !cell_rc) return fail(MAPF_EINVAL, "set_policy: the greedy policy needs cell_rc");
     HIP_TRY(hipStreamSynchronize(h->stream));   // no launch may still be reading the old table
     h->drop_policy_table();                     // either policy leaves table mode
     h->drop_policy_joint();                     // ... and joint mode
+    h->drop_policy_group();                     // ... and group mode
     if (policy == MAPF_POLICY_RANDOM) {
         h->policy_cells.reset();
         return MAPF_OK;
@@ -1216,6 +1343,7 @@ int mapf_graph_begin(mapf_handle_t h) {
     if (h->episode_budget) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with an episode budget cannot be recorded (mapf_set_episode_budget(h, 0) first)");
     if (h->log_capacity) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with an episode log cannot be recorded (mapf_set_episode_log(h, 0) first)");
     if (h->pair_slots) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle with a conflict matrix cannot be recorded (mapf_set_conflict_pairs(h, 0, NULL) first)");
+    if (h->group.table) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle under the group policy cannot be recorded (mapf_set_policy or mapf_set_policy_table first)");
     if (h->joint.table) return fail(MAPF_EUNSUPPORTED, "graph_begin: a handle under the joint table policy cannot be recorded (mapf_set_policy or mapf_set_policy_table first)");
     HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed));
     h->capturing = true;

@@ -45,11 +45,11 @@ static hipError_t launch_rollout_lq(const LqPlan &plan, int n_agents, const Roll
 }
 
 hipError_t launch_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, hipStream_t stream, const TablePolicy *table,
-                          const EpisodeLimit *limit, const EpisodeBudget *budget, const ConflictPairs *pairs, const JointPolicy *joint, const EpisodeLog *log) {
-    if (n_agents < 1 || (joint && (table || args.actions))) return hipErrorInvalidValue;   // (one policy per launch: the C ABI passes at most one)
+                          const EpisodeLimit *limit, const EpisodeBudget *budget, const ConflictPairs *pairs, const JointPolicy *joint, const EpisodeLog *log, const GroupPolicy *group) {
+    if (n_agents < 1 || (joint && (table || args.actions)) || (group && (table || joint || args.actions))) return hipErrorInvalidValue;   // (one policy per launch: the C ABI passes at most one)
     if (args.n_envs == 0) return hipSuccess;
     const RolloutRoute r = route_rollout(n_agents, args, tune, prefer, table != nullptr, table ? table->table_bytes : 0u, limit != nullptr, budget != nullptr,
-                                         pairs != nullptr, joint != nullptr, log != nullptr);
+                                         pairs != nullptr, joint != nullptr, log != nullptr, group != nullptr);
     if (!limit_block_complete(limit, budget, true, args.rec_local != nullptr, args.auto_reset)) return hipErrorInvalidValue;
     if (pairs && !(pairs->matrix && pairs->n_slots != 0u)) return hipErrorInvalidValue;
     if (log && !(budget && log->partial && log->records && log->capacity != 0u)) return hipErrorInvalidValue;   // (a log comes with a budget only)
@@ -59,6 +59,17 @@ hipError_t launch_rollout(int n_agents, const RolloutArgs &args, const RolloutTu
         case KernelFamily::LaneGroup: break;
     }
     if (joint && !(joint->table && joint->offset && joint->partner && joint->table_bytes != 0u)) return hipErrorInvalidValue;
+    if (group) {   // the route took the lane-group plan of the launch's form, marked `group`: the unit of that form
+        if (!(group->table && group->rows && group->members && group->book && group->slots)) return hipErrorInvalidValue;
+        if (log) return pairs ? launch_rollout_lg_group_log_pairs_budget(r.lg, n_agents, args, stream, *group, limit, budget, log, pairs)
+                              : launch_rollout_lg_group_log_budget(r.lg, n_agents, args, stream, *group, limit, budget, log, pairs);
+        if (pairs) return budget ? launch_rollout_lg_group_pairs_budget(r.lg, n_agents, args, stream, *group, limit, budget, log, pairs)
+                          : (limit ? launch_rollout_lg_group_pairs_limit(r.lg, n_agents, args, stream, *group, limit, budget, log, pairs)
+                                   : launch_rollout_lg_group_pairs_plain(r.lg, n_agents, args, stream, *group, limit, budget, log, pairs));
+        return budget ? launch_rollout_lg_group_budget(r.lg, n_agents, args, stream, *group, limit, budget, log, pairs)
+                      : (limit ? launch_rollout_lg_group_limit(r.lg, n_agents, args, stream, *group, limit, budget, log, pairs)
+                               : launch_rollout_lg_group_plain(r.lg, n_agents, args, stream, *group, limit, budget, log, pairs));
+    }
     if (log) {   // the route took the lane-group budget plan, marked `log`: the unit of the launch's policy arm, with the matrix or without
         if (joint) return pairs ? launch_rollout_lg_log_joint_pairs_budget(r.lg, n_agents, args, stream, table, joint, limit, budget, log, pairs)
                                 : launch_rollout_lg_log_joint_budget(r.lg, n_agents, args, stream, table, joint, limit, budget, log, pairs);

@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <string>
 
+#include "mapf_group_table.hpp"
+
 namespace mapf {
 
 // Merged slip distribution of one agent for one equality pattern of its three candidate cells
@@ -171,6 +173,22 @@ struct JointPolicy {
     uint32_t broadcast;            // offset and partner are [A]
 };
 
+// Group policy (include/mapf_hip.h MAPF_POLICY_GROUP): the device copies mapf_set_policy_group made.  Every agent has a solo row, as
+// under TablePolicy; an agent of a group of 2..4 takes its byte of the entry of the group's current joint cell where the group's
+// book has one (the open-addressing table of mapf_group_table.hpp), else the byte of its row.  One more block beside the others: the
+// group instances (csrc_group/mapf_lg_group.hip) take it first, where the table instances take TablePolicy -- never beside it or
+// JointPolicy.
+struct GroupPolicy {
+    const uint8_t *table;          // [n_rows * V] the solo rows' action bytes 0..4 (the allocation is padded to a multiple of 16 bytes)
+    const uint16_t *rows;          // [E*A] or [A]: the row an agent follows where its group's book has no entry
+    const uint16_t *members;       // [E*A*4] or [A*4]: the agents of the agent's group, ascending, 0xFFFF behind the last
+    const uint32_t *book;          // [E*A] or [A]: the group's book (ignored for a solo agent)
+    const GroupSlot *slots;        // [mask + 1] all books' entries
+    uint32_t mask;                 // capacity - 1, the capacity a power of two
+    uint32_t max_probe;            // the longest probe chain the builder produced: the bound of the kernel's probe loop
+    uint32_t broadcast;            // rows, members and book are per agent, shared by all envs
+};
+
 // Episode step limit (include/mapf_hip.h mapf_set_episode_limit): the handle's per-env ages, the limit and where a launch
 // reports its truncations.  Travels beside the argument blocks as the table policy does -- StepArgs, RolloutArgs, and with them
 // every kernel that exists without the limit, stay as they are; the limit instances are kernels of their own (mapf_lg_limit.hip).
@@ -317,11 +335,13 @@ enum class FamilyPreference { Auto, ThreadPerEnv, LaneGroup };
 // substitutes scratch for absent ones.  limit / budget: those of a handle that has them, or null; with a budget `limit` is
 // non-null too, max_steps 0 on a handle without a limit.  pairs: the conflict matrix of a handle that counts, or null.
 // joint: the joint table policy of an actions == null launch, or null -- never beside `table`.  log: the episode log of a handle
-// that keeps one, or null; only beside a budget)
+// that keeps one, or null; only beside a budget.  group: the group policy of an actions == null launch, or null -- never beside
+// `table` or `joint`)
 hipError_t launch_step(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, hipStream_t stream, const EpisodeLimit *limit = nullptr);
 hipError_t launch_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, hipStream_t stream,
                           const TablePolicy *table = nullptr, const EpisodeLimit *limit = nullptr, const EpisodeBudget *budget = nullptr,
-                          const ConflictPairs *pairs = nullptr, const JointPolicy *joint = nullptr, const EpisodeLog *log = nullptr);
+                          const ConflictPairs *pairs = nullptr, const JointPolicy *joint = nullptr, const EpisodeLog *log = nullptr,
+                          const GroupPolicy *group = nullptr);
 // is the step launch_step would launch a thread-per-env one (one thread per env), else lg_group_size(A) threads per env?
 bool step_is_thread_per_env(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, const EpisodeLimit *limit);
 
@@ -360,6 +380,14 @@ MAPF_LG_JOINT_LAUNCHERS(X)
                                             const JointPolicy *joint, const EpisodeLimit *limit, const EpisodeBudget *budget, const EpisodeLog *log,       \
                                             const ConflictPairs *pairs);
 MAPF_LG_LOG_LAUNCHERS(X)
+#undef X
+// ... and the instances that follow a group policy: ../csrc_group/mapf_lg_group.hip, compiled once per form (plain, limit, budget, each
+// without and with the conflict matrix; the budget form with the episode log, likewise).  ONE signature again
+#define MAPF_LG_GROUP_LAUNCHERS(X) X(plain) X(limit) X(budget) X(pairs_plain) X(pairs_limit) X(pairs_budget) X(log_budget) X(log_pairs_budget)
+#define X(form)                                                                                                                              \
+    hipError_t launch_rollout_lg_group_##form(const LgRolloutPlan &plan, int n_agents, const RolloutArgs &args, hipStream_t stream, const GroupPolicy &group, \
+                                              const EpisodeLimit *limit, const EpisodeBudget *budget, const EpisodeLog *log, const ConflictPairs *pairs);
+MAPF_LG_GROUP_LAUNCHERS(X)
 #undef X
 hipError_t launch_reset_log_partials(EpisodeLogPartial *partial, const uint8_t *mask, uint64_t n_envs, hipStream_t stream);
 hipError_t launch_step_lg(const LgStepPlan &plan, int n_agents, const StepArgs &args, hipStream_t stream);

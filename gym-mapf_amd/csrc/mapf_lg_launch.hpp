@@ -7,6 +7,7 @@
 //              pairs/mapf_lg_pairs.hip: the instances of the three that count conflicting pairs, guarded only;
 //              ../csrc_joint/mapf_lg_joint.hip: the instances that follow a joint table policy, guarded only and never streamed -- it
 //              launches through the TABLE arm (no streamed actions) and its plan is marked `joint`, which the name reads;
+//              ../csrc_group/mapf_lg_group.hip: the instances that follow a group policy, likewise (plan marked `group`);
 //   step    -- Family::kernel<L, FULL, EXT_UNIFORMS>() likewise, of lg_step_kernel (mapf_lg_step_kernel.hpp).  mapf_lg_kernels.hip:
 //              the plain instances; mapf_lg_limit.hip: the limit instances.
 // `extra` are the kernel's arguments behind (args, A): nothing, the table policy, the episode limit, or both in that order; the
@@ -26,8 +27,9 @@ hipError_t launch_lg_rollout_instance(const LgRolloutPlan &plan, const RolloutAr
                                   : Family::template kernel<L, FULL, false, RECORD, STREAM, TABLE>(plan.dense);
     if (plan.lds_bytes > 32 * 1024) {
         // (the most a CU has beside the instance's static LDS: kLdsReserve, and kPairsLdsBytes more in the instances that count pairs,
-        // kLogLdsBytes more in those that keep an episode log)
-        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(kLdsBytes - kLdsReserve - (plan.pairs ? kPairsLdsBytes : 0) - (plan.log ? kLogLdsBytes : 0)))) return e;
+        // kLogLdsBytes more in those that keep an episode log, kGroupLdsBytes more in those that follow a group policy)
+        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), int(kLdsBytes - kLdsReserve - (plan.pairs ? kPairsLdsBytes : 0) - (plan.log ? kLogLdsBytes : 0) -
+                                                                                         (plan.group ? kGroupLdsBytes : 0)))) return e;
     }
     char name[kKernelNameBytes];
     lg_rollout_kernel_name(name, plan, RECORD, STREAM, TABLE);

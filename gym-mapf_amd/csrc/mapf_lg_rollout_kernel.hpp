@@ -9,6 +9,12 @@
 //     segment base, a row stride (V, or 0 when solo) and a selector -- the lane that holds the partner and which half of its cell
 //     word -- wait in registers; the step reads the partner lane's cells with one ds_bpermute per agent (a solo agent is its own
 //     partner, so one formula serves both), then gathers the byte from global memory.  STREAM is false.
+//   GroupPolicy   -- the group policy (MAPF_POLICY_GROUP), in TablePolicy's / JointPolicy's place and never beside either: every agent has
+//     a solo row; an agent of a group of 2..4 takes its byte of the entry of the group's current joint cell where the group's book has
+//     one, else its row's byte.  Per agent a row base, the book's number (none: solo, a ghost slot, a lane past the last env) and ONE
+//     register of four 7-bit selectors (the lane that holds each member and the half of its cell word), the agent's position in the
+//     list and the group's size wait in registers; the step reads the members' cell words with ds_bpermute, forms the key and runs the
+//     bounded probe loop of mapf_group_table.hpp over the open-addressing table in global memory.  STREAM is false.
 //   EpisodeLimit  -- the episode step limit (include/mapf_hip.h mapf_set_episode_limit): the env's age is carried in a register
 //     beside `terminal`, truncations are counted like episodes, the truncated byte is stored with the delayed flag bytes, and the
 //     env goes back to its start cells on done OR truncated.  These instances have no DENSE form: always the guarded one.
@@ -81,18 +87,30 @@ __device__ __forceinline__ void lg_count_pairs(const LaneCtx<L> &x, const uint32
     }
 }
 
+// a pointer every lane holds the same value of, moved into scalar registers (two v_readfirstlane)
+template <class T>
+__device__ __forceinline__ T *uniform_pointer(T *ptr) {
+    const uint64_t bits = reinterpret_cast<uint64_t>(ptr);
+    // (the builtin returns a signed int: each half goes through uint32_t, else a low word with bit 31 set sign-extends over the high one)
+    const uint32_t hi = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(bits >> 32)))), lo = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(bits))));
+    return reinterpret_cast<T *>((uint64_t(hi) << 32) | uint64_t(lo));
+}
+
 template <int L, bool FULL, bool MV_LDS, bool RECORD, bool STREAM, bool DENSE, class... Extra>
 __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(const RolloutArgs p, const uint32_t n_agents, const Extra... extra) {
     constexpr bool TABLE = has_kernel_arg<TablePolicy, Extra...>, LIMIT = has_kernel_arg<EpisodeLimit, Extra...>,
                    BUDGET = has_kernel_arg<EpisodeBudget, Extra...>, PAIRS = has_kernel_arg<ConflictPairs, Extra...>,
-                   JOINT = has_kernel_arg<JointPolicy, Extra...>, LOG = has_kernel_arg<EpisodeLog, Extra...>;
+                   JOINT = has_kernel_arg<JointPolicy, Extra...>, LOG = has_kernel_arg<EpisodeLog, Extra...>,
+                   GROUP = has_kernel_arg<GroupPolicy, Extra...>;
     static_assert(BUDGET || !LOG, "a log instance is a budget instance");
     static_assert(!(TABLE && STREAM), "a table instance runs the launches without streamed actions");
     static_assert(!(JOINT && (TABLE || STREAM || DENSE)), "a joint instance: no table policy beside it, no streamed actions, guarded");
+    static_assert(!(GROUP && (TABLE || JOINT || STREAM || DENSE)), "a group instance: no other table policy beside it, no streamed actions, guarded");
     static_assert(!(LIMIT && DENSE) && (LIMIT || !BUDGET), "the limit instances are guarded; a budget instance takes the limit block too");
     static_assert(!(PAIRS && DENSE), "the instances that count conflicting pairs are guarded");
     const auto tp = kernel_arg<TablePolicy>(extra...);       // by value: an empty tag where the instance has no such argument
     const auto jp = kernel_arg<JointPolicy>(extra...);
+    const auto gp = kernel_arg<GroupPolicy>(extra...);
     const auto lim = kernel_arg<EpisodeLimit>(extra...);
     const auto bud = kernel_arg<EpisodeBudget>(extra...);
     __shared__ SlipRow slip[8];
@@ -118,6 +136,26 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
         static_assert(sizeof(LogLds) <= kLogLdsBytes, "the room plan_rollout_lg leaves");
         if (threadIdx.x == 0u) lg_lds = LogLds{kernel_arg<EpisodeLog>(extra...), lim.age, lim.out_truncations, bud.left, bud.out_live_steps};   // (the staging below ends with __syncthreads())
         lg = &lg_lds;
+    }
+    // the group policy's scalars wait there as well (kGroupLdsBytes, planned likewise): the step reads the two table addresses, the
+    // mask and the probe bound back instead of holding six scalar registers across the step loop.  A group instance carries its
+    // selectors, books and rows in five registers per lane and needs more in the probe; it gets them back from the addresses of the
+    // totals, the ages and the episodes left, which wait here too and are formed again at the launch's end
+    struct GroupLds {
+        const uint8_t *table; const GroupSlot *slots; uint32_t mask, max_probe;
+        double *out_returns; uint32_t *out_episodes, *out_collisions, *age, *out_truncations, *left, *out_live_steps;
+    };
+    const GroupLds *gl = nullptr;
+    if constexpr (GROUP) {
+        __shared__ GroupLds gl_lds;
+        static_assert(sizeof(GroupLds) <= kGroupLdsBytes, "the room route_rollout leaves");
+        if (threadIdx.x == 0u) {   // (the staging below ends with __syncthreads())
+            GroupLds v{gp.table, gp.slots, gp.mask, gp.max_probe, p.out_returns, p.out_episodes, p.out_collisions, nullptr, nullptr, nullptr, nullptr};
+            if constexpr (LIMIT) { v.age = lim.age; v.out_truncations = lim.out_truncations; }
+            if constexpr (BUDGET) { v.left = bud.left; v.out_live_steps = bud.out_live_steps; }
+            gl_lds = v;
+        }
+        gl = &gl_lds;
     }
     extern __shared__ __attribute__((aligned(16))) MoveEntry lds_mv[];
     bool live_rt;
@@ -164,6 +202,8 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
     using gu32 = __attribute__((address_space(1))) uint32_t *;
     using gu8 = __attribute__((address_space(1))) uint8_t *;
     using gu16 = __attribute__((address_space(1))) uint16_t *;
+    // (a GROUP instance uses these addresses, and those of the ages and the episodes left below, for the initial loads only: it
+    // forms them again from its LDS block at the launch's end, so the values pinned here die before the step loop)
     gf64 ret_p = (gf64)(p.out_returns ? at(p.out_returns, e) : nullptr);
     gu32 epi_p = (gu32)(p.out_episodes ? at(p.out_episodes, e) : nullptr);
     gu32 col_p = (gu32)(p.out_collisions ? at(p.out_collisions, e) : nullptr);
@@ -315,6 +355,42 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
         asm volatile("" : "+v"(jbase0), "+v"(jbase1), "+v"(jstride0), "+v"(jstride1), "+v"(jsel0), "+v"(jsel1));
     }
 
+    // group policy: per agent the row's base, the group's book (kGroupEmptyBook: none -- a solo agent, a ghost slot, a lane past the
+    // last env) and one register of selectors: bits 7k .. 7k+6 name the lane that holds member k's cell (6 bits) and the half of that
+    // lane's cell word (bit 6), bits 28-29 the agent's own position in the list, bits 30-31 the group's size - 1.  Positions past the
+    // group's size select the agent's own lane; their cell in the key is 0xFFFF.  (A list the host has refused -- a member not below A,
+    // a list without the agent -- leaves the agent on its row.)  Integers in VGPRs, as the joint policy's
+    uint32_t grows = 0u, gbook0 = kGroupEmptyBook, gbook1 = kGroupEmptyBook, gsel0 = 0u, gsel1 = 0u;
+    if constexpr (GROUP) {
+        uint32_t grow0, grow1;   // (both rows in one register: row0 | row1 << 16; ghost slots: row 0, whose bytes are never used)
+        load_pair<uint16_t>(gp.rows, gp.broadcast ? 0 : e, n_agents, x.g, x.v0, x.v1, grow0, grow1);
+        grows = grow0 | (grow1 << 16);
+        auto prepare = [&](const bool valid, const uint32_t me, uint32_t &book, uint32_t &sel) __attribute__((always_inline)) {
+            const uint32_t self = (x.base + (me >> 1)) | ((me & 1u) << 6);
+            sel = self * 0x204081u;   // self at bits 0, 7, 14 and 21
+            if (!valid) return;
+            const uint32_t idx = (gp.broadcast ? 0u : e) * n_agents + me;
+            const uint2 w = *reinterpret_cast<const uint2 *>(at(gp.members, idx * 4u));   // (four u16: 8 bytes, 8-byte aligned)
+            const uint32_t member[4] = {w.x & 0xFFFFu, w.x >> 16, w.y & 0xFFFFu, w.y >> 16};
+            uint32_t size = 0u, pos = 4u;
+            bool open = true;
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; ++k) {
+                open = open && member[k] < n_agents;
+                if (open) {
+                    ++size;
+                    sel = (sel & ~(0x7Fu << (7u * k))) | (((x.base + (member[k] >> 1)) | ((member[k] & 1u) << 6)) << (7u * k));
+                    if (member[k] == me) pos = k;
+                }
+            }
+            if (size >= 2u && pos < 4u) book = *at(gp.book, idx);
+            sel |= ((pos & 3u) << 28) | ((max(size, 1u) - 1u) << 30);
+        };
+        prepare(x.v0, 2u * x.g, gbook0, gsel0);
+        prepare(x.v1, 2u * x.g + 1u, gbook1, gsel1);
+        asm volatile("" : "+v"(grows), "+v"(gbook0), "+v"(gbook1), "+v"(gsel0), "+v"(gsel1));
+    }
+
     const uint64_t t_first = first_step_index(p);
     for (uint32_t s = 0; s < p.n_steps; ++s) {
         const uint64_t t = t_first + s;
@@ -346,6 +422,41 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
             }
             act0 = jp.table[jbase0 + cur0 * jstride0 + ((o0 >> (jsel0 >> 6)) & 0xFFFFu)];
             act1 = jp.table[jbase1 + cur1 * jstride1 + ((o1 >> (jsel1 >> 6)) & 0xFFFFu)];
+        } else if constexpr (GROUP) {   // group policy: the byte of the entry of (my group's book, its members' cells), else of (my row, my cell)
+            // the row bytes first: their latency overlaps the probe.  Every lane is active here, as the cross-lane reads need it; the
+            // probe loop behind them is plain divergent code without a cross-lane operation: only the agents with a book enter it
+            using gslot = const __attribute__((address_space(1))) u32x4 *;   // (one probe: one global_load_dwordx4)
+            using gbyte = const __attribute__((address_space(1))) uint8_t *;
+            const uint32_t pk = cur0 | (cur1 << 16);
+            // (the block is the same for every lane: the addresses and the two integers go through scalar registers for the section only)
+            const GroupLds g = *gl;
+            const gbyte g_table = (gbyte)uniform_pointer(g.table);
+            const gslot g_slots = (gslot)uniform_pointer(g.slots);
+            const uint32_t g_mask = __builtin_amdgcn_readfirstlane(g.mask), g_max_probe = __builtin_amdgcn_readfirstlane(g.max_probe);
+            const uint32_t row_act0 = g_table[(grows & 0xFFFFu) * p.c.n_cells + cur0], row_act1 = g_table[(grows >> 16) * p.c.n_cells + cur1];
+            auto group_action = [&](uint32_t sel, const uint32_t book, const uint32_t row_act) __attribute__((always_inline)) {
+                // (opaque here, so that the four lane addresses and shifts are extracted in the step and not hoisted out of the loop
+                // into eight registers per agent)
+                asm volatile("" : "+v"(sel));
+                uint32_t cell[4];
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; ++k) {
+                    uint32_t w = pk;   // (a group of one lane holds both cells itself)
+                    if constexpr (L > 1) w = uint32_t(__shfl(int(pk), int((sel >> (7u * k)) & 63u), 64));
+                    cell[k] = (w >> (((sel >> (7u * k + 6u)) & 1u) * 16u)) & 0xFFFFu;
+                    if (k > (sel >> 30)) cell[k] = kGroupPad;
+                }
+                uint32_t act = row_act;
+                if (book != kGroupEmptyBook) {
+                    const uint32_t found = group_lookup([&](uint32_t i) { const u32x4 s = g_slots[i]; return GroupSlot{s.x, s.y, s.z, s.w}; },
+                                                        g_mask, g_max_probe, cell[0] | (cell[1] << 16), cell[2] | (cell[3] << 16), book);
+                    // (an entry's bytes are 0..4: the host has checked them; min: a wrong table still indexes the move table in bounds)
+                    if (found != kGroupMiss) act = min((found >> (((sel >> 28) & 3u) * 8u)) & 0xFFu, 4u);
+                }
+                return act;
+            };
+            act0 = group_action(gsel0, gbook0, row_act0);
+            act1 = group_action(gsel1, gbook1, row_act1);
         } else if (p.policy_cells) {   // greedy policy (ghost slots read cell 0: their actions are never used)
             act0 = greedy_action(p.policy_cells, p.c.n_cells, cur0, goal_rc0);
             act1 = greedy_action(p.policy_cells, p.c.n_cells, cur1, goal_rc1);
@@ -446,6 +557,19 @@ __global__ void __launch_bounds__(rollout_max_block<L>()) lg_rollout_kernel(cons
     if (!live) return;
     store_cells<FULL>(p.state, e, n_agents, x.g, x.v0, x.v1, cur0, cur1);
     if (leader) {
+        if constexpr (GROUP) {   // (the addresses the step loop did not carry)
+            ret_p = (gf64)(gl->out_returns ? at(gl->out_returns, e) : nullptr);
+            epi_p = (gu32)(gl->out_episodes ? at(gl->out_episodes, e) : nullptr);
+            col_p = (gu32)(gl->out_collisions ? at(gl->out_collisions, e) : nullptr);
+            if constexpr (LIMIT && !LOG) {
+                age_p = (gu32)at(gl->age, e);
+                trn_p = (gu32)(gl->out_truncations ? at(gl->out_truncations, e) : nullptr);
+            }
+            if constexpr (BUDGET && !LOG) {
+                left_p = (gu32)at(gl->left, e);
+                liv_p = (gu32)(gl->out_live_steps ? at(gl->out_live_steps, e) : nullptr);
+            }
+        }
         if constexpr (LOG) {   // (the addresses the step loop did not carry)
             age_p = (gu32)at(lg->age, e);
             trn_p = (gu32)(lg->out_truncations ? at(lg->out_truncations, e) : nullptr);

@@ -364,6 +364,12 @@ void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, 
     const char *form = plan.budget ? (log ? "BUDGET,LOG" : "BUDGET") : (plan.limit ? "LIMIT" : (plan.dense ? "DENSE" : "GUARDED"));
     const char *note = plan.budget ? (log ? "; episode budget; episode log" : "; episode budget") : (plan.limit ? "; episode step limit" : "");
     const bool joint = plan.joint && table_policy;   // (the joint launcher passes table_policy: a launch without streamed actions)
+    if (plan.group && table_policy) {                // (the group launcher likewise)
+        snprintf(name, kKernelNameBytes, "lg_rollout_kernel_group%s%s<L=%d,%s,%s,%s,GROUP,%s%s> block=%u (pair layout: 2 agents per lane%s%s; group policy: books probed in global memory)",
+                 family, plan.pairs ? "_pairs" : "", plan.L, plan.full ? "FULL" : "RAGGED", plan.mv_lds ? "MV_LDS" : "MV_GLOBAL", record ? "RECORD" : "TOTALS", form,
+                 plan.pairs ? ",PAIRS" : "", plan.block, note, plan.pairs ? "; conflict matrix" : "");
+        return;
+    }
     snprintf(name, kKernelNameBytes, "lg_rollout_kernel%s%s%s<L=%d,%s,%s,%s,%s,%s%s> block=%u (pair layout: 2 agents per lane%s%s%s)", joint ? "_joint" : (table_policy ? "_table" : ""),
              family, plan.pairs ? "_pairs" : "", plan.L, plan.full ? "FULL" : "RAGGED", plan.mv_lds ? "MV_LDS" : "MV_GLOBAL", record ? "RECORD" : "TOTALS",
              joint ? "JOINT" : (table_policy ? "TABLE" : (streamed ? "STREAM" : "POLICY")), form, plan.pairs ? ",PAIRS" : "", plan.block, note, plan.pairs ? "; conflict matrix" : "",
@@ -491,20 +497,23 @@ static bool prefers_tpe(FamilyPreference prefer, int n_agents) {
 }
 
 RolloutRoute route_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool table_policy, size_t table_bytes,
-                           bool limited, bool budgeted, bool pairs, bool joint, bool logged) {
+                           bool limited, bool budgeted, bool pairs, bool joint, bool logged, bool group) {
     RolloutRoute r;
     logged = logged && budgeted;   // (a log launch is a budget launch: one of the three branches below, whose plan takes the mark)
     RolloutTuning with_log = tune;   // (kLogLdsBytes of static LDS more than the others, as the matrix has: the largest tables stay in global memory)
     if (logged) with_log.mv_lds_max_bytes = std::min(tune.mv_lds_max_bytes, kLdsBytes - kPairsLdsBytes - kLogLdsBytes);
-    if (joint) {   // the joint instances exist in the lane-group family only, guarded, one form per (limit, budget, pairs)
+    if (joint || group) {   // the joint and the group instances exist in the lane-group family only, guarded, one form per (limit, budget, pairs)
         RolloutTuning t = logged ? with_log : tune;   // (with the matrix: its block's static LDS, as below)
         if (pairs) t.mv_lds_max_bytes = std::min(t.mv_lds_max_bytes, kLdsBytes - kPairsLdsBytes);
+        // (a group instance: kGroupLdsBytes more again, beside the matrix's and the log's)
+        if (group && !joint) t.mv_lds_max_bytes = std::min(t.mv_lds_max_bytes, kLdsBytes - kPairsLdsBytes - kLogLdsBytes - kGroupLdsBytes);
         r.lg = plan_rollout_lg(n_agents, args, t, limited || budgeted);
         r.lg.budget = budgeted;
         r.lg.pairs = pairs;
         r.lg.log = logged;
         r.lg.dense = false;
-        r.lg.joint = true;
+        r.lg.joint = joint;
+        r.lg.group = group && !joint;   // (one policy per launch: the dispatcher refuses both)
         return r;
     }
     if (pairs) {   // the instances that count exist in the lane-group family only, guarded, one form per (limit, budget)

@@ -69,6 +69,9 @@ constexpr unsigned kLgRolloutMaxBlock = 1024u, kLgRolloutMaxBlock16 = 512u;
 constexpr size_t kPairsLdsBytes = 32;
 // ... and the instances that keep an episode log (their EpisodeLog block and four addresses of the limit and the budget), likewise
 constexpr size_t kLogLdsBytes = 64;
+// ... and the instances that follow a group policy (the policy's two table addresses, mask and probe bound, and seven addresses of the
+// totals, the limit and the budget), likewise
+constexpr size_t kGroupLdsBytes = 96;
 // The instance lg_rollout_kernel<L, full, mv_lds, ., ., dense> (or lg_rollout_kernel_table<L, full, mv_lds, ., dense>) and its geometry;
 // under `limit` the instance of the same fields among the limit kernels (mapf_lg_limit.hip), which are never dense
 struct LgRolloutPlan {
@@ -83,6 +86,7 @@ struct LgRolloutPlan {
     unsigned block = 0, grid = 0;
     size_t lds_bytes = 0;            // dynamic LDS segment: the move table, or 0 (the launcher raises the limit beyond 32 KB)
     bool log = false;                // ... and, of a budget plan, the instances that keep an episode log (csrc_log/mapf_lg_log.hip): never dense
+    bool group = false;              // ... and, of any of the eight, the instances that follow a group policy (csrc_group/mapf_lg_group.hip): never dense
 };
 // (limited: the launch runs under an episode step limit (EpisodeLimit, mapf_kernels.hpp).  Apart from the packed table instances
 // behind MAPF_TUNE limit_packed=1 (LqPlan::limit) the limit instances exist in the lane-group family only, so no other packed plan
@@ -96,6 +100,7 @@ LgStepPlan plan_step_lg(int n_agents, const StepArgs &args, bool limited = false
 // A pairs plan's name says _pairs behind the kernel's name and PAIRS behind the form (GUARDED, LIMIT or BUDGET).
 // A log plan's name says _log behind _budget_guarded and LOG behind BUDGET.
 // A joint plan's name (its launcher passes table_policy) says _joint and JOINT where a table launch says _table and TABLE, and ends with the joint policy's note.
+// A group plan's name likewise says _group and GROUP, and ends with the group policy's note.
 void lg_rollout_kernel_name(char *name, const LgRolloutPlan &plan, bool record, bool streamed, bool table_policy);
 void lg_step_kernel_name(char *name, const LgStepPlan &plan, bool ext_uniforms);
 
@@ -132,6 +137,8 @@ void transitions_kernel_name(char *name, const TransitionsPlan &plan, uint32_t n
 // route_rollout / route_step, in this order:
 //   a joint table policy takes the lane-group plan of its form (plain, limit or budget; with the conflict matrix or without), marked
 //     `joint` and never dense, before anything else: whatever the handle prefers, limit_packed and the tuning say;
+//   a group policy likewise takes the lane-group plan of its form (with the episode log where the handle keeps one), marked `group`
+//     and never dense, before anything else;
 //   a conflict matrix takes the lane-group plan of its form (plain, limit or budget), marked `pairs` and never dense, before
 //     anything else: whatever the handle prefers and whatever limit_packed says;
 //   a budget takes the lane-group budget plan (a limit plan marked `budget`) before anything else;
@@ -148,9 +155,10 @@ struct RolloutRoute { KernelFamily family = KernelFamily::LaneGroup; TpePlan tpe
 struct StepRoute { KernelFamily family = KernelFamily::LaneGroup; TpePlan tpe; StepPlan lq; LgStepPlan lg; };
 // (table_policy: the launch follows the table policy, of table_bytes action bytes; limited / budgeted: it runs under an episode
 // step limit / an episode budget; pairs: the handle counts conflicting pairs; joint: the launch follows the joint table policy;
-// logged: the handle keeps an episode log (beside a budget only).  args is never dereferenced)
+// logged: the handle keeps an episode log (beside a budget only); group: the launch follows the group policy.  args is never dereferenced)
 RolloutRoute route_rollout(int n_agents, const RolloutArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool table_policy, size_t table_bytes,
-                           bool limited, bool budgeted, bool pairs = false, bool joint = false, bool logged = false);
+                           bool limited, bool budgeted, bool pairs = false, bool joint = false, bool logged = false,
+                           bool group = false);
 // (ext_uniforms: the caller supplies the uniforms)
 StepRoute route_step(int n_agents, const StepArgs &args, const RolloutTuning &tune, FamilyPreference prefer, bool limited, bool ext_uniforms);
 

@@ -1,6 +1,7 @@
 // Host construction of the tables the kernels read (mapf_tables.hpp): host-only, no kernel and no runtime call.
 #include "mapf_tables.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -199,6 +200,102 @@ bool build_greedy_cells(const uint16_t *nbr, uint32_t V, const uint32_t *cell_rc
         cells[v] = make_uint2(cell_rc[v], best);
     }
     return true;
+}
+
+// ------------------------------------------------------------------- the group policy
+bool validate_group_plan(const GroupPlanArrays &g, std::string *err) {
+    const auto say = [&](const std::string &what) { *err = "set_policy_group: " + what; return false; };
+    const auto num = [](uint64_t v) { return std::to_string(v); };
+    const uint64_t A = g.A, V = g.V;
+    // the table policy's own checks
+    if (g.n_rows == 0 || g.n_rows > 65536u) return say("n_rows must be 1..65536");
+    const uint64_t bytes = uint64_t(g.n_rows) * V;
+    if (bytes > 0x7FFFFFFFull) return say("table (n_rows * V bytes) exceeds 2 GiB");
+    for (uint64_t i = 0; i < bytes; ++i)
+        if (g.table[i] > 4u) return say("table[" + num(i) + "] = " + num(g.table[i]) + " is not an action (0..4)");
+    const uint64_t n_index = g.broadcast ? A : g.E * A;
+    for (uint64_t i = 0; i < n_index; ++i)
+        if (g.row_index[i] >= g.n_rows) return say("row_index[" + num(i) + "] = " + num(g.row_index[i]) + " is not below n_rows");
+    // the books' ranges
+    if (g.n_entries > kGroupMaxEntries) return say("n_entries = " + num(g.n_entries) + " exceeds 2^24");
+    if (g.book_begin) {
+        if (g.book_begin[0] != 0u) return say("book_begin[0] = " + num(g.book_begin[0]) + " is not 0");
+        for (uint32_t b = 0; b < g.n_books; ++b)
+            if (g.book_begin[b + 1] < g.book_begin[b]) return say("book_begin[" + num(b + 1) + "] = " + num(g.book_begin[b + 1]) + " is below book_begin[" + num(b) + "]");
+        if (g.book_begin[g.n_books] != g.n_entries) return say("book_begin[" + num(g.n_books) + "] = " + num(g.book_begin[g.n_books]) + " is not n_entries");
+    }
+    // the groups
+    for (uint64_t i = 0; i < n_index; ++i) {
+        const uint64_t row = i - i % A, me = i % A;
+        const uint16_t *list = g.members + i * 4u;
+        uint32_t size = 0;
+        bool has_me = false;
+        for (uint32_t k = 0; k < 4u; ++k) {
+            const uint64_t at = i * 4u + k;
+            if (list[k] == kGroupPad) continue;
+            if (list[k] >= A) return say("members[" + num(at) + "] = " + num(list[k]) + " is not below n_agents");
+            if (size != k) return say("members[" + num(at) + "] = " + num(list[k]) + " follows padding: padding must be trailing");
+            if (k > 0 && list[k] <= list[k - 1]) return say("members[" + num(at) + "] = " + num(list[k]) + " is not above members[" + num(at - 1) + "]: the list must be ascending");
+            has_me = has_me || list[k] == me;
+            ++size;
+        }
+        if (!has_me) return say("members[" + num(i * 4u) + "..]: the list of agent " + num(me) + " does not contain it");
+        // (without books every group falls back to its rows, and `book` is not read)
+        const bool booked = size >= 2u && g.n_books != 0u;
+        if (booked && g.book[i] >= g.n_books) return say("book[" + num(i) + "] = " + num(g.book[i]) + " is not below n_books");
+        for (uint32_t k = 0; k < size; ++k) {
+            const uint64_t other = row + list[k];
+            if (memcmp(g.members + other * 4u, list, 4 * sizeof(uint16_t)) != 0)
+                return say("members[" + num(other * 4u) + "..]: agent " + num(list[k]) + " is a member of agent " + num(me) + "'s group (members[" + num(i * 4u) + "..]) but its list differs");
+            if (booked && g.book[other] != g.book[i])
+                return say("book[" + num(other) + "] = " + num(g.book[other]) + " differs from book[" + num(i) + "] = " + num(g.book[i]) + " of the same group");
+        }
+    }
+    // the entries
+    for (uint64_t n = 0; n < g.n_entries; ++n) {
+        const GroupEntry &entry = g.entries[n];
+        uint32_t size = 0;
+        for (uint32_t k = 0; k < 4u; ++k) {
+            const std::string at = "entries[" + num(n) + "]";
+            if (entry.action[k] > 4u) return say(at + ".action[" + num(k) + "] = " + num(entry.action[k]) + " is not an action (0..4)");
+            if (entry.cell[k] == kGroupPad) {
+                if (entry.action[k] != 0u) return say(at + ".action[" + num(k) + "] = " + num(entry.action[k]) + " at a padded position must be 0");
+                continue;
+            }
+            if (entry.cell[k] >= V) return say(at + ".cell[" + num(k) + "] = " + num(entry.cell[k]) + " is not a cell (below V) and not padding");
+            if (size != k) return say(at + ".cell[" + num(k) + "] = " + num(entry.cell[k]) + " follows padding: padding must be trailing");
+            ++size;
+        }
+    }
+    return true;
+}
+
+bool build_group_table(const GroupEntry *entries, uint64_t n_entries, const uint32_t *book_begin, uint32_t n_books, GroupTable *out, std::string *err) {
+    uint64_t capacity = 1;
+    while (capacity < 2u * n_entries) capacity <<= 1;
+    out->slots.assign(size_t(capacity), GroupSlot{0u, 0u, kGroupEmptyBook, 0u});
+    out->max_probe = 0;
+    const uint32_t mask = uint32_t(capacity - 1u);
+    for (uint32_t b = 0; b < n_books; ++b)
+        for (uint64_t n = book_begin[b]; n < book_begin[b + 1]; ++n) {
+            const GroupEntry &entry = entries[n];
+            const GroupSlot s{uint32_t(entry.cell[0]) | uint32_t(entry.cell[1]) << 16, uint32_t(entry.cell[2]) | uint32_t(entry.cell[3]) << 16, b,
+                              uint32_t(entry.action[0]) | uint32_t(entry.action[1]) << 8 | uint32_t(entry.action[2]) << 16 | uint32_t(entry.action[3]) << 24};
+            uint32_t i = group_hash(s.c01, s.c23, s.book) & mask, chain = 1;
+            for (; out->slots[i].book != kGroupEmptyBook; i = (i + 1u) & mask, ++chain)   // (at most half the slots are taken: an empty one comes)
+                if (out->slots[i].c01 == s.c01 && out->slots[i].c23 == s.c23 && out->slots[i].book == b) {
+                    *err = "set_policy_group: entries[" + std::to_string(n) + "] has the same four cells as an earlier entry of book " + std::to_string(b);
+                    return false;
+                }
+            out->slots[i] = s;
+            out->max_probe = std::max(out->max_probe, chain);
+        }
+    return true;
+}
+
+uint32_t lookup_group_table(const GroupTable &table, const uint16_t cell[4], uint32_t book, uint32_t *probes) {
+    return group_lookup([&](uint32_t i) { return table.slots[i]; }, uint32_t(table.slots.size() - 1u), table.max_probe, uint32_t(cell[0]) | uint32_t(cell[1]) << 16,
+                        uint32_t(cell[2]) | uint32_t(cell[3]) << 16, book, probes);
 }
 
 }  // namespace mapf

@@ -37,4 +37,36 @@ ScenTable build_scen_table(const uint16_t *start, bool start_broadcast, const ui
 // not match the neighbour table.
 bool build_greedy_cells(const uint16_t *nbr, uint32_t V, const uint32_t *cell_rc, std::vector<uint2> *cells, std::string *err);
 
+// Group policy (include/mapf_hip.h MAPF_POLICY_GROUP): what mapf_set_policy_group is handed, as host arrays -- the header names them.
+// An entry is the header's mapf_group_entry: four u16 cells, then four action bytes.
+struct GroupEntry { uint16_t cell[4]; uint8_t action[4]; };
+static_assert(sizeof(GroupEntry) == 12, "mapf_group_entry");
+struct GroupPlanArrays {
+    uint32_t V = 0, A = 0;
+    uint64_t E = 0;
+    const uint8_t *table = nullptr;        // [n_rows * V]
+    uint32_t n_rows = 0;
+    const uint16_t *row_index = nullptr;   // [E*A], or [A] when broadcast
+    const uint16_t *members = nullptr;     // [E*A*4] / [A*4]
+    const uint32_t *book = nullptr;        // [E*A] / [A]
+    const GroupEntry *entries = nullptr;   // [n_entries]
+    uint64_t n_entries = 0;
+    const uint32_t *book_begin = nullptr;  // [n_books + 1]
+    uint32_t n_books = 0;
+    bool broadcast = false;
+};
+// Every rule of the header about these arrays (the pointers are non-null where the header demands it: the caller has looked), in the
+// header's order; false (*err names the offending index) at the first one broken.
+bool validate_group_plan(const GroupPlanArrays &plan, std::string *err);
+// The device table of all books (mapf_group_table.hpp): capacity a power of two >= 2 * n_entries, linear probing; max_probe is the
+// longest chain produced -- the slots a lookup reads, at most, before it meets an entry that is there.  false (*err names the second
+// entry) when two entries of one book have the same four cells.
+struct GroupTable {
+    std::vector<GroupSlot> slots;
+    uint32_t max_probe = 0;
+};
+bool build_group_table(const GroupEntry *entries, uint64_t n_entries, const uint32_t *book_begin, uint32_t n_books, GroupTable *out, std::string *err);
+// The host lookup through the shared probe function: the entry's four action bytes as one word, or kGroupMiss; *probes: slots read
+uint32_t lookup_group_table(const GroupTable &table, const uint16_t cell[4], uint32_t book, uint32_t *probes);
+
 }  // namespace mapf

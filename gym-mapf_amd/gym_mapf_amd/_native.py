@@ -16,7 +16,7 @@ MAPF_MAKESPAN, MAPF_SOC = 0, 1
 MAPF_FLAG_DEVICE_PTRS, MAPF_FLAG_START_BROADCAST, MAPF_FLAG_GOAL_BROADCAST = 0x1, 0x2, 0x4
 MAPF_FLAG_THREAD_PER_ENV, MAPF_FLAG_LANE_GROUP = 0x10, 0x20
 MAPF_TPE_MAX_AGENTS = 16
-MAPF_POLICY_RANDOM, MAPF_POLICY_GREEDY, MAPF_POLICY_TABLE, MAPF_POLICY_JOINT = 0, 1, 2, 3
+MAPF_POLICY_RANDOM, MAPF_POLICY_GREEDY, MAPF_POLICY_TABLE, MAPF_POLICY_JOINT, MAPF_POLICY_GROUP = 0, 1, 2, 3, 4
 MAPF_POLICY_ROWS_BROADCAST = 0x1
 MAPF_STEP_AUTO_RESET = 0x1
 MAPF_KERNEL_STEP, MAPF_KERNEL_ROLLOUT, MAPF_KERNEL_TRANSITIONS = 0, 1, 2
@@ -53,6 +53,16 @@ EPISODE_RECORD_DTYPE = [('ret', '<f8'), ('steps', '<u4'), ('outcome', '<u4')]
 MAPF_EPISODE_DONE, MAPF_EPISODE_COLLISION, MAPF_EPISODE_TRUNCATED = 0x1, 0x2, 0x4
 
 
+class MapfGroupEntry(Structure):
+    """mapf_group_entry: one entry of a book of the group policy (mapf_set_policy_group)"""
+    _fields_ = [('cell', c_uint16 * 4), ('action', c_uint8 * 4)]
+
+
+# the same 12 bytes as a numpy structured dtype
+GROUP_ENTRY_DTYPE = [('cell', '<u2', 4), ('action', 'u1', 4)]
+MAPF_GROUP_PAD, MAPF_GROUP_MISS = 0xFFFF, 0xFFFFFFFF
+
+
 # every symbol include/mapf_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     'mapf_create': (c_int, [POINTER(MapfDesc), POINTER(c_void_p)]),
@@ -75,6 +85,8 @@ SIGNATURES = {
     'mapf_set_policy': (c_int, [c_void_p, c_int, c_void_p]),
     'mapf_set_policy_table': (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
     'mapf_set_policy_joint': (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32]),
+    'mapf_set_policy_group': (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32]),
+    'mapf_policy_group_stats': (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint32)]),
     'mapf_transitions': (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
     'mapf_transitions_window': (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p,
@@ -103,6 +115,8 @@ SIGNATURES = {
     'mapf_abi_version': (c_int, []),
     'mapf_debug_rollout_plan': (c_int, [c_uint32, c_int, c_uint64, c_uint32, c_int, c_int, c_int, c_char_p, POINTER(c_uint64)]),
     'mapf_debug_rollout_plan_limited': (c_int, [c_uint32, c_int, c_uint64, c_uint32, c_int, c_int, c_int, c_char_p, c_uint32, POINTER(c_uint64)]),
+    'mapf_debug_policy_group': (c_int, [c_uint32, c_uint32, c_uint64, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32,
+                                        c_uint32, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64), POINTER(c_uint32)]),
 }
 
 _lib = None

@@ -470,7 +470,8 @@ class VecMapfEnv:
                                                      int(t0), int(n_steps)))
         return out
 
-    def set_policy(self, policy='random', table=None, rows=None, offsets=None, partners=None):
+    def set_policy(self, policy='random', table=None, rows=None, offsets=None, partners=None, members=None, book=None, entry_cells=None,
+                   entry_actions=None, book_begin=None):
         """On-device policy of ``rollout(actions=None)``: ``'random'`` (default; the uniform-random action stream),
         ``'greedy'`` -- every agent takes the first action in ACTIONS order whose intended target is closest
         (Manhattan distance) to its goal, i.e. the first unblocked move one step closer, else STAY -- or ``'table'``:
@@ -485,7 +486,34 @@ class VecMapfEnv:
         or [A] = the agent it is merged with, or itself; HOST arrays, copied.  A solo agent on cell ``c`` takes
         ``table[offsets[e, i] + c]``, an agent merged with ``j`` takes ``table[offsets[e, i] + c_i * V + c_j]``.
         ``envs/policies.py`` builds the three (``pair_shortest_path_rows``, ``pair_rows_from_policy``, ``join_plan``).  Joint
-        launches always run a lane-group kernel (``last_kernel`` says JOINT); ``graph_begin`` is refused in this mode."""
+        launches always run a lane-group kernel (``last_kernel`` says JOINT); ``graph_begin`` is refused in this mode.
+
+        ``'group'``: a plan in which GROUPS of two to four agents were merged and replanned on the joint cells the planner visited
+        (include/mapf_hip.h MAPF_POLICY_GROUP).  ``table`` [R, V] and ``rows`` [E, A] or [A] are the solo rows of ``'table'``;
+        ``members`` [E, A, 4] or [A, 4] lists every agent's group in ascending order, padded with 0xFFFF; ``book`` [E, A] or [A] names
+        the group's book; ``entry_cells`` uint16 [N, 4] and ``entry_actions`` uint8 [N, 4] are the entries of all books (padded
+        positions: 0xFFFF and 0), ``book_begin`` [n_books + 1] where each book begins; HOST arrays, copied.  An agent of a group takes
+        its byte of the entry whose cells equal the members' cells if the group's book has one, else ``table[rows[e, i], c]``.
+        ``envs/policies.py`` builds them (``group_shortest_path_entries``, ``group_entries_from_policy``, ``join_group_plan``).  Group
+        launches always run a lane-group kernel (``last_kernel`` says GROUP); ``graph_begin`` is refused in this mode."""
+        if policy == 'group':
+            if offsets is not None or partners is not None:
+                raise ValueError("offsets= and partners= belong to policy='joint'")
+            V = len(self.grid.tables()[0])
+            args = self._group_arguments(V, self.n_envs, self.n_agents, table, rows, members, book, entry_cells, entry_actions, book_begin)
+            table8, rows16, members16, book32, entries, begin32 = args
+            # (entries and book_begin may be null only without books: books that are all empty still name an array)
+            no_books = begin32.size == 1
+            held = entries if entries.size else np.zeros(1, entries.dtype)
+            nat.check(self._lib.mapf_set_policy_group(self._h, table8.ctypes.data, table8.shape[0], rows16.ctypes.data, members16.ctypes.data, book32.ctypes.data,
+                                                      None if no_books else held.ctypes.data, entries.size,
+                                                      None if no_books else begin32.ctypes.data, begin32.size - 1,
+                                                      nat.MAPF_POLICY_ROWS_BROADCAST if rows16.ndim == 1 else 0))
+            self._rollout_io = None
+            self.policy = policy
+            return
+        if any(a is not None for a in (members, book, entry_cells, entry_actions, book_begin)):
+            raise ValueError("members=, book=, entry_cells=, entry_actions= and book_begin= belong to policy='group'")
         if (policy not in ('table', 'joint') and table is not None) or (policy != 'table' and rows is not None):
             raise ValueError("table= and rows= belong to policy='table'" + (" (policy='joint' takes table=, offsets= and partners=)" if policy == 'joint' else ''))
         if policy != 'joint' and (offsets is not None or partners is not None):
@@ -518,7 +546,7 @@ class VecMapfEnv:
             nat.check(self._lib.mapf_set_policy_joint(self._h, table8.ctypes.data, table8.size, offsets32.ctypes.data, partners16.ctypes.data,
                                                       nat.MAPF_POLICY_ROWS_BROADCAST if offsets32.ndim == 1 else 0))
         else:
-            raise ValueError("policy must be 'random', 'greedy', 'table' or 'joint'")
+            raise ValueError("policy must be 'random', 'greedy', 'table', 'joint' or 'group'")
         self._rollout_io = None            # (a cached argument block must not outlive a policy change)
         self.policy = policy
 
@@ -555,6 +583,107 @@ class VecMapfEnv:
             raise ValueError('offsets%s = %d: the segment of %d bytes ends past the table of %d' % (where(bad[0]), off[tuple(bad[0])],
                                                                                                V if part[tuple(bad[0])] == bad[0][1] else V * V, table.size))
         return (np.ascontiguousarray(table, dtype=np.uint8), np.ascontiguousarray(offsets, dtype=np.uint32), np.ascontiguousarray(partners, dtype=np.uint16))
+
+    def policy_group_stats(self):
+        """(slots, longest probe chain) of the device table of a handle under ``set_policy('group')``"""
+        slots, chain = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        nat.check(self._lib.mapf_policy_group_stats(self._h, ctypes.byref(slots), ctypes.byref(chain)))
+        return slots.value, chain.value
+
+    @staticmethod
+    def _group_arguments(V, n_envs, n_agents, table, rows, members, book, entry_cells, entry_actions, book_begin):
+        """The arrays of ``set_policy('group')`` as the library takes them -- (uint8 [R, V], uint16 rows, uint16 members, uint32 book,
+        entries as ``_native.GROUP_ENTRY_DTYPE`` [N], uint32 book_begin [n_books + 1]) -- after the checks the library repeats
+        (include/mapf_hip.h MAPF_POLICY_GROUP); a ``ValueError`` names the offending entry.  ``entry_cells``, ``entry_actions`` and
+        ``book_begin`` may all be None: no books.  Needs no handle."""
+        if table is None or rows is None or members is None or book is None:
+            raise ValueError("policy='group' needs table= [R, V], rows= and book= [E, A] or [A], members= [E, A, 4] or [A, 4]")
+        if (entry_cells is None) != (entry_actions is None) or (entry_cells is None) != (book_begin is None):
+            raise ValueError("entry_cells=, entry_actions= and book_begin= come together (or none of them: no books)")
+        if V > 65535:
+            raise ValueError("policy='group' needs a map of at most 65535 free cells (cell 0xFFFF is the padding of keys), got %d" % V)
+        ints = VecMapfEnv._host_ints
+        table, rows, members, book = ints(table, 'table'), ints(rows, 'rows'), ints(members, 'members'), ints(book, 'book')
+        if table.ndim != 2 or table.shape[1] != V or not 1 <= table.shape[0] <= 65536:
+            raise ValueError('table must be [R, V] with V = %d free cells and 1 <= R <= 65536, got %r' % (V, tuple(table.shape)))
+        shapes = ((n_envs, n_agents), (n_agents,))
+        if tuple(rows.shape) not in shapes or tuple(book.shape) != tuple(rows.shape) or tuple(members.shape) != tuple(rows.shape) + (4,):
+            raise ValueError('rows and book must both be [E, A] = %r or both [A], and members that shape + [4]; got %r, %r and %r'
+                             % (shapes[0], tuple(rows.shape), tuple(book.shape), tuple(members.shape)))
+        bad = np.argwhere((table < 0) | (table > 4))
+        if bad.size:
+            raise ValueError('table holds action codes 0..4 (STAY, UP, RIGHT, DOWN, LEFT), found table[%d, %d] = %d' % (bad[0][0], bad[0][1], table[tuple(bad[0])]))
+        if rows.min() < 0 or rows.max() >= table.shape[0]:
+            raise ValueError('rows must name table rows 0..%d, found %d' % (table.shape[0] - 1, rows.max() if rows.max() >= table.shape[0] else rows.min()))
+        if entry_cells is None:
+            cells, actions, begin = np.zeros((0, 4), np.int64), np.zeros((0, 4), np.int64), np.zeros(1, np.int64)
+        else:
+            cells, actions, begin = ints(entry_cells, 'entry_cells'), ints(entry_actions, 'entry_actions'), ints(book_begin, 'book_begin')
+            begin = begin.astype(np.int64)
+        if cells.ndim != 2 or cells.shape[1] != 4 or tuple(actions.shape) != tuple(cells.shape) or cells.shape[0] > 1 << 24:
+            raise ValueError('entry_cells and entry_actions must both be [N, 4] with N <= 2**24, got %r and %r' % (tuple(cells.shape), tuple(actions.shape)))
+        if begin.ndim != 1 or begin.size < 1 or begin[0] != 0 or begin[-1] != cells.shape[0] or (np.diff(begin) < 0).any():
+            raise ValueError('book_begin must be [n_books + 1], non-decreasing from 0 to N = %d, got %r' % (cells.shape[0], begin.tolist()[:8]))
+        n_books = begin.size - 1
+        PAD = nat.MAPF_GROUP_PAD
+        where = lambda k: '[%d, %d]' % (k[0], k[1]) if rows.ndim == 2 else '[%d]' % k[1]   # (the entry's name: [e, i], or [i] of shared arrays)
+        mem = members.reshape(-1, n_agents, 4).astype(np.int64)
+        bk = book.reshape(-1, n_agents).astype(np.int64)
+        pad = mem == PAD
+        bad = np.argwhere(~pad & ((mem < 0) | (mem >= n_agents)))
+        if bad.size:
+            raise ValueError('members%s[%d] = %d is not an agent 0..%d and not padding (0xFFFF)' % (where(bad[0]), bad[0][2], mem[tuple(bad[0])], n_agents - 1))
+        bad = np.argwhere(pad[:, :, :-1] & ~pad[:, :, 1:])
+        if bad.size:
+            raise ValueError('members%s[%d] follows padding: padding must be trailing' % (where(bad[0]), bad[0][2] + 1))
+        bad = np.argwhere(~pad[:, :, 1:] & (mem[:, :, 1:] <= mem[:, :, :-1]))
+        if bad.size:
+            raise ValueError('members%s is not ascending at position %d' % (where(bad[0]), bad[0][2] + 1))
+        me = np.arange(n_agents, dtype=np.int64)[None, :, None]
+        bad = np.argwhere(~(mem == me).any(axis=2))
+        if bad.size:
+            raise ValueError('members%s does not contain agent %d itself' % (where(bad[0]), bad[0][1]))
+        size = (~pad).sum(axis=2)
+        other = np.where(pad, me, mem)                                     # (a padded position: the agent itself)
+        rows_of = np.arange(mem.shape[0])[:, None, None]
+        bad = np.argwhere((mem[rows_of, other] != mem[:, :, None, :]).any(axis=3))
+        if bad.size:
+            e, i, k = bad[0]
+            raise ValueError('members%s names agent %d, whose list differs' % (where(bad[0]), other[e, i, k]))
+        booked = (size >= 2) & (n_books != 0)                              # (without books every group falls back to its rows: book is not read)
+        bad = np.argwhere(booked & ((bk < 0) | (bk >= n_books)))
+        if bad.size:
+            raise ValueError('book%s = %d is not a book 0..%d' % (where(bad[0]), bk[tuple(bad[0])], n_books - 1))
+        bad = np.argwhere(booked[:, :, None] & (bk[rows_of, other] != bk[:, :, None]))
+        if bad.size:
+            e, i, k = bad[0]
+            raise ValueError('book%s = %d, but agent %d of the same group has book %d' % (where(bad[0]), bk[e, i], other[e, i, k], bk[e, other[e, i, k]]))
+        if (bk < 0).any() or (bk > 0xFFFFFFFF).any():
+            raise ValueError('book must be 0 .. 2**32 - 1')
+        cpad = cells == PAD
+        bad = np.argwhere(~cpad & ((cells < 0) | (cells >= V)))
+        if bad.size:
+            raise ValueError('entry_cells[%d, %d] = %d is not a cell 0..%d and not padding (0xFFFF)' % (bad[0][0], bad[0][1], cells[tuple(bad[0])], V - 1))
+        bad = np.argwhere(cpad[:, :-1] & ~cpad[:, 1:])
+        if bad.size:
+            raise ValueError('entry_cells[%d, %d] follows padding: padding must be trailing' % (bad[0][0], bad[0][1] + 1))
+        bad = np.argwhere((actions < 0) | (actions > 4))
+        if bad.size:
+            raise ValueError('entry_actions[%d, %d] = %d is not an action code 0..4' % (bad[0][0], bad[0][1], actions[tuple(bad[0])]))
+        bad = np.argwhere(cpad & (actions != 0))
+        if bad.size:
+            raise ValueError('entry_actions[%d, %d] = %d at a padded position must be 0' % (bad[0][0], bad[0][1], actions[tuple(bad[0])]))
+        if cells.shape[0]:
+            keyed = np.concatenate([np.repeat(np.arange(n_books), np.diff(begin))[:, None], cells], axis=1)
+            order = np.lexsort(keyed.T[::-1])
+            same = np.flatnonzero((keyed[order][1:] == keyed[order][:-1]).all(axis=1))
+            if same.size:
+                a, b = sorted((int(order[same[0]]), int(order[same[0] + 1])))
+                raise ValueError('entry_cells[%d] has the same four cells as entry_cells[%d] of the same book' % (b, a))
+        entries = np.zeros(cells.shape[0], nat.GROUP_ENTRY_DTYPE)
+        entries['cell'], entries['action'] = cells, actions
+        return (np.ascontiguousarray(table, dtype=np.uint8), np.ascontiguousarray(rows, dtype=np.uint16), np.ascontiguousarray(members, dtype=np.uint16),
+                np.ascontiguousarray(book, dtype=np.uint32), entries, np.ascontiguousarray(begin, dtype=np.uint32))
 
     def set_episode_limit(self, n):
         """Episode step limit: an episode that has taken ``n`` steps without ending is TRUNCATED -- with ``auto_reset`` the env goes

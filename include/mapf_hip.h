@@ -407,13 +407,64 @@ int mapf_set_policy_table(mapf_handle_t h, const uint8_t *table, uint32_t n_rows
  * mapf_set_policy(h, MAPF_POLICY_RANDOM | MAPF_POLICY_GREEDY, ...) and mapf_set_policy_table leave joint mode and free
  * the copies; mapf_set_policy_joint leaves table mode.  mapf_set_policy(h, MAPF_POLICY_JOINT, ...) is MAPF_EINVAL.
  * mapf_last_kernel(h, MAPF_KERNEL_ROLLOUT) of a joint launch says _joint and JOINT: always a lane-group kernel.
- * Out of scope: groups of three or more (V^3 bytes), a policy argument for mapf_step, packed and thread-per-env forms,
+ * Groups of three or more, whose dense form would cost V^3 bytes per agent, are MAPF_POLICY_GROUP, below (sparse books).
+ * Out of scope: a policy argument for mapf_step, packed and thread-per-env forms,
  * the multi-map / union-map wrappers and the scalar MapfEnv, graph recording of joint launches, anything that computes
  * a policy on the device.
  */
 #define MAPF_POLICY_JOINT 3
 int mapf_set_policy_joint(mapf_handle_t h, const uint8_t *table, uint64_t table_bytes,
                           const uint32_t *offset, const uint16_t *partner, uint32_t flags);
+
+/*
+ * MAPF_POLICY_GROUP: the table policy for plans in which groups of two to four agents were merged and replanned jointly
+ * on the joint cells the planner visited (RTDP, a windowed joint search, a local repair around the conflict cells): the
+ * form is SPARSE.  Every agent has a solo row, as under MAPF_POLICY_TABLE; every group has a BOOK of entries (joint cell ->
+ * the members' actions).  An agent of a group takes its action from the entry of the group's current joint cell if the
+ * book has one, and otherwise from its solo row.  Also serves a pair with a small repair book in place of 2 * V * V bytes.
+ *   table u8[n_rows * V], row_index u16[E * A]: the solo rows, MAPF_POLICY_TABLE's two arrays.
+ *   members u16[E * A * 4]: members[e,i] lists the agents of i's group in ascending order, padded at the end with 0xFFFF.
+ *     The list contains i; every agent in it carries the identical list; its size G is 1..4, G == 1 a solo agent.
+ *   book u32[E * A]: book[e,i] names the group's book: the same for all members and below n_books; ignored for a solo agent.
+ *   entries mapf_group_entry[n_entries], book_begin u32[n_books + 1]: book b is entries[book_begin[b] .. book_begin[b+1]);
+ *     book_begin[0] == 0, book_begin[n_books] == n_entries, non-decreasing.  n_books == 0 with n_entries == 0 is legal: every
+ *     group then falls back to its rows, and book is not read.
+ * With MAPF_POLICY_ROWS_BROADCAST row_index, members and book are [A], [A * 4] and [A] TOGETHER, shared by all envs.
+ * All pointers are HOST pointers in every handle mode and are copied.
+ *   The key of a group in a step is the four u16 (c[m0], c[m1], ...): the members' cells on entry to the step, after any
+ *   auto-reset, with 0xFFFF at the padded positions.  An entry matches when its four cells equal the key; an entry of another
+ *   arity never matches.
+ *   Agent i at position p of its group, G >= 2, with a matching entry in the group's book, takes entry.action[p].  Every other
+ *   agent-step takes table[row_index[e,i] * V + c_i].
+ * Everything else is as under MAPF_POLICY_JOINT: slip, collisions, reward and termination are exactly those of a mapf_step
+ * with these actions, and so are both Philox streams' counters, the episode limit, the episode budget, the conflict matrix
+ * and the episode log; the policy stream is not drawn; terminal and parked steps are no-ops; a rollout with streamed
+ * actions ignores the policy; mapf_step* are unaffected.
+ * Validated on the host before any device work, MAPF_EINVAL with a mapf_last_error that names the offending index: null
+ * handle or pointer (entries and book_begin may be NULL only when n_entries == 0 && n_books == 0); the table policy's own
+ * checks; a member >= A that is not padding, padding that is not trailing, a list that is not ascending, a list without i;
+ * a member whose list (or book) differs; book[e,i] >= n_books for G >= 2 (n_books > 0); a broken book_begin; an entry cell >= V that is
+ * not 0xFFFF, padding in an entry that is not trailing; an action above 4, a nonzero action at a padded position; two
+ * entries of one book with the same four cells; n_entries > 2^24; unknown flag bits.  V = 65536 would make cell 0xFFFF
+ * ambiguous: the mode needs V <= 65535 (MAPF_EUNSUPPORTED otherwise).
+ * Refused while recording and while recorded graphs live; mapf_graph_begin refuses a handle in the mode; a refused call
+ * leaves the previous policy in force.  mapf_set_policy(h, MAPF_POLICY_RANDOM | MAPF_POLICY_GREEDY, ...),
+ * mapf_set_policy_table and mapf_set_policy_joint leave the mode and free the copies; mapf_set_policy(h,
+ * MAPF_POLICY_GROUP, ...) is MAPF_EINVAL.  mapf_last_kernel(h, MAPF_KERNEL_ROLLOUT) of a group launch says _group and GROUP
+ * where a joint launch says _joint and JOINT: always a lane-group kernel.
+ * On the device all books lie in one open-addressing table of 16-byte slots (capacity: a power of two >= 2 * n_entries,
+ * linear probing); a lookup reads at most as many slots as the longest chain the host produced while building it.
+ * Out of scope: groups of five or more; packed and thread-per-env forms; the single step; recorded graphs; the multi-map
+ * and union-map wrappers and the scalar MapfEnv; anything that computes or repairs a plan on the device.
+ */
+#define MAPF_POLICY_GROUP 4
+typedef struct mapf_group_entry { uint16_t cell[4]; uint8_t action[4]; } mapf_group_entry;   /* 12 bytes */
+int mapf_set_policy_group(mapf_handle_t h, const uint8_t *table, uint32_t n_rows, const uint16_t *row_index,
+                          const uint16_t *members, const uint32_t *book,
+                          const mapf_group_entry *entries, uint64_t n_entries,
+                          const uint32_t *book_begin, uint32_t n_books, uint32_t flags);
+/* The device table of a handle in the mode (MAPF_EINVAL otherwise): its slots, and the longest probe chain.  No device touched. */
+int mapf_policy_group_stats(mapf_handle_t h, uint64_t *slots, uint32_t *max_probe);
 
 /*
  * MapfEnv.P[s][a] (mapf_env.py:448-478 _get_transitions): for each of n_queries (state, joint action) pairs,
@@ -560,6 +611,18 @@ int mapf_debug_rollout_plan(uint32_t n_cells, int n_agents, uint64_t n_envs, uin
  * LDS bytes of the launch, blocks} of the lane-group limit instance that takes the launch. */
 int mapf_debug_rollout_plan_limited(uint32_t n_cells, int n_agents, uint64_t n_envs, uint32_t n_steps, int streamed, int delta_rows,
                                     int n_cu, const char *tune, uint32_t max_steps, uint64_t out[6]);
+
+/* Diagnostic, no device needed and none touched: validates a group plan for a batch of n_envs envs of n_agents agents on a map
+ * of n_cells cells exactly as mapf_set_policy_group does (same return codes and mapf_last_error texts), builds the device table
+ * on the host, and looks n_keys keys up through the probe function the kernel uses.  key_cells u16[n_keys * 4], key_book
+ * u32[n_keys]; out_actions u32[n_keys]: the entry's four action bytes (action[0] lowest) or 0xFFFFFFFF where the book has no
+ * such entry; out_probes u32[n_keys] (may be NULL): slots read; out_slots, out_max_probe (may be NULL): as
+ * mapf_policy_group_stats reports them. */
+int mapf_debug_policy_group(uint32_t n_cells, uint32_t n_agents, uint64_t n_envs, const uint8_t *table, uint32_t n_rows,
+                            const uint16_t *row_index, const uint16_t *members, const uint32_t *book,
+                            const mapf_group_entry *entries, uint64_t n_entries, const uint32_t *book_begin, uint32_t n_books,
+                            uint32_t flags, uint64_t n_keys, const uint16_t *key_cells, const uint32_t *key_book,
+                            uint32_t *out_actions, uint32_t *out_probes, uint64_t *out_slots, uint32_t *out_max_probe);
 
 #ifdef __cplusplus
 }

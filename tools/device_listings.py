@@ -43,6 +43,11 @@ def log_units():
     return dict(line.split() for line in _make('print-log-kernel-units').splitlines())
 
 
+def group_units():
+    """{name: source unit} of the Makefile's fifth table: the compilations that follow a group policy, whose source lies beside csrc"""
+    return dict(line.split() for line in _make('print-group-kernel-units').splitlines())
+
+
 def listings(*names):
     """{name: listing text} for the named compilations (a kernel-holding one or a host unit); for all kernel-holding ones if none is named"""
     names = names or tuple(units())
